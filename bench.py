@@ -21,11 +21,17 @@ flat fp32 gradient and every rank runs the optimizer on the whole W (dp.AllReduc
 reduce-scatter the W gradient, run the optimizer on their row chunk, all-gather the low-precision shadow and rebuild its transpose locally
 (dp.ShardedExchange); mining is per rank (SURVEY 8e mode ii).
 
-Prints ONE JSON line (rank 0).  `kernels` / `roofline` come from HIP events recorded on the step's stream around each kernel
-(dae_plan_profile mode 3: the pairs are handed to hipExtLaunchKernelGGL and carry each dispatch's own begin / end; launches and steps run
-back to back), in a second pass so that `value` is never measured with profiling on; `fit` is the same workload through
-DenoisingAutoencoder.fit() (N * timed epochs / wall, first epoch excluded); `cpu_baseline` times the PyTorch-CPU fp32
-restatement of the reference step (oracle/torch_baseline.py; TF 1.12 cannot run here) on a bounded sample.
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: set up, pre-warm + warm up, time exactly
+--steps steps, write --dump-outputs if asked, print `metric` / `value` / `unit` / `higher_is_better` / `dtype` / `ms_per_step`.
+Everything else is measured with --full only: `long_run` (the same loop over >= 50 ms), the N > 1 collective timings, `kernels` /
+`roofline` from HIP events recorded on the step's stream around each kernel (dae_plan_profile mode 3: the pairs are handed to
+hipExtLaunchKernelGGL and carry each dispatch's own begin / end; launches and steps run back to back), in a second pass so that `value`
+is never measured with profiling on; `fit` is the same workload through DenoisingAutoencoder.fit() (N * timed epochs / wall, first
+epoch excluded); the other precision modes over the same K steps; `cpu_baseline` times the PyTorch-CPU fp32 restatement of the
+reference step (oracle/torch_baseline.py; TF 1.12 cannot run here) on a bounded sample.  The --no-* options drop single legs of --full.
+
+--dump-outputs DIR writes what the timed path's last step hands its caller (the trained parameters and that step's stats row) as
+float32 .npy files; the pre-warm is a fixed number of steps, so the same arguments give the same inputs to that step in every run.
 """
 import argparse
 import glob
@@ -51,6 +57,7 @@ PEAK_VALU_TLANEOPS = 39.3      # 256 CUs x 4 SIMDs x 16 lanes/clk x 2.4 GHz: one
 MINER_CYCLES_PER_CELL = 12.25
 PEAK_MINER_TCELLS = 256 * 4 * 64 * 2.4e9 / MINER_CYCLES_PER_CELL / 1e12
                                # (packed-fp32 instructions count once; they issue at this rate too on this part)
+DUMP_W_BYTES = 48 << 20        # --dump-outputs: enc_w above this size is written as a seeded row sample (c4's W is 200 MB; all files stay under 64 MB)
 
 CONFIGS = {
     "c1": dict(rows=8000, features=10000, cf=20, batch=800, strategy="none", kind="csr_binary", loss="cross_entropy",
@@ -100,7 +107,14 @@ def parse():
     ap.add_argument("--exchange-impl", default="auto", choices=["auto", "native", "torch"],
                     help="N>1, all-reduce exchange: who issues the collective -- native = the C ABI's own RCCL communicator on the step's stream "
                          "(dae_dp_exchange), torch = torch.distributed's process group; auto = native over the nccl backend")
-    ap.add_argument("--prewarm", type=float, default=0.25, help="seconds of untimed steps of the same loop before the W warm-up steps (clock ramp of a fresh process); 0 = none")
+    ap.add_argument("--prewarm", type=float, default=0.25, help="seconds of untimed steps of the same loop before the W warm-up steps (clock ramp of a fresh process), "
+                                                                  "run as a fixed count of steps at a nominal 250 us each; 0 = none")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: long_run, collective timings (N>1), per-kernel table + roofline, fit(), "
+                         "the other precision modes, cpu_baseline (the --no-* options drop single legs)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (enc_w, enc_b, dec_b, step_stats; enc_w as a fixed, seeded "
+                         "row sample when larger than %d MB) as DIR/<name>.npy in float32" % (DUMP_W_BYTES >> 20))
     ap.add_argument("--profile-steps", type=int, default=20)
     ap.add_argument("--profile-mode", default="stamps", choices=["stamps", "queued", "sync"],
                     help="how the per-kernel HIP events are taken (dae_plan_profile): stamps = event pairs stamped by the dispatch itself "
@@ -110,10 +124,10 @@ def parse():
     ap.add_argument("--fit-epochs", type=int, default=6)
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="code-path choice of the plan for A/B measurements (dae_plan_set_option), e.g. --option overlap=1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-fit", action="store_true")
-    ap.add_argument("--no-fp32", action="store_true", help="skip the precision='fp32' leg of the same K steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the per-kernel table and roofline")
+    ap.add_argument("--no-fit", action="store_true", help="--full: skip the fit() legs")
+    ap.add_argument("--no-fp32", action="store_true", help="--full: skip the legs of the other precision modes over the same K steps")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for N>1 (nccl == RCCL; gloo only to exercise the N>1 code path on one GPU)")
     ap.add_argument("--single-device", action="store_true", help="testing aid: every rank uses cuda:0")
@@ -474,8 +488,8 @@ def timed_steps(run, steps, warmup):
     return dp.allreduce_max_float(time.perf_counter() - t0)
 
 
-def box_info(torch):
-    """Which box / clocks produced this line (the pool's boxes differ by up to 1.3x on one binary)."""
+def box_info(torch, smi):
+    """Which box / clocks produced this line (the pool's boxes differ by up to 1.3x on one binary); smi: also the rocm-smi clock / power readout."""
     import socket
     import subprocess
     info = {"host": socket.gethostname(), "device": torch.cuda.get_device_name(0), "cpus": _cpu_budget()}
@@ -485,6 +499,8 @@ def box_info(torch):
         info["max_sclk_mhz"] = getattr(p, "clock_rate", 0) / 1e3
     except Exception:        # noqa: BLE001
         pass
+    if not smi:
+        return info
     try:
         out = subprocess.run(["/opt/rocm/bin/rocm-smi", "--showclocks", "--showpower", "--csv"], capture_output=True, text=True, timeout=20).stdout
         rows = [r for r in out.splitlines() if r.strip()]
@@ -500,21 +516,36 @@ def _prewarm_clocks(torch, run, seconds=0.25):
     steady clocks.  A fresh process starts from the idle power state and this latency-bound step climbs to its steady rate over tens of milliseconds
     (tools/region_trace.py, profiles/r06_region_trace.txt: 211 -> 202 -> 197 -> 194 us per step over the first 60 ms; a 0.25 s bf16 matmul in front -- rounds 3-5 --
     changed nothing).  Reported in the JSON line as `prewarm`; the W warm-up steps and the K timed steps follow exactly as the contract asks."""
-    t0 = time.perf_counter()
-    n = 0
-    if run.world > 1:
-        # every step holds a collective: all ranks must run the SAME number of steps -- a count fixed from the time budget (~250 us per step), not a clock
-        n = max(20, int(seconds / 250e-6) // 20 * 20)
-        for _ in range(n):
-            run.step()
-        torch.cuda.synchronize()
-        return n
-    while time.perf_counter() - t0 < seconds:
-        for _ in range(20):
-            run.step()
-        n += 20
-        torch.cuda.synchronize()
+    # a count fixed from the time budget (~250 us per step), not a clock: with N > 1 every step holds a collective and all ranks must run the SAME number
+    # of steps, and the timed steps must start from the same state in every run (--dump-outputs compares runs output for output)
+    n = max(20, int(seconds / 250e-6) // 20 * 20)
+    for _ in range(n):
+        run.step()
+    torch.cuda.synchronize()
     return n
+
+
+def dump_outputs(run, out_dir):
+    """--dump-outputs: what the timed path's last step hands its caller -- the parameters it trained (named as DenoisingAutoencoder.get_model_parameters()
+    names them) and that step's stats row (cost, autoencoder, triplet, fraction, num, n_valid) -- as float32 DIR/<name>.npy.  An enc_w above DUMP_W_BYTES
+    is written as a fixed, seeded sample of its rows (the row indices beside it as enc_w_rows, float64).  N > 1: call on every rank (gather_master is a
+    collective); rank 0 writes."""
+    L = run.L
+    if run.world > 1:
+        run.exchange.gather_master()          # the sharded exchange keeps each rank's fp32 master rows only
+    if run.rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    W, bh, bv = run.eng.get_params()
+    arrays = {"enc_b": bh, "dec_b": bv, "step_stats": run.stats[(run.step_i - 1) % run.nb, :L.STAT_NVALID + 1].cpu().numpy()}
+    if W.nbytes > DUMP_W_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(W.shape[0], DUMP_W_BYTES // W[0].nbytes, replace=False))    # its own generator: np.random's stream is the feeder's
+        arrays["enc_w_rows"] = rows.astype(np.float64)
+        W = W[rows]
+    arrays["enc_w"] = W
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64 if name == "enc_w_rows" else np.float32))
+    _log("outputs of the last timed step written to %s: %s" % (out_dir, ", ".join(sorted(arrays))))
 
 
 def self_launch(n):
@@ -583,11 +614,13 @@ def main():
     _log("runner ready")
 
     dt = timed_steps(run, a.steps, a.warmup)
+    if a.dump_outputs:
+        dump_outputs(run, a.dump_outputs)
     last = run.stats.cpu().numpy()
     # the driver's K can make a 3 ms timed region: repeat the same loop over >= 50 ms and report it beside `value`
     long_run = None
     k2 = int(np.ceil(0.06 / max(dt / a.steps, 1e-6)))
-    if k2 > a.steps:
+    if a.full and k2 > a.steps:
         dt2 = timed_steps(run, k2, 0)
         long_run = {"steps": k2, "seconds": dt2, "value": k2 * c["batch"] * world / dt2, "ms_per_step": 1e3 * dt2 / k2,
                     "note": "the same step loop repeated over >= 50 ms = %d steps (`value` / `ms_per_step` are over exactly --steps = %d steps, as the contract asks)" % (k2, a.steps)}
@@ -601,10 +634,10 @@ def main():
         "value": value, "unit": "samples/s",
         "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_per_step,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.precision, "data": "synthetic",
-        "fit": None,          # filled below: the same workload through DenoisingAutoencoder.fit() (timed over ~0.1 s; the sturdier figure)
-        "timed_region": {"steps": a.steps, "seconds": dt}, "long_run": long_run, "box": box_info(torch),
+        "fit": None,          # filled below with --full: the same workload through DenoisingAutoencoder.fit() (timed over ~0.1 s; the sturdier figure)
+        "timed_region": {"steps": a.steps, "seconds": dt}, "long_run": long_run, "box": box_info(torch, smi=a.full),
         "prewarm": {"seconds": a.prewarm, "steps": n_prewarm, "what": "untimed steps of the same loop before the W warm-up steps (clock ramp of a fresh process; --prewarm 0 disables)"},
-        "precision_note": ("`value`, `kernels`, `roofline` are measured in precision=%r -- %s; the other modes are the objects `f16x2` / `bf16x3` / `fp32` / `bf16` "
+        "precision_note": ("`value`, `kernels`, `roofline` are measured in precision=%r -- %s; with --full the other modes are the objects `f16x2` / `bf16x3` / `fp32` / `bf16` "
                            "below, `bf16` being faster but outside the 1e-4 gate" % (a.precision, "what precision='auto' (the product default) resolves to for "
                            "this config's triplet strategy: the cheapest mode measured to hold the reference's loss curve within 1e-4 over 100 steps (batch_hard: inside the oracle's own envelope)" if a.precision_asked == "auto" else "as asked")),
         "config": {"workload": f"{a.config} = BASELINE.json {c['baseline']}; per GPU: synthetic {c['rows']}x{c['features']} {c['kind']}, "
@@ -625,27 +658,29 @@ def main():
     if a.option:
         out["config"]["plan_options"] = list(a.option)
     if run.exchange:
-        # the collectives of the LAST `steps` steps, timed by events on the step's stream (a second, short pass keeps the host
-        # event synchronisation out of the timed region above)
-        for _ in range(min(20, a.steps)):
-            run.step(); run.exchange.collect_time()
-        out["collective_us"] = 1e3 * run.exchange.collective_ms / max(1, min(20, a.steps))
+        if a.full:
+            # the collectives of the LAST `steps` steps, timed by events on the step's stream (a second, short pass keeps the host
+            # event synchronisation out of the timed region above)
+            for _ in range(min(20, a.steps)):
+                run.step(); run.exchange.collect_time()
+            out["collective_us"] = 1e3 * run.exchange.collective_ms / max(1, min(20, a.steps))
         comm = getattr(run.exchange, "comm", None)
         out["exchange"] = {"class": type(run.exchange).__name__, "buckets": getattr(run.exchange, "buckets", None),
                            "issued_by": "C ABI (dae_dp_exchange: RCCL on the step's stream, %s)" % comm.library if comm is not None else "torch.distributed process group",
                            "collective_us_brackets": "all-reduce + optimizer (everything behind the phase-1 step)" if comm is not None else "the collective(s) alone"}
         out["ranks_seen"] = comm.ranks_seen if comm is not None else int(dp.allreduce_sum_float(1.0))
-        # exposed = what the exchange adds to a step on the critical path: the step with it minus the same local step without it
-        # (phase-1 step alone, timed back to back below); only the reduce-scatter overlaps compute (the step's tail kernel)
-        torch.cuda.synchronize(); dp.barrier()
-        t1 = time.perf_counter()
-        for s_ in range(min(20, a.steps)):
-            rows, labs = run.batch(s_ % run.nb)
-            run.eng.train_step(rows, labs, run.stats[s_ % run.nb], phase=1, **run.plan)
-        torch.cuda.synchronize()
-        local_us = dp.allreduce_max_float(time.perf_counter() - t1) * 1e6 / max(1, min(20, a.steps))
-        out["local_step_us"] = local_us
-        out["exposed_us"] = max(0.0, 1e3 * out["ms_per_step"] - local_us)
+        if a.full:
+            # exposed = what the exchange adds to a step on the critical path: the step with it minus the same local step without it
+            # (phase-1 step alone, timed back to back below); only the reduce-scatter overlaps compute (the step's tail kernel)
+            torch.cuda.synchronize(); dp.barrier()
+            t1 = time.perf_counter()
+            for s_ in range(min(20, a.steps)):
+                rows, labs = run.batch(s_ % run.nb)
+                run.eng.train_step(rows, labs, run.stats[s_ % run.nb], phase=1, **run.plan)
+            torch.cuda.synchronize()
+            local_us = dp.allreduce_max_float(time.perf_counter() - t1) * 1e6 / max(1, min(20, a.steps))
+            out["local_step_us"] = local_us
+            out["exposed_us"] = max(0.0, 1e3 * out["ms_per_step"] - local_us)
         out["multi_gpu_note"] = ("no N > 1 hardware number exists for this code until the driver's SCALE run: the exchange has only run "
                                  "as a one-rank RCCL group and over gloo (tests/test_dp_gloo.py, tests/test_hip_dp.py)")
         if type(run.exchange).__name__.endswith("AllReduceExchange"):
@@ -655,7 +690,7 @@ def main():
                                                                                    + run.eng.rows_alloc * run.eng.Hp * (2 if a.precision == "bf16" else 4)))
 
     _log("timed region done: %.1f us/step" % (1e6 * dt / a.steps))
-    if rank == 0 and not a.no_roofline:
+    if a.full and rank == 0 and not a.no_roofline:
         eng = run.eng
 
         def profile_pass(mode):
@@ -759,8 +794,9 @@ def main():
         out["longest_kernel"] = {"slot": longest[0], "avg_us": longest[1]["avg_us"], "time_share": longest[1]["time_share"],
                                  "frac": longest[1].get("frac"), "bound": longest[1].get("bound")}
     run.close()
-    _log("profile pass done")
-    if rank == 0 and world == 1 and not a.no_fit:
+    if a.full:
+        _log("profile pass done")
+    if a.full and rank == 0 and world == 1 and not a.no_fit:
         epoch_s = (dt / a.steps) * run.nb
         epochs = max(a.fit_epochs, min(200, int(0.1 / max(epoch_s, 1e-6)) + 2))
         out["fit"] = {a.rng: fit_leg(a, a.rng, epochs)}
@@ -774,8 +810,8 @@ def main():
                                  "--rng numpy to time it"}
         out["fit"]["note"] = ("DenoisingAutoencoder.fit() on the same workload: N * timed epochs / wall, first epoch excluded; rng=numpy is the "
                               "reference-exact legacy stream (keep decisions drawn one epoch ahead on a feeder thread)")
-    _log("fit legs done")
-    if rank == 0 and world == 1 and not a.no_fp32:
+        _log("fit legs done")
+    if a.full and rank == 0 and world == 1 and not a.no_fp32:
         # the same K steps in the other precision modes (never allowed to take the bench line down with them)
         import copy
         from dae_rnn_news_recommendation_amd import _lib as _L
@@ -807,7 +843,7 @@ def main():
             except Exception as ex:      # noqa: BLE001
                 out[mode] = {"error": repr(ex)[:300]}
             _log(mode + " leg done")
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a)
         _log("cpu baseline done")
         if out["cpu_baseline"]["value"]:

@@ -193,6 +193,36 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     assert d["value"] > 0 and np.isfinite(d["final_losses"]["cost"])
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps and measures nothing beside its headline (that is --full's); --dump-outputs writes the last
+    timed step's parameters and stats as float32 .npy, and the same arguments give the same outputs in a second process (the pre-warm is a step count)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    runs = []
+    for i in range(2):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--prewarm", "0.005", "--rows", "1600",
+               "--dump-outputs", str(tmp_path / f"out{i}")]
+        out = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 7 and d["timed_region"]["steps"] == 7 and d["prewarm"]["steps"] == 20
+        assert d["value"] > 0 and d["higher_is_better"] is True and d["unit"] == "samples/s" and d["dtype"] == "f16x2h"
+        assert abs(d["ms_per_step"] - 1e3 * d["timed_region"]["seconds"] / 7) < 1e-9
+        assert d["fit"] is None and d["long_run"] is None and not {"kernels", "roofline", "cpu_baseline", "fp32", "bf16"} & set(d)
+        runs.append({k: np.load(tmp_path / f"out{i}" / (k + ".npy")) for k in ("enc_w", "enc_b", "dec_b", "step_stats")})
+    r0, r1 = runs
+    assert r0["enc_w"].shape == (10000, 500) and r0["enc_b"].shape == (500,) and r0["dec_b"].shape == (10000,) and r0["step_stats"].shape == (6,)
+    for k in r0:
+        assert r0[k].dtype == np.float32 and np.isfinite(r0[k]).all(), k
+        np.testing.assert_allclose(r1[k], r0[k], rtol=1e-4, atol=1e-6 * float(np.abs(r0[k]).max()), err_msg=k)
+    assert r0["step_stats"][0] > 0                           # the cost of the last step
+
+
 @pytest.mark.parametrize("precision,tol", [("fp32", 3e-5), ("auto", 1e-4)])
 @pytest.mark.parametrize("strategy,opt", [("batch_all", "gradient_descent"), ("none", "momentum")])
 def test_cli_training_values_match_the_oracle(tmp_path, monkeypatch, capsys, precision, tol, strategy, opt):

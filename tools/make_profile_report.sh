@@ -31,12 +31,12 @@ python tools/pmc_summary.py $OUT/pmc_fetch5/f5_results.db $OUT/pmc_write5/w5_res
 rm -rf $OUT/pmc_fetch $OUT/pmc_write $OUT/pmc_sq $OUT/pmc_sq2 $OUT/pmc_fetch4 $OUT/pmc_write4 $OUT/pmc_fetch5 $OUT/pmc_write5
 # the traffic file bench.py quotes (same kernels, same box, minutes apart)
 python tools/build_profile_summary.py $OUT $TAG --traffic-only > /dev/null
-$T python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_form.json 2> $OUT/bench.err      # exactly the driver's command
-$T python bench.py --config c2 --steps 300 --warmup 30 > $OUT/bench_c2.json 2>> $OUT/bench.err
-$T python bench.py --config c1 --steps 300 --warmup 30 > $OUT/bench_c1.json 2>> $OUT/bench.err
-$T python bench.py --config c3 --steps 300 --warmup 30 > $OUT/bench_c3.json 2>> $OUT/bench.err
-$T python bench.py --config c5 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_c5.json 2>> $OUT/bench.err
-$T python bench.py --config c4 --steps 100 --warmup 10 > $OUT/bench_c4.json 2>> $OUT/bench.err
+$T python bench.py --steps 20 --warmup 5 --full > $OUT/bench_driver_form.json 2> $OUT/bench.err      # the driver's command (+ --full: long_run and the other legs)
+$T python bench.py --config c2 --steps 300 --warmup 30 --full > $OUT/bench_c2.json 2>> $OUT/bench.err
+$T python bench.py --config c1 --steps 300 --warmup 30 --full > $OUT/bench_c1.json 2>> $OUT/bench.err
+$T python bench.py --config c3 --steps 300 --warmup 30 --full > $OUT/bench_c3.json 2>> $OUT/bench.err
+$T python bench.py --config c5 --steps 200 --warmup 20 --full --no-cpu-baseline > $OUT/bench_c5.json 2>> $OUT/bench.err
+$T python bench.py --config c4 --steps 100 --warmup 10 --full > $OUT/bench_c4.json 2>> $OUT/bench.err
 $T rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-roofline --no-fit --no-fp32 > $OUT/bench_under_rocprof.json 2> $OUT/trace.err
 python tools/rocprof_summary.py $OUT/trace/t_results.db > $OUT/kernel_stats.md
 python tools/trace_gaps.py $OUT/trace/t_results.db > $OUT/trace_gaps.txt 2>&1
