@@ -106,16 +106,9 @@ struct dae_plan {
     int pev_used;
     hipEvent_t pev[PROF_POOL];
     int pev_slot[PROF_POOL / 2];
-    // second stream for the miner chain (gram -> sweep -> finalize -> sym_scale): with batch_all the row weights
-    // depend on the labels only, so the chain is independent of the decode GEMM and runs beside it
-    hipStream_t side;
-    hipEvent_t ev_fork, ev_join;
     bool ev_dw_live;                  // ev_dw was recorded by the last dae_train_step (an event that never was recorded does not hold a waiter back)
     hipEvent_t ev_dw;                 // recorded right behind the kernel that completes the W gradient (dae_plan_dw_event): a data-parallel
                                       // caller starts its reduce-scatter from here, beside the step's tail kernel
-    bool overlap_ok;
-    int overlap_mode;                 // option "overlap" value: 1 = fork the decode before the Gram launch, 2 = after it (the Gram kernel needs a whole CU's LDS per workgroup
-                                      // and cannot start beside resident decode workgroups), 3 = like 2 with the MINER on the side stream and the decode on the step's
     bool sym_ride_ok;                 // Gs = a/Nv (G + G^T) computed by rider workgroups of the decode launch instead of its own launch
     bool miner_order_ok;              // dispatch the batch_all workgroups by descending sweep cost (LabelJob::order)
     int32_t* miner_order;
@@ -152,9 +145,6 @@ struct dae_plan {
                                      // DEC_WIDE_ROUNDS rounds of the chip's 768 slots (option "decode_bn" = 64 | 128 | 0 auto; before dae_plan_bind)
     bool dw_pair_ok;                 // option "dw_pair": split-bf16 dW kernel streams x~^T resp. delta2^T_hi ONCE for the hi and lo image of delta1^T resp. h^T
     bool xct2_clean;
-    uint32_t* xtb;                   // x~^T as a bit image [Fp x Bpm/32] (binary CSR + bf16: operand of the sparse half of the dW kernel)
-    bool xtb_clean;                  // the bit image holds only zeros (every step clears what it set; see step_tail_kernel)
-    bool dw_bits_ok;               // option "dw_bits" = 0: dense x~^T image and a K = 2 Bp dW GEMM (A/B, equivalence tests)
     bool enc_w32_ok;                 // option "encode_w32": bf16 mode encodes from the fp32 MASTER weights (h fp32-accurate); 0 = from W_lo
     int w32_cols;                    // option "encode_w32_cols": 128 (default) or 64 H columns per workgroup of that kernel
     bool gram_split;                 // Gram matrix as a 3-term split-bf16 MFMA GEMM (bf16 mode) instead of exact-fp32 MFMA
@@ -240,7 +230,6 @@ static uint64_t carve(dae_plan* p, char* base) {
     p->h_t = take(Hp * Bp * es);
     p->delta1_t = take(Hp * Bp * es);
     p->delta1_lo = take(Bp * Hp * es);
-    p->xtb = (uint32_t*)take(Fp * (Bp / 32) * 4);
     p->dh_extra = (float*)take(Bp * Hp * 4);
     const uint32_t T = p->x3 ? p->terms : 0u;          // lo images exist only for the product terms that read them
     p->W_lo2 = take((T & X3T_DEC_WLO) ? Fp * Hp * 2 : 256);
@@ -334,15 +323,13 @@ extern "C" int dae_plan_create(const dae_config* cfg, dae_plan** out) {
     p->label_enc_ok = true;
     p->ce_literal = false;
     p->xbits_ok = cfg->dtype == DAE_BF16;
-    p->xct_clean = false; p->xtb_clean = false; p->xct2_clean = false;
-    p->dw_bits_ok = false;                             // measured slower than streaming the dense image (profiles/r03_experiments.md)
+    p->xct_clean = false; p->xct2_clean = false;
     p->enc_w32_ok = cfg->dtype == DAE_BF16;
     p->w32_cols = 128;                                 // measured: 128-column fp32 slices (5.2 MB, served by the MALL) beat 64-column ones
     // binary CSR + bf16: x~ goes to the encode GEMM as a bit image whenever the 8-wave bit kernel can run the shape
     p->bits_ok = cfg->dtype == DAE_BF16 && encode_bits_fits(p->Bpm, p->Hp, p->Fp, p->s_enc);
     p->sparse_ok = true;
     p->miner_order_ok = true; p->sym_ride_ok = true; p->miner_ranges_ok = true;
-    p->overlap_ok = false;                              // measured: running the miner chain beside decode is SLOWER (0.410 vs 0.351 ms/step)
     p->cos_zstore_ok = true;
     *out = p;
     return 0;
@@ -353,10 +340,7 @@ extern "C" void dae_plan_destroy(dae_plan* p) {
     if (p->ev0) (void)hipEventDestroy(p->ev0);
     if (p->ev1) (void)hipEventDestroy(p->ev1);
     for (int i = 0; i < dae_plan::PROF_POOL; ++i) if (p->pev[i]) (void)hipEventDestroy(p->pev[i]);
-    if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
-    if (p->ev_join) (void)hipEventDestroy(p->ev_join);
     if (p->ev_dw) (void)hipEventDestroy(p->ev_dw);
-    if (p->side) (void)hipStreamDestroy(p->side);
     delete p;
 }
 
@@ -369,7 +353,6 @@ extern "C" int dae_plan_set_option(dae_plan* p, const char* name, int32_t value)
     else if (!strcmp(name, "encode_bits")) p->bits_ok = on && p->cfg.dtype == DAE_BF16 && encode_bits_fits(p->Bpm, p->Hp, p->Fp, p->s_enc);
     else if (!strcmp(name, "x_bits")) p->xbits_ok = on && p->cfg.dtype == DAE_BF16;
     else if (!strcmp(name, "fused_opt")) p->fuse_opt_ok = on;
-    else if (!strcmp(name, "dw_bits")) p->dw_bits_ok = on;
     else if (!strcmp(name, "dw_pair")) p->dw_pair_ok = on;
     else if (!strcmp(name, "dw_tr")) { DAE_CHECK_ARG(value >= -1 && value <= 1, "plan_set_option: dw_tr is -1 (auto), 0 or 1"); p->dw_tr_mode = value; p->xct_clean = false; }
     else if (!strcmp(name, "encode_w32")) p->enc_w32_ok = on && p->cfg.dtype == DAE_BF16;
@@ -377,14 +360,11 @@ extern "C" int dae_plan_set_option(dae_plan* p, const char* name, int32_t value)
     else if (!strcmp(name, "tail")) p->tail_ok = on;
     else if (!strcmp(name, "label_with_encode")) p->label_enc_ok = on;
     else if (!strcmp(name, "ce_literal")) p->ce_literal = on;
-    else if (!strcmp(name, "overlap")) { p->overlap_ok = on; p->overlap_mode = value; }
     else if (!strcmp(name, "gather_tile")) set_gather_tile(value);        // process-wide: tile shape of the dense gather (A/B measurements)
     else if (!strcmp(name, "dw_rounds")) { DAE_CHECK_ARG(value >= 1 && value <= 64, "plan_set_option: dw_rounds in 1..64"); set_use_glds(-100 - value); }   // process-wide, like miner_pack
-    else if (!strcmp(name, "decode_pair")) set_use_glds(on ? -14 : -13);   // process-wide: the decode's two W terms as paired K-loop stages (one h tile, both W tiles)
     else if (!strcmp(name, "cos_zstore")) p->cos_zstore_ok = on;
     else if (!strcmp(name, "gram_fused")) set_use_glds(on ? -20 : -19);    // process-wide: the split Gram's three products per K tile in one LDS stage (gram64f_kernel; default on), 0 = the K-concatenated walk (gram64_kernel)
     else if (!strcmp(name, "decode_x3")) set_use_glds(on ? -18 : -17);     // process-wide: the split modes' decode on the K loops that keep the hi stage's fragments in registers (mainloop_n64_x3 / _c2; default on, binary input)
-    else if (!strcmp(name, "decode_ast")) set_use_glds(on ? -16 : -15);    // process-wide: the A-stationary persistent decode kernel (gemm_decode_ast; default off: measured slower)
     else if (!strcmp(name, "pad_skip")) set_use_glds(on ? -12 : -11);      // process-wide: 0 = multiply / evaluate the all-padding 32-row blocks of the last batch tile too (A/B)
     else if (!strcmp(name, "miner_order")) p->miner_order_ok = on;
     else if (!strcmp(name, "miner_ranges")) p->miner_ranges_ok = on;
@@ -478,7 +458,7 @@ extern "C" int dae_plan_bind(dae_plan* p, const dae_buffers* bufs) {
     carve(p, (char*)bufs->workspace);
     p->bound = true;
     p->xct_clean = false;            // a (re)bound workspace has not been cleared: the next backward step memsets x~^T once
-    p->xtb_clean = false; p->xct2_clean = false;
+    p->xct2_clean = false;
     return 0;
 }
 
@@ -492,7 +472,7 @@ extern "C" void* dae_plan_buffer(dae_plan* p, const char* name) {
     if (!p || !p->bound || !name) return nullptr;
 #define DAE_BUF(n) if (!strcmp(name, #n)) return (void*)p->n;
     DAE_BUF(hcat_a) DAE_BUF(hcat_b) DAE_BUF(x) DAE_BUF(xc) DAE_BUF(xct) DAE_BUF(h_lo) DAE_BUF(h_t) DAE_BUF(Gs) DAE_BUF(delta2) DAE_BUF(delta2_t) DAE_BUF(delta1_t)
-    DAE_BUF(delta1_lo) DAE_BUF(xtb) DAE_BUF(W_lo2) DAE_BUF(Wt_lo2) DAE_BUF(h_t2) DAE_BUF(delta2_2) DAE_BUF(delta2_t2) DAE_BUF(delta1_t2) DAE_BUF(x_2) DAE_BUF(xct_2) DAE_BUF(xc_2)
+    DAE_BUF(delta1_lo) DAE_BUF(W_lo2) DAE_BUF(Wt_lo2) DAE_BUF(h_t2) DAE_BUF(delta2_2) DAE_BUF(delta2_t2) DAE_BUF(delta1_t2) DAE_BUF(x_2) DAE_BUF(xct_2) DAE_BUF(xc_2)
     DAE_BUF(slabs) DAE_BUF(h_f32) DAE_BUF(D_slabs) DAE_BUF(G) DAE_BUF(rowloss_part) DAE_BUF(dbv_part) DAE_BUF(colsum_part)
     DAE_BUF(cos_part) DAE_BUF(cos_stats) DAE_BUF(cw) DAE_BUF(loss_part) DAE_BUF(dw_f32) DAE_BUF(tri_scalars) DAE_BUF(dh_extra)
     DAE_BUF(tile_part) DAE_BUF(cnt_part) DAE_BUF(role_cnt) DAE_BUF(dw_i32) DAE_BUF(n_same) DAE_BUF(nvalid) DAE_BUF(dw_i64)
@@ -637,8 +617,6 @@ static int train_step_body(dae_plan* p, const dae_step* s, void* stream) {
     // phase 1 / 5 (data parallel) in bf16 mode: the same kernel in its gradient-only form when the shape fits it
     const bool apply_now = (s->phase == 0 || s->phase == 3);
     const bool fuse_opt0 = backward && apply_now && dt == DAE_BF16 && p->fuse_opt_ok;
-    // binary CSR + bf16 + the fused sparse encode: x~^T is a BIT image (1.1 MB) from which the dW kernel's producer waves build the
-    // A tiles of its x~^T.delta1 segment in LDS; otherwise the dense x~^T image (18 MB, scattered / un-scattered every step) is streamed
     const bool src_binary = s->c_indptr ? !s->c_values : (p->b.indptr && !p->b.values);
     const bool x3 = p->x3;
     const uint32_t T = x3 ? p->terms : 0u;                   // lo product terms that are multiplied (X3T_*)
@@ -647,9 +625,7 @@ static int train_step_body(dae_plan* p, const dae_step* s, void* stream) {
     // data-parallel gradient-only phases) take the N-segment dW GEMM to memory + the optimizer kernel that writes all four shadows
     const bool fuse_opt = fuse_opt0 && (!x3 || dw_x3_fits(Fp, Hp, Bp));
     // (split-bf16 mode: the gradient-only form of the same N-segment kernel, fp32 gradient to the flat buffer)
-    const bool dw_pc_grad = backward && !apply_now && dt == DAE_BF16 && p->fuse_opt_ok && (x3 ? dw_x3_fits(Fp, Hp, Bp) : dw_bits_fits(Fp, Hp, Bp));
-    const bool dw_bits = p->dw_bits_ok && use_sparse && src_binary && backward && dt == DAE_BF16 && (fuse_opt || dw_pc_grad) &&
-                           dw_bits_fits(Fp, Hp, Bp);
+    const bool dw_pc_grad = backward && !apply_now && dt == DAE_BF16 && p->fuse_opt_ok && (x3 ? dw_x3_fits(Fp, Hp, Bp) : dw_grad_fits(Fp, Hp, Bp));
     // contractions over the BATCH (dW's K, the Gs.h segment of dh) stop at the last 64-deep K tile that holds a real row: the images are zero beyond B, and
     // B = 800 pads to 896 = 14 K tiles of which 13 hold data
     const int Bk = (B + 63) / 64 * 64;
@@ -658,7 +634,7 @@ static int train_step_body(dae_plan* p, const dae_step* s, void* stream) {
     // (16-bit modes without lo images of x~ / delta2 / delta1 / h in dW: f16x2, bf16, f16); decided from plan state and shapes only, so that the
     // phase-4 / phase-5 halves of an externally mined step agree
     const bool dw_plain2 = !x3 || !(T & (X3T_DW_D1LO | X3T_DW_HLO | X3T_DW_D2LO | X3T_XV));
-    const bool dw_tr = (p->dw_tr_mode == 1 || (p->dw_tr_mode < 0 && dense_in)) && dt == DAE_BF16 && backward && (fuse_opt || dw_pc_grad) && dw_plain2 && !dw_bits && (use_sparse || dense_in) &&
+    const bool dw_tr = (p->dw_tr_mode == 1 || (p->dw_tr_mode < 0 && dense_in)) && dt == DAE_BF16 && backward && (fuse_opt || dw_pc_grad) && dw_plain2 && (use_sparse || dense_in) &&
                        (x3 || dw_pc_taken(Fp, Hp, Bk, Bk, !fuse_opt));
     if (x3) {
         // split-bf16 mode: CSR input encoded from the fp32 master weights (h is fp32-accurate and its hi / lo images come from the same
@@ -668,7 +644,6 @@ static int train_step_body(dae_plan* p, const dae_step* s, void* stream) {
         //  W-row bytes -- and the triplet leg of c2 leaves the gate at step 5 (1.5e-3): refused, not offered)
         DAE_CHECK_ARG((use_sparse && p->enc_w32_ok) || dense_in, "train_step: split-bf16 mode needs the fp32-master sparse encode (CSR input) or a dense train set");
         DAE_CHECK_ARG(!p->b.grad_lo, "train_step: split-bf16 mode exchanges fp32 gradients (no bf16 gradient image)");
-        DAE_CHECK_ARG(!dw_bits, "train_step: split-bf16 mode streams the dense x~^T image (option dw_bits off)");
     }
     // split-bf16 mode with VALUED input (tf-idf, salt-and-pepper copies, decay noise's scale factor): x~ = scale * v is not exact in bf16, so
     // x~^T and the clean rows x get lo images too (xct_2, x_2) and the dW contraction walks 6 segments; binary data with a bf16-exact scale
@@ -680,11 +655,10 @@ static int train_step_body(dae_plan* p, const dae_step* s, void* stream) {
     }
     const bool x2_clean = x3 && (T & X3T_XV) && !use_xbits && (p->b.values || p->b.dense);    // the clean rows get a lo image (valued CSR / dense train set)
     if (!resume && backward && csr_in) {
-        if (dw_bits) { if (!(tail && p->xtb_clean)) PROF(PS_MEMSET, memset_async(p->xtb, (size_t)Fp * (ldB / 32) * 4, st)); }
-        else if (!(tail && p->xct_clean)) PROF(PS_MEMSET, memset_async(p->xct, (size_t)Fp * ldB * p->es, st));
+        if (!(tail && p->xct_clean)) PROF(PS_MEMSET, memset_async(p->xct, (size_t)Fp * ldB * p->es, st));
         if (x3_vals && !(tail && p->xct2_clean)) PROF(PS_MEMSET, memset_async(p->xct_2, (size_t)Fp * ldB * 2, st));
     }
-    if (backward) { if (dw_bits) p->xtb_clean = false; else p->xct_clean = false; if (x3_vals) p->xct2_clean = false; }
+    if (backward) { p->xct_clean = false; if (x3_vals) p->xct2_clean = false; }
     const int64_t slab = (int64_t)Bp * Hp;
     int enc_label_done = 0;
     bool labels_done = ext_mine;               // label statistics already produced by a workgroup of an earlier launch (or by the caller)
@@ -713,9 +687,8 @@ static int train_step_body(dae_plan* p, const dae_step* s, void* stream) {
         q.corr_frac = s->corr_frac; q.scale = s->scale;
         q.h_f32 = p->h_f32; q.h_lo = p->h_lo; q.ldh = Hp; q.h_t = p->h_t; q.ldht = ldB;
         q.hcat_a = p->gram_split ? p->hcat_a : nullptr; q.hcat_b = p->gram_split ? p->hcat_b : nullptr;
-        q.x_bits = own_clean ? p->x_bits : nullptr; q.ldxb = Fp / 32; q.xct = (backward && !dw_bits) ? p->xct : nullptr; q.ldt = dw_tr ? Fp : ldB;
+        q.x_bits = own_clean ? p->x_bits : nullptr; q.ldxb = Fp / 32; q.xct = backward ? p->xct : nullptr; q.ldt = dw_tr ? Fp : ldB;
         q.xct_rm = dw_tr ? 1 : 0;
-        q.xtb = (backward && dw_bits) ? p->xtb : nullptr; q.ldxt = ldB / 32;
         q.rowsq = own_clean ? rowsq : nullptr;
         q.h_t2 = (T & (X3T_DH_HLO | X3T_DW_HLO)) ? p->h_t2 : nullptr;
         q.xct2 = (x3_vals && backward) ? p->xct_2 : nullptr;
@@ -771,12 +744,31 @@ static int train_step_body(dae_plan* p, const dae_step* s, void* stream) {
     } else if (!labels_done) {
         PROF(PS_LABEL, dae_label_stats(s->labels, B, Bp, c.triplet, p->n_same, p->acc, p->nvalid, p->dw_i64, p->cw, c.alpha, p->tri_scalars, stream));
     }
-    bool forked = false, sym_ride = false;
+    bool sym_ride = false;
     const bool fold_finalize = (c.triplet == DAE_TRIPLET_BATCH_ALL && !c.pos_triplets_only) && !ext_mine;
-    // 7. decode + reconstruction loss + d cost/d z2   (K3/K4) -- on stream `ds`; `ride`: the launch also scales G + G^T (sym_scale)
+    if (!ext_mine && (c.triplet == DAE_TRIPLET_BATCH_ALL || c.triplet == DAE_TRIPLET_BATCH_HARD)) {
+        const int64_t dslab = (int64_t)Bp * Bp;
+        // the label block of this step's encode launch also ranked the anchors by sweep cost (only then is the buffer current)
+        const int32_t* order = (labels_done && !ext_mine && p->miner_order_ok && c.triplet == DAE_TRIPLET_BATCH_ALL) ? p->miner_order : nullptr;
+        const int32_t* cls = (labels_done && !ext_mine && p->miner_ranges_ok && c.triplet == DAE_TRIPLET_BATCH_ALL) ? p->cls_range : nullptr;
+        PROF(PS_GRAM, launch_gram(p, Bp, Hp, dslab, st));
+        if (c.triplet == DAE_TRIPLET_BATCH_ALL)
+            PROF(PS_MINER, launch_batch_all(p->D_slabs, p->s_gram, dslab, Bp, s->labels, B, Bp, 0, B,
+                                     (c.pos_triplets_only ? DAE_MINER_POS_ONLY : 0) | (dt == DAE_BF16 ? DAE_MINER_FAST : 0), p->loss_part,
+                                     p->cnt_part, p->G, p->role_cnt, order, st, cls));
+        else
+            PROF(PS_MINER, dae_triplet_batch_hard(p->D_slabs, p->s_gram, dslab, Bp, s->labels, B, Bp, p->loss_part, p->cnt_part, p->dw_i32, p->G,
+                                      stream));
+        if (!fold_finalize)   // batch_all over all valid triplets: scale comes from label_stats, sums from step_stats
+            PROF(PS_TRI_FIN, dae_triplet_finalize(c.triplet, c.pos_triplets_only, B, Bp, c.alpha, p->loss_part, p->cnt_part, p->nvalid,
+                                    p->dw_i32, p->role_cnt, p->dw_f32, p->cw, p->tri_scalars, stream));
+        sym_ride = backward && p->sym_ride_ok;                   // the decode launch below carries it
+        if (backward && !sym_ride) PROF(PS_SYM, launch_sym_scale(p->G, B, Bp, p->tri_scalars, dt, p->Gs, osc, st));
+    }
+    // 7. decode + reconstruction loss + d cost/d z2   (K3/K4); `sym_ride`: the launch also scales G + G^T (sym_scale)
     const int dbn = plan_dec_bn(p);
     const int ncw = 2 * Fp / dbn;
-    auto decode_section = [&](hipStream_t ds, bool ride) -> int {
+    {
         DecodeEpi e;
         memset(&e, 0, sizeof(e));
         e.bv = p->b.bv; e.x = p->x; e.ldx = Fp; e.x_bits = use_xbits ? p->x_bits : nullptr; e.ldxb = Fp / 32; e.cw = p->cw; e.cos_stats = is_cos ? p->cos_stats : nullptr;
@@ -785,7 +777,7 @@ static int train_step_body(dae_plan* p, const dae_step* s, void* stream) {
         e.delta2 = backward ? p->delta2 : nullptr; e.ldd = Fp; e.delta2_t = (backward && !dw_tr) ? p->delta2_t : nullptr; e.lddt = ldB;
         e.B = B; e.F = F; e.Bp = Bp; e.Fp = Fp; e.dec_act = c.dec_act; e.loss_func = c.loss_func; e.ce_literal = p->ce_literal ? 1 : 0;
         e.op_scale = osc; e.bn = dbn;
-        if (ride) { e.sym_G = p->G; e.sym_scalars = p->tri_scalars; e.sym_Gs = p->Gs; e.sym_B = B; e.sym_Bp = Bp; }
+        if (sym_ride) { e.sym_G = p->G; e.sym_scalars = p->tri_scalars; e.sym_Gs = p->Gs; e.sym_B = B; e.sym_Bp = Bp; }
         // z2 = h W^T: one K segment, or -- split-bf16 -- (h_hi, W_hi) (h_hi, W_lo) (h_lo, W_hi); the row-major h_hi / h_lo are the first and
         // third block of the Gram operand hcat_a = [hi | hi | lo] (leading dimension 3 Hp)
         GemmSegDesc dsegs[3] = {{p->h_lo, Hp, p->b.W_lo, Hp, Hp}, {nullptr, 0, nullptr, 0, 0}, {nullptr, 0, nullptr, 0, 0}};
@@ -802,62 +794,16 @@ static int train_step_body(dae_plan* p, const dae_step* s, void* stream) {
             e.cos_pass = 1;
             const bool zs = backward && p->cos_zstore_ok && p->zbuf;
             if (zs) { e.z_io = p->zbuf; e.ldz = Fp; e.z_mode = 1; }
-            PROF(PS_DECODE, launch_decode_loss_n(dt, Bp, Fp, dsegs, ndseg, e, ds));
+            PROF(PS_DECODE, launch_decode_loss_n(dt, Bp, Fp, dsegs, ndseg, e, st));
             if (zs) e.z_mode = 2;
-            PROF(PS_COS_REDUCE, dae_cos_reduce(p->cos_part, ncw, B, Bp, p->cos_stats, p->rowloss_part, (void*)ds));
+            PROF(PS_COS_REDUCE, dae_cos_reduce(p->cos_part, ncw, B, Bp, p->cos_stats, p->rowloss_part, stream));
             e.sym_G = nullptr;                                 // the first pass carried the rider
-            if (backward) { e.cos_pass = 2; PROF(PS_DECODE, launch_decode_loss_n(dt, Bp, Fp, dsegs, ndseg, e, ds)); }
+            if (backward) { e.cos_pass = 2; PROF(PS_DECODE, launch_decode_loss_n(dt, Bp, Fp, dsegs, ndseg, e, st)); }
         } else {
             e.cos_pass = 0;
-            PROF(PS_DECODE, launch_decode_loss_n(dt, Bp, Fp, dsegs, ndseg, e, ds));
+            PROF(PS_DECODE, launch_decode_loss_n(dt, Bp, Fp, dsegs, ndseg, e, st));
         }
-        return 0;
-    };
-    if (!ext_mine && (c.triplet == DAE_TRIPLET_BATCH_ALL || c.triplet == DAE_TRIPLET_BATCH_HARD)) {
-        const int64_t dslab = (int64_t)Bp * Bp;
-        // the label block of this step's encode launch also ranked the anchors by sweep cost (only then is the buffer current)
-        const int32_t* order = (labels_done && !ext_mine && p->miner_order_ok && c.triplet == DAE_TRIPLET_BATCH_ALL) ? p->miner_order : nullptr;
-        const int32_t* cls = (labels_done && !ext_mine && p->miner_ranges_ok && c.triplet == DAE_TRIPLET_BATCH_ALL) ? p->cls_range : nullptr;
-        // batch_all (all valid triplets): cw comes from the labels alone -> the Gram -> miner chain (VALU work, the longer of the two) and
-        // the decode kernel (MFMA + loss epilogue) are independent until dL/dh.  Option "overlap": the decode forks onto the side stream,
-        // the chain stays on the step's stream and joins before the dh GEMM (never while profiling: the slot events are per stream)
-        const bool overlap = p->overlap_ok && !p->prof && c.triplet == DAE_TRIPLET_BATCH_ALL && !c.pos_triplets_only;
-        const bool gram_first = overlap && p->overlap_mode >= 2;
-        if (gram_first) PROF(PS_GRAM, launch_gram(p, Bp, Hp, dslab, st));
-        if (overlap) {
-            if (!p->side) {
-                DAE_CHECK_HIP(hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking));
-                DAE_CHECK_HIP(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
-                DAE_CHECK_HIP(hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming));
-            }
-            DAE_CHECK_HIP(hipEventRecord(p->ev_fork, st));
-            DAE_CHECK_HIP(hipStreamWaitEvent(p->side, p->ev_fork, 0));
-            if (p->overlap_mode != 3) {
-                RC(decode_section(p->side, false));
-                DAE_CHECK_HIP(hipEventRecord(p->ev_join, p->side));
-            }
-            forked = true;
-        }
-        if (!gram_first) PROF(PS_GRAM, launch_gram(p, Bp, Hp, dslab, st));
-        if (c.triplet == DAE_TRIPLET_BATCH_ALL)
-            PROF(PS_MINER, launch_batch_all(p->D_slabs, p->s_gram, dslab, Bp, s->labels, B, Bp, 0, B,
-                                     (c.pos_triplets_only ? DAE_MINER_POS_ONLY : 0) | (dt == DAE_BF16 ? DAE_MINER_FAST : 0), p->loss_part,
-                                     p->cnt_part, p->G, p->role_cnt, order, st, cls));
-        else
-            PROF(PS_MINER, dae_triplet_batch_hard(p->D_slabs, p->s_gram, dslab, Bp, s->labels, B, Bp, p->loss_part, p->cnt_part, p->dw_i32, p->G,
-                                      stream));
-        if (overlap && p->overlap_mode == 3) {                // the miner's workgroups are queued first, the decode's fill in beside / behind them
-            RC(decode_section(p->side, false));
-            DAE_CHECK_HIP(hipEventRecord(p->ev_join, p->side));
-        }
-        if (!fold_finalize)   // batch_all over all valid triplets: scale comes from label_stats, sums from step_stats
-            PROF(PS_TRI_FIN, dae_triplet_finalize(c.triplet, c.pos_triplets_only, B, Bp, c.alpha, p->loss_part, p->cnt_part, p->nvalid,
-                                    p->dw_i32, p->role_cnt, p->dw_f32, p->cw, p->tri_scalars, stream));
-        sym_ride = backward && p->sym_ride_ok && !forked;        // the decode launch below carries it
-        if (backward && !sym_ride) PROF(PS_SYM, launch_sym_scale(p->G, B, Bp, p->tri_scalars, dt, p->Gs, osc, st));
     }
-    if (forked) DAE_CHECK_HIP(hipStreamWaitEvent(st, p->ev_join, 0));   // join: delta2 and the loss partials are ready
-    else RC(decode_section(st, sym_ride));
     // 8. statistics of this step (autoencoder.py:233 fetch list)
     StatsArgs sa{is_cos ? p->rowloss_part : nullptr, 1, is_cos ? nullptr : p->tile_part, (Bp / 128) * (Fp / dbn), p->cw, B, Bp,
                  c.triplet == 3 ? DAE_TRIPLET_BATCH_HARD : c.triplet, c.alpha, p->tri_scalars,
@@ -907,11 +853,8 @@ static int train_step_body(dae_plan* p, const dae_step* s, void* stream) {
         if (x3) {   // x~^T.(d1_hi + d1_lo) + (d2^T_hi, h^T_hi) (d2^T_hi, h^T_lo) (d2^T_lo, h^T_hi); the epilogue writes both parts of both shadows
             oe.W_lo2 = (T & X3T_DEC_WLO) ? p->W_lo2 : nullptr; oe.Wt_lo2 = p->Wt_lo2;     // W_lo2 feeds the decode's (h_hi, W_lo) term only
             PROF(PS_DW_GEMM, launch_dw_opt_n(Fp, Hp, ws3, 6, oe, st, p->dw_pair_ok, dw_tr));
-        } else if (dw_bits) {
-            DwBitsArgs xa{p->xtb, ldB / 32, s->scale};
-            PROF(PS_DW_GEMM, launch_dw_opt(Fp, Hp, nullptr, ldB, p->delta1_t, ldB, Bk, p->delta2_t, ldB, p->h_t, ldB, Bk, oe, st, &xa));
         } else {
-            PROF(PS_DW_GEMM, launch_dw_opt(Fp, Hp, a_x, lda_w, p->delta1_t, ldB, Bk, a_d2, lda_w, p->h_t, ldB, Bk, oe, st, nullptr, dw_tr));
+            PROF(PS_DW_GEMM, launch_dw_opt(Fp, Hp, a_x, lda_w, p->delta1_t, ldB, Bk, a_d2, lda_w, p->h_t, ldB, Bk, oe, st, dw_tr));
         }
     } else if (x3) {
         PROF(PS_DW_GEMM, launch_gemm_f32out_n(dt, Fp, Hp, ws3, 6, p->b.grad, Hp, 1, 0, st, GEMM_ROLE_DW, nullptr, nullptr, oinv));
@@ -932,10 +875,10 @@ static int train_step_body(dae_plan* p, const dae_step* s, void* stream) {
                     fuse_bias ? 1 : 0, c.opt, plan_lr(p, s->adam_t), c.momentum, s->grad_scale, p->b.bv,
                     p->b.opt_s1 ? p->b.opt_s1 + boff : nullptr, p->b.opt_s2 ? p->b.opt_s2 + boff : nullptr};
         ClearArgs ca{s->c_indptr ? s->c_indptr : p->b.indptr, s->c_indptr ? s->c_indices : p->b.indices,
-                     (s->c_indptr && s->c_row_idx) ? s->c_row_idx : s->row_idx, B, F, dw_bits ? nullptr : p->xct, dw_tr ? (int64_t)Fp : (int64_t)ldB, p->es,
-                     dw_bits ? p->xtb : nullptr, ldB / 32, x3_vals ? p->xct_2 : nullptr, dw_tr ? 1 : 0};
+                     (s->c_indptr && s->c_row_idx) ? s->c_row_idx : s->row_idx, B, F, p->xct, dw_tr ? (int64_t)Fp : (int64_t)ldB, p->es,
+                     x3_vals ? p->xct_2 : nullptr, dw_tr ? 1 : 0};
         PROF(PS_BIAS, launch_step_tail(ba, &sa, csr_in ? &ca : nullptr, st));
-        if (csr_in) { if (dw_bits) p->xtb_clean = true; else p->xct_clean = true; if (x3_vals) p->xct2_clean = true; }
+        if (csr_in) { p->xct_clean = true; if (x3_vals) p->xct2_clean = true; }
     } else {
         PROF(PS_BIAS, dae_bias_grads(p->dbv_part, 2 * Bp / 128, p->colsum_part, Bp / 32, p->b.bh, H, Hp, F, Fp, c.enc_act, g_bh, g_bh + Hp,
                                      fuse_bias ? 1 : 0, c.opt, plan_lr(p, s->adam_t), c.momentum, s->grad_scale, p->b.bv,

@@ -107,13 +107,6 @@ __device__ __forceinline__ float sat16(float v) {
     if constexpr (kF16) return __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f);
     return v;
 }
-// host side: the 16-bit image of a finite float (round to nearest even) -- operands the launchers build themselves (the value of a kept entry)
-static inline uint32_t host_f2bf(float f) {
-    if (kF16) { const _Float16 h = static_cast<_Float16>(f); uint16_t b; memcpy(&b, &h, 2); return b; }
-    uint32_t u; memcpy(&u, &f, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
 
 template <typename T> struct Elem;
 template <> struct Elem<float> {

@@ -298,8 +298,6 @@ struct EncCsrArgs {
     void* xct; int64_t ldt;                     // x~^T [Fp x ldt] scatter target (pre-zeroed) or NULL
     void* xct2;                                 // split-bf16 mode, x~ not exact in bf16: lo image of x~^T (same layout, pre-zeroed) or NULL
     int xct_rm;                                 // 1: xct / xct2 are row-major x~ [Bp x ldt] (entry (i, col) at i * ldt + col)
-    uint32_t* xtb; int64_t ldxt;                // x~^T as a BIT image [Fp x ldxt words] (pre-zeroed; bit i of row f <=> entry (i, f) kept) or NULL
-    int xtl_off, Fp;                            // xtl_off > 0: LDS byte image [Fp] of the workgroup's 8 batch rows at that offset (else global atomics)
     float* rowsq;                               // [Bp] or NULL
     int n_slices;
     LabelJob job; int label_block;
@@ -375,15 +373,12 @@ __global__ __launch_bounds__(ENC_THREADS, 4) void encode_csr_kernel(EncCsrArgs a
     const int sub = lane >> 4, part = lane & 15;                         // 4 entries per load instruction, 16 lanes per W-row slice
     // side images: task t is produced by the workgroups of slice t % n_slices
     const bool do_xbits = a.x_bits && slice == 0;
-    const bool do_xct = (a.xct || a.xtb) && slice == 1 % a.n_slices;
+    const bool do_xct = a.xct && slice == 1 % a.n_slices;
     const bool do_rowsq = a.rowsq && slice == 2 % a.n_slices;
-    // x~^T bits of this workgroup's 8 batch rows (i0 is a multiple of 8): ONE byte per feature, assembled in LDS (bit r of byte f =
-    // row i0 + r keeps feature f) and stored as bytes -- the workgroup owns byte i0 / 8 of every feature row, so no global atomics
-    uint32_t* xtl = reinterpret_cast<uint32_t*>(smem + a.xtl_off);
-    const bool xt_lds = do_xct && a.xtb && a.xtl_off > 0;
-    if (do_xbits) for (int k = tid; k < ENC_ROWS * (int)a.ldxb; k += ENC_THREADS) xb[k] = 0u;
-    if (xt_lds) for (int k = tid; k < a.Fp / 4; k += ENC_THREADS) xtl[k] = 0u;
-    if (do_xbits || xt_lds) __syncthreads();
+    if (do_xbits) {
+        for (int k = tid; k < ENC_ROWS * (int)a.ldxb; k += ENC_THREADS) xb[k] = 0u;
+        __syncthreads();
+    }
     const char* Wb = reinterpret_cast<const char*>(a.W) + (int64_t)slice * COLS * sizeof(WT) + part * (CPL * sizeof(WT));
     const uint64_t ldw_b = (uint64_t)(a.ldw * (int64_t)sizeof(WT));
     T* xct = reinterpret_cast<T*>(a.xct);
@@ -436,15 +431,10 @@ __global__ __launch_bounds__(ENC_THREADS, 4) void encode_csr_kernel(EncCsrArgs a
                 const float v = valid ? vv[u] : 0.f;
                 const float w = keep ? v * a.scale : 0.f;
                 if (do_xbits && valid) atomicOr(&xb[r * a.ldxb + (col[u] >> 5)], 1u << (col[u] & 31));
-                if (do_xct && keep) {
-                    // x~^T for the dW GEMM: a bit per kept entry (binary data; integer OR -> order-independent), or the dense scatter
-                    if (xt_lds) atomicOr(&xtl[col[u] >> 2], 1u << (8 * (col[u] & 3) + r));
-                    else if (a.xtb) atomicOr(&a.xtb[(int64_t)col[u] * a.ldxt + (i >> 5)], 1u << (i & 31));
-                    else {
-                        const int64_t o = a.xct_rm ? (int64_t)i * a.ldt + col[u] : (int64_t)col[u] * a.ldt + i;
-                        xct[o] = Elem<T>::from(w);
-                        if (a.xct2) reinterpret_cast<T*>(a.xct2)[o] = elem_residual<T>(w);
-                    }
+                if (do_xct && keep) {                    // x~^T for the dW GEMM
+                    const int64_t o = a.xct_rm ? (int64_t)i * a.ldt + col[u] : (int64_t)col[u] * a.ldt + i;
+                    xct[o] = Elem<T>::from(w);
+                    if (a.xct2) reinterpret_cast<T*>(a.xct2)[o] = elem_residual<T>(w);
                 }
                 if (do_rowsq) sq += v * v;
                 const bool kp = w != 0.f;
@@ -561,18 +551,6 @@ __global__ __launch_bounds__(ENC_THREADS, 4) void encode_csr_kernel(EncCsrArgs a
             a.x_bits[(int64_t)(i0 + rr) * a.ldxb + w] = xb[k];
         }
     }
-    if (xt_lds) {                                    // (the barriers above ordered every LDS atomic before these reads)
-        uint8_t* xt8 = reinterpret_cast<uint8_t*>(a.xtb) + (i0 >> 3);
-        const int64_t ld8 = a.ldxt * 4;
-        for (int k = tid; k < a.Fp / 4; k += ENC_THREADS) {
-            uint32_t w = xtl[k];
-            while (w) {
-                const int q = __builtin_ctz(w) >> 3;
-                xt8[(int64_t)(4 * k + q) * ld8] = (uint8_t)(w >> (8 * q));
-                w &= ~(0xffu << (8 * q));
-            }
-        }
-    }
 }
 
 __global__ void rowsq_reduce_kernel(const float* __restrict__ part, int nparts, int Bp, float* __restrict__ rowsq) {
@@ -641,7 +619,6 @@ int dae::launch_encode_csr(const EncCsrLaunch& q, hipStream_t st) {
     DAE_CHECK_ARG(q.ldw >= Hp && q.ldh >= Hp && (!q.h_t || q.ldht >= Bp), "encode_csr: leading dimensions too small");
     DAE_CHECK_ARG(!q.x_bits || (!q.values && q.ldxb >= dae_pad(q.F) / 32), "encode_csr: the bit image of x needs binary data and ldxb >= Fp/32");
     DAE_CHECK_ARG(!q.xct || q.ldt >= (q.xct_rm ? (int)dae_pad(q.F) : Bp), "encode_csr: ldt too small");
-    DAE_CHECK_ARG(!q.xtb || (!q.values && q.ldxt >= Bp / 32 && !q.xct), "encode_csr: the bit image of x~^T needs binary data, ldxt >= Bp/32 and no dense x~^T");
     DAE_CHECK_ARG(!q.label_job || q.label_job->Bp <= 1024, "encode_csr: in-kernel label statistics need a padded batch <= 1024");
     DAE_CHECK_ARG((q.hcat_a == nullptr) == (q.hcat_b == nullptr), "encode_csr: hcat_a/hcat_b must be given together");
     EncCsrArgs a;
@@ -651,7 +628,7 @@ int dae::launch_encode_csr(const EncCsrLaunch& q, hipStream_t st) {
     a.corr_mode = q.corr_mode; a.keep_bits = q.keep_bits; a.seed = q.seed; a.stream = q.rng_stream; a.corr_frac = q.corr_frac; a.scale = q.scale;
     a.enc_act = q.enc_act; a.h_f32 = q.h_f32; a.h_lo = q.h_lo; a.ldh = q.ldh; a.h_t = q.h_t; a.ldht = q.ldht; a.h_t2 = q.h_t2;
     a.hcat_a = (bf16_t*)q.hcat_a; a.hcat_b = (bf16_t*)q.hcat_b; a.x_bits = q.x_bits; a.ldxb = q.ldxb; a.xct = q.xct; a.ldt = q.ldt;
-    a.xtb = q.xtb; a.ldxt = q.ldxt; a.xct2 = q.xct2; a.xct_rm = q.xct_rm;
+    a.xct2 = q.xct2; a.xct_rm = q.xct_rm;
     DAE_CHECK_ARG(!q.xct2 || (q.xct && q.dtype == DAE_BF16), "encode_csr: the lo image of x~^T needs the dense x~^T and bf16");
     const int cols = enc_cols(q.dtype, q.w_f32, q.w32_cols);
     a.rowsq = q.rowsq; a.n_slices = Hp / cols;
@@ -659,8 +636,6 @@ int dae::launch_encode_csr(const EncCsrLaunch& q, hipStream_t st) {
     a.label_block = q.label_job ? nblk : -1;
     if (q.label_job) a.job = *q.label_job;
     size_t lds = encode_csr_lds_bytes(q.dtype, q.w_f32, q.w32_cols, q.x_bits ? q.ldxb : 0);
-    a.Fp = (int)dae_pad(q.F);
-    if (q.xtb && lds + (size_t)a.Fp <= 64 * 1024) { a.xtl_off = (int)lds; lds += (size_t)a.Fp; }     // else: global atomics
     if (q.label_job && lds < (size_t)LABEL_SMEM_BYTES) lds = LABEL_SMEM_BYTES;
     DAE_CHECK_ARG(lds <= 64 * 1024, "encode_csr: %zu B of LDS for the bit rows of %d features (route the clean rows through dae_gather_csr)", lds, q.F);
     dim3 grid(nblk + (q.label_job ? 1 : 0)), block(ENC_THREADS);

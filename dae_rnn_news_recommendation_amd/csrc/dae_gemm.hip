@@ -760,15 +760,6 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_nt_pc(GemmParams p, float*
 // one k step ahead (48 VGPRs) so that the master weights of the tile can stay prefetched in registers (80 VGPRs, SGD).
 // The last row tile is partial (10112 = 63 x 160 + 32): its out-of-range rows load row Fp-1 and are never stored.
 //
-// XBITS (binary CSR input): x~^T never exists as an 18 MB image that is mostly zeros.  It arrives as a BIT image (bit i of row f
-// <=> entry (i, f) of the batch was kept; written by the encode launch, 1.1 MB) and the A tiles of the x~^T . delta1 segment
-// are BUILT in LDS by the producer waves (zero fill + one 2-byte store per set bit, or an arithmetic expansion when a word is
-// dense -- the popular features of a Zipf vocabulary are kept in most rows, so their rows are NOT sparse), exactly as
-// gemm_encode_bits_pc builds x~.  Only delta1^T is streamed for that segment: 187 MB through the LDS-DMA path per launch instead
-// of 258 MB, and an XCD's share of the operands (3.2 MB) fits its 4 MiB L2.  Same MFMA products and accumulation order as the
-// dense image -> bit-identical gradients.  (A sum over the kept entries instead -- "sparse x~^T.delta1" -- was built and
-// measured first: 0.11 GFLOP, but half of the entries sit in 3 % of the feature rows and one tile took 120 us;
-// profiles/r03_experiments.md.)
 // OPT == DW_GRAD_ONLY: no optimizer, the gradient tile goes to memory (fp32 `grad` and / or bf16 `grad_lo`): the data-parallel step.
 // ------------------------------------------------------------------------------------------------
 constexpr int DW_BM = 160, DW_MB = DW_BM / 32;                         // rows per tile, MFMA row blocks per consumer wave
@@ -780,21 +771,14 @@ constexpr int DW_P1 = DW_BM * 2 + 16;                                  // staged
 constexpr int DW_RING = DW_NST * DW_STAGE;                             // 144 KiB (the epilogue tiles, 86 KiB, reuse it)
 constexpr int DW_GRAD_ONLY = DW_OPT_GRAD_ONLY;                         // OPT value: gradient to memory, no update
 constexpr int DW_LDS = DW_RING;
-constexpr int DWB_MAXKT = 16;                                          // XBITS: K tiles of the x~^T segment (Bp <= 1024)
 // PAIR (split-bf16 mode): a stage holds ONE A tile and TWO B tiles (A . [B_hi ; B_lo]: the hi and lo images of delta1^T resp. h^T share the
 // x~^T resp. delta2^T_hi tile), so the pair costs one A stream, 7 fragment reads per 10 MFMAs instead of 12, and one barrier instead of two
 constexpr int DW_STAGE2 = DW_A_BYTES + 2 * TILE_BYTES;                 // 52 KiB
 constexpr int DW_NST2 = 3;
 constexpr int DW_RING2 = DW_NST2 * DW_STAGE2;                          // 156 KiB
 
-struct DwBits {
-    const uint32_t* xtb; int64_t ldxt;       // x~^T bit image [Mrows x ldxt words]
-    int nwords;                              // Bp / 32
-    uint32_t one;                            // bf16 bits of the value of a kept entry (the corruption's scale factor; 1.0 for masking noise)
-};
-
-__device__ __forceinline__ void wait_vm_n(int n) {   // counted vmcnt wait for the op counts a mixed (4 / 9 pieces per stage) ring can leave in flight
-    switch (n) {
+__device__ __forceinline__ void wait_vm_n(int n) {   // counted vmcnt wait for the op counts the ring can leave in flight (9 or 13 pieces per stage;
+    switch (n) {                                      // 4, 8, 12 and 17 are counts of a former 4-piece stage, kept so that the compiled waits stay as measured)
         case 0: wait_vm<0>(); break;
         case 4: wait_vm<4>(); break;
         case 8: wait_vm<8>(); break;
@@ -825,11 +809,11 @@ template <int OFF> __device__ __forceinline__ i32x2 lds_read_tr16_b64(uint32_t a
 constexpr int DW_TR_PITCH = DW_BM * 2;                                  // bytes per k row of the [k][m] A image
 static_assert(64 * DW_TR_PITCH == DW_A_BYTES, "the [k][m] image of a K tile fills the A tile exactly");
 
-template <int OPT, bool XBITS, bool X3 = false, bool PAIR = false, bool TRA = false>      // X3 (split-bf16 mode): the lo images of both shadows are written too (e.W_lo2 / e.Wt_lo2)
-__global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi e, int Mrows, DwBits xb) {
+template <int OPT, bool X3 = false, bool PAIR = false, bool TRA = false>      // X3 (split-bf16 mode): the lo images of both shadows are written too (e.W_lo2 / e.Wt_lo2)
+__global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi e, int Mrows) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    static_assert(!PAIR || (X3 && !XBITS), "paired stages exist for the split-bf16 contraction on dense operand images");
-    static_assert(!TRA || (!PAIR && !XBITS), "the transposed-A form streams plain K segments of dense row-major images");
+    static_assert(!PAIR || X3, "paired stages exist for the split-bf16 contraction");
+    static_assert(!TRA || !PAIR, "the transposed-A form streams plain K segments of dense row-major images");
     constexpr int STG = PAIR ? DW_STAGE2 : DW_STAGE;                        // bytes per ring stage
     constexpr int NSTG = PAIR ? DW_NST2 : DW_NST;                           // ring depth
     // PAIR: does K tile t belong to a segment with a second B operand?  (uniform; a walk over <= 6 segments)
@@ -866,7 +850,6 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
 #else
     const int nk = p.ktiles_total;
 #endif
-    const int nk0 = p.seg[0].ktiles;                                        // XBITS: K tiles whose A operand is built from the bit image
     const int row0_m = tm * DW_BM, row0_n = tn * BN;
     constexpr bool UPDATE = OPT != DW_GRAD_ONLY;
 #ifdef DAE_DW_PROBE
@@ -899,31 +882,8 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
     }
 
     if (wave8 >= 4) {
-        // ================= producer: per K tile 5 A pieces (DMA, or built from bits) + 4 B pieces =================
+        // ================= producer: per K tile 5 A pieces + 4 B pieces (PAIR: + 4 of the second B tile) =================
         const int wave = wave8 - 4;
-        // XBITS: this wave builds tile rows [40 wave, +40): item 0 of a lane = (row 40 wave + (lane >> 1), 32-column half lane & 1),
-        // item 1 (lanes 0..15) = (row 40 wave + 32 + (lane >> 1), half).  The lane's bit words of EVERY K tile of the segment are
-        // loaded here, once, into registers that rotate by one per built stage (no run-time register index, and no ordinary
-        // load inside the LDS-DMA loop -- hipcc would drain the DMA queue at its use)
-        uint32_t bw0[DWB_MAXKT], bw1[DWB_MAXKT];
-        const int half = lane & 1;
-        const int lrow_a = wave * 40 + (lane >> 1), lrow_b = wave * 40 + 32 + (lane >> 1);
-        if constexpr (XBITS) {
-            const bool ok_a = row0_m + lrow_a < Mrows, ok_b = lane < 16 && row0_m + lrow_b < Mrows;
-            const uint32_t* pa = xb.xtb + (int64_t)min(row0_m + lrow_a, Mrows - 1) * xb.ldxt;
-            const uint32_t* pb = xb.xtb + (int64_t)min(row0_m + lrow_b, Mrows - 1) * xb.ldxt;
-#pragma unroll
-            for (int t = 0; t < DWB_MAXKT; ++t) {
-                const int wi = min(2 * t + half, xb.nwords - 1);
-                bw0[t] = pa[wi]; bw1[t] = pb[wi];
-            }
-#pragma unroll
-            for (int t = 0; t < DWB_MAXKT; ++t) {
-                const bool in = 2 * t + half < xb.nwords;
-                bw0[t] = (in && ok_a) ? bw0[t] : 0u;
-                bw1[t] = (in && ok_b) ? bw1[t] : 0u;
-            }
-        }
         uint32_t voA[5], voB[4];
         const char *gA = nullptr, *gB = nullptr, *gB2 = nullptr;
         int64_t a_adv = BKB;                                                 // bytes the A stream advances per K tile (TRA: 64 batch rows)
@@ -954,53 +914,14 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
             gB = p.seg[sg].Bt + (int64_t)k * BKB;
         };
         seg_setup(0);
-        // one (row, half) item of the A tile of the stage in `slot`: 32 consecutive k of tile row `lrow` from one bit word
-        auto build_item = [&](char* slot, int lrow, uint32_t word, bool dense) {
-            const uint32_t swz = (uint32_t)((lrow >> 1) & 7);
-            if (dense) {                                   // arithmetic expansion: 8 bits -> 8 bf16 (0 / one) per 16-byte slot
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    i32x4 v;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const uint32_t b2 = (word >> (8 * j + 2 * q)) & 3u;
-                        v[q] = (int)(((b2 & 1u) * xb.one) | ((b2 >> 1) * (xb.one << 16)));
-                    }
-                    *reinterpret_cast<i32x4*>(slot + lrow * BKB + (((uint32_t)(half * 4 + j) ^ swz) << 4)) = v;
-                }
-            } else {
-                while (word) {                             // one 2-byte store per set bit (in-order LDS: lands after the zero fill)
-                    const int bb = __builtin_ctz(word);
-                    word &= word - 1;
-                    const uint32_t k = (uint32_t)(half * 32 + bb);
-                    *reinterpret_cast<bf16_t*>(slot + lrow * BKB + (((k >> 3) ^ swz) << 4) + (k & 7) * 2) = (bf16_t)xb.one;
-                }
-            }
-        };
-        auto build_a = [&](char* slot) {                   // consumes bw0[0] / bw1[0] and rotates the registers
-            const uint32_t w0 = bw0[0], w1 = bw1[0];
-#pragma unroll
-            for (int t = 0; t + 1 < DWB_MAXKT; ++t) { bw0[t] = bw0[t + 1]; bw1[t] = bw1[t + 1]; }
-            const bool dense = __builtin_amdgcn_ballot_w64(__builtin_popcount(w0) > 6 || __builtin_popcount(w1) > 6) != 0ull;
-            if (!dense) {                                  // zero this wave's 40 rows (5 KiB): 5 x ds_write_b128 per lane
-                const i32x4 z = {0, 0, 0, 0};
-#pragma unroll
-                for (int i = 0; i < 5; ++i) *reinterpret_cast<i32x4*>(slot + wave * 40 * BKB + i * 1024 + lane * 16) = z;
-            }
-            build_item(slot, lrow_a, w0, dense);
-            if (lane < 16) build_item(slot, lrow_b, w1, dense);
-        };
-        auto dma_stage = [&](char* slot) {                 // returns nothing; issues 9 (dense A) or 4 (built A) pieces
-            const bool built = XBITS && kt_dma < nk0;
+        auto dma_stage = [&](char* slot) {                 // issues 9 pieces (13 with a second B tile)
 #if defined(DAE_DW_PROBE) && (DAE_DW_PROBE & 16)
             if (true) { ++kt_dma; return; }                // probe: no operand stream (the consumers multiply whatever the ring holds)
 #endif
-            if (!built) {
 #pragma unroll
-                for (int i = 0; i < 5; ++i)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gA + voA[i]),
-                                                     (__attribute__((address_space(3))) void*)(slot + (i * 4 + wave) * 1024), 16, 0, 0);
-            }
+            for (int i = 0; i < 5; ++i)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gA + voA[i]),
+                                                 (__attribute__((address_space(3))) void*)(slot + (i * 4 + wave) * 1024), 16, 0, 0);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gB + voB[i]),
@@ -1013,17 +934,16 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
                                                          (__attribute__((address_space(3))) void*)(slot + DW_A_BYTES + TILE_BYTES + (i * 4 + wave) * 1024), 16, 0, 0);
                 }
             }
-            if (built) build_a(slot);
             ++kt_dma;
             if (kt_dma == seg_end) { if (kt_dma < p.ktiles_total) seg_setup(kt_dma); }
             else { gA += a_adv; gB += BKB; if constexpr (PAIR) { if (gB2) gB2 += BKB; } }
         };
-        auto ops = [&](int st) { return st >= nk ? 0 : ((XBITS && st < nk0) ? 4 : (pair_of(st) ? 13 : 9)); };   // LDS-DMA pieces of stage st (per wave)
+        auto ops = [&](int st) { return st >= nk ? 0 : (pair_of(st) ? 13 : 9); };   // LDS-DMA pieces of stage st (per wave)
 #pragma unroll
         for (int st = 0; st < NSTG; ++st)
             if (st < nk) dma_stage(lds + st * STG);
         wait_vm_n(ops(1) + ops(2) + (PAIR ? 0 : ops(3)));                   // stage 0 landed (older plain loads return first)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                  // ... and every A tile built so far is written
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         int cur = 0;
         for (int i = 0; i < nk; ++i) {
@@ -1706,92 +1626,6 @@ int launch_gram64(const void* hcat_a, const void* hcat_b, int Bp, int Hp, float*
     return 0;
 }
 
-// Paired form of the same loop for the split modes' two W terms, z2 = h.W_hi^T + h.W_lo^T: both K segments multiply the SAME A tile (h), so a stage
-// holds ONE A tile and the B tiles of BOTH segments (16 + 8 + 8 KiB).  Per K tile pair a wave then issues 8 LDS-DMA pieces and 16 fragment reads for its
-// 16 MFMAs instead of 12 and 24 -- the decode's K loop is bound by exactly those two (LDS bandwidth and LDS-DMA issue) -- at one barrier pair
-// instead of two.  64 KiB of LDS per workgroup: two workgroups per CU instead of three.  The accumulation order differs from the unpaired walk
-// ((hi, lo) interleaved per K tile instead of all hi then all lo): same products, fp32 sums in another order.
-template <typename T>
-__device__ __forceinline__ void mainloop_n64_pair(const GemmParams& p, int tm, int tn, char* lds, f32x16 (&acc)[2][1]) {
-    constexpr int BT = 64 * BKB;                       // one B tile: 8 KiB
-    constexpr int STAGE = TILE_BYTES + 2 * BT;         // 32 KiB
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int row0_m = tm * BM, row0_n = tn * 64;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][0][r] = 0.f;
-    const int nk = p.seg[0].ktiles;                    // both segments: the same K extent (checked by the launcher)
-    if (nk <= 0) return;
-    uint32_t voA[4], voB[2];
-    const uint32_t lda = (uint32_t)p.seg[0].lda_b, ldb = (uint32_t)p.seg[0].ldb_b;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = (i * 4 + wave) * 8 + (lane >> 3);
-        voA[i] = (uint32_t)(row0_m + row) * lda + (uint32_t)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = (i * 4 + wave) * 8 + (lane >> 3);
-        voB[i] = (uint32_t)(row0_n + row) * ldb + (uint32_t)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
-    }
-    const char *gA = p.seg[0].A, *gB0 = p.seg[0].Bt, *gB1 = p.seg[1].Bt;
-    auto dma_stage = [&](char* slot) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gA + voA[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + (i * 4 + wave) * 1024), 16, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gB0 + voB[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + TILE_BYTES + (i * 4 + wave) * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gB1 + voB[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + TILE_BYTES + BT + (i * 4 + wave) * 1024), 16, 0, 0);
-        }
-        gA += BKB; gB0 += BKB; gB1 += BKB;
-    };
-    const int r = lane & 31, g = lane >> 5;
-    const int swz = (r >> 1) & 7;
-    const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-    const uint32_t offa = (wm * 64 + r) * BKB, offb = TILE_BYTES + (wn * 32 + r) * BKB;
-    uint32_t so[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) so[kk] = (uint32_t)(((kk * 2 + g) ^ swz) << 4);
-    dma_stage(lds);
-    for (int i = 0; i < nk; ++i) {
-        if (i + 1 < nk) { dma_stage(lds + ((i + 1) & 1) * STAGE); wait_vm<8>(); }
-        else wait_vm<0>();
-        __builtin_amdgcn_s_barrier();                  // stage i landed for every wave
-        asm volatile("" ::: "memory");
-        const uint32_t sb = lbase + (i & 1) * STAGE;
-        i32x4 fa[4][2], fb0[4], fb1[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            fa[kk][0] = lds_read_b128(sb + offa + so[kk]);
-            fa[kk][1] = lds_read_b128_off4096(sb + offa + so[kk]);
-            fb0[kk] = lds_read_b128(sb + offb + so[kk]);
-            fb1[kk] = lds_read_b128(sb + offb + BT + so[kk]);
-        }
-#define DAE_N64P_GROUP(KK, CNT)                                  \
-    asm volatile("s_waitcnt lgkmcnt(" #CNT ")" ::: "memory");    \
-    __builtin_amdgcn_sched_barrier(0);                           \
-    Mma<T>::run(fa[KK][0], fb0[KK], acc[0][0]);                  \
-    Mma<T>::run(fa[KK][1], fb0[KK], acc[1][0]);                  \
-    Mma<T>::run(fa[KK][0], fb1[KK], acc[0][0]);                  \
-    Mma<T>::run(fa[KK][1], fb1[KK], acc[1][0]);
-        DAE_N64P_GROUP(0, 12)
-        DAE_N64P_GROUP(1, 8)
-        DAE_N64P_GROUP(2, 4)
-        DAE_N64P_GROUP(3, 0)
-#undef DAE_N64P_GROUP
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();                  // every wave has read slot i & 1: iteration i+1 may refill it
-        asm volatile("" ::: "memory");
-    }
-}
-
 // Three-term form for the split modes that keep h AND W as hi + lo (f16x2h: z2 = h_hi.W_hi^T + h_hi.W_lo^T + h_lo.W_hi^T).  The plain walk streams three K
 // segments -- 3 stages per K tile, every h_hi and every W_hi tile fetched and read twice.  Here the stages alternate (h_hi, W_hi)[k] -> (h_lo, W_lo)[k]
 // and the hi stage's fragments STAY IN REGISTERS (48 VGPRs: the kernel has the room at three workgroups per CU) over the lo stage, which multiplies
@@ -1906,8 +1740,8 @@ __device__ __forceinline__ void mainloop_n64_x3(const GemmParams& p, int tm, int
 
 // Two-term form (the split modes that keep only W as hi + lo in the decode -- f16x2d, f16x2: z2 = h.W_hi^T + h.W_lo^T) with the same register carry: the hi
 // stage holds (h, W_hi)[k], the lo stage ONLY the 8 KiB W_lo[k] tile, multiplied with the h fragments still in registers (32 VGPRs).  Per K tile and wave
-// 8 LDS-DMA pieces and 16 fragment reads for the 16 MFMAs instead of 12 and 24 -- what mainloop_n64_pair buys, without its 64 KiB of LDS (three
-// workgroups per CU stay).  Same products as the two-segment walk, (hi, lo) interleaved per K tile.
+// 8 LDS-DMA pieces and 16 fragment reads for the 16 MFMAs instead of 12 and 24, at the unchanged 48 KiB of LDS (three workgroups per CU stay).  Same
+// products as the two-segment walk, (hi, lo) interleaved per K tile.
 template <typename T>
 __device__ __forceinline__ void mainloop_n64_c2(const GemmParams& p, int tm, int tn, char* lds, f32x16 (&acc)[2][1]) {
     constexpr int STAGE = DecGeo<64>::STAGE;
@@ -2012,11 +1846,10 @@ __device__ __forceinline__ void mainloop_n64_c2(const GemmParams& p, int tm, int
 
 constexpr float CE_FAST_ZMAX = 14.0f;               // sigmoid(14) = 1 - 8.3e-7: five fp32 ulps from saturation
 constexpr int DECODE_NST = 2;
-template <typename T, int LOSS, int ACT, bool XBITS = false, int BN_T = 128, bool RES = false, bool PAIRD = false, bool X3 = false, bool C2 = false>   // RES (split-bf16 mode): also the lo images of delta2 / delta2^T; PAIRD: mainloop_n64_pair; X3: mainloop_n64_x3; C2: mainloop_n64_c2
-__global__ __launch_bounds__(GEMM_THREADS, PAIRD ? 2 : DecGeo<BN_T>::WG_PER_CU) void gemm_decode_loss(GemmParams p, DecodeEpi e) {
-    static_assert(!PAIRD || (BN_T == 64 && sizeof(T) == 2 && !RES), "the paired K loop exists for the 64-column 16-bit kernel");
-    static_assert(!X3 || (BN_T == 64 && sizeof(T) == 2 && !RES && !PAIRD), "the three-term K loop exists for the 64-column 16-bit kernel");
-    static_assert(!C2 || (BN_T == 64 && sizeof(T) == 2 && !X3 && !PAIRD), "the two-term register-carry K loop exists for the 64-column 16-bit kernel");
+template <typename T, int LOSS, int ACT, bool XBITS = false, int BN_T = 128, bool RES = false, bool X3 = false, bool C2 = false>   // RES (split-bf16 mode): also the lo images of delta2 / delta2^T; X3: mainloop_n64_x3; C2: mainloop_n64_c2
+__global__ __launch_bounds__(GEMM_THREADS, DecGeo<BN_T>::WG_PER_CU) void gemm_decode_loss(GemmParams p, DecodeEpi e) {
+    static_assert(!X3 || (BN_T == 64 && sizeof(T) == 2 && !RES), "the three-term K loop exists for the 64-column 16-bit kernel");
+    static_assert(!C2 || (BN_T == 64 && sizeof(T) == 2 && !X3), "the two-term register-carry K loop exists for the 64-column 16-bit kernel");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     using Geo = DecGeo<BN_T>;
     constexpr int NTB = Geo::NTB, WCOLS = Geo::WCOLS, P0 = Geo::P0, P1 = Geo::P1;
@@ -2082,7 +1915,6 @@ __global__ __launch_bounds__(GEMM_THREADS, PAIRD ? 2 : DecGeo<BN_T>::WG_PER_CU) 
                 }
     } else {
     if constexpr (BN_T == 128) gemm_mainloop<T, DECODE_NST>(p, tm, tn, kt0, kt1, lds, acc);
-    else if constexpr (PAIRD) mainloop_n64_pair<T>(p, tm, tn, lds, acc);
     else if constexpr (X3) mainloop_n64_x3<T>(p, tm, tn, lds, acc);
     else if constexpr (C2) mainloop_n64_c2<T>(p, tm, tn, lds, acc);
     else mainloop_n64<T>(p, tm, tn, lds, acc);
@@ -2441,491 +2273,6 @@ __global__ __launch_bounds__(GEMM_THREADS, PAIRD ? 2 : DecGeo<BN_T>::WG_PER_CU) 
 }
 
 // ------------------------------------------------------------------------------------------------
-// A-stationary persistent decode (round 6; 16-bit modes, K = Hp <= 512, every K segment over the SAME h -- f16x2's (h, W_hi) (h, W_lo), plain bf16 / f16).
-//
-// gemm_decode_loss<.., 64> is bound by neither the MFMA pipe nor HBM at c2: per K tile a 128 x 64 workgroup moves 24 KiB through LDS-DMA and reads 48 KiB
-// of fragments for 32 MFMAs, holds ONE K tile in flight (48 KiB of LDS = two stages), and a launch is 1106 one-tile workgroups in 1.44 rounds of the chip's 768
-// slots (tools/decode_quant_probe.sh: t = 17 us + 24 ns per tile).  Every phase of it is a latency chain.  Here
-//   * h never stays in LDS: wave w of a workgroup owns rows [32 w, +32) of a 128-row panel and keeps their fragments over the WHOLE K in registers
-//     (8 K tiles x 4 k-steps x 16 B = 128 VGPRs), filled once per panel through the same ring the W tiles use; both W terms of the split modes multiply
-//     the same registers;
-//   * only W streams afterwards: one 64-row B tile (8 KiB) per K tile through a 7-slot LDS-DMA ring -- six K tiles in flight per workgroup instead of one --
-//     at ONE barrier per K tile; a wave reads the whole B tile (8 ds_read_b128) for its 8 MFMAs: 40 KiB of LDS traffic per K tile instead of 72;
-//   * workgroups are persistent, two per CU; each walks a contiguous run of tiles of ITS XCD's column band (the band's W rows, 2.5 MB hi + lo, stay in that
-//     XCD's L2).  The ring runs across tile boundaries: while a tile's loss is evaluated the next tile's first six B tiles are already on their way;
-//   * the epilogue is wave-local: a wave's 32 rows are its own, so the clean-input bits, the row weights, the staged delta2 rows and their coalesced
-//     stores need no workgroup barrier (one remains, for the column sums of the bias gradient); delta2^T leaves straight from the accumulator layout
-//     (8-byte pieces: four consecutive batch rows of one feature), so no second staging tile exists;
-//   * the Gs rider tiles are done by the same workgroups before their first slots land (no extra workgroups queueing for a slot).
-// The arithmetic is gemm_decode_loss's (same FAST / literal split, same op_scale, same partial-sum layouts; the column / row partial sums are added in the
-// order of the 4 x 1 wave layout).  Reference: autoencoder.py:395-415 (decode), triplet_loss_utils.py:262-277 (weighted_loss).
-// ------------------------------------------------------------------------------------------------
-// workgroup barrier that orders LDS accesses only: __syncthreads() also waits vmcnt(0), i.e. for every LDS-DMA slot and global store still in flight
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-struct DecAst {
-    static constexpr int NST = 6;                          // ring slots (7 would be 79 KiB per workgroup: measured ONE resident workgroup per CU then)
-    static constexpr int SLOT = 64 * BKB;                  // one slot: 64 rows x 128 B = 8 KiB (a B tile of W rows, or half of an A tile of h rows)
-    static constexpr int RING = NST * SLOT;
-    static constexpr int MAXKT = 8;                        // K tiles whose A fragments a wave holds (Hp <= 512 in 16-bit elements)
-    static constexpr int P0 = 64 * 2 + 16;                 // staged row pitch of a wave's [32][64] delta2 rows (16-bit + 16 B pad)
-    static constexpr int R0W = 32 * P0;                    // per wave
-    // floats behind the four R0W blocks: per wave [32] cw, [32] rowsum / sum y^2, [32] sum xhat.y, [32] 1/|x|, [32] cyy, [32] cxy, [32][2] x bits; shared [4][64] colsum, [4] loss shares
-    static constexpr int WAVE_FLOATS = 6 * 32 + 64;
-    static constexpr int AUX_FLOATS = 4 * WAVE_FLOATS + 4 * 64 + 4;
-    static constexpr int EPI_BYTES = 4 * R0W + AUX_FLOATS * 4;
-    static constexpr int LDS_BYTES = RING + EPI_BYTES;
-};
-static_assert(2 * DecAst::LDS_BYTES <= 160 * 1024, "two persistent decode workgroups per CU");
-static_assert(DecAst::RING >= 64 * 65 * 4, "the Gs rider tile fits the ring");
-__device__ __forceinline__ void wait_vm_2n(int n) {        // vmcnt(2 n): the pieces of n younger ring slots (2 per wave each) may stay in flight
-    switch (n) {
-        case 0: wait_vm<0>(); break;
-        case 1: wait_vm<2>(); break;
-        case 2: wait_vm<4>(); break;
-        case 3: wait_vm<6>(); break;
-        case 4: wait_vm<8>(); break;
-        case 5: wait_vm<10>(); break;
-        default: wait_vm<12>(); break;
-    }
-}
-
-template <int LOSS, int ACT, bool XBITS>
-__global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_decode_ast(GemmParams p, DecodeEpi e) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    using T = bf16_t;
-    constexpr int BN_T = 64, NT = 2, P0 = DecAst::P0, NST = DecAst::NST, SLOT = DecAst::SLOT;
-    constexpr bool IS_COS = (LOSS == DAE_LOSS_COSINE);
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = lane >> 5, c = lane & 31;
-    char* epi = lds + DecAst::RING;
-    // timing probe (DecodeEpi::dbg & 64): workgroup b leaves 100 MHz timestamps in dbv_part[b * 32 ..] (as uint64) instead of the bias-gradient partials
-    int n_stamp = 0;
-    auto stamp = [&]() {
-        if ((e.dbg & 64) && threadIdx.x == 0 && n_stamp < 16)
-            reinterpret_cast<unsigned long long*>(e.dbv_part)[(int64_t)blockIdx.x * 16 + n_stamp] = __builtin_amdgcn_s_memrealtime();
-        ++n_stamp;
-    };
-    stamp();
-
-    // ---- this workgroup's run of tiles: XCD x = b % nx owns the column tiles [c0, c1); its workgroups split the band's tiles_m * nc tiles, panel-major ----
-    const int nwg = (int)gridDim.x, b = (int)blockIdx.x;
-    const int nx = nwg < 8 ? nwg : 8;
-    const int x = b % nx, j = b / nx, J = (nwg - x + nx - 1) / nx;
-    const int c0 = (p.tiles_n * x) / nx, c1 = (p.tiles_n * (x + 1)) / nx, nc = c1 - c0;
-    const int n_x = p.tiles_m * nc;
-    const int i0 = (int)(((int64_t)n_x * j) / J), i1 = (int)(((int64_t)n_x * (j + 1)) / J);
-    const int ntiles = i1 - i0;
-    const int nkt = p.seg[0].ktiles, nseg = p.nseg;                          // K tiles per segment (<= 8); segments share h
-
-    // ---- Gs rider tiles (DecodeEpi::sym_*) first: the ring is still empty ----
-    if (e.sym_G) {
-        const int nt64 = e.sym_Bp / 64;
-        for (int t = b; t < nt64 * nt64; t += nwg) {
-            sym_scale_tile<T>(e.sym_G, e.sym_B, e.sym_Bp, e.sym_scalars, reinterpret_cast<T*>(e.sym_Gs), t % nt64, t / nt64,
-                              reinterpret_cast<float(*)[65]>(lds), e.op_scale);
-            __syncthreads();
-        }
-    }
-    if (ntiles <= 0) return;
-
-    // ---- producer: the slot stream, in RUNS of nkt slots (K tiles 0 .. nkt-1 of one 64-row block).  Per tile: [h rows [0, 64) | h rows [64, 128)] when the tile
-    // opens a new panel, then one run of W rows per K segment.  Kept small on purpose (one call site, pointer bumps; the run switch is the only slow path):
-    // an earlier form with the switch logic inlined at 24 sites of an unrolled K loop was 60 KB of code and spent 0.3 - 0.7 us per ring step fetching it.
-    constexpr int L = NST - 1;                             // slots in flight ahead of the consumer
-    const uint32_t lda = (uint32_t)p.seg[0].lda_b, ldb = (uint32_t)p.seg[0].ldb_b;
-    uint32_t vrow[2], vsl[2];                              // this lane's row of a slot's two pieces and the (swizzled) 16-byte slot it fetches
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        vrow[i] = (uint32_t)((i * 4 + wave) * 8 + (lane >> 3));
-        vsl[i] = (uint32_t)(((lane & 7) ^ ((vrow[i] >> 1) & 7)) << 4);
-    }
-    const int runs_per_tile = 2 + nseg;                    // run 0 / 1: the A halves (only when the panel changes), run 2 + s: segment s
-    int p_it = 0, p_run = 0, p_left = 0, p_tm = -1, p_tn = 0;
-    uint32_t ps_off = 0;                                   // ring byte offset of the next slot to fill
-    const char* p_src = nullptr;
-    uint32_t vo0 = 0, vo1 = 0;
-    bool p_more = true;
-    auto run_setup = [&]() {                               // p_run of tile p_it starts
-        p_left = nkt;
-        // (no dynamic index into the kernarg struct, no table of per-lane offsets: either would live in scratch, a ~1 us reload on the producer's path)
-        const uint32_t ld = p_run < 2 ? lda : ldb;
-        p_src = p_run < 2 ? p.seg[0].A + ((int64_t)p_tm * BM + p_run * 64) * lda : (p_run == 2 ? p.seg[0].Bt : p.seg[1].Bt) + (int64_t)p_tn * BN_T * ldb;
-        vo0 = vrow[0] * ld + vsl[0];
-        vo1 = vrow[1] * ld + vsl[1];
-    };
-    auto tile_open = [&]() {
-        const int i = i0 + p_it;
-        const int tm = i / nc;
-        p_tn = c0 + i % nc;
-        p_run = tm != p_tm ? 0 : 2;
-        p_tm = tm;
-        run_setup();
-    };
-    auto dma_one = [&]() {
-        char* slot = lds + ps_off;
-        if (!(e.dbg & 4)) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p_src + vo0),
-                                             (__attribute__((address_space(3))) void*)(slot + wave * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p_src + vo1),
-                                             (__attribute__((address_space(3))) void*)(slot + (4 + wave) * 1024), 16, 0, 0);
-        }
-        p_src += BKB;
-        ps_off += SLOT;
-        if (ps_off == DecAst::RING) ps_off = 0;
-        if (--p_left == 0) {                               // next run / next tile / end of the stream
-            if (++p_run < runs_per_tile) run_setup();
-            else if (++p_it < ntiles) tile_open();
-            else p_more = false;
-        }
-    };
-    tile_open();
-#pragma nounroll
-    for (int s = 0; s < L && p_more; ++s) dma_one();
-    stamp();
-
-    const T* X = reinterpret_cast<const T*>(e.x);
-    T* D2 = reinterpret_cast<T*>(e.delta2);
-    T* D2T = reinterpret_cast<T*>(e.delta2_t);
-    const bool pass1 = IS_COS && e.cos_pass == 1;
-    char* R0 = epi + wave * DecAst::R0W;               // this wave's rows: x tile, overwritten in place by delta2   [32][P0]
-    float* auxw = reinterpret_cast<float*>(epi + 4 * DecAst::R0W) + wave * DecAst::WAVE_FLOATS;
-    float* cw_l = auxw;                                // [32] row weights of this wave's rows
-    float* rs_l = auxw + 32;                           // [32] row sums (loss), or sum y^2 (cosine pass 1)
-    float* xy_l = auxw + 64;                           // [32] sum xhat.y (cosine pass 1)
-    float* inx_l = auxw + 96;                          // [32] 1/|x|            (cosine)
-    float* cyy_l = auxw + 128;                         // [32] sum y^2          (cosine pass 2)
-    float* cxy_l = auxw + 160;                         // [32] sum xhat.y       (cosine pass 2)
-    uint32_t* xb_l = reinterpret_cast<uint32_t*>(auxw + 192);   // [32][2] bit image of this wave's clean-input rows (XBITS)
-    float* colsum_l = reinterpret_cast<float*>(epi + 4 * DecAst::R0W) + 4 * DecAst::WAVE_FLOATS;   // [4 (wave)][64]
-    float* share_l = colsum_l + 4 * 64;                // [4] the waves' shares of sum_i cw_i * rowloss_i
-
-    const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-    const int swz = (c >> 1) & 7;
-    uint32_t so[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) so[kk] = (uint32_t)(c * BKB) + (uint32_t)(((kk * 2 + g) ^ swz) << 4);
-    const uint32_t a_row_off = (uint32_t)((wave & 1) * 32 * BKB);        // this wave's 32 rows inside its A half slot
-    uint32_t cs_off = 0;                               // ring byte offset of the next slot to consume
-
-    i32x4 fa[DecAst::MAXKT][4];                        // this wave's h fragments: rows [32 wave, +32) of the panel, all of K
-#pragma unroll
-    for (int kt = 0; kt < DecAst::MAXKT; ++kt)
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) fa[kt][kk] = i32x4{0, 0, 0, 0};
-    int tm_loaded = -1;
-    for (int it = 0; it < ntiles; ++it) {
-        const int ti = i0 + it;
-        const int tm = ti / nc, tn = c0 + ti % nc;
-        // ---- tile prologue: what the epilogue needs from memory is requested now and parked in a few registers across the K loop ----
-        uint32_t xb = 0;
-        if constexpr (XBITS) xb = e.x_bits[(int64_t)(tm * BM + wave * 32 + (lane & 31)) * e.ldxb + tn * 2 + (lane >> 5)];
-        const float cw_r = e.cw[tm * BM + wave * 32 + (lane & 31)];                 // zero beyond B by construction
-        float bvv[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) bvv[nt] = (tn * BN_T + c + nt * 32) < e.F ? e.bv[tn * BN_T + c + nt * 32] : 0.f;
-
-        f32x16 acc[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
-
-        // ---- the tile's runs, one ring slot per step: passes 0 / 1 move the new panel's h fragments ring -> registers (the waves of that row half read),
-        //      passes 2 + s multiply K segment s.  One barrier per step; the body of K tile kt is selected by a uniform switch so that fa[kt] stays a
-        //      compile-time register index while the loop itself is NOT unrolled ----
-        auto ring_step = [&]() -> uint32_t {
-            // the slot to consume has landed once at most the pieces of the L - 1 younger slots are outstanding (exactly L are issued ahead while the
-            // stream lasts; behind its end everything outstanding is waited for)
-            if (p_more) wait_vm<2 * (L - 1)>(); else wait_vm<0>();
-            __builtin_amdgcn_s_barrier();              // it landed for every wave, and every wave is done reading the slot consumed one step ago
-            asm volatile("" ::: "memory");
-            if (p_more) dma_one();                     // refill that slot: L stay in flight
-            const uint32_t sb = lbase + cs_off;
-            cs_off += SLOT;
-            if (cs_off == DecAst::RING) cs_off = 0;
-            return sb;
-        };
-        if (tm != tm_loaded) {                         // a new panel: runs 0 / 1 move its h fragments ring -> registers (the waves of that row half read)
-#pragma nounroll
-            for (int half = 0; half < 2; ++half) {
-#pragma unroll
-                for (int kt = 0; kt < DecAst::MAXKT; ++kt) {
-                    if (kt < nkt) {
-                        const uint32_t sb = ring_step();
-                        if ((wave >> 1) == half && !(e.dbg & 1)) {
-#pragma unroll
-                            for (int kk = 0; kk < 4; ++kk) fa[kt][kk] = lds_read_b128(sb + a_row_off + so[kk]);
-                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        }
-                    }
-                }
-            }
-            stamp();
-        }
-        // runs 2 + s multiply K segment s, one ring slot per step.  The body of K tile kt is selected by a uniform switch so that fa[kt] stays a
-        // compile-time register index while the loop itself is NOT unrolled (one copy of the ring step)
-        for (int sg = 0; sg < nseg; ++sg) {
-#pragma nounroll
-            for (int kt = 0; kt < nkt; ++kt) {
-                const uint32_t sb = ring_step();
-                if (!(e.dbg & 2)) {
-                    // B fragments of k-step kk for both column blocks; two k-steps are in flight at a time (16 registers, not 32: beside the 128 of h
-                    // the full set pushed one K tile of h into scratch)
-                    i32x4 f0a = lds_read_b128(sb + so[0]), f0b = lds_read_b128_off4096(sb + so[0]);
-                    i32x4 f1a = lds_read_b128(sb + so[1]), f1b = lds_read_b128_off4096(sb + so[1]);
-                    i32x4 f2a, f2b, f3a, f3b;
-#define DAE_AST_MM(KT, KK, FA, FB)                               \
-    __builtin_amdgcn_sched_barrier(0);                           \
-    Mma<T>::run(fa[KT][KK], FA, acc[0]);                         \
-    Mma<T>::run(fa[KT][KK], FB, acc[1]);                         \
-    __builtin_amdgcn_sched_barrier(0);
-#define DAE_AST_BCASE(KT)                                                                                       \
-    case KT:                                                                                                    \
-        asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");                                                      \
-        DAE_AST_MM(KT, 0, f0a, f0b)                                                                             \
-        f2a = lds_read_b128(sb + so[2]); f2b = lds_read_b128_off4096(sb + so[2]);                               \
-        asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");                                                      \
-        DAE_AST_MM(KT, 1, f1a, f1b)                                                                             \
-        f3a = lds_read_b128(sb + so[3]); f3b = lds_read_b128_off4096(sb + so[3]);                               \
-        asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");                                                      \
-        DAE_AST_MM(KT, 2, f2a, f2b)                                                                             \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                      \
-        DAE_AST_MM(KT, 3, f3a, f3b)                                                                             \
-        break;
-                    switch (kt) { DAE_AST_BCASE(0) DAE_AST_BCASE(1) DAE_AST_BCASE(2) DAE_AST_BCASE(3) DAE_AST_BCASE(4) DAE_AST_BCASE(5) DAE_AST_BCASE(6) DAE_AST_BCASE(7) default: break; }
-#undef DAE_AST_BCASE
-#undef DAE_AST_MM
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // (the default case: no read may stay pending into the next step)
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-        tm_loaded = tm;
-
-        stamp();
-        // ---- epilogue of tile (tm, tn): gemm_decode_loss's arithmetic on the wave layout 4 x 1 (wave w: rows [32 w, +32), all 64 columns), wave-local ----
-        // Everything below is recomputed per tile from a laundered lane id: hoisted out of the tile loop, the epilogue's per-lane addresses and constants
-        // (~60 VGPRs) sat beside the 128 A registers through the K loop and went to scratch -- and a scratch reload in a kernel with two waves per SIMD is
-        // a ~1 us stall each (measured: 22 us of the kernel).
-        {
-        int lane_l = threadIdx.x & 63;
-        asm volatile("" : "+v"(lane_l));
-        const int lane = lane_l, g = lane >> 5, c = lane & 31;
-        const int row0 = tm * BM + wave * 32;          // first batch row of this wave
-        if (lane < 32) cw_l[lane] = cw_r;
-        if constexpr (XBITS) {
-            xb_l[(lane & 31) * 2 + (lane >> 5)] = xb;
-        } else {                                       // valued clean rows: this wave's [32][64] tile, fetched now (binary input is the hot case)
-            i32x4 xr[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int ch = lane + 64 * i;
-                xr[i] = *reinterpret_cast<const i32x4*>(X + (int64_t)(row0 + (ch >> 3)) * e.ldx + tn * BN_T + (ch & 7) * 8);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int ch = lane + 64 * i;
-                *reinterpret_cast<i32x4*>(R0 + (ch >> 3) * P0 + (ch & 7) * 16) = xr[i];
-            }
-        }
-        if constexpr (IS_COS) {
-            if (lane < 32) {
-                inx_l[lane] = rsqrtf(fmaxf(e.cos_stats[row0 + lane], 1e-12f));
-                cyy_l[lane] = e.cos_pass == 2 ? e.cos_stats[e.Bp + row0 + lane] : 0.f;
-                cxy_l[lane] = e.cos_pass == 2 ? e.cos_stats[2 * e.Bp + row0 + lane] : 0.f;
-            }
-        }
-        const int lrow0 = 4 * g;                       // row of r = 0 inside the wave's 32
-        const float eps = 1e-16f;
-        float colsum[NT], cm[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            colsum[nt] = 0.f;
-            cm[nt] = (tn * BN_T + c + nt * 32) < e.F ? 1.f : 0.f;
-        }
-        char* r0_lane = R0 + lrow0 * P0 + c * 2;
-        T* d2t_lane = D2T ? D2T + (int64_t)(tn * BN_T + c) * e.lddt + row0 + lrow0 : nullptr;
-        const bool want_rows = e.rowloss_part != nullptr;
-        const float osc = e.op_scale;
-        float wl_acc = 0.f;                            // this lane's share of sum_i cw_i * loss_if
-        auto epi_block = [&](auto R4, auto FASTV) {
-            constexpr int r4 = decltype(R4)::value;
-            constexpr bool FAST = decltype(FASTV)::value;
-            constexpr int rloc = 8 * r4;
-            float d2v[NT][4];
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-                const int r = r4 * 4 + qq;
-                const int lrow = lrow0 + rloc + qq;
-                const float cwi = cw_l[lrow];
-                float rl = 0.f, s_yy = 0.f, s_xy = 0.f;
-                float inx = 0.f, cs_yy = 0.f, cs_xy = 0.f;
-                if constexpr (IS_COS) { inx = inx_l[lrow]; cs_yy = cyy_l[lrow]; cs_xy = cxy_l[lrow]; }
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const float z = acc[nt][r] + bvv[nt];
-                    float xv;
-                    if constexpr (XBITS) xv = (float)((xb_l[lrow * 2 + nt] >> c) & 1u);
-                    else xv = bf2f(*reinterpret_cast<const bf16_t*>(r0_lane + (rloc + qq) * P0 + nt * 64));
-                    float l = 0.f, dy = 0.f;
-                    if constexpr (FAST) {
-                        const float en = __builtin_amdgcn_exp2f(-fabsf(z) * kLog2e);          // exp(-|z|)
-                        const float op = 1.0f + en;
-                        const float rr = __builtin_amdgcn_rcpf(op);
-                        const float yv = z >= 0.f ? rr : en * rr;
-                        l = kLn2 * __builtin_amdgcn_logf(op) + fmaxf(z, 0.f) - xv * z;
-                        const float d2 = (cwi * cm[nt]) * (yv - xv);
-                        rl += cm[nt] * l;
-                        colsum[nt] += d2;
-                        const float d2s = sat16(d2 * osc);                  // the 16-bit images hold op_scale * delta2
-                        d2v[nt][qq] = d2s;
-                        *reinterpret_cast<bf16_t*>(r0_lane + (rloc + qq) * P0 + nt * 64) = f2bf_hw(d2s);
-                        continue;
-                    }
-                    const float y = act_fwd<ACT>(z);
-                    if constexpr (LOSS == DAE_LOSS_CROSS_ENTROPY) {
-                        const float a = y + eps, bb = (1.0f - y) + eps;         // reference op order: (1.-y)+1e-16
-                        const float la = __builtin_amdgcn_logf(a), lb = __builtin_amdgcn_logf(bb);
-                        l = -kLn2 * (xv * la + (1.0f - xv) * lb);
-                        dy = (1.0f - xv) * __builtin_amdgcn_rcpf(bb) - xv * __builtin_amdgcn_rcpf(a);
-                    } else if constexpr (LOSS == DAE_LOSS_MEAN_SQUARED) {
-                        const float d = xv - y;
-                        l = d * d;
-                        dy = -2.0f * d;
-                    } else {
-                        const float xh = xv * inx;
-                        if (pass1) {
-                            s_yy += cm[nt] * y * y;
-                            s_xy += cm[nt] * xh * y;
-                        } else {
-                            const float big = cs_yy >= 1e-12f ? 1.f : 0.f;      // tf.maximum routes grad to sum y^2 iff >= eps
-                            const float s = rsqrtf(fmaxf(cs_yy, 1e-12f));
-                            dy = -(xh * s - big * cs_xy * s * s * s * y);
-                        }
-                    }
-                    const float d2 = pass1 ? 0.f : (cwi * cm[nt]) * dy * act_bwd<ACT>(y);   // cw is 0 on padded rows
-                    rl += cm[nt] * l;
-                    colsum[nt] += d2;
-                    const float d2s = sat16(d2 * osc);
-                    d2v[nt][qq] = d2s;
-                    *reinterpret_cast<bf16_t*>(r0_lane + (rloc + qq) * P0 + nt * 64) = f2bf_hw(d2s);
-                }
-                // wavefront (DPP) sum over the 32 lanes that share this row; lanes 16..31 / 48..63 hold it
-                if constexpr (IS_COS) {
-                    if (pass1) {
-                        s_yy = half32_sum_hi(s_yy); s_xy = half32_sum_hi(s_xy);
-                        if (c == 31) { rs_l[lrow] = s_yy; xy_l[lrow] = s_xy; }
-                    }
-                } else {
-                    wl_acc += cwi * rl;
-                    if (want_rows) {
-                        rl = half32_sum_hi(rl);
-                        if (c == 31) rs_l[lrow] = rl;
-                    }
-                }
-            }
-            // delta2^T straight from the accumulator layout: four consecutive batch rows of feature (c + 32 nt) are 8 contiguous bytes of its image row
-            // (the g = 0 / g = 1 lanes of a column write adjacent pieces; a column's 64 bytes of this wave complete within the four blocks)
-            if (d2t_lane && !pass1 && !(e.dbg & 32)) {
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    uint2 v;
-                    v.x = f2bf_pack_hw(d2v[nt][0], d2v[nt][1]);
-                    v.y = f2bf_pack_hw(d2v[nt][2], d2v[nt][3]);
-                    *reinterpret_cast<uint2*>(d2t_lane + (int64_t)nt * 32 * e.lddt + rloc) = v;
-                }
-            }
-            // one block's sums are closed before the next block starts: left free, the scheduler sank all 16 column-sum / loss-share additions behind the
-            // four blocks and carried their 48 operands there -- through scratch, with 128 registers of h resident
-            asm volatile("" : "+v"(colsum[0]), "+v"(colsum[1]), "+v"(wl_acc));
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        // this wave's 32 rows are pure batch padding (rows >= B): delta2 = 0 without evaluating the loss (cw is 0 there)
-        const int vblk = e.no_pad_skip ? 4 : min(4, (e.B - tm * BM + 31) >> 5);
-        bool fast = false;
-        if constexpr (LOSS == DAE_LOSS_CROSS_ENTROPY && ACT == DAE_ACT_SIGMOID) {
-            float zmax = 0.f;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) zmax = fmaxf(zmax, fabsf(acc[nt][r] + bvv[nt]));
-            fast = __builtin_amdgcn_ballot_w64(!(zmax < CE_FAST_ZMAX)) == 0ull && !e.ce_literal;   // NaN logits take the literal path
-        }
-        if (wave >= vblk || (e.dbg & 8)) {
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-#pragma unroll
-                    for (int qq = 0; qq < 4; ++qq) *reinterpret_cast<bf16_t*>(r0_lane + (8 * r4 + qq) * P0 + nt * 64) = (bf16_t)0;
-                    uint2 z; z.x = 0u; z.y = 0u;
-                    if (d2t_lane && !pass1 && !(e.dbg & 32)) *reinterpret_cast<uint2*>(d2t_lane + (int64_t)nt * 32 * e.lddt + 8 * r4) = z;
-                }
-            if (lane < 32) { rs_l[lane] = 0.f; xy_l[lane] = 0.f; }
-        } else if (fast) {
-            if constexpr (LOSS == DAE_LOSS_CROSS_ENTROPY && ACT == DAE_ACT_SIGMOID) {
-                epi_block(std::integral_constant<int, 0>{}, std::true_type{});
-                epi_block(std::integral_constant<int, 1>{}, std::true_type{});
-                epi_block(std::integral_constant<int, 2>{}, std::true_type{});
-                epi_block(std::integral_constant<int, 3>{}, std::true_type{});
-            }
-        } else {
-            epi_block(std::integral_constant<int, 0>{}, std::false_type{});
-            epi_block(std::integral_constant<int, 1>{}, std::false_type{});
-            epi_block(std::integral_constant<int, 2>{}, std::false_type{});
-            epi_block(std::integral_constant<int, 3>{}, std::false_type{});
-        }
-        if (!pass1) {                                       // column sums of this wave's 32 rows: rows of g = 0 and g = 1, then one lane per column
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const float v = colsum[nt] + __shfl_xor(colsum[nt], 32, 64);
-                if (g == 0) colsum_l[wave * BN_T + c + nt * 32] = v;
-            }
-        }
-        if constexpr (!IS_COS) {
-            if (e.tile_part) {
-                const float v = wave64_sum_hi(wl_acc);
-                if (lane == 63) share_l[wave] = v;
-            }
-        }
-        // ---- this wave's rows leave the CU: delta2 as coalesced 16-byte pieces of 128-byte row runs, the per-row partial sums ----
-        if (!pass1 && D2 && !(e.dbg & 16)) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int ch = lane + 64 * i;
-                *reinterpret_cast<i32x4*>(D2 + (int64_t)(row0 + (ch >> 3)) * e.ldd + tn * BN_T + (ch & 7) * 8) =
-                    *reinterpret_cast<const i32x4*>(R0 + (ch >> 3) * P0 + (ch & 7) * 16);
-            }
-        }
-        {
-            // two partial rows per column tile in the consumers' layout: [0] = the row sums of the 64 columns, [1] = 0
-            const int k = lane & 31, w = lane >> 5;
-            const bool rowok = (row0 + k) < e.B;
-            if constexpr (IS_COS) {
-                if (pass1) {
-                    e.cos_part[(int64_t)(tn * 2 + w) * e.Bp + row0 + k] = (rowok && w == 0) ? rs_l[k] : 0.f;
-                    e.cos_part[(int64_t)(2 * p.tiles_n + tn * 2 + w) * e.Bp + row0 + k] = (rowok && w == 0) ? xy_l[k] : 0.f;
-                }
-            } else {
-                if (e.rowloss_part) e.rowloss_part[(int64_t)(tn * 2 + w) * e.Bp + row0 + k] = (rowok && w == 0) ? rs_l[k] : 0.f;
-            }
-        }
-        lds_barrier();                                      // the four waves' column sums and loss shares are in LDS
-        if (e.dbv_part && !pass1 && wave < 2 && !(e.dbg & 64)) {             // two partial rows per row tile: rows [0, 64) and [64, 128) of the panel; wave w2 adds its pair
-            e.dbv_part[(int64_t)(tm * 2 + wave) * e.Fp + tn * BN_T + lane] = colsum_l[(2 * wave) * BN_T + lane] + colsum_l[(2 * wave + 1) * BN_T + lane];
-        }
-        if constexpr (!IS_COS) {
-            if (e.tile_part && wave == 2 && lane == 0) e.tile_part[tm * p.tiles_n + tn] = (share_l[0] + share_l[1]) + (share_l[2] + share_l[3]);
-        }
-        stamp();
-        // (the next tile's first ring_step barrier orders these LDS reads before the next epilogue's writes)
-        }   // (laundered-id scope of the epilogue)
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------
 static int g_nst = 2;   // staging variant of the plain GEMM: 0 register-staged, 2/3/4 global_load_lds ring depth
@@ -3037,19 +2384,10 @@ static decode_fn decode_kernel_wide(int loss, int act, bool xbits) {
 #undef DAE_DKW
     return nullptr;
 }
-// the 64-column kernel with the paired K loop (two K segments that share their A operand: the split modes' h.W_hi + h.W_lo)
-static decode_fn decode_kernel_pair(int loss, int act, bool xbits) {
-#define DAE_DKP(LV, AV)                                                                                       \
-    if (loss == LV && act == AV)                                                                              \
-        return xbits ? gemm_decode_loss<bf16_t, LV, AV, true, DECODE_BN_BF16, false, true> : gemm_decode_loss<bf16_t, LV, AV, false, DECODE_BN_BF16, false, true>;
-    DAE_DKP(0, 0) DAE_DKP(0, 1) DAE_DKP(0, 2) DAE_DKP(1, 0) DAE_DKP(1, 1) DAE_DKP(1, 2) DAE_DKP(2, 0) DAE_DKP(2, 1) DAE_DKP(2, 2)
-#undef DAE_DKP
-    return nullptr;
-}
 // the 64-column kernel with the three-term K loop (mainloop_n64_x3: (h_hi, W_hi) (h_hi, W_lo) (h_lo, W_hi) in two stages per K tile)
 // (binary input = the bit image of x only: with the 16-byte x prefetch registers on top the loop does not fit the 168 VGPRs of three workgroups per CU)
 static decode_fn decode_kernel_x3(int loss, int act) {
-#define DAE_DK3(LV, AV) if (loss == LV && act == AV) return gemm_decode_loss<bf16_t, LV, AV, true, DECODE_BN_BF16, false, false, true>;
+#define DAE_DK3(LV, AV) if (loss == LV && act == AV) return gemm_decode_loss<bf16_t, LV, AV, true, DECODE_BN_BF16, false, true>;
     DAE_DK3(0, 0) DAE_DK3(0, 1) DAE_DK3(0, 2) DAE_DK3(1, 0) DAE_DK3(1, 1) DAE_DK3(1, 2) DAE_DK3(2, 0) DAE_DK3(2, 1) DAE_DK3(2, 2)
 #undef DAE_DK3
     return nullptr;
@@ -3058,25 +2396,12 @@ static decode_fn decode_kernel_x3(int loss, int act) {
 static decode_fn decode_kernel_c2(int loss, int act, bool res) {
 #define DAE_DKC(LV, AV)                                                                                       \
     if (loss == LV && act == AV)                                                                              \
-        return res ? gemm_decode_loss<bf16_t, LV, AV, true, DECODE_BN_BF16, true, false, false, true> : gemm_decode_loss<bf16_t, LV, AV, true, DECODE_BN_BF16, false, false, false, true>;
+        return res ? gemm_decode_loss<bf16_t, LV, AV, true, DECODE_BN_BF16, true, false, true> : gemm_decode_loss<bf16_t, LV, AV, true, DECODE_BN_BF16, false, false, true>;
     DAE_DKC(0, 0) DAE_DKC(0, 1) DAE_DKC(0, 2) DAE_DKC(1, 0) DAE_DKC(1, 1) DAE_DKC(1, 2) DAE_DKC(2, 0) DAE_DKC(2, 1) DAE_DKC(2, 2)
 #undef DAE_DKC
     return nullptr;
 }
-// the A-stationary persistent kernel (gemm_decode_ast)
-static decode_fn decode_kernel_ast(int loss, int act, bool xbits) {
-#define DAE_DKA(LV, AV)                                                                                       \
-    if (loss == LV && act == AV)                                                                              \
-        return xbits ? gemm_decode_ast<LV, AV, true> : gemm_decode_ast<LV, AV, false>;
-    DAE_DKA(0, 0) DAE_DKA(0, 1) DAE_DKA(0, 2) DAE_DKA(1, 0) DAE_DKA(1, 1) DAE_DKA(1, 2) DAE_DKA(2, 0) DAE_DKA(2, 1) DAE_DKA(2, 2)
-#undef DAE_DKA
-    return nullptr;
-}
-static int g_decode_dbg = 0;       // dae_set_glds(-500000 - bits): timing probes of gemm_decode_ast (DecodeEpi::dbg)
 static int g_decode_x3 = 1;        // dae_set_glds(-17) off / (-18) on; plan option "decode_x3": the three-term decode (f16x2h) on mainloop_n64_x3 instead of three K segments
-static int g_decode_ast = 0;       // dae_set_glds(-15) off / (-16) on; plan option "decode_ast".  OFF: measured 44 us against 38 for the tile kernel at c2 (profiles/r06_decode_ast.txt)
-constexpr int DECODE_PAIR_LDS = 2 * (TILE_BYTES + 2 * 64 * BKB) > DecGeo<DECODE_BN_BF16>::EPI_BYTES ? 2 * (TILE_BYTES + 2 * 64 * BKB) : DecGeo<DECODE_BN_BF16>::EPI_BYTES;
-static int g_decode_pair = 0;      // dae_set_glds(-13) off / (-14) on; plan option "decode_pair"
 template <typename T> static decode_fn decode_kernel(int loss, int act) {
 #define DAE_DK(LV, AV) if (loss == LV && act == AV) return gemm_decode_loss<T, LV, AV, false, (sizeof(T) == 2 ? DECODE_BN_BF16 : BN)>;
     DAE_DK(0, 0) DAE_DK(0, 1) DAE_DK(0, 2) DAE_DK(1, 0) DAE_DK(1, 1) DAE_DK(1, 2) DAE_DK(2, 0) DAE_DK(2, 1) DAE_DK(2, 2)
@@ -3201,12 +2526,14 @@ int launch_gemm_f32out_n(int dtype, int M, int N, const GemmSegDesc* segs, int n
     return 0;
 }
 
-// can the 160 x 128 producer/consumer kernel run this shape with x~^T as a bit image?  (one round of the chip, the bit words of
-// the segment fit the producers' registers, whole 64-deep K tiles)
-bool dw_bits_fits(int M, int N, int Bp) {
+// does the gradient-only form of the 160 x 128 producer/consumer kernel take this shape (the data-parallel phases, bf16 / f16)?  One round
+// of the chip, whole 64-deep K tiles.  Bp <= 1024 is the bound of a bit-image form of x~^T that the kernel once had; it is kept so that
+// the dispatch stays what it was (larger batches take the GEMM to memory and the optimizer kernel).
+constexpr int DW_GRAD_MAXKT = 16;
+bool dw_grad_fits(int M, int N, int Bp) {
     if (gemm_init()) return false;
     const int tiles_m = (M + DW_BM - 1) / DW_BM, tiles_n = N / BN, per = (tiles_m + 7) / 8;
-    return N % BN == 0 && Bp % 64 == 0 && Bp / 64 <= DWB_MAXKT && 8 * per * tiles_n <= g_cus * g_dw_rounds && g_dw_pc != 0;
+    return N % BN == 0 && Bp % 64 == 0 && Bp / 64 <= DW_GRAD_MAXKT && 8 * per * tiles_n <= g_cus * g_dw_rounds && g_dw_pc != 0;
 }
 
 bool dw_x3_fits(int M, int N, int Bp) {
@@ -3224,11 +2551,10 @@ bool dw_pc_taken(int M, int N, int K0, int K1, bool grad_only) {
 }
 
 int launch_dw_opt(int M, int N, const void* A0, int64_t lda0, const void* Bt0, int64_t ldb0, int K0, const void* A1, int64_t lda1,
-                  const void* Bt1, int64_t ldb1, int K1, const OptEpi& e, hipStream_t st, const DwBitsArgs* xa, bool tra) {
+                  const void* Bt1, int64_t ldb1, int K1, const OptEpi& e, hipStream_t st, bool tra) {
     GemmParams p;
-    // xa: segment 0's A operand is the bit image (A0 == NULL); fill_params only needs a non-null, aligned placeholder
     {
-        const GemmSegDesc segs2[2] = {{xa ? Bt0 : A0, xa ? ldb0 : lda0, Bt0, ldb0, K0}, {A1, lda1, Bt1, ldb1, K1}};
+        const GemmSegDesc segs2[2] = {{A0, lda0, Bt0, ldb0, K0}, {A1, lda1, Bt1, ldb1, K1}};
         if (int rc = fill_params_n(p, DAE_BF16, M, N, segs2, 2, 1, BN, tra)) return rc;
     }
     if (int rc = gemm_init()) return rc;
@@ -3244,38 +2570,24 @@ int launch_dw_opt(int M, int N, const void* A0, int64_t lda0, const void* Bt0, i
         const int tiles_m = (M + DW_BM - 1) / DW_BM, tiles_n = N / BN;
         const int per = (tiles_m + 7) / 8;
         const bool fits = g_dw_pc && K0 % 64 == 0 && K1 % 64 == 0 && 8 * per * tiles_n <= g_cus * g_dw_rounds;
-        DAE_CHECK_ARG(!xa || (fits && K0 / 64 <= DWB_MAXKT && xa->xtb && xa->ldxt >= K0 / 32),
-                      "dw: the bit-image form of x~^T does not fit this shape (M=%d N=%d Bp=%d)", M, N, K0);
         DAE_CHECK_ARG(!grad_only || fits, "dw: the gradient-only form runs on the 160 x 128 kernel only (M=%d N=%d)", M, N);
-        if (fits && (xa || grad_only || g_dw_pc == 2 || g_dw_rounds > 1 || 8 * per * tiles_n > (3 * g_cus) / 4)) {
-            typedef void (*dwpc_fn)(GemmParams, OptEpi, int, DwBits);
-            static const dwpc_fn pcs[2][5] = {
-                {gemm_dw_pc<DAE_OPT_SGD, false>, gemm_dw_pc<DAE_OPT_ADAGRAD, false>, gemm_dw_pc<DAE_OPT_MOMENTUM, false>, gemm_dw_pc<DAE_OPT_ADAM, false>,
-                 gemm_dw_pc<DW_GRAD_ONLY, false>},
-                {gemm_dw_pc<DAE_OPT_SGD, true>, gemm_dw_pc<DAE_OPT_ADAGRAD, true>, gemm_dw_pc<DAE_OPT_MOMENTUM, true>, gemm_dw_pc<DAE_OPT_ADAM, true>,
-                 gemm_dw_pc<DW_GRAD_ONLY, true>}};
-            static const dwpc_fn pcs_tr[5] = {gemm_dw_pc<DAE_OPT_SGD, false, false, false, true>, gemm_dw_pc<DAE_OPT_ADAGRAD, false, false, false, true>,
-                                              gemm_dw_pc<DAE_OPT_MOMENTUM, false, false, false, true>, gemm_dw_pc<DAE_OPT_ADAM, false, false, false, true>,
-                                              gemm_dw_pc<DW_GRAD_ONLY, false, false, false, true>};
+        if (fits && (grad_only || g_dw_pc == 2 || g_dw_rounds > 1 || 8 * per * tiles_n > (3 * g_cus) / 4)) {
+            typedef void (*dwpc_fn)(GemmParams, OptEpi, int);
+            static const dwpc_fn pcs[5] = {gemm_dw_pc<DAE_OPT_SGD>, gemm_dw_pc<DAE_OPT_ADAGRAD>, gemm_dw_pc<DAE_OPT_MOMENTUM>, gemm_dw_pc<DAE_OPT_ADAM>,
+                                           gemm_dw_pc<DW_GRAD_ONLY>};
+            static const dwpc_fn pcs_tr[5] = {gemm_dw_pc<DAE_OPT_SGD, false, false, true>, gemm_dw_pc<DAE_OPT_ADAGRAD, false, false, true>,
+                                              gemm_dw_pc<DAE_OPT_MOMENTUM, false, false, true>, gemm_dw_pc<DAE_OPT_ADAM, false, false, true>,
+                                              gemm_dw_pc<DW_GRAD_ONLY, false, false, true>};
             static int pc_rc = [] {
                 int rc = 0;
-                for (int v = 0; v < 2; ++v)
-                    for (dwpc_fn f : pcs[v])
-                        rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, DW_LDS);
+                for (dwpc_fn f : pcs) rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, DW_LDS);
                 for (dwpc_fn f : pcs_tr) rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, DW_LDS);
                 return rc;
             }();
             DAE_CHECK_ARG(pc_rc == 0, "dw_pc: hipFuncSetAttribute failed");
-            DAE_CHECK_ARG(!tra || !xa, "dw: the transposed-A form takes dense row-major images (no bit image)");
             GemmParams q = p;
             q.tiles_m = tiles_m; q.tiles_n = tiles_n;
-            DwBits xb; memset(&xb, 0, sizeof(xb));
-            if (xa) {
-                xb.xtb = xa->xtb; xb.ldxt = xa->ldxt; xb.nwords = K0 / 32;
-                xb.one = host_f2bf(xa->scale);                  // 16-bit image of the scale, round to nearest even (a finite positive factor)
-                q.seg[0].A = nullptr;
-            }
-            DAE_LAUNCH(tra ? pcs_tr[e.opt] : pcs[xa ? 1 : 0][e.opt], dim3(8 * per * tiles_n), dim3(PC_THREADS), DW_LDS, st, q, e, M, xb);
+            DAE_LAUNCH(tra ? pcs_tr[e.opt] : pcs[e.opt], dim3(8 * per * tiles_n), dim3(PC_THREADS), DW_LDS, st, q, e, M);
             DAE_CHECK_LAUNCH();
             return 0;
         }
@@ -3291,7 +2603,7 @@ int launch_dw_opt(int M, int N, const void* A0, int64_t lda0, const void* Bt0, i
     }();
     DAE_CHECK_ARG(attr_rc == 0, "dw_opt: hipFuncSetAttribute failed");
     static_assert(DAE_OPT_SGD == 0 && DAE_OPT_ADAGRAD == 1 && DAE_OPT_MOMENTUM == 2 && DAE_OPT_ADAM == 3, "optimizer enum order");
-    DAE_CHECK_ARG(!xa && !grad_only, "dw: this shape needs the dense x~^T image and the fused-optimizer form");
+    DAE_CHECK_ARG(!grad_only, "dw: this shape needs the fused-optimizer form");
     DAE_LAUNCH(fns[e.opt], dim3(grid_blocks(p)), dim3(GEMM_THREADS), ldsb, st, p, e);
     DAE_CHECK_LAUNCH();
     return 0;
@@ -3338,16 +2650,16 @@ int launch_dw_opt_n(int M, int N, const GemmSegDesc* segs_in, int nsegs_in, cons
     for (int i = 0; i < nsegs; ++i) k64 = k64 && segs[i].K % 64 == 0;
     DAE_CHECK_ARG(g_dw_pc && k64 && 8 * per * tiles_n <= g_cus * g_dw_rounds_split,
                   "dw_opt_n: the split-mode dW kernel runs shapes of at most %d 160 x 128 tiles per CU (M=%d N=%d)", g_dw_rounds_split, M, N);
-    typedef void (*dwpc_fn)(GemmParams, OptEpi, int, DwBits);
-    static const dwpc_fn x3s[2][5] = {{gemm_dw_pc<DAE_OPT_SGD, false, true>, gemm_dw_pc<DAE_OPT_ADAGRAD, false, true>,
-                                       gemm_dw_pc<DAE_OPT_MOMENTUM, false, true>, gemm_dw_pc<DAE_OPT_ADAM, false, true>, gemm_dw_pc<DW_GRAD_ONLY, false, true>},
-                                      {gemm_dw_pc<DAE_OPT_SGD, false, true, true>, gemm_dw_pc<DAE_OPT_ADAGRAD, false, true, true>,
-                                       gemm_dw_pc<DAE_OPT_MOMENTUM, false, true, true>, gemm_dw_pc<DAE_OPT_ADAM, false, true, true>,
-                                       gemm_dw_pc<DW_GRAD_ONLY, false, true, true>}};
+    typedef void (*dwpc_fn)(GemmParams, OptEpi, int);
+    static const dwpc_fn x3s[2][5] = {{gemm_dw_pc<DAE_OPT_SGD, true>, gemm_dw_pc<DAE_OPT_ADAGRAD, true>,
+                                       gemm_dw_pc<DAE_OPT_MOMENTUM, true>, gemm_dw_pc<DAE_OPT_ADAM, true>, gemm_dw_pc<DW_GRAD_ONLY, true>},
+                                      {gemm_dw_pc<DAE_OPT_SGD, true, true>, gemm_dw_pc<DAE_OPT_ADAGRAD, true, true>,
+                                       gemm_dw_pc<DAE_OPT_MOMENTUM, true, true>, gemm_dw_pc<DAE_OPT_ADAM, true, true>,
+                                       gemm_dw_pc<DW_GRAD_ONLY, true, true>}};
     static_assert(DW_GRAD_ONLY == 4, "the gradient-only instantiation sits at index 4");
-    static const dwpc_fn x3s_tr[5] = {gemm_dw_pc<DAE_OPT_SGD, false, true, false, true>, gemm_dw_pc<DAE_OPT_ADAGRAD, false, true, false, true>,
-                                      gemm_dw_pc<DAE_OPT_MOMENTUM, false, true, false, true>, gemm_dw_pc<DAE_OPT_ADAM, false, true, false, true>,
-                                      gemm_dw_pc<DW_GRAD_ONLY, false, true, false, true>};
+    static const dwpc_fn x3s_tr[5] = {gemm_dw_pc<DAE_OPT_SGD, true, false, true>, gemm_dw_pc<DAE_OPT_ADAGRAD, true, false, true>,
+                                      gemm_dw_pc<DAE_OPT_MOMENTUM, true, false, true>, gemm_dw_pc<DAE_OPT_ADAM, true, false, true>,
+                                      gemm_dw_pc<DW_GRAD_ONLY, true, false, true>};
     static int rc3 = [] {
         int rc = 0;
         for (dwpc_fn f : x3s_tr) rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, DW_LDS);
@@ -3358,8 +2670,7 @@ int launch_dw_opt_n(int M, int N, const GemmSegDesc* segs_in, int nsegs_in, cons
     DAE_CHECK_ARG(rc3 == 0, "dw_opt_n: hipFuncSetAttribute failed");
     GemmParams q = p;
     q.tiles_m = tiles_m; q.tiles_n = tiles_n;
-    DwBits xb; memset(&xb, 0, sizeof(xb));
-    DAE_LAUNCH(tra ? x3s_tr[e.opt] : x3s[any_pair ? 1 : 0][e.opt], dim3(8 * per * tiles_n), dim3(PC_THREADS), any_pair ? DW_RING2 : DW_LDS, st, q, e, M, xb);
+    DAE_LAUNCH(tra ? x3s_tr[e.opt] : x3s[any_pair ? 1 : 0][e.opt], dim3(8 * per * tiles_n), dim3(PC_THREADS), any_pair ? DW_RING2 : DW_LDS, st, q, e, M);
     DAE_CHECK_LAUNCH();
     return 0;
 }
@@ -3388,26 +2699,9 @@ int launch_decode_loss_n(int dtype, int Bp, int Fp, const GemmSegDesc* segs, int
         DAE_CHECK_ARG(dtype == DAE_BF16 && e.ldxb >= Fp / 32 && ((uintptr_t)e.x_bits % 4) == 0, "decode_loss: bad x bit image");
         k = decode_kernel_xbits(e.loss_func, e.dec_act);
     }
-    // two K segments over the same A operand and K extent (the split modes' decode): the paired K loop
-    bool paird = false;
-    if (g_decode_pair && dtype == DAE_BF16 && !wide && !(e.delta2_2 || e.delta2_t2 || e.x2) && p.nseg == 2 && p.seg[0].A == p.seg[1].A &&
-        p.seg[0].lda_b == p.seg[1].lda_b && p.seg[0].ldb_b == p.seg[1].ldb_b && p.seg[0].ktiles == p.seg[1].ktiles) {
-        paird = true;
-        k = decode_kernel_pair(e.loss_func, e.dec_act, e.x_bits != nullptr);
-        static int pair_rc = [] {
-            int rc = 0;
-            for (int l = 0; l < 3; ++l)
-                for (int a = 0; a < 3; ++a)
-                    for (int x = 0; x < 2; ++x)
-                        rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_kernel_pair(l, a, x != 0)),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, DECODE_PAIR_LDS);
-            return rc;
-        }();
-        DAE_CHECK_ARG(pair_rc == 0, "decode_loss: hipFuncSetAttribute failed");
-    }
     // three K segments (h_hi, W_hi) (h_hi, W_lo) (h_lo, W_hi) over one K extent: the two-stage walk that keeps the hi fragments in registers
     bool x3d = false;
-    if (g_decode_x3 && dtype == DAE_BF16 && e.x_bits && !wide && !paird && !(e.delta2_2 || e.delta2_t2 || e.x2) && p.nseg == 3 && p.seg[0].A == p.seg[1].A &&
+    if (g_decode_x3 && dtype == DAE_BF16 && e.x_bits && !wide && !(e.delta2_2 || e.delta2_t2 || e.x2) && p.nseg == 3 && p.seg[0].A == p.seg[1].A &&
         p.seg[0].Bt == p.seg[2].Bt && p.seg[0].A != p.seg[2].A && p.seg[0].Bt != p.seg[1].Bt && p.seg[0].lda_b == p.seg[1].lda_b && p.seg[0].lda_b == p.seg[2].lda_b &&
         p.seg[0].ldb_b == p.seg[1].ldb_b && p.seg[0].ldb_b == p.seg[2].ldb_b && p.seg[0].ktiles == p.seg[1].ktiles && p.seg[0].ktiles == p.seg[2].ktiles) {
         x3d = true;
@@ -3424,7 +2718,7 @@ int launch_decode_loss_n(int dtype, int Bp, int Fp, const GemmSegDesc* segs, int
     }
     // two K segments over the same h (h.W_hi + h.W_lo), binary input: the register-carry walk (the lo stage is the W_lo tile alone)
     bool c2d = false;
-    if (g_decode_x3 && dtype == DAE_BF16 && e.x_bits && !wide && !paird && !x3d && !e.x2 && p.nseg == 2 && p.seg[0].A == p.seg[1].A && p.seg[0].Bt != p.seg[1].Bt &&
+    if (g_decode_x3 && dtype == DAE_BF16 && e.x_bits && !wide && !x3d && !e.x2 && p.nseg == 2 && p.seg[0].A == p.seg[1].A && p.seg[0].Bt != p.seg[1].Bt &&
         p.seg[0].lda_b == p.seg[1].lda_b && p.seg[0].ldb_b == p.seg[1].ldb_b && p.seg[0].ktiles == p.seg[1].ktiles) {
         c2d = true;
         static int c2_rc = [] {
@@ -3440,31 +2734,6 @@ int launch_decode_loss_n(int dtype, int Bp, int Fp, const GemmSegDesc* segs, int
     }
     if (e.op_scale == 0.f) e.op_scale = 1.f;
     e.no_pad_skip = g_pad_skip ? 0 : 1;
-    e.dbg = g_decode_dbg;
-    // A-stationary persistent form: 16-bit, 64-column tiles, no lo images, every K segment over the same h with K <= 8 tiles (Hp <= 512)
-    bool ast = g_decode_ast && dtype == DAE_BF16 && !wide && !paird && !x3d && !c2d && !(e.delta2_2 || e.delta2_t2 || e.x2) && p.seg[0].ktiles <= DecAst::MAXKT && p.nseg <= 2;
-    for (int s = 1; s < p.nseg && ast; ++s)
-        ast = p.seg[s].A == p.seg[0].A && p.seg[s].lda_b == p.seg[0].lda_b && p.seg[s].ldb_b == p.seg[0].ldb_b && p.seg[s].ktiles == p.seg[0].ktiles;
-    if (ast) {
-        decode_fn ka = decode_kernel_ast(e.loss_func, e.dec_act, e.x_bits != nullptr);
-        static int ast_rc = [] {
-            int rc = 0;
-            for (int l = 0; l < 3; ++l)
-                for (int a = 0; a < 3; ++a)
-                    for (int x = 0; x < 2; ++x)
-                        rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_kernel_ast(l, a, x != 0)),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, DecAst::LDS_BYTES);
-            return rc;
-        }();
-        DAE_CHECK_ARG(ast_rc == 0, "decode_loss: hipFuncSetAttribute failed");
-        if (e.sym_G) DAE_CHECK_ARG(e.sym_scalars && e.sym_Gs && e.sym_Bp % 64 == 0 && e.sym_B <= e.sym_Bp, "decode_loss: bad sym_scale rider");
-        const int tiles = p.tiles_m * p.tiles_n;
-        int nwg = 2 * (g_cus > 0 ? g_cus : 256);          // two resident workgroups per CU
-        if (nwg > tiles) nwg = tiles;
-        DAE_LAUNCH(ka, dim3(nwg), dim3(GEMM_THREADS), DecAst::LDS_BYTES, st, p, e);
-        DAE_CHECK_LAUNCH();
-        return 0;
-    }
     if (wide) {
         k = decode_kernel_wide(e.loss_func, e.dec_act, e.x_bits != nullptr);
         static int wide_rc = [] {
@@ -3501,7 +2770,7 @@ int launch_decode_loss_n(int dtype, int Bp, int Fp, const GemmSegDesc* segs, int
     }
     dim3 grid(nblocks), block(GEMM_THREADS);
     static_assert(DecGeo<DECODE_BN_BF16>::LDS_BYTES >= 64 * 65 * 4 && DecGeo<BN>::LDS_BYTES >= 64 * 65 * 4, "rider tile must fit the decode LDS");
-    DAE_LAUNCH(k, grid, block, paird ? DECODE_PAIR_LDS : ((dtype == DAE_BF16 && !wide) ? DecGeo<DECODE_BN_BF16>::LDS_BYTES : DecGeo<BN>::LDS_BYTES), st, p, e);
+    DAE_LAUNCH(k, grid, block, (dtype == DAE_BF16 && !wide) ? DecGeo<DECODE_BN_BF16>::LDS_BYTES : DecGeo<BN>::LDS_BYTES, st, p, e);
     DAE_CHECK_LAUNCH();
     return 0;
 }
@@ -3758,16 +3027,11 @@ void set_use_glds(int nst) {
     if (nst == -5) { g_dw_pc = 2; return; }          // tests: the 160 x 128 kernel for every grid that fits one round
     if (nst == -6) { g_w8 = 0; return; }             // A/B: never the 256 x 256 / 8-MFMA-wave kernel
     if (nst == -7) { g_w8 = 1; return; }
-    if (nst <= -500000 && nst > -500128) { g_decode_dbg = -500000 - nst; return; }
     if (nst <= -100 && nst > -1000) { g_dw_rounds = g_dw_rounds_split = (-nst - 100 < 1 ? 1 : -nst - 100); return; }    // rounds of the chip the 160 x 128 dW kernel may take
-    if (nst == -13) { g_decode_pair = 0; return; }
-    if (nst == -14) { g_decode_pair = 1; return; }
     if (nst == -19) { g_gram_fused = 0; return; }
     if (nst == -20) { g_gram_fused = 1; return; }
     if (nst == -17) { g_decode_x3 = 0; return; }
     if (nst == -18) { g_decode_x3 = 1; return; }
-    if (nst == -15) { g_decode_ast = 0; return; }
-    if (nst == -16) { g_decode_ast = 1; return; }
     if (nst == -11) { g_pad_skip = 0; return; }
     if (nst == -12) { g_pad_skip = 1; return; }
     if (nst == -9) { g_pc_vec = 0; return; }         // A/B: gemm_nt_pc stores its tile as dwords straight from the accumulators
@@ -3776,7 +3040,7 @@ void set_use_glds(int nst) {
         if (gemm_init() == 0) g_cus = -nst - 1000;   // dispatch (one-round kernels, label riders, 256 x 256 slices) is exercised on any box
         return;
     }
-    g_nst = nst;
+    if (nst >= 0) g_nst = nst;                        // staging variant of the plain GEMM; an unrecognised negative code changes nothing
 }
 
 }  // namespace dae

@@ -32,7 +32,6 @@ struct DecodeEpi {
     // the loss, the bias-gradient partials and everything fp32 stay unscaled
     float op_scale;
     int no_pad_skip;          // 1: evaluate every 32-row block, padding included (A/B; set by the launcher from the process-wide switch)
-    int dbg;                  // timing probes of gemm_decode_ast (dae_set_glds(-500000 - bits); results are garbage when set): 1 no A loads, 2 no fragment reads / MFMAs, 4 no LDS-DMA, 8 no epilogue arithmetic, 16 no tile stores
     float* z_io; int64_t ldz; // cosine only: the logits' GEMM part (accumulators, before the bias) of the statistics pass, Bp x Fp fp32 in the kernel's own register order (ldz unused) -- z_mode 1: pass 1 stores them,
     int z_mode;               // z_mode 2: pass 2 LOADS them instead of running the K loop again (the same fp32 values the recomputation would produce); 0 / NULL: recompute
     int bn;                   // tile width (columns of y per workgroup): 0 = the mode's default (decode_tile_n), 128 = the wide 16-bit kernel; the partial-sum arrays
@@ -115,7 +114,6 @@ struct EncCsrLaunch {
     float* h_f32; void* h_lo; int64_t ldh; void* h_t; int64_t ldht; void* hcat_a; void* hcat_b;
     uint32_t* x_bits; int64_t ldxb; void* xct; int64_t ldt; float* rowsq;
     const LabelJob* label_job;
-    uint32_t* xtb; int64_t ldxt;   // x~^T as a bit image [Fp x ldxt words] (binary data; pre-zeroed) instead of the dense xct
     int w_f32;                     // bf16 activations only: W points at the fp32 MASTER weights [Fp x ldw] (h is then fp32-accurate)
     int w32_cols;                  // w_f32: 64 (default: one 2.6 MB slice per XCD L2) or 128 columns per workgroup
     void* h_t2;                    // split-bf16 mode: lo image of h^T [Hp x ldht] (h_t holds hi); NULL otherwise
@@ -138,7 +136,6 @@ struct StatsArgs {
 };
 struct ClearArgs {            // CSR rows whose entries were scattered into x~^T [Fp x ldt] this step
     const int64_t* indptr; const int32_t* indices; const int32_t* row_idx; int B, F; void* xct; int64_t ldt; int es;
-    uint32_t* xtb; int64_t ldxt;   // the bit image of x~^T instead of the dense one (xct == NULL): clears the word holding bit (i, col)
     void* xct2;                    // split-bf16 mode with inexact x~: the lo image of x~^T, cleared alongside (bf16; NULL otherwise)
     int rm;                        // 1: xct / xct2 are row-major x~ [Bp x ldt] (entry (i, col) at i * ldt + col), see EncCsrLaunch::xct_rm
 };
@@ -176,16 +173,10 @@ struct OptEpi {
     float gin;                // the accumulated tile is multiplied by this first (1 / op_scale of the 16-bit delta images; 0 is read as 1)
 };
 enum { DW_OPT_GRAD_ONLY = 4 };
-// x~^T handed to the dW kernel as a BIT image (binary CSR input): the A tiles of the x~^T.delta1 segment are built in LDS
-struct DwBitsArgs {
-    const uint32_t* xtb; int64_t ldxt;   // [Fp x ldxt words]: bit i of row f <=> entry (i, f) of the batch kept
-    float scale;                         // value of a kept entry
-};
-bool dw_bits_fits(int M, int N, int Bp);
+bool dw_grad_fits(int M, int N, int Bp);     // bf16 / f16: can launch_dw_opt take this shape in its gradient-only form (one round of the chip, Bp <= 1024)?
 bool dw_x3_fits(int M, int N, int Bp);       // split-bf16 mode: can launch_dw_opt_n (one 160 x 128 tile per CU, whole 64-deep K tiles) run the shape?
-// xa != NULL: segment 0 is x~^T (bit image, A0 ignored) . Bt0 = delta1^T; segment 1 = delta2^T . h^T as usual
 int launch_dw_opt(int M, int N, const void* A0, int64_t lda0, const void* Bt0, int64_t ldb0, int K0, const void* A1, int64_t lda1,
-                  const void* Bt1, int64_t ldb1, int K1, const OptEpi& e, hipStream_t st, const DwBitsArgs* xa = nullptr, bool tra = false);
+                  const void* Bt1, int64_t ldb1, int K1, const OptEpi& e, hipStream_t st, bool tra = false);
 // tra: the A operands are ROW-MAJOR batch images [K x M] (x~, delta2: lda = their leading dimension) read through transposing LDS reads (gemm_dw_pc<TRA>)
 bool dw_pc_taken(int M, int N, int K0, int K1, bool grad_only);
 // split-bf16 mode (e.Wt_lo2 set, e.W_lo2 optional); pair: segments that share their A operand run as paired stages (one A tile, two B tiles)

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define DAE_PAD 128
-#define DAE_ABI_VERSION 6   /* 6: dae_comm_* / dae_allreduce_grads / dae_dp_exchange / dae_dp_bands (the data-parallel collective in the C ABI, RCCL on the step's stream); 5: dae_storage_format (the fp16 build libdae_hip_f16.so), options x3_terms / op_scale_log2, DAE_WAIT_DW_CREATED = 100; 4: DAE_BF16X3 (split-bf16 mode), dae_gemm_nt_n; 3: dae_buffers.grad_lo, options dw_bits / encode_w32; 2: dae_step.c_row_idx, plan options, phases 4/5, sharded apply */
+#define DAE_ABI_VERSION 6   /* 6: dae_comm_* / dae_allreduce_grads / dae_dp_exchange / dae_dp_bands (the data-parallel collective in the C ABI, RCCL on the step's stream); 5: dae_storage_format (the fp16 build libdae_hip_f16.so), options x3_terms / op_scale_log2, DAE_WAIT_DW_CREATED = 100; 4: DAE_BF16X3 (split-bf16 mode), dae_gemm_nt_n; 3: dae_buffers.grad_lo, option encode_w32 (and one since removed); 2: dae_step.c_row_idx, plan options, phases 4/5, sharded apply */
 
 enum { DAE_BF16 = 0, DAE_F32 = 1,
        DAE_BF16X3 = 2 /* dae_config.dtype only: bf16 storage and MFMA, but every stored operand of the three gradient GEMMs is kept as
@@ -434,12 +434,10 @@ int      dae_plan_sync_shadows(dae_plan* p, void* stream);
  * entries, dae_encode_csr -- default on; 0 = dense MFMA encode GEMM), "encode_bits" (dense path: x~ as a bit image into the encode
  * GEMM; on by default for binary CSR + bf16), "x_bits" (clean rows as a bit image into the decode epilogue), "fused_opt" (optimizer in the
  * dW GEMM's epilogue), "tail" (bias gradients + statistics + x~^T un-scatter in one launch), "label_with_encode", "ce_literal"
- * (cross_entropy always by the reference-literal formula), "overlap" (batch_all: the decode kernel forks onto a side stream beside the Gram -> miner chain and joins before the dh
- * GEMM; off: measured slower, two cross-stream waits per step), "gather_tile" (process-wide: tile of the dense-ndarray gather, bit 0 = 128
+ * (cross_entropy always by the reference-literal formula), "gather_tile" (process-wide: tile of the dense-ndarray gather, bit 0 = 128
  * features instead of 64, bit 1 = 128 rows instead of 64; 0 is the measured best), "miner_tile" (process-wide: 1 = lane-grid batch_all kernel,
  * default), "miner_order" / "miner_ranges" / "sym_in_decode" (side jobs riding on other launches), "gram_fp32" (exact-fp32 Gram
- * matrix in bf16 mode; before dae_plan_bind only), "dw_bits" (binary CSR + bf16: x~^T reaches the dW kernel as a bit image and the A tiles of
- * its x~^T.delta1 segment are built in LDS instead of streamed -- off by default: measured slower than the dense image), "miner_pack"
+ * matrix in bf16 mode; before dae_plan_bind only), "miner_pack"
  * (batch_all workgroups = one resident round, each walking the anchor list in snake order; 0 = one workgroup per anchor), "encode_w32" (bf16 mode: the
  * sparse encode reads the fp32 master weights, so h -- and with the split-bf16 Gram matrix the triplet leg -- is fp32-accurate; default
  * on; a sharded-optimizer exchange must turn it off because only W_lo is current on every rank), "encode_w32_cols" (128 | 64 columns

@@ -309,30 +309,9 @@ def test_dw_producer_consumer_kernel_equals_four_wave_kernel(opt):
         assert _rel(u, np.asarray(v, np.float64)) < 3e-6
 
 
-@pytest.mark.parametrize("opt", ["gradient_descent", "adam"])
-@pytest.mark.parametrize("strategy", ["none", "batch_all"])
-def test_dw_bit_image_of_xt_equals_dense_xt_image(opt, strategy):
-    """Binary CSR + bf16, option dw_bits = 1: x~^T reaches the dW kernel as a BIT image and the producer waves build the A tiles of
-    the x~^T.delta1 segment in LDS; the default (0) streams the dense bf16 x~^T image.  Same MFMA operands in the same order:
-    statistics, gradients and parameters are bit-identical -- and the bit image is clean again after every step."""
-    from dae_rnn_news_recommendation_amd import _lib as L
-    lib = L.load()
-    try:
-        lib.dae_set_glds(-5)
-        a, _, pa = _run_case("bf16", strategy, "cross_entropy", ("sigmoid", "sigmoid"), opt, steps=3, seed=61, options={"dw_bits": 1})
-        b, _, pb = _run_case("bf16", strategy, "cross_entropy", ("sigmoid", "sigmoid"), opt, steps=3, seed=61, options={"dw_bits": 0})
-    finally:
-        lib.dae_set_glds(-4)
-    for (_, sa, dWa, dbha, dbva), (_, sb, dWb, dbhb, dbvb) in zip(a, b):
-        assert np.array_equal(sa[:6], sb[:6])
-        assert np.array_equal(dWa, dWb) and np.array_equal(dbha, dbhb) and np.array_equal(dbva, dbvb)
-    for u, v in zip(pa, pb):
-        assert np.array_equal(np.asarray(u), np.asarray(v))
-
-
-def test_dw_bit_image_dense_rows_and_global_atomics_fallback():
-    """A batch whose popular features are kept in most rows (dense bit words take the arithmetic expansion) and F = 30000 (the
-    LDS byte image of x~^T does not fit: global atomic OR instead) against the oracle."""
+def test_dw_dense_rows_and_wide_feature_count_match_oracle():
+    """A batch whose popular features are kept in most rows (dense columns of x~^T) and F = 30000, on the 160 x 128 dW kernel, against the
+    oracle -- and the dense x~^T image is clean again after the step (the step tail un-scatters what the encode launch wrote)."""
     from dae_rnn_news_recommendation_amd import _lib as L
     from dae_rnn_news_recommendation_amd.engine import Engine
     rng = np.random.default_rng(64)
@@ -343,7 +322,6 @@ def test_dw_bit_image_dense_rows_and_global_atomics_fallback():
         lab = rng.integers(0, 3, N).astype(np.int32)
         W0 = torch.as_tensor(rng.uniform(-0.05, 0.05, (F, H)).astype(np.float32)).to(torch.bfloat16).float().numpy()
         eng = Engine(F, H, B, dtype="bf16", triplet="batch_all", learning_rate=0.05)
-        eng.set_option("dw_bits", 1)
         L.load().dae_set_glds(-5)
         try:
             eng.upload_csr(m); eng.set_params(W0)
@@ -357,13 +335,12 @@ def test_dw_bit_image_dense_rows_and_global_atomics_fallback():
                                dt=np.float64)
         dW, dbh, dbv = eng.grads()
         assert _rel(dW, r["dW"]) < 2e-2, (F, _rel(dW, r["dW"]))
-        assert int(eng.buffer("xtb", (eng.Fp, eng.Bpm // 32), torch.int32).abs().sum().item()) == 0      # cleaned by the step tail
+        assert int(eng.buffer("xct", (eng.Fp, eng.Bpm), torch.int16).ne(0).sum().item()) == 0      # cleaned by the step tail
 
 
-def test_dw_bit_image_with_decay_scale_matches_oracle():
-    """corr_type 'decay' (scale 0.7 on every stored entry, utils.py:147-159): the built A tiles carry bf16(scale) per set bit."""
-    out, ref, got = _run_case("bf16", "batch_all", "cross_entropy", ("sigmoid", "sigmoid"), "gradient_descent", steps=2, seed=62, scale=0.7,
-                              options={"dw_bits": 1})
+def test_dw_with_decay_scale_matches_oracle():
+    """corr_type 'decay' (scale 0.7 on every stored entry, utils.py:147-159): x~^T carries bf16(scale) per kept entry into the dW kernel."""
+    out, ref, got = _run_case("bf16", "batch_all", "cross_entropy", ("sigmoid", "sigmoid"), "gradient_descent", steps=2, seed=62, scale=0.7)
     for r, st, dW, dbh, dbv in out:
         assert abs(st[0] - r["cost"]) <= 3e-4 * abs(r["cost"])
         assert _rel(dW, r["dW"]) < 2e-2 and _rel(dbh, r["dbh"]) < 2e-2

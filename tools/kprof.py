@@ -22,7 +22,7 @@ ap.add_argument("--lib", default="", help="alternative libdae_hip build (probe v
 ap.add_argument("--lib-f16", default="", help="alternative libdae_hip_f16 build (A/B of two builds on one box; tools only)")
 ap.add_argument("--queued", action="store_true", help="queued event pairs (dae_plan_profile mode 2): no host wait between the launches of a step")
 ap.add_argument("--stamps", action="store_true", help="pairs stamped by the dispatch itself (dae_plan_profile mode 3): the kernel's own duration")
-ap.add_argument("--glds", type=int, action="append", default=[], help="dae_set_glds code(s), e.g. -8 = dW on the producer/consumer kernel")
+ap.add_argument("--glds", type=int, action="append", default=[], help="dae_set_glds code(s), e.g. -5 = dW on the producer/consumer kernel for every grid that fits one round")
 a = ap.parse_args()
 if a.lib:
     L.LIB_PATH = os.path.abspath(a.lib)
