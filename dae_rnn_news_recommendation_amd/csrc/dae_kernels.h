@@ -76,6 +76,10 @@ int launch_gemm_f32out_n(int dtype, int M, int N, const GemmSegDesc* segs, int n
 // K slices the 256 x 256 / 8-MFMA-wave kernel wants for this shape (0: the shape stays on the 128 x 128 kernels); see dae_gemm.hip
 int gemm_w8_splits(int dtype, int M, int N, int ktiles);
 enum { GEMM_ROLE_GENERIC = 0, GEMM_ROLE_ENCODE = 1, GEMM_ROLE_DH = 2, GEMM_ROLE_DW = 3, GEMM_ROLE_GRAM = 4 };
+// rows of X normalised as dae_pairwise_similarity does (norm option, then l2 when cosine) into the zero-padded fp32 image Y [Np x ldy]
+// (dae_similarity.hip: row_normalize_kernel)
+int launch_row_normalize(const float* X, int64_t ldx, int N, int D, int norm, int cosine, float* Y, int64_t ldy, int Dp, int Np,
+                         hipStream_t st);
 int launch_decode_loss(int dtype, int Bp, int Fp, int Hp, const void* h_lo, int64_t ldh, const void* W_lo, int64_t ldw,
                        const DecodeEpi& e, hipStream_t st);
 int launch_decode_loss_n(int dtype, int Bp, int Fp, const GemmSegDesc* segs, int nsegs, const DecodeEpi& e, hipStream_t st);

@@ -50,6 +50,14 @@ __global__ __launch_bounds__(256) void row_normalize_kernel(const float* __restr
     for (int j = tid; j < Dp; j += 256) y[j] = j < D ? (x[j] * s1) * s2 : 0.f;
 }
 
+// the padded operand image Y [Np x ldy] of X for dae_topk_similarity (dae_topk.hip), by the kernel above
+int launch_row_normalize(const float* X, int64_t ldx, int N, int D, int norm, int cosine, float* Y, int64_t ldy, int Dp, int Np,
+                         hipStream_t st) {
+    DAE_LAUNCH(row_normalize_kernel, dim3(Np), dim3(256), 0, st, X, ldx, N, D, norm, cosine, Y, ldy, Dp);
+    DAE_CHECK_LAUNCH();
+    return 0;
+}
+
 __global__ void zero_diag_kernel(float* __restrict__ out, int64_t ldo, int N) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < N) out[(int64_t)i * ldo + i] = 0.f;

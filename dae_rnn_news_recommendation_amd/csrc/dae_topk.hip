@@ -1,0 +1,228 @@
+// dae_topk.hip -- the k most similar corpus rows of every query row, without the N x N matrix (dae_topk_similarity).
+//
+// The scores are those of dae_pairwise_similarity: rows normalised by row_normalize_kernel (dae_similarity.hip) into
+// zero-padded fp32 operand images, products on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32) of dae_gemm_tile.h.  What is
+// new is the epilogue: the 128 x 128 score tile never leaves the CU, only the candidates that enter a row's running top-k.
+//
+// Order.  Every (score, index) pair maps to one 64-bit key, score_key(score) << 32 | ~index: a larger key is a better pair,
+// i.e. score descending, then index ascending -- a total order, so the result does not depend on tiling, on the corpus
+// split or on the grid, and is bit-identical run to run.  Key 0 (below every finite score) marks an empty slot.
+//
+// Phase A, topk_tiles_kernel: grid = (query tiles) x (corpus slices), 256 threads (4 waves).  A workgroup walks the
+// 128-column corpus tiles of its slice; per tile
+//   1. gemm_mainloop<float, 2>: the 128 x 128 fp32 score tile in the accumulators (LDS: the 2 x 32 KiB staging ring);
+//   2. the accumulators go to LDS as a [128][128] fp32 tile, over the dead staging ring (64 KiB);
+//   3. wave w owns query rows 32w .. 32w+31.  Per row the 64 lanes hold 2 columns each and compare their keys with the
+//      row's threshold (the key of its current k-th entry, LDS); a ballot finds the few that beat it, and only then is
+//      the row's sorted list (k keys in the global partial buffer, L2-resident) merged with them: every old entry moves
+//      down by the number of candidates above it, every candidate lands at (old entries above it: binary search) +
+//      (candidates above it), positions >= k drop out.
+// LDS: 64 KiB tile / staging + 1 KiB thresholds + 0.5 KiB list lengths + 4 x 2 KiB merge scratch = 73.5 KiB, two
+// workgroups per CU.  Phase B, topk_merge_kernel: one workgroup per query row merges the `splits` sorted lists the same
+// way (each entry's rank = its position + the entries above it in the other lists) and writes idx / score.
+#include "dae_gemm_tile.h"
+
+namespace dae {
+
+constexpr int TOPK_MAX = 128;
+constexpr int TOPK_SLOTS = 512;            // workgroups in flight on the MI355X: 256 CUs x 2 (the slice count is sized for it)
+constexpr int TOPK_MAX_SPLITS = 32;        // bounds phase B's LDS (32 lists x 128 keys x 8 B)
+constexpr int TOPK_TILE_BYTES = BM * BN * 4;
+constexpr int TOPK_LDS = TOPK_TILE_BYTES + 128 * 8 + 128 * 4 + 4 * 2 * TOPK_MAX * 8;
+
+__device__ __forceinline__ uint64_t topk_key(float s, int j) {
+    if (s == 0.f) s = 0.f;                                      // -0 and +0 are one score
+    const uint32_t u = __float_as_uint(s);
+    const uint32_t h = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((uint64_t)h << 32) | (uint32_t)~(uint32_t)j;
+}
+
+// number of keys of the descending list L[0, n) above x
+__device__ __forceinline__ int keys_above(const uint64_t* L, int n, uint64_t x) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int m = (lo + hi) >> 1;
+        if (L[m] > x) lo = m + 1; else hi = m;
+    }
+    return lo;
+}
+
+struct TopkParams {
+    GemmParams g;                 // one K segment: A = query image, Bt = corpus image
+    int Nq, Nc, Nqp, k, exclude_self, splits, ctiles;
+    uint64_t* part;               // [splits][Nqp][k] sorted keys
+    int* part_n;                  // [splits][Nqp] valid keys per list
+};
+
+__global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams p) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    float* tile = reinterpret_cast<float*>(lds);
+    uint64_t* th = reinterpret_cast<uint64_t*>(lds + TOPK_TILE_BYTES);
+    int* len = reinterpret_cast<int*>(th + 128);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint64_t* Ls = reinterpret_cast<uint64_t*>(len + 128) + wave * 2 * TOPK_MAX;     // this wave's copy of the list being merged
+    uint64_t* Cs = Ls + TOPK_MAX;                                                    // and its candidates
+    const int split = blockIdx.x % p.splits, qt = blockIdx.x / p.splits;
+    const int ct0 = (int)((int64_t)p.ctiles * split / p.splits), ct1 = (int)((int64_t)p.ctiles * (split + 1) / p.splits);
+    const int k = p.k;
+    if (tid < 128) { th[tid] = 0; len[tid] = 0; }
+    const int wm = wave >> 1, wn = wave & 1, g = lane >> 5, c = lane & 31;
+    const uint64_t below = (1ull << lane) - 1ull;
+    for (int ct = ct0; ct < ct1; ++ct) {
+        f32x16 acc[2][2];
+        gemm_mainloop<float, 2>(p.g, qt, ct, 0, p.g.ktiles_total, lds, acc);
+        __syncthreads();                                        // every wave is done with the staging ring
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    tile[(wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g) * BN + wn * 64 + nt * 32 + c] = acc[mt][nt][r];
+        __syncthreads();
+        const int j0 = ct * BN + lane, j1 = j0 + 64;
+        for (int rr = 0; rr < 32; ++rr) {
+            const int row = wave * 32 + rr, gi = qt * BM + row;
+            if (gi >= p.Nq) break;
+            const uint64_t t = th[row];
+            const bool ok0 = j0 < p.Nc && !(p.exclude_self && j0 == gi), ok1 = j1 < p.Nc && !(p.exclude_self && j1 == gi);
+            const uint64_t c0 = ok0 ? topk_key(tile[row * BN + lane], j0) : 0, c1 = ok1 ? topk_key(tile[row * BN + 64 + lane], j1) : 0;
+            const bool in0 = c0 > t, in1 = c1 > t;
+            const uint64_t b0 = __ballot(in0), b1 = __ballot(in1);
+            if ((b0 | b1) == 0) continue;
+            // ---- merge the candidates into the row's list ----
+            const int n0 = __popcll(b0), n = n0 + __popcll(b1);
+            const int m = len[row];
+            uint64_t* L = p.part + ((int64_t)split * p.Nqp + gi) * k;
+            const uint64_t e0 = lane < m ? L[lane] : 0, e1 = lane + 64 < m ? L[lane + 64] : 0;
+            if (in0) Cs[__popcll(b0 & below)] = c0;
+            if (in1) Cs[n0 + __popcll(b1 & below)] = c1;
+            if (lane < m) Ls[lane] = e0;
+            if (lane + 64 < m) Ls[lane + 64] = e1;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            int r0 = lane, r1 = lane + 64, q0 = 0, q1 = 0;      // new positions: old entries / candidates
+            for (int q = 0; q < n; ++q) {
+                const uint64_t x = Cs[q];
+                r0 += x > e0; r1 += x > e1; q0 += x > c0; q1 += x > c1;
+            }
+            if (in0) q0 += keys_above(Ls, m, c0);
+            if (in1) q1 += keys_above(Ls, m, c1);
+            if (lane < m && r0 < k) L[r0] = e0;
+            if (lane + 64 < m && r1 < k) L[r1] = e1;
+            if (in0 && q0 < k) L[q0] = c0;
+            if (in1 && q1 < k) L[q1] = c1;
+            const int m2 = min(k, m + n);
+            if (m2 == k) {                                      // the k-th entry is the new threshold
+                if (lane < m && r0 == k - 1) th[row] = e0;
+                if (lane + 64 < m && r1 == k - 1) th[row] = e1;
+                if (in0 && q0 == k - 1) th[row] = c0;
+                if (in1 && q1 == k - 1) th[row] = c1;
+            }
+            if (lane == 0) len[row] = m2;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // Ls / Cs are rewritten by the next row's merge
+            __builtin_amdgcn_wave_barrier();
+        }
+        __syncthreads();                                        // the tile is the next K loop's staging ring
+    }
+    if (tid < 128 && qt * BM + tid < p.Nq) p.part_n[(int64_t)split * p.Nqp + qt * BM + tid] = len[tid];
+}
+
+__global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* __restrict__ part, const int* __restrict__ part_n, int Nqp,
+                                                         int splits, int k, int32_t* __restrict__ idx, float* __restrict__ score,
+                                                         int64_t ldk) {
+    __shared__ uint64_t keys[TOPK_MAX_SPLITS * TOPK_MAX];
+    __shared__ int off[TOPK_MAX_SPLITS + 1];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) {
+        off[0] = 0;
+        for (int s = 0; s < splits; ++s) off[s + 1] = off[s] + part_n[(int64_t)s * Nqp + row];
+    }
+    __syncthreads();
+    const int total = off[splits];
+    for (int s = 0; s < splits; ++s) {
+        const uint64_t* L = part + ((int64_t)s * Nqp + row) * k;
+        for (int p = tid; p < off[s + 1] - off[s]; p += 256) keys[off[s] + p] = L[p];
+    }
+    __syncthreads();
+    int32_t* oi = idx + (int64_t)row * ldk;
+    float* os = score + (int64_t)row * ldk;
+    for (int e = tid; e < total; e += 256) {
+        int s = 0;
+        while (e >= off[s + 1]) ++s;
+        const uint64_t x = keys[e];
+        int rank = e - off[s];
+        for (int t = 0; t < splits; ++t)
+            if (t != s) rank += keys_above(keys + off[t], off[t + 1] - off[t], x);
+        if (rank < k) {
+            const uint32_t h = (uint32_t)(x >> 32);
+            oi[rank] = (int32_t)~(uint32_t)x;
+            os[rank] = __uint_as_float((h & 0x80000000u) ? (h & 0x7fffffffu) : ~h);
+        }
+    }
+    for (int r = total + tid; r < k; r += 256) { oi[r] = -1; os[r] = -__builtin_inff(); }
+}
+
+static int topk_splits(int Nq, int Nc) {
+    const int64_t qt = pad128(Nq) / BM, ct = pad128(Nc) / BN;
+    int64_t s = TOPK_SLOTS / qt;
+    if (s > ct) s = ct;
+    if (s > TOPK_MAX_SPLITS) s = TOPK_MAX_SPLITS;
+    return s < 1 ? 1 : (int)s;
+}
+static inline uint64_t al256(uint64_t b) { return (b + 255) / 256 * 256; }
+
+}  // namespace dae
+
+using namespace dae;
+
+extern "C" uint64_t dae_topk_similarity_workspace(int32_t Nq, int32_t Nc, int32_t D, int32_t k) {
+    if (Nq <= 0 || Nc <= 0 || D <= 0 || k <= 0) return 0;
+    const uint64_t Nqp = pad128(Nq), Ncp = pad128(Nc), Dp = pad128(D), s = topk_splits(Nq, Nc);
+    return al256(Nqp * Dp * 4) + al256(Ncp * Dp * 4) + al256(s * Nqp * (uint64_t)k * 8) + al256(s * Nqp * 4);
+}
+
+extern "C" int dae_topk_similarity(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                                   int32_t norm, int32_t metric, int32_t k, int32_t exclude_self, int32_t* idx, float* score,
+                                   int64_t ldk, void* workspace, uint64_t workspace_bytes, void* stream) {
+    DAE_CHECK_ARG(Q && idx && score && workspace && Nq > 0 && D > 0 && ldq >= D, "topk_similarity: bad input");
+    DAE_CHECK_ARG(C ? (Nc > 0 && ldc >= D) : Nc == Nq, "topk_similarity: bad corpus (C == NULL means the corpus is Q: pass Nc == Nq)");
+    DAE_CHECK_ARG(norm >= 0 && norm <= 3, "topk_similarity: norm must be 0 (none), 1 (l1), 2 (l2) or 3 (max)");
+    DAE_CHECK_ARG(metric == 0 || metric == 1, "topk_similarity: metric must be 0 (cosine) or 1 (linear kernel)");
+    DAE_CHECK_ARG(k >= 1 && k <= TOPK_MAX, "topk_similarity: k must be in 1..%d (got %d)", TOPK_MAX, k);
+    DAE_CHECK_ARG(!exclude_self || !C, "topk_similarity: exclude_self needs C == NULL (the corpus is Q itself)");
+    DAE_CHECK_ARG(ldk >= k, "topk_similarity: ldk (%lld) must be >= k (%d)", (long long)ldk, k);
+    const int64_t Nqp = pad128(Nq), Ncp = pad128(Nc), Dp = pad128(D);
+    DAE_CHECK_ARG(Nqp * Dp * 4 < (1ll << 32) && Ncp * Dp * 4 < (1ll << 32), "topk_similarity: an operand image exceeds 4 GiB");
+    DAE_CHECK_ARG(workspace_bytes >= dae_topk_similarity_workspace(Nq, Nc, D, k),
+                  "topk_similarity: workspace too small (%llu < %llu bytes)", (unsigned long long)workspace_bytes,
+                  (unsigned long long)dae_topk_similarity_workspace(Nq, Nc, D, k));
+    DAE_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "topk_similarity: workspace must be 256-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int splits = topk_splits(Nq, Nc);
+    char* w = (char*)workspace;
+    float* Qi = (float*)w;           w += al256(Nqp * Dp * 4);
+    float* Ci = C ? (float*)w : Qi;  w += al256(Ncp * Dp * 4);
+    uint64_t* part = (uint64_t*)w;   w += al256((uint64_t)splits * Nqp * k * 8);
+    int* part_n = (int*)w;
+    const int cosine = metric == 0 ? 1 : 0;
+    if (int rc = launch_row_normalize(Q, ldq, Nq, D, norm, cosine, Qi, Dp, (int)Dp, (int)Nqp, st)) return rc;
+    if (C)
+        if (int rc = launch_row_normalize(C, ldc, Nc, D, norm, cosine, Ci, Dp, (int)Dp, (int)Ncp, st)) return rc;
+    TopkParams p;
+    memset(&p, 0, sizeof(p));
+    p.g.seg[0].A = (const char*)Qi; p.g.seg[0].Bt = (const char*)Ci;
+    p.g.seg[0].lda_b = p.g.seg[0].ldb_b = Dp * 4;
+    p.g.seg[0].ktiles = p.g.ktiles_total = (int)(Dp * 4 / BKB);
+    p.g.nseg = 1; p.g.splits = 1; p.g.out_scale = 1.f;
+    p.Nq = Nq; p.Nc = Nc; p.Nqp = (int)Nqp; p.k = k; p.exclude_self = exclude_self ? 1 : 0; p.splits = splits;
+    p.ctiles = (int)(Ncp / BN); p.part = part; p.part_n = part_n;
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_tiles_kernel),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, TOPK_LDS);
+    DAE_CHECK_HIP(attr);
+    DAE_LAUNCH(topk_tiles_kernel, dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), TOPK_LDS, st, p);
+    DAE_CHECK_LAUNCH();
+    DAE_LAUNCH(topk_merge_kernel, dim3(Nq), dim3(256), 0, st, part, part_n, (int)Nqp, splits, k, idx, score, ldk);
+    DAE_CHECK_LAUNCH();
+    return 0;
+}

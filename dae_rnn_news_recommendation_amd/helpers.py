@@ -7,7 +7,9 @@
 ``main_autoencoder.py:307-317`` runs six times right after training (embeddings, binary BoW, TF-IDF; train and
 validation).  Same name, arguments, assert and return value; the normalisation, the N x N product (exact-fp32 MFMA) and
 the diagonal fill run on the MI355X through ``dae_pairwise_similarity``.  No CPU implementation: without the built
-library / a GPU this raises."""
+library / a GPU this raises.
+* ``most_similar`` -- top-k retrieval by the same scores without the N x N matrix (``dae_topk_similarity``), and
+  ``label_precision_at_k`` (host code) to score such a result against labels."""
 from __future__ import annotations
 
 import numpy as np
@@ -153,7 +155,100 @@ def pairwise_similarity(in_df, norm="", metric="cosine", set_diagonal_zero=True,
     return res.cpu().numpy()
 
 
-_STAT_KEYS = ("auroc", "n_related", "n_unrelated", "mean_related", "mean_unrelated")
+def _device_matrix(torch, data, dev):
+    """A 2-D contiguous float32 CUDA tensor of ``data`` (ndarray, list, scipy.sparse -- densified on the device -- or tensor)."""
+    if isinstance(data, torch.Tensor):
+        X = data.to(device=dev, dtype=torch.float32)
+    else:
+        import scipy.sparse as sp
+        if sp.issparse(data):
+            import warnings
+            m = data.tocsr().astype(np.float32)
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")                        # torch: "sparse CSR tensor support is in beta state"
+                X = _csr_to_dense(torch, m, dev)
+        else:
+            X = torch.as_tensor(np.asarray(data, dtype=np.float32)).to(dev)
+    if X.dim() != 2:
+        raise ValueError("Expected 2D array")
+    return X.contiguous()
+
+
+def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candidates=None, *, return_tensor=False, device=None):
+    """The ``k`` most similar rows of ``candidates`` (default: ``in_df`` itself) for every row of ``in_df``, by the scores
+    ``pairwise_similarity`` would give (same ``norm`` / ``metric``, same exact-fp32 products), without the N x N matrix:
+    ``dae_topk_similarity`` keeps a running top-k per row inside the GEMM's epilogue.
+
+    Both inputs take the containers of ``pairwise_similarity`` (ndarray, list, scipy.sparse, CUDA tensor).  ``exclude_self``
+    (default: True without ``candidates``, False with them) drops each row's own index -- unlike ``set_diagonal_zero``, which
+    keeps the self pair at score 0.  Rows are ordered by score descending, ties by index ascending; with fewer than ``k``
+    candidates the tail is index -1, score -inf.  1 <= k <= 128.  Returns ``(indices int64 [N x k], scores float32 [N x k])``
+    as ndarrays, or as CUDA tensors with ``return_tensor=True``."""
+    import torch
+    assert metric in ["cosine", "linear kernel"]                      # helpers.py:34
+    if norm not in _NORMS:
+        raise ValueError(f"'{norm}' is not a supported norm")         # sklearn.preprocessing.normalize's message
+    if exclude_self is None:
+        exclude_self = candidates is None
+    elif exclude_self and candidates is not None:
+        raise ValueError("exclude_self=True needs candidates=None (the self pair exists only when the corpus is in_df itself)")
+    lib = L.load()
+    dev = torch.device("cuda" if device is None else device)
+    Q = _device_matrix(torch, in_df, dev)
+    Cm = None if candidates is None else _device_matrix(torch, candidates, dev)
+    Nq, D = int(Q.shape[0]), int(Q.shape[1])
+    if Cm is not None and int(Cm.shape[1]) != D:
+        raise ValueError(f"candidates have {int(Cm.shape[1])} columns, in_df has {D}")
+    Nc = Nq if Cm is None else int(Cm.shape[0])
+    k = int(k)
+    idx = torch.empty((Nq, max(k, 1)), dtype=torch.int32, device=dev)
+    score = torch.empty((Nq, max(k, 1)), dtype=torch.float32, device=dev)
+    ws_bytes = int(lib.dae_topk_similarity_workspace(Nq, Nc, D, k))
+    ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
+    off = (-ws.data_ptr()) % 256
+    import ctypes
+    with torch.cuda.device(dev):
+        L.call("dae_topk_similarity", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D, _NORMS[norm],
+               _METRICS[metric], k, 1 if exclude_self else 0, L.ptr(idx), L.ptr(score), idx.stride(0),
+               ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
+    idx = idx.long()
+    if return_tensor:
+        return idx, score
+    return idx.cpu().numpy(), score.cpu().numpy()
+
+
+def _label_keys(labels):
+    """Labels as float64 (numeric) with a validity mask: negative / NaN labels are missing, as in visualize_pairwise_similarity."""
+    lab = np.asarray(labels)
+    lab = lab.reshape(lab.shape[0], -1)[:, 0] if lab.ndim > 1 else lab
+    if lab.dtype.kind in "biuf":
+        v = lab.astype(np.float64)
+        return v, np.isfinite(v) & (v >= 0)
+    return lab, np.array([x is not None for x in lab], dtype=bool)
+
+
+def label_precision_at_k(indices, labels, candidate_labels=None):
+    """Precision@k of a retrieval result: the mean, over the queries, of the fraction of each query's ``k`` returned indices
+    whose label equals the query's label.  ``labels`` are the query labels; ``candidate_labels`` those of the corpus the
+    indices point into (default: ``labels``, i.e. the corpus is the query set).  Queries whose label is negative or NaN
+    are skipped; an index of -1 (fewer than k candidates) or a candidate with a missing label counts as a miss.  Host code.
+    Returns ``(precision, number of queries counted)``; precision is NaN when no query counts."""
+    idx = np.asarray(indices)
+    if idx.ndim != 2:
+        raise ValueError("indices must be [n_queries x k]")
+    ql, qv = _label_keys(labels)
+    cl, cv = (ql, qv) if candidate_labels is None else _label_keys(candidate_labels)
+    if ql.shape[0] != idx.shape[0]:
+        raise ValueError(f"{ql.shape[0]} labels for {idx.shape[0]} queries")
+    if idx.shape[1] == 0 or not qv.any():
+        return float("nan"), 0
+    safe = np.where(idx >= 0, idx, 0)
+    hit = (idx >= 0) & cv[safe] & (cl[safe] == ql[:, None])
+    frac = hit[qv].mean(axis=1)
+    return float(frac.mean()), int(qv.sum())
+
+
+_STAT_KEYS = ("auroc","n_related", "n_unrelated", "mean_related", "mean_unrelated")
 
 
 def visualize_pairwise_similarity(labels, pairwise_similarity_metrics, plot='boxplot', title=None, figsize=(16, 9), save_path=None,

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define DAE_PAD 128
-#define DAE_ABI_VERSION 6   /* 6: dae_comm_* / dae_allreduce_grads / dae_dp_exchange / dae_dp_bands (the data-parallel collective in the C ABI, RCCL on the step's stream); 5: dae_storage_format (the fp16 build libdae_hip_f16.so), options x3_terms / op_scale_log2, DAE_WAIT_DW_CREATED = 100; 4: DAE_BF16X3 (split-bf16 mode), dae_gemm_nt_n; 3: dae_buffers.grad_lo, option encode_w32 (and one since removed); 2: dae_step.c_row_idx, plan options, phases 4/5, sharded apply */
+#define DAE_ABI_VERSION 7   /* 7: dae_topk_similarity / dae_topk_similarity_workspace (fused similarity + top-k retrieval); 6:dae_comm_* / dae_allreduce_grads / dae_dp_exchange / dae_dp_bands (the data-parallel collective in the C ABI, RCCL on the step's stream); 5: dae_storage_format (the fp16 build libdae_hip_f16.so), options x3_terms / op_scale_log2, DAE_WAIT_DW_CREATED = 100; 4: DAE_BF16X3 (split-bf16 mode), dae_gemm_nt_n; 3: dae_buffers.grad_lo, option encode_w32 (and one since removed); 2: dae_step.c_row_idx, plan options, phases 4/5, sharded apply */
 
 enum { DAE_BF16 = 0, DAE_F32 = 1,
        DAE_BF16X3 = 2 /* dae_config.dtype only: bf16 storage and MFMA, but every stored operand of the three gradient GEMMs is kept as
@@ -409,6 +409,27 @@ uint64_t dae_pairwise_similarity_workspace(int32_t N, int32_t D);
 int dae_pairwise_similarity(const float* X, int64_t ldx, int32_t N, int32_t D, int32_t norm, int32_t metric,
                             int32_t zero_diagonal, float* out, int64_t ldo, void* workspace,
                             uint64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
+ * Retrieval: the k most similar corpus rows of every query row, without an N x N matrix (the top-k that
+ * helpers.pairwise_similarity + a sort would give; helpers.most_similar).
+ *   Q [Nq x ldq] fp32 queries; C [Nc x ldc] fp32 corpus, or C == NULL: the corpus is Q itself (pass Nc == Nq).
+ *   norm, metric: exactly as dae_pairwise_similarity (0 none / 1 'l1' / 2 'l2' / 3 'max'; 0 'cosine' / 1 'linear kernel').
+ *   Score of (i, j): the exact-fp32 MFMA dot product of the two normalised rows -- the value dae_pairwise_similarity writes.
+ *   Output, per query row i: idx[i * ldk + r] (int32 corpus row) and score[i * ldk + r] (fp32), r < k, ldk >= k, ordered by
+ *   score descending, then index ascending (a total order: the result is bit-identical run to run and independent of the
+ *   grid).  When fewer than k candidates exist the tail is idx = -1, score = -inf.
+ *   exclude_self (only with C == NULL) drops the pair j == i.  Unlike the reference's set_diagonal_zero, which keeps
+ *   the self pair at score 0 in the matrix, the self pair is removed from the candidates altogether.
+ *   1 <= k <= 128.  Non-finite inputs are out of scope (their order is undefined).
+ *   workspace: dae_topk_similarity_workspace(Nq, Nc, D, k) bytes, 256-byte aligned: the two normalised operand images
+ *   plus per-row partial lists, O(Nq * splits * k) -- no N x N buffer.  Each operand image must stay below 4 GiB.
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_topk_similarity_workspace(int32_t Nq, int32_t Nc, int32_t D, int32_t k);
+int dae_topk_similarity(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc,
+                        int32_t D, int32_t norm, int32_t metric, int32_t k, int32_t exclude_self,
+                        int32_t* idx, float* score, int64_t ldk, void* workspace, uint64_t workspace_bytes,
+                        void* stream);
 
 /* Related / unrelated pair statistics of an N x N similarity matrix: the numbers behind
  * helpers.visualize_pairwise_similarity (helpers.py:79-135) -- AUROC of "same label" vs "different label" over the strict

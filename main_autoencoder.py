@@ -78,6 +78,10 @@ def build_parser():
     p.add_argument("--data_parallel", default=False, **b)
     p.add_argument("--similarity", default=True, **b,
                    help="after training: the N x N cosine similarities the reference computes (:307-317), on the device")
+    p.add_argument("--top_k", type=int, default=0,
+                   help="K > 0: after training, the K most similar train articles of every train (and validation) article, written to "
+                        "article_encoded[_validate]_top{K}.npz, with precision@K of the input vectors and of the embedding when labels exist "
+                        "(no N x N matrix: works with --similarity False on corpora too large for it)")
     return p
 
 
@@ -142,6 +146,33 @@ def evaluate_similarity(a, trX, vlX, trY, vlY, emb, emb_v, plot_dir=None):
         del S
     print('calculate similarity done')
     return rows
+
+
+def evaluate_top_k(a, trX, vlX, trY, vlY, emb, emb_v, data_dir):
+    """--top_k K: the K nearest train articles of every train article (itself excluded) and of every validation article, by
+    the cosine of the embeddings (helpers.most_similar, no N x N matrix), saved as ``indices`` / ``scores`` in
+    article_encoded[_validate]_top{K}.npz; with labels, precision@K of the input vectors (the metric of evaluate_similarity)
+    against that of the embedding."""
+    from dae_rnn_news_recommendation_amd import helpers
+    K = a.top_k
+    print('calculate top %d' % K)
+    metric_in = 'linear kernel' if a.input_format == 'tfidf' else 'cosine'
+    sets = [('train', trX, emb, trY, None, None, None, 'article_encoded_top%d.npz' % K)]
+    if emb_v is not None:
+        sets.append(('validate', vlX, emb_v, vlY, trX, emb, trY, 'article_encoded_validate_top%d.npz' % K))
+    out = {}
+    for name, X, E, y, Xc, Ec, yc, fname in sets:
+        idx, score = helpers.most_similar(E, k=K, candidates=Ec)
+        np.savez(data_dir + fname, indices=idx, scores=score)
+        out[name] = idx
+        print('  %-9s %5d queries -> %s' % (name, idx.shape[0], fname))
+        if y is not None:
+            idx_in, _ = helpers.most_similar(X, k=K, metric=metric_in, candidates=Xc)
+            p_in, n = helpers.label_precision_at_k(idx_in, y, yc)
+            p_emb, _ = helpers.label_precision_at_k(idx, y, yc)
+            print('  precision@%d %-9s input vectors %.4f  embedding %.4f  (%d queries)' % (K, name, p_in, p_emb, n))
+    print('calculate top %d done' % K)
+    return out
 
 
 # artefact names of the reference's data directory (main_autoencoder.py:227-244, restored at :162-174)
@@ -221,6 +252,8 @@ def main(argv=None):
             helpers.save_file(pd.DataFrame({'label_' + a.label: vlY}), model.tsv_dir + 'article_label_validate.tsv')
     if a.similarity and dp.rank() == 0:
         evaluate_similarity(a, trX, vlX, trY, vlY, emb, emb_v, model.plot_dir)
+    if a.top_k > 0 and dp.rank() == 0:
+        evaluate_top_k(a, trX, vlX, trY, vlY, emb, emb_v, model.data_dir)
     if model.samples_per_sec:
         print('training throughput: %.0f samples/s over %d epochs; embeddings %s -> %s' %
               (model.samples_per_sec, a.num_epochs, emb.shape, model.data_dir))
