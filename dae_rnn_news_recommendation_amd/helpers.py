@@ -9,7 +9,10 @@ validation).  Same name, arguments, assert and return value; the normalisation, 
 the diagonal fill run on the MI355X through ``dae_pairwise_similarity``.  No CPU implementation: without the built
 library / a GPU this raises.
 * ``most_similar`` -- top-k retrieval by the same scores without the N x N matrix (``dae_topk_similarity``), and
-  ``label_precision_at_k`` (host code) to score such a result against labels."""
+  ``label_precision_at_k`` (host code) to score such a result against labels.
+* ``similar_pairs`` -- near-duplicate search: every pair scoring at least a threshold, without the N x N matrix
+  (``dae_threshold_pairs``); ``duplicate_groups`` and ``duplicate_pair_precision`` (host code) turn the pairs into the
+  de-duplication rule "keep the first article of each story" and score them against labels."""
 from __future__ import annotations
 
 import numpy as np
@@ -246,6 +249,107 @@ def label_precision_at_k(indices, labels, candidate_labels=None):
     hit = (idx >= 0) & cv[safe] & (cl[safe] == ql[:, None])
     frac = hit[qv].mean(axis=1)
     return float(frac.mean()), int(qv.sum())
+
+
+def similar_pairs(in_df, threshold, norm="", metric="cosine", candidates=None, *, max_pairs=None, return_tensor=False, device=None):
+    """Every pair (i, j) whose ``pairwise_similarity`` score (same ``norm`` / ``metric``, same exact-fp32 products) is at least
+    ``threshold``, without the N x N matrix: ``dae_threshold_pairs`` filters the score tiles in the GEMM's epilogue.
+
+    Without ``candidates`` the corpus is ``in_df`` itself and the strict lower triangle is searched (``j < i``: every unordered
+    pair once, never the self pair; the tiles above the diagonal are not computed).  With ``candidates`` every (query row,
+    candidate row) pair counts.  Inputs take the containers of ``most_similar``.  A NaN score never qualifies.  The pairs
+    are ordered by ``i`` ascending, then ``j`` ascending, bit-identical run to run.
+
+    The result's size is not known beforehand: the library is called with room for ``max(65536, 8 * rows)`` pairs and, when
+    more qualify, once more with the exact count.  With ``max_pairs`` set, a count above it raises ``ValueError`` (naming
+    the count) instead of allocating.  Returns ``(rows int64, cols int64, scores float32)`` as ndarrays, or as CUDA
+    tensors with ``return_tensor=True``."""
+    import ctypes
+    import torch
+    assert metric in ["cosine", "linear kernel"]                      # helpers.py:34
+    if norm not in _NORMS:
+        raise ValueError(f"'{norm}' is not a supported norm")         # sklearn.preprocessing.normalize's message
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("threshold is NaN")
+    lib = L.load()
+    dev = torch.device("cuda" if device is None else device)
+    Q = _device_matrix(torch, in_df, dev)
+    Cm = None if candidates is None else _device_matrix(torch, candidates, dev)
+    Nq, D = int(Q.shape[0]), int(Q.shape[1])
+    if Cm is not None and int(Cm.shape[1]) != D:
+        raise ValueError(f"candidates have {int(Cm.shape[1])} columns, in_df has {D}")
+    Nc = Nq if Cm is None else int(Cm.shape[0])
+    capacity = max(65536, 8 * Nq)
+    if max_pairs is not None:
+        capacity = min(capacity, max(int(max_pairs), 0))
+    count = ctypes.c_uint64(0)
+    for _ in range(2):
+        rows = torch.empty(capacity, dtype=torch.int32, device=dev)
+        cols = torch.empty(capacity, dtype=torch.int32, device=dev)
+        score = torch.empty(capacity, dtype=torch.float32, device=dev)
+        ws_bytes = int(lib.dae_threshold_pairs_workspace(Nq, Nc, D, capacity))
+        ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
+        off = (-ws.data_ptr()) % 256
+        with torch.cuda.device(dev):
+            L.call("dae_threshold_pairs", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
+                   _NORMS[norm], _METRICS[metric], threshold, L.ptr(rows) if capacity else None, L.ptr(cols) if capacity else None,
+                   L.ptr(score) if capacity else None, capacity, ctypes.byref(count), ctypes.c_void_p(ws.data_ptr() + off),
+                   ws_bytes, L.current_stream())
+        del ws
+        n = int(count.value)
+        if max_pairs is not None and n > int(max_pairs):
+            raise ValueError(f"{n} pairs score at least {threshold}, more than max_pairs={int(max_pairs)}")
+        if n <= capacity:
+            break
+        capacity = n                                                  # the count is exact: the second call fits
+    else:
+        raise RuntimeError(f"dae_threshold_pairs counted {n} pairs after reporting {capacity}")
+    rows, cols, score = rows[:n].long(), cols[:n].long(), score[:n].clone()
+    if return_tensor:
+        return rows, cols, score
+    return rows.cpu().numpy(), cols.cpu().numpy(), score.cpu().numpy()
+
+
+def duplicate_groups(rows, cols, n):
+    """Connected components of the pair graph over ``n`` items (``rows[p]`` -- ``cols[p]`` are its edges, e.g. the result of
+    ``similar_pairs``).  Returns ``(group, keep)``: ``group`` (int64 ``[n]``) is the smallest index of the item's
+    component, so an item with no partner is its own group; ``keep`` (bool ``[n]``) is true for exactly that smallest
+    index -- the de-duplication rule "keep the first article of each story".  Host code."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    n = int(n)
+    r = np.asarray(rows, dtype=np.int64).ravel()
+    c = np.asarray(cols, dtype=np.int64).ravel()
+    if r.shape != c.shape:
+        raise ValueError(f"{r.shape[0]} rows for {c.shape[0]} cols")
+    if r.size and (min(r.min(), c.min()) < 0 or max(r.max(), c.max()) >= n):
+        raise ValueError(f"pair indices must be in 0..{n - 1}")
+    if n == 0:
+        return np.zeros(0, np.int64), np.zeros(0, bool)
+    graph = coo_matrix((np.ones(r.size, np.int8), (r, c)), shape=(n, n))
+    _, comp = connected_components(graph, directed=False)
+    first = np.full(int(comp.max()) + 1, n, dtype=np.int64)
+    np.minimum.at(first, comp, np.arange(n, dtype=np.int64))
+    group = first[comp]
+    return group, group == np.arange(n)
+
+
+def duplicate_pair_precision(rows, cols, labels, candidate_labels=None):
+    """The share of the pairs ``(rows[p], cols[p])`` whose two labels are equal.  ``labels`` are those of the rows;
+    ``candidate_labels`` those of the corpus the cols point into (default: ``labels``, i.e. the corpus is the query set).
+    Pairs with a missing label (negative or NaN, the rule of ``label_precision_at_k``) are skipped.  Host code.  Returns
+    ``(precision, number of pairs counted)``; precision is NaN when no pair counts."""
+    r = np.asarray(rows, dtype=np.int64).ravel()
+    c = np.asarray(cols, dtype=np.int64).ravel()
+    if r.shape != c.shape:
+        raise ValueError(f"{r.shape[0]} rows for {c.shape[0]} cols")
+    lab, valid = _label_keys(labels)
+    clab, cvalid = (lab, valid) if candidate_labels is None else _label_keys(candidate_labels)
+    ok = valid[r] & cvalid[c]
+    if not ok.any():
+        return float("nan"), 0
+    return float((lab[r[ok]] == clab[c[ok]]).mean()), int(ok.sum())
 
 
 _STAT_KEYS = ("auroc","n_related", "n_unrelated", "mean_related", "mean_unrelated")

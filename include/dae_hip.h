@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define DAE_PAD 128
-#define DAE_ABI_VERSION 7   /* 7: dae_topk_similarity / dae_topk_similarity_workspace (fused similarity + top-k retrieval); 6:dae_comm_* / dae_allreduce_grads / dae_dp_exchange / dae_dp_bands (the data-parallel collective in the C ABI, RCCL on the step's stream); 5: dae_storage_format (the fp16 build libdae_hip_f16.so), options x3_terms / op_scale_log2, DAE_WAIT_DW_CREATED = 100; 4: DAE_BF16X3 (split-bf16 mode), dae_gemm_nt_n; 3: dae_buffers.grad_lo, option encode_w32 (and one since removed); 2: dae_step.c_row_idx, plan options, phases 4/5, sharded apply */
+#define DAE_ABI_VERSION 8   /* 8: dae_threshold_pairs / dae_threshold_pairs_workspace (near-duplicate search: all pairs over a threshold); 7: dae_topk_similarity / dae_topk_similarity_workspace (fused similarity + top-k retrieval); 6:dae_comm_* / dae_allreduce_grads / dae_dp_exchange / dae_dp_bands (the data-parallel collective in the C ABI, RCCL on the step's stream); 5: dae_storage_format (the fp16 build libdae_hip_f16.so), options x3_terms / op_scale_log2, DAE_WAIT_DW_CREATED = 100; 4: DAE_BF16X3 (split-bf16 mode), dae_gemm_nt_n; 3: dae_buffers.grad_lo, option encode_w32 (and one since removed); 2: dae_step.c_row_idx, plan options, phases 4/5, sharded apply */
 
 enum { DAE_BF16 = 0, DAE_F32 = 1,
        DAE_BF16X3 = 2 /* dae_config.dtype only: bf16 storage and MFMA, but every stored operand of the three gradient GEMMs is kept as
@@ -430,6 +430,29 @@ int dae_topk_similarity(const float* Q, int64_t ldq, int32_t Nq, const float* C,
                         int32_t D, int32_t norm, int32_t metric, int32_t k, int32_t exclude_self,
                         int32_t* idx, float* score, int64_t ldk, void* workspace, uint64_t workspace_bytes,
                         void* stream);
+
+/* -------------------------------------------------------------------------------------------------
+ * Near-duplicate search: every pair (i, j) whose score reaches a threshold, without an N x N matrix (the range query
+ * of article de-duplication; helpers.similar_pairs).
+ *   Q, ldq, Nq, C, ldc, Nc, D, norm, metric: exactly as dae_topk_similarity, and the same scores.
+ *   A pair qualifies when score(i, j) >= threshold, i < Nq, j < Nc and, with C == NULL (the corpus is Q itself), j < i:
+ *   the strict lower triangle, i.e. every unordered pair once and never the self pair.  A NaN score never qualifies; a NaN
+ *   threshold is an argument error; -inf / +inf thresholds are allowed.  In self mode only the tiles on or below the
+ *   diagonal are computed.
+ *   *count_host (host memory) receives the exact number of qualifying pairs, whatever the capacity, and the stream is
+ *   synchronised before the call returns.  If *count_host <= capacity, rows / cols / scores [0, *count_host) (device
+ *   memory, `capacity` entries each) hold the pairs ordered by i ascending, then j ascending -- bit-identical run to run
+ *   and independent of the grid.  Otherwise the three arrays are unspecified and the return value is still 0: allocate
+ *   *count_host entries and call again.  capacity == 0 with NULL arrays is a pure count.
+ *   workspace: dae_threshold_pairs_workspace(Nq, Nc, D, capacity) bytes, 256-byte aligned: the two normalised operand
+ *   images, the unsorted records, the sort's scratch and the cursor -- linear in Nq, Nc and capacity, no Nq x Nc term.
+ *   Each operand image must stay below 4 GiB.
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_threshold_pairs_workspace(int32_t Nq, int32_t Nc, int32_t D, uint64_t capacity);
+int dae_threshold_pairs(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc,
+                        int32_t D, int32_t norm, int32_t metric, float threshold, int32_t* rows, int32_t* cols,
+                        float* scores, uint64_t capacity, uint64_t* count_host, void* workspace,
+                        uint64_t workspace_bytes, void* stream);
 
 /* Related / unrelated pair statistics of an N x N similarity matrix: the numbers behind
  * helpers.visualize_pairwise_similarity (helpers.py:79-135) -- AUROC of "same label" vs "different label" over the strict

@@ -82,6 +82,11 @@ def build_parser():
                    help="K > 0: after training, the K most similar train articles of every train (and validation) article, written to "
                         "article_encoded[_validate]_top{K}.npz, with precision@K of the input vectors and of the embedding when labels exist "
                         "(no N x N matrix: works with --similarity False on corpora too large for it)")
+    p.add_argument("--dup_threshold", type=float, default=0.0,
+                   help="T > 0: after training, every pair of train articles whose embeddings have cosine >= T (near duplicates), written "
+                        "to article_encoded_dups.npz with the de-duplication groups (keep the first article of each story), and the "
+                        "validation articles against the train corpus to article_encoded_validate_dups.npz; with labels, the share of "
+                        "pairs with equal labels (no N x N matrix: works with --similarity False)")
     return p
 
 
@@ -175,6 +180,37 @@ def evaluate_top_k(a, trX, vlX, trY, vlY, emb, emb_v, data_dir):
     return out
 
 
+def evaluate_duplicates(a, trY, vlY, emb, emb_v, data_dir):
+    """--dup_threshold T: the pairs of train articles whose embeddings have cosine >= T (helpers.similar_pairs, no N x N matrix),
+    saved with their connected components (``group``: first article of the story, ``keep``: that article) in
+    article_encoded_dups.npz; validation articles against the train corpus in article_encoded_validate_dups.npz (pairs only).
+    With labels, the share of pairs whose two labels are equal."""
+    from dae_rnn_news_recommendation_amd import helpers
+    T = a.dup_threshold
+    print('calculate duplicates at cosine >= %g' % T)
+    out = {}
+    rows, cols, scores = helpers.similar_pairs(emb, T)
+    group, keep = helpers.duplicate_groups(rows, cols, emb.shape[0])
+    np.savez(data_dir + 'article_encoded_dups.npz', rows=rows, cols=cols, scores=scores, group=group, keep=keep, threshold=np.float32(T))
+    out['train'] = (rows, cols, scores, group, keep)
+    line = '  train     %d pairs, %d groups of more than one article, %d articles dropped' % (
+        rows.shape[0], int((np.bincount(group, minlength=1) > 1).sum()), int((~keep).sum()))
+    if trY is not None:
+        line += ', pair precision %.4f (%d pairs)' % helpers.duplicate_pair_precision(rows, cols, trY)
+    print(line)
+    if emb_v is not None:
+        rows, cols, scores = helpers.similar_pairs(emb_v, T, candidates=emb)
+        np.savez(data_dir + 'article_encoded_validate_dups.npz', rows=rows, cols=cols, scores=scores, threshold=np.float32(T))
+        out['validate'] = (rows, cols, scores)
+        line = '  validate  %d pairs with train articles, %d of %d validation articles have one' % (
+            rows.shape[0], np.unique(rows).shape[0], emb_v.shape[0])
+        if vlY is not None and trY is not None:
+            line += ', pair precision %.4f (%d pairs)' % helpers.duplicate_pair_precision(rows, cols, vlY, trY)
+        print(line)
+    print('calculate duplicates done')
+    return out
+
+
 # artefact names of the reference's data directory (main_autoencoder.py:227-244, restored at :162-174)
 def _artefact(kind, a, validate=False):
     suffix = "_validate" if validate else ""
@@ -254,6 +290,8 @@ def main(argv=None):
         evaluate_similarity(a, trX, vlX, trY, vlY, emb, emb_v, model.plot_dir)
     if a.top_k > 0 and dp.rank() == 0:
         evaluate_top_k(a, trX, vlX, trY, vlY, emb, emb_v, model.data_dir)
+    if a.dup_threshold > 0 and dp.rank() == 0:
+        evaluate_duplicates(a, trY, vlY, emb, emb_v, model.data_dir)
     if model.samples_per_sec:
         print('training throughput: %.0f samples/s over %d epochs; embeddings %s -> %s' %
               (model.samples_per_sec, a.num_epochs, emb.shape, model.data_dir))
