@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libdae_hip.so")
 #   "bf16"  libdae_hip.so      bfloat16 images, v_mfma_f32_32x32x16_bf16   precision 'bf16' | 'bf16x3' | 'fp32'
 #   "f16"   libdae_hip_f16.so  IEEE fp16 images, v_mfma_f32_32x32x16_f16   precision 'f16x2' (the default 'auto') | 'f16' | 'f16x3'
 LIB_PATHS = {"bf16": LIB_PATH, "f16": os.path.join(_HERE, "libdae_hip_f16.so")}
-ABI_VERSION = 8
+ABI_VERSION = 9
 # precision name -> (library build, dae_config.dtype, lo product terms of the split mode or None = the build's default)
 X3T_ALL = (1 << 11) - 1
 # lo product terms of the split 16-bit modes (dae_plan_set_option "x3_terms"; bits X3T_* of csrc/dae_kernels.h)
@@ -119,6 +119,9 @@ SIGNATURES = {
     "dae_topk_similarity": (i32, [vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, i64, vp, u64, vp]),
     "dae_threshold_pairs_workspace": (u64, [i32, i32, i32, u64]),
     "dae_threshold_pairs": (i32, [vp, i64, i32, vp, i64, i32, i32, i32, i32, f32, vp, vp, vp, u64, vp, vp, u64, vp]),
+    "dae_pair_hist_max_bins": (i32, []),
+    "dae_pair_hist_workspace": (u64, [i32, i32, i32, i32]),
+    "dae_pair_hist": (i32, [vp, i64, i32, vp, vp, i64, i32, vp, i32, i32, i32, f32, f32, i32, vp, vp, vp, u64, vp]),
     "dae_pair_stats_workspace": (u64, [i32]),
     "dae_pair_stats": (i32, [vp, i64, vp, i32, vp, vp, u64, vp]),
     "dae_gemm_trace": (i32, [i32, i32, i32, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, vp, i64, i32, i64, i32, vp, vp]),

@@ -12,7 +12,10 @@ library / a GPU this raises.
   ``label_precision_at_k`` (host code) to score such a result against labels.
 * ``similar_pairs`` -- near-duplicate search: every pair scoring at least a threshold, without the N x N matrix
   (``dae_threshold_pairs``); ``duplicate_groups`` and ``duplicate_pair_precision`` (host code) turn the pairs into the
-  de-duplication rule "keep the first article of each story" and score them against labels."""
+  de-duplication rule "keep the first article of each story" and score them against labels.
+* ``label_similarity_stats`` -- the related-vs-unrelated AUROC and box-plot numbers of ``visualize_pairwise_similarity``
+  without the N x N matrix: ``dae_pair_hist`` reduces the score tiles into one histogram per class, and
+  ``stats_from_histograms`` (host code) derives the AUROC with a bracket that certifies it, and the quartiles."""
 from __future__ import annotations
 
 import numpy as np
@@ -402,4 +405,188 @@ def visualize_pairwise_similarity(labels, pairwise_similarity_metrics, plot='box
         path = path[:-4] + ".json" if path.lower().endswith(".png") else path + ".json"
         with open(path, "w") as fh:
             json.dump(res, fh, indent=1)
+    return res
+
+
+def _label_ids(labels, n):
+    """int32 labels by the missing-label rule of visualize_pairwise_similarity: negative, NaN and inf labels are missing (-1)."""
+    lab = np.asarray(labels)
+    if lab.shape[0] != n:
+        raise ValueError(f"{lab.shape[0]} labels for {n} rows")
+    lab = lab.reshape(n, -1)[:, 0]
+    if lab.dtype.kind == 'f':
+        lab = np.where(np.isfinite(lab), lab, -1.0)
+    return np.ascontiguousarray(np.where(lab < 0, -1, lab).astype(np.int32))
+
+
+def stats_from_histograms(hist_related, hist_unrelated, score_range, *, min_related=None, max_related=None, min_unrelated=None,
+                          max_unrelated=None, sum_related=None, sum_unrelated=None):
+    """AUROC and box-plot numbers of two score populations known only through their histograms over the same ``bins``
+    equal-width bins of ``score_range = (lo, hi)`` (bin of ``s``: ``clamp(floor((s - lo) * bins / (hi - lo)), 0, bins - 1)``, so
+    the two end bins also hold whatever lies outside the range).  Host code, integer arithmetic on the counts.
+
+    * ``auroc``: pairs (related, unrelated) in different bins are ordered by their bins, pairs sharing a bin count as ties (1/2).
+      ``auroc_low`` / ``auroc_high`` = ``auroc`` -/+ half the share of pairs sharing a bin: binning is monotone, so the exact
+      tie-aware AUROC of the scores lies inside whatever their distribution -- a certificate, not an error estimate.
+    * ``related`` / ``unrelated``: ``min``, ``q1``, ``median``, ``q3``, ``max`` at numpy's positions ``q * (n - 1)``: the two order
+      statistics either side of the position are each represented by the midpoint of the bin that holds them (clipped to
+      ``[min, max]``) and interpolated linearly as numpy does, so the error is at most half a bin, and a bin holding one
+      distinct value at its centre (integer scores in unit bins) gives the exact quartile.  ``related_bounds`` /
+      ``unrelated_bounds`` give, per quartile, the bracket (lower edge of the lower statistic's bin, upper edge of the upper
+      one's) clipped to ``[min, max]``, which the exact quartile lies in; the edges are widened by the few fp32 roundings of the
+      bin index.
+    * ``min`` / ``max`` / ``sum`` of a class, when known exactly, are passed in; otherwise the outer edges of its first / last
+      occupied bin and the midpoint sum stand in.  An empty class gives NaN, as ``visualize_pairwise_similarity`` does."""
+    rel = [int(x) for x in np.asarray(hist_related).ravel()]
+    un = [int(x) for x in np.asarray(hist_unrelated).ravel()]
+    bins = len(rel)
+    if len(un) != bins or bins < 1:
+        raise ValueError("the two histograms must have the same, non-zero number of bins")
+    lo, hi = float(np.float32(score_range[0])), float(np.float32(score_range[1]))
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError("score_range must be finite with lo < hi")
+    if min(rel) < 0 or min(un) < 0:
+        raise ValueError("negative count")
+    span = float(np.float32(hi) - np.float32(lo))
+    slack = 4.0 * 2.0 ** -24 * max(abs(lo), abs(hi), span)               # roundings of s - lo, * bins, / span, in score units
+    nan = float("nan")
+    n_rel, n_un = sum(rel), sum(un)
+    res = {"auroc": nan, "n_related": n_rel, "n_unrelated": n_un, "mean_related": nan, "mean_unrelated": nan,
+           "auroc_low": nan, "auroc_high": nan}
+    if n_rel and n_un:
+        below = wins2 = ties = 0                                         # wins2 = 2 * (wins + ties / 2)
+        for b in range(bins):
+            wins2 += rel[b] * (2 * below + un[b])
+            ties += rel[b] * un[b]
+            below += un[b]
+        den = 2 * n_rel * n_un
+        res["auroc"] = wins2 / den
+        res["auroc_low"] = (wins2 - ties) / den
+        res["auroc_high"] = (wins2 + ties) / den
+
+    def edge(b):
+        return lo + b * span / bins
+
+    def one_class(h, n, vmin, vmax, vsum):
+        five = dict.fromkeys(("min", "q1", "median", "q3", "max"), nan)
+        bounds = {k: (nan, nan) for k in ("q1", "median", "q3")}
+        if n == 0:
+            return nan, five, bounds
+        cum = np.cumsum(np.asarray(h, dtype=np.int64))
+        first, last = int(np.searchsorted(cum, 0, side="right")), int(np.searchsorted(cum, n - 1, side="right"))
+        vmin = edge(first) if vmin is None else float(vmin)
+        vmax = edge(last + 1) if vmax is None else float(vmax)
+        if vsum is None:
+            vsum = float(sum(c * min(max(edge(b) + 0.5 * span / bins, vmin), vmax) for b, c in enumerate(h) if c))
+        five["min"], five["max"] = vmin, vmax
+
+        def clip(v):
+            return min(max(v, vmin), vmax)
+        for name, q in (("q1", 0.25), ("median", 0.5), ("q3", 0.75)):
+            pos = q * (n - 1)
+            r0, r1 = int(np.floor(pos)), int(np.ceil(pos))
+            b0, b1 = int(np.searchsorted(cum, r0, side="right")), int(np.searchsorted(cum, r1, side="right"))
+            v0, v1 = clip(edge(b0) + 0.5 * span / bins), clip(edge(b1) + 0.5 * span / bins)
+            five[name] = v0 + (v1 - v0) * (pos - r0)
+            # the end bins also hold whatever the clamp put there: their outer edges are min / max
+            bounds[name] = (vmin if b0 == 0 else clip(edge(b0) - slack), vmax if b1 == bins - 1 else clip(edge(b1 + 1) + slack))
+        return float(vsum) / n, five, bounds
+
+    res["mean_related"], res["related"], res["related_bounds"] = one_class(rel, n_rel, min_related, max_related, sum_related)
+    res["mean_unrelated"], res["unrelated"], res["unrelated_bounds"] = one_class(un, n_un, min_unrelated, max_unrelated, sum_unrelated)
+    return res
+
+
+def label_similarity_stats(in_df, labels, norm="", metric="cosine", candidates=None, candidate_labels=None, *, bins=2048,
+                           score_range=None, refine=False, return_histograms=False, save_path=None, title=None, device=None):
+    """The numbers of ``visualize_pairwise_similarity(labels, pairwise_similarity(in_df, norm, metric))`` without the N x N matrix:
+    ``dae_pair_hist`` bins every pair's score (same ``norm`` / ``metric``, same exact-fp32 products as ``similar_pairs``) into one
+    histogram per class inside the GEMM's epilogue, and ``stats_from_histograms`` derives the statistics.
+
+    Pairs and classes as there: without ``candidates`` the pairs ``j < i`` of ``in_df``; with ``candidates`` (and their
+    ``candidate_labels``) every (row, candidate) pair; a pair counts when both labels are present (negative, NaN and inf labels
+    are missing) and is related when they are equal.  Inputs take the containers of ``similar_pairs``.
+
+    Returns the dict of ``visualize_pairwise_similarity`` -- ``auroc``, ``n_related``, ``n_unrelated``, ``mean_related``,
+    ``mean_unrelated``, the ``related`` / ``unrelated`` five-number dicts, ``title`` -- plus ``auroc_low`` / ``auroc_high`` (a bracket
+    that is certain to hold the exact tie-aware AUROC of the same scores; its width is the share of pairs sharing a bin),
+    ``related_bounds`` / ``unrelated_bounds`` (brackets of the quartiles), ``score_range``, ``bins``, ``n_nan`` (pairs with a NaN
+    score: in no bin and in no count).  ``min``, ``max`` and the means are exact (fp32 values; fp64 sums); the counts are
+    integers and the sums are reduced in a fixed shape, so the result is bit-identical run to run.
+
+    ``bins`` <= 2048.  ``score_range=None`` is the automatic range: [-1, 1] for cosine, the Cauchy-Schwarz bound of the row norms
+    for the linear kernel.  ``refine=True`` calls the library a second time over ``(min, max)`` of the scores seen in the first
+    call, which narrows the brackets when the automatic range is much wider than the data (raw linear-kernel scores with one
+    long row); the first call's bracket is kept under ``first_pass``.  ``return_histograms=True`` adds ``hist_related``,
+    ``hist_unrelated`` (uint64) and ``bin_edges`` (float64, bins + 1): enough to draw the ROC curve and the box plot.
+    ``save_path`` writes the dict (without the arrays) as JSON with the ``.png`` -> ``.json`` rule of
+    ``visualize_pairwise_similarity``."""
+    import ctypes
+    import json
+    import torch
+    assert metric in ["cosine", "linear kernel"]                      # helpers.py:34
+    if norm not in _NORMS:
+        raise ValueError(f"'{norm}' is not a supported norm")         # sklearn.preprocessing.normalize's message
+    lib = L.load()
+    bins = int(bins)
+    if not 2 <= bins <= int(lib.dae_pair_hist_max_bins()):
+        raise ValueError(f"bins must be in 2..{int(lib.dae_pair_hist_max_bins())} (got {bins})")
+    if (candidates is None) != (candidate_labels is None):
+        raise ValueError("candidates and candidate_labels go together")
+    if score_range is None:
+        lo, hi = 0.0, 0.0                                             # lo >= hi: the library's automatic range
+    else:
+        lo, hi = float(score_range[0]), float(score_range[1])
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+            raise ValueError("score_range must be finite with lo < hi")
+    dev = torch.device("cuda" if device is None else device)
+    Q = _device_matrix(torch, in_df, dev)
+    Cm = None if candidates is None else _device_matrix(torch, candidates, dev)
+    Nq, D = int(Q.shape[0]), int(Q.shape[1])
+    if Cm is not None and int(Cm.shape[1]) != D:
+        raise ValueError(f"candidates have {int(Cm.shape[1])} columns, in_df has {D}")
+    Nc = Nq if Cm is None else int(Cm.shape[0])
+    lq = _label_ids(labels, Nq)
+    lc = None if Cm is None else _label_ids(candidate_labels, Nc)
+    ws_bytes = int(lib.dae_pair_hist_workspace(Nq, Nc, D, bins))
+    ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
+    off = (-ws.data_ptr()) % 256
+
+    def run(lo, hi):
+        hist = np.zeros((2, bins), dtype=np.uint64)
+        out = (ctypes.c_double * 16)()
+        with torch.cuda.device(dev):
+            L.call("dae_pair_hist", L.ptr(Q), Q.stride(0), Nq, lq.ctypes.data_as(ctypes.c_void_p), L.ptr(Cm),
+                   0 if Cm is None else Cm.stride(0), Nc, None if lc is None else lc.ctypes.data_as(ctypes.c_void_p), D, _NORMS[norm],
+                   _METRICS[metric], lo, hi, bins, hist.ctypes.data_as(ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p),
+                   ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
+        v = [float(x) for x in out]
+        have_r, have_u = v[0] > 0, v[1] > 0
+        st = stats_from_histograms(hist[0], hist[1], (v[9], v[10]),
+                                   min_related=v[5] if have_r else None, max_related=v[6] if have_r else None,
+                                   min_unrelated=v[7] if have_u else None, max_unrelated=v[8] if have_u else None,
+                                   sum_related=v[3] if have_r else None, sum_unrelated=v[4] if have_u else None)
+        st["score_range"] = (v[9], v[10])
+        st["bins"] = bins
+        st["n_nan"] = int(v[2])
+        return st, hist
+
+    res, hist = run(lo, hi)
+    if refine:
+        seen = [res[c][k] for c, n in (("related", "n_related"), ("unrelated", "n_unrelated")) if res[n] for k in ("min", "max")]
+        if seen and np.isfinite(min(seen)) and np.isfinite(max(seen)) and min(seen) < max(seen):
+            first = {k: res[k] for k in ("auroc", "auroc_low", "auroc_high", "score_range")}
+            res, hist = run(min(seen), max(seen))
+            res["first_pass"] = first
+    res["title"] = title
+    if save_path is not None:
+        path = str(save_path)
+        path = path[:-4] + ".json" if path.lower().endswith(".png") else path + ".json"
+        with open(path, "w") as fh:
+            json.dump(res, fh, indent=1)
+    if return_histograms:
+        lo_, hi_ = res["score_range"]
+        span = float(np.float32(hi_) - np.float32(lo_))
+        res["hist_related"], res["hist_unrelated"] = hist[0].copy(), hist[1].copy()
+        res["bin_edges"] = lo_ + np.arange(bins + 1, dtype=np.float64) * span / bins
     return res

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define DAE_PAD 128
-#define DAE_ABI_VERSION 8   /* 8: dae_threshold_pairs / dae_threshold_pairs_workspace (near-duplicate search: all pairs over a threshold); 7: dae_topk_similarity / dae_topk_similarity_workspace (fused similarity + top-k retrieval); 6:dae_comm_* / dae_allreduce_grads / dae_dp_exchange / dae_dp_bands (the data-parallel collective in the C ABI, RCCL on the step's stream); 5: dae_storage_format (the fp16 build libdae_hip_f16.so), options x3_terms / op_scale_log2, DAE_WAIT_DW_CREATED = 100; 4: DAE_BF16X3 (split-bf16 mode), dae_gemm_nt_n; 3: dae_buffers.grad_lo, option encode_w32 (and one since removed); 2: dae_step.c_row_idx, plan options, phases 4/5, sharded apply */
+#define DAE_ABI_VERSION 9   /* 9: dae_pair_hist / dae_pair_hist_workspace / dae_pair_hist_max_bins (label AUROC and pair statistics from fused per-class score histograms); 8: dae_threshold_pairs / dae_threshold_pairs_workspace (near-duplicate search: all pairs over a threshold); 7: dae_topk_similarity / dae_topk_similarity_workspace (fused similarity + top-k retrieval); 6:dae_comm_* / dae_allreduce_grads / dae_dp_exchange / dae_dp_bands (the data-parallel collective in the C ABI, RCCL on the step's stream); 5: dae_storage_format (the fp16 build libdae_hip_f16.so), options x3_terms / op_scale_log2, DAE_WAIT_DW_CREATED = 100; 4: DAE_BF16X3 (split-bf16 mode), dae_gemm_nt_n; 3: dae_buffers.grad_lo, option encode_w32 (and one since removed); 2: dae_step.c_row_idx, plan options, phases 4/5, sharded apply */
 
 enum { DAE_BF16 = 0, DAE_F32 = 1,
        DAE_BF16X3 = 2 /* dae_config.dtype only: bf16 storage and MFMA, but every stored operand of the three gradient GEMMs is kept as
@@ -453,6 +453,36 @@ int dae_threshold_pairs(const float* Q, int64_t ldq, int32_t Nq, const float* C,
                         int32_t D, int32_t norm, int32_t metric, float threshold, int32_t* rows, int32_t* cols,
                         float* scores, uint64_t capacity, uint64_t* count_host, void* workspace,
                         uint64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
+ * Label statistics without an N x N matrix: the per-class score histograms of all row pairs (helpers.label_similarity_stats).
+ *   Q, ldq, Nq, C, ldc, Nc, D, norm, metric: exactly as dae_threshold_pairs, and the same scores.  labels_q_host int32[Nq] and,
+ *   with C, labels_c_host int32[Nc] on the HOST (with C == NULL the corpus and its labels are Q's; labels_c_host is ignored).
+ *   A pair (i, j) counts when i < Nq, j < Nc, both labels are >= 0 and, with C == NULL, j < i (the strict lower triangle);
+ *   it is "related" when the two labels are equal, "unrelated" otherwise.  In self mode only the tiles on or below the
+ *   diagonal are computed.
+ *   A score s falls in bin clamp(floor((s - lo) * bins / (hi - lo)), 0, bins - 1), computed in fp32 exactly as written
+ *   (IEEE subtract, multiply by (float) bins, divide by the fp32 difference hi - lo); a NaN score is counted in n_nan and in
+ *   no bin.  2 <= bins <= dae_pair_hist_max_bins() (2048: the two histograms stay in LDS beside the GEMM's staging ring).
+ *   lo >= hi asks for the automatic range, returned in out16: [-1, 1] for cosine; for the linear kernel [-M, M] with
+ *   M = (largest row 2-norm of the query image) x (largest row 2-norm of the corpus image), rounded up by one part in 2^20.
+ *   lo / hi NaN or infinite are argument errors.
+ *   hist_host (host, uint64[2][bins]): related, then unrelated counts -- integers, bit-identical run to run and independent
+ *   of the grid.  out16_host (host): [0] n_related, [1] n_unrelated (the histograms' totals), [2] n_nan, [3] sum of the
+ *   related scores, [4] of the unrelated ones (fp64, reduced in a fixed shape: bit-identical run to run on one device),
+ *   [5] min related, [6] max related, [7] min unrelated, [8] max unrelated (exact fp32 values; NaN, like the sums, where
+ *   the class is empty), [9] lo, [10] hi as used, [11] workgroups of the grid, [12] tiles computed, [13..15] NaN.
+ *   Synchronises the stream (returns host numbers).
+ *   workspace: dae_pair_hist_workspace(Nq, Nc, D, bins) bytes, 256-byte aligned: the two normalised operand images, the
+ *   labels, the global histogram and one small record per workgroup -- linear in Nq and Nc, no Nq x Nc term and no
+ *   per-pair term.  Each operand image must stay below 4 GiB.
+ * ------------------------------------------------------------------------------------------------- */
+int32_t dae_pair_hist_max_bins(void);
+uint64_t dae_pair_hist_workspace(int32_t Nq, int32_t Nc, int32_t D, int32_t bins);
+int dae_pair_hist(const float* Q, int64_t ldq, int32_t Nq, const int32_t* labels_q_host, const float* C, int64_t ldc,
+                  int32_t Nc, const int32_t* labels_c_host, int32_t D, int32_t norm, int32_t metric, float lo, float hi,
+                  int32_t bins, uint64_t* hist_host, double* out16_host, void* workspace, uint64_t workspace_bytes,
+                  void* stream);
 
 /* Related / unrelated pair statistics of an N x N similarity matrix: the numbers behind
  * helpers.visualize_pairwise_similarity (helpers.py:79-135) -- AUROC of "same label" vs "different label" over the strict

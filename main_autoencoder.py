@@ -87,6 +87,10 @@ def build_parser():
                         "to article_encoded_dups.npz with the de-duplication groups (keep the first article of each story), and the "
                         "validation articles against the train corpus to article_encoded_validate_dups.npz; with labels, the share of "
                         "pairs with equal labels (no N x N matrix: works with --similarity False)")
+    p.add_argument("--label_stats", default=False, **b,
+                   help="after training (needs labels): the related-vs-unrelated AUROC, with a bracket that certifies it, and the box-plot "
+                        "numbers of the input vectors and of the embeddings, written to similarity_stats_<name>.json (per-class score "
+                        "histograms, no N x N matrix: works with --similarity False)")
     return p
 
 
@@ -150,6 +154,32 @@ def evaluate_similarity(a, trX, vlX, trY, vlY, emb, emb_v, plot_dir=None):
         print(line)
         del S
     print('calculate similarity done')
+    return rows
+
+
+def evaluate_label_stats(a, trX, vlX, trY, vlY, emb, emb_v, plot_dir=None):
+    """--label_stats: the four jobs of evaluate_similarity through helpers.label_similarity_stats (dae_pair_hist: per-class score
+    histograms in the GEMM's epilogue, no N x N matrix).  Prints the same per-job line with the AUROC's bracket appended and, with
+    ``plot_dir``, writes similarity_stats_<name>.json."""
+    from dae_rnn_news_recommendation_amd import helpers
+    assert trY is not None, "--label_stats needs labels"
+    print('calculate label statistics')
+    metric_in = 'linear kernel' if a.input_format == 'tfidf' else 'cosine'
+    stem_in = 'tfidf' if a.input_format == 'tfidf' else 'binary_count'
+    jobs = [('input vectors (train)', trX, metric_in, trY, stem_in), ('embedding (train)', emb, 'cosine', trY, 'encoded')]
+    if vlX is not None and vlY is not None:
+        jobs += [('input vectors (validate)', vlX, metric_in, vlY, stem_in + '_validate'),
+                 ('embedding (validate)', emb_v, 'cosine', vlY, 'encoded_validate')]
+    rows = []
+    for name, M, metric, y, stem in jobs:
+        ids = np.unique(np.asarray(y), return_inverse=True)[1]
+        st = helpers.label_similarity_stats(M, ids, metric=metric, title=name,
+                                            save_path=None if plot_dir is None else plot_dir + 'similarity_stats_' + stem + '.png')
+        print('  %-26s %5d x %-5d  AUROC %.4f  median sim related %.4f  unrelated %.4f  (%d / %d pairs)  AUROC in [%.6f, %.6f]' % (
+            name, M.shape[0], M.shape[0], st['auroc'], st['related']['median'], st['unrelated']['median'], st['n_related'],
+            st['n_unrelated'], st['auroc_low'], st['auroc_high']))
+        rows.append((name, st))
+    print('calculate label statistics done')
     return rows
 
 
@@ -288,6 +318,8 @@ def main(argv=None):
             helpers.save_file(pd.DataFrame({'label_' + a.label: vlY}), model.tsv_dir + 'article_label_validate.tsv')
     if a.similarity and dp.rank() == 0:
         evaluate_similarity(a, trX, vlX, trY, vlY, emb, emb_v, model.plot_dir)
+    if a.label_stats and dp.rank() == 0:
+        evaluate_label_stats(a, trX, vlX, trY, vlY, emb, emb_v, model.plot_dir)
     if a.top_k > 0 and dp.rank() == 0:
         evaluate_top_k(a, trX, vlX, trY, vlY, emb, emb_v, model.data_dir)
     if a.dup_threshold > 0 and dp.rank() == 0:
