@@ -17,6 +17,10 @@
 //      the row's sorted list (k keys in the global partial buffer, L2-resident) merged with them: every old entry moves
 //      down by the number of candidates above it, every candidate lands at (old entries above it: binary search) +
 //      (candidates above it), positions >= k drop out.
+//      With an exclusion list (dae_topk_similarity_ex: a sorted CSR row of corpus indices per query row, the articles a user
+//      has already read) the lanes whose key beat the threshold look their column up in the row's list (binary search) and
+//      the ballot is taken again: the test runs only on the few candidates that would enter a merge, and an excluded
+//      candidate never takes one of the k slots.  topk_tiles_kernel<false> is the kernel without the list, unchanged.
 // LDS: 64 KiB tile / staging + 1 KiB thresholds + 0.5 KiB list lengths + 4 x 2 KiB merge scratch = 73.5 KiB, two
 // workgroups per CU.  Phase B, topk_merge_kernel: one workgroup per query row merges the `splits` sorted lists the same
 // way (each entry's rank = its position + the entries above it in the other lists) and writes idx / score.
@@ -52,8 +56,21 @@ struct TopkParams {
     int Nq, Nc, Nqp, k, exclude_self, splits, ctiles;
     uint64_t* part;               // [splits][Nqp][k] sorted keys
     int* part_n;                  // [splits][Nqp] valid keys per list
+    const int64_t* excl_indptr;   // [Nq + 1] exclusion CSR (topk_tiles_kernel<true> only): row i's list is
+    const int32_t* excl_items;    // excl_items[excl_indptr[i] .. excl_indptr[i + 1]), ascending and unique
 };
 
+// is j in the ascending list X[0, n)?
+__device__ __forceinline__ bool excl_has(const int32_t* X, int n, int j) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int m = (lo + hi) >> 1;
+        if (X[m] < j) lo = m + 1; else hi = m;
+    }
+    return lo < n && X[lo] == j;
+}
+
+template <bool EXCL>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     float* tile = reinterpret_cast<float*>(lds);
@@ -87,9 +104,20 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams 
             const uint64_t t = th[row];
             const bool ok0 = j0 < p.Nc && !(p.exclude_self && j0 == gi), ok1 = j1 < p.Nc && !(p.exclude_self && j1 == gi);
             const uint64_t c0 = ok0 ? topk_key(tile[row * BN + lane], j0) : 0, c1 = ok1 ? topk_key(tile[row * BN + 64 + lane], j1) : 0;
-            const bool in0 = c0 > t, in1 = c1 > t;
-            const uint64_t b0 = __ballot(in0), b1 = __ballot(in1);
+            bool in0 = c0 > t, in1 = c1 > t;
+            uint64_t b0 = __ballot(in0), b1 = __ballot(in1);
             if ((b0 | b1) == 0) continue;
+            if constexpr (EXCL) {                               // drop the candidates in the row's exclusion list, then ballot again
+                const int64_t x0 = p.excl_indptr[gi];
+                const int xn = (int)(p.excl_indptr[gi + 1] - x0);
+                if (xn > 0) {
+                    const int32_t* X = p.excl_items + x0;
+                    if (in0 && excl_has(X, xn, j0)) in0 = false;
+                    if (in1 && excl_has(X, xn, j1)) in1 = false;
+                    b0 = __ballot(in0); b1 = __ballot(in1);
+                    if ((b0 | b1) == 0) continue;
+                }
+            }
             // ---- merge the candidates into the row's list ----
             const int n0 = __popcll(b0), n = n0 + __popcll(b1);
             const int m = len[row];
@@ -182,9 +210,16 @@ extern "C" uint64_t dae_topk_similarity_workspace(int32_t Nq, int32_t Nc, int32_
     return al256(Nqp * Dp * 4) + al256(Ncp * Dp * 4) + al256(s * Nqp * (uint64_t)k * 8) + al256(s * Nqp * 4);
 }
 
-extern "C" int dae_topk_similarity(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
-                                   int32_t norm, int32_t metric, int32_t k, int32_t exclude_self, int32_t* idx, float* score,
-                                   int64_t ldk, void* workspace, uint64_t workspace_bytes, void* stream) {
+extern "C" uint64_t dae_topk_similarity_ex_workspace(int32_t Nq, int32_t Nc, int32_t D, int32_t k) {
+    return dae_topk_similarity_workspace(Nq, Nc, D, k);         // the exclusion lists are read in place
+}
+
+extern "C" int dae_topk_similarity_ex(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                                      int32_t norm, int32_t metric, int32_t k, int32_t exclude_self, const int64_t* excl_indptr,
+                                      const int32_t* excl_items, int32_t* idx, float* score, int64_t ldk, void* workspace,
+                                      uint64_t workspace_bytes, void* stream) {
+    DAE_CHECK_ARG((excl_indptr == nullptr) == (excl_items == nullptr),
+                  "topk_similarity: excl_indptr and excl_items go together (exactly one of them is NULL)");
     DAE_CHECK_ARG(Q && idx && score && workspace && Nq > 0 && D > 0 && ldq >= D, "topk_similarity: bad input");
     DAE_CHECK_ARG(C ? (Nc > 0 && ldc >= D) : Nc == Nq, "topk_similarity: bad corpus (C == NULL means the corpus is Q: pass Nc == Nq)");
     DAE_CHECK_ARG(norm >= 0 && norm <= 3, "topk_similarity: norm must be 0 (none), 1 (l1), 2 (l2) or 3 (max)");
@@ -217,12 +252,24 @@ extern "C" int dae_topk_similarity(const float* Q, int64_t ldq, int32_t Nq, cons
     p.g.nseg = 1; p.g.splits = 1; p.g.out_scale = 1.f;
     p.Nq = Nq; p.Nc = Nc; p.Nqp = (int)Nqp; p.k = k; p.exclude_self = exclude_self ? 1 : 0; p.splits = splits;
     p.ctiles = (int)(Ncp / BN); p.part = part; p.part_n = part_n;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_tiles_kernel),
+    p.excl_indptr = excl_indptr; p.excl_items = excl_items;
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_tiles_kernel<false>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, TOPK_LDS);
     DAE_CHECK_HIP(attr);
-    DAE_LAUNCH(topk_tiles_kernel, dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), TOPK_LDS, st, p);
+    static const hipError_t attr_x = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_tiles_kernel<true>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, TOPK_LDS);
+    DAE_CHECK_HIP(attr_x);
+    if (excl_indptr) DAE_LAUNCH(topk_tiles_kernel<true>, dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), TOPK_LDS, st, p);
+    else DAE_LAUNCH(topk_tiles_kernel<false>, dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), TOPK_LDS, st, p);
     DAE_CHECK_LAUNCH();
     DAE_LAUNCH(topk_merge_kernel, dim3(Nq), dim3(256), 0, st, part, part_n, (int)Nqp, splits, k, idx, score, ldk);
     DAE_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int dae_topk_similarity(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                                   int32_t norm, int32_t metric, int32_t k, int32_t exclude_self, int32_t* idx, float* score,
+                                   int64_t ldk, void* workspace, uint64_t workspace_bytes, void* stream) {
+    return dae_topk_similarity_ex(Q, ldq, Nq, C, ldc, Nc, D, norm, metric, k, exclude_self, nullptr, nullptr, idx, score, ldk, workspace,
+                                  workspace_bytes, stream);
 }

@@ -15,7 +15,11 @@ library / a GPU this raises.
   de-duplication rule "keep the first article of each story" and score them against labels.
 * ``label_similarity_stats`` -- the related-vs-unrelated AUROC and box-plot numbers of ``visualize_pairwise_similarity``
   without the N x N matrix: ``dae_pair_hist`` reduces the score tiles into one histogram per class, and
-  ``stats_from_histograms`` (host code) derives the AUROC with a bracket that certifies it, and the quartiles."""
+  ``stats_from_histograms`` (host code) derives the AUROC with a bracket that certifies it, and the quartiles.
+* ``user_states`` -- the decaying user model of "Embedding-based News Recommendation for Millions of Users": a decay-weighted
+  mean of the embeddings of the articles a user has read (``dae_user_states``); ``recommend`` -- the top-k articles by
+  ``user . article`` that the user has not read yet (``most_similar(exclude=...)``, ``dae_topk_similarity_ex``);
+  ``next_click_metrics`` (host code) scores such a list against one held-out click per user."""
 from __future__ import annotations
 
 import numpy as np
@@ -180,7 +184,45 @@ def _device_matrix(torch, data, dev):
     return X.contiguous()
 
 
-def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candidates=None, *, return_tensor=False, device=None):
+def _csr_lists(lists, what="histories"):
+    """``(indptr int64 [n + 1], items int64 [nnz])`` of a list of index sequences, or of an ``(indptr, items)`` pair -- a *tuple* of
+    two arrays; a list is always taken as one sequence per row."""
+    if isinstance(lists, tuple) and len(lists) == 2:
+        indptr = np.ascontiguousarray(np.asarray(lists[0], dtype=np.int64).ravel())
+        items = np.ascontiguousarray(np.asarray(lists[1]).ravel())
+        if indptr.size < 1 or indptr[0] != 0 or (np.diff(indptr) < 0).any() or indptr[-1] != items.size:
+            raise ValueError(f"{what}: indptr must start at 0, be non-decreasing and end at len(items)")
+        return indptr, items
+    rows = [np.asarray(r).ravel() for r in lists]
+    rows = [r if r.size else r.astype(np.int64) for r in rows]          # an empty row has no dtype of its own
+    indptr = np.zeros(len(rows) + 1, dtype=np.int64)
+    indptr[1:] = np.cumsum([r.size for r in rows])
+    items = np.concatenate(rows) if indptr[-1] else np.zeros(0, dtype=np.int64)
+    return indptr, items
+
+
+def normalize_exclusions(exclude, n_rows, n_candidates):
+    """The exclusion lists of ``most_similar`` / ``recommend`` in the form ``dae_topk_similarity_ex`` reads: ``(indptr int64
+    [n_rows + 1], items int32)``, every row's items ascending and unique, indices outside ``[0, n_candidates)`` dropped.
+    ``exclude``: a list of ``n_rows`` index sequences or an ``(indptr, items)`` tuple.  Host code."""
+    indptr, items = _csr_lists(exclude, "exclude")
+    if indptr.size - 1 != int(n_rows):
+        raise ValueError(f"exclude has {indptr.size - 1} rows for {int(n_rows)} queries")
+    if items.size and items.dtype.kind not in "iu":
+        raise ValueError("exclude must hold integer indices")
+    items = items.astype(np.int64)
+    rows = np.repeat(np.arange(int(n_rows), dtype=np.int64), np.diff(indptr))
+    ok = (items >= 0) & (items < int(n_candidates))
+    keys = np.unique(rows[ok] * int(n_candidates) + items[ok])          # sorted by row, then item; duplicates gone
+    out_ptr = np.zeros(int(n_rows) + 1, dtype=np.int64)
+    if int(n_candidates) > 0:
+        out_ptr[1:] = np.cumsum(np.bincount(keys // int(n_candidates), minlength=int(n_rows)))
+        return out_ptr, (keys % int(n_candidates)).astype(np.int32)
+    return out_ptr, np.zeros(0, dtype=np.int32)
+
+
+def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candidates=None, *, exclude=None, return_tensor=False,
+                 device=None):
     """The ``k`` most similar rows of ``candidates`` (default: ``in_df`` itself) for every row of ``in_df``, by the scores
     ``pairwise_similarity`` would give (same ``norm`` / ``metric``, same exact-fp32 products), without the N x N matrix:
     ``dae_topk_similarity`` keeps a running top-k per row inside the GEMM's epilogue.
@@ -189,7 +231,12 @@ def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candi
     (default: True without ``candidates``, False with them) drops each row's own index -- unlike ``set_diagonal_zero``, which
     keeps the self pair at score 0.  Rows are ordered by score descending, ties by index ascending; with fewer than ``k``
     candidates the tail is index -1, score -inf.  1 <= k <= 128.  Returns ``(indices int64 [N x k], scores float32 [N x k])``
-    as ndarrays, or as CUDA tensors with ``return_tensor=True``."""
+    as ndarrays, or as CUDA tensors with ``return_tensor=True``.
+
+    ``exclude`` (default None: nothing) names, per query row, candidates that must not be returned -- a list of index sequences
+    or an ``(indptr, items)`` tuple; it is sorted, de-duplicated and stripped of indices outside the corpus here
+    (``normalize_exclusions``).  An excluded candidate is skipped before it can take one of the k slots
+    (``dae_topk_similarity_ex``), so a row still gets k results when k others exist.  Allowed together with ``exclude_self``."""
     import torch
     assert metric in ["cosine", "linear kernel"]                      # helpers.py:34
     if norm not in _NORMS:
@@ -214,13 +261,148 @@ def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candi
     off = (-ws.data_ptr()) % 256
     import ctypes
     with torch.cuda.device(dev):
-        L.call("dae_topk_similarity", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D, _NORMS[norm],
-               _METRICS[metric], k, 1 if exclude_self else 0, L.ptr(idx), L.ptr(score), idx.stride(0),
-               ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
+        if exclude is None:
+            L.call("dae_topk_similarity", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D, _NORMS[norm],
+                   _METRICS[metric], k, 1 if exclude_self else 0, L.ptr(idx), L.ptr(score), idx.stride(0),
+                   ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
+        else:
+            xp, xi = normalize_exclusions(exclude, Nq, Nc)
+            xp_d = torch.from_numpy(xp).to(dev)
+            xi_d = torch.from_numpy(xi if xi.size else np.zeros(1, dtype=np.int32)).to(dev)      # never a NULL pointer
+            L.call("dae_topk_similarity_ex", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
+                   _NORMS[norm], _METRICS[metric], k, 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(idx), L.ptr(score),
+                   idx.stride(0), ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
     idx = idx.long()
     if return_tensor:
         return idx, score
     return idx.cpu().numpy(), score.cpu().numpy()
+
+
+def decay_factors(indptr, timestamps, beta, time_unit=None):
+    """Per-event decay factors of ``user_states`` from event times: ``beta ** ((t_e - t_{e-1}) / time_unit)`` for every event but a
+    user's first (whose factor is ignored; 1 is written), computed in float64 and rounded once to float32.  ``timestamps`` has
+    the layout of the items (one per event); within a user they must not decrease (``ValueError``).  ``time_unit`` defaults to
+    1 and must be positive.  Host code."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    t = np.asarray(timestamps, dtype=np.float64).ravel()
+    if t.size != int(indptr[-1]):
+        raise ValueError(f"{t.size} timestamps for {int(indptr[-1])} events")
+    beta = float(beta)
+    if not 0.0 <= beta <= 1.0:
+        raise ValueError(f"beta must be in [0, 1] (got {beta})")
+    unit = 1.0 if time_unit is None else float(time_unit)
+    if not (unit > 0.0 and np.isfinite(unit)):
+        raise ValueError(f"time_unit must be positive and finite (got {time_unit})")
+    if not np.isfinite(t).all():
+        raise ValueError("timestamps must be finite")
+    dt = np.zeros(t.size, dtype=np.float64)
+    dt[1:] = t[1:] - t[:-1]
+    first = indptr[:-1][np.diff(indptr) > 0]
+    dt[first] = 0.0
+    if (dt < 0).any():
+        e = int(np.flatnonzero(dt < 0)[0])
+        raise ValueError(f"timestamps decrease within a user (event {e}, user {int(np.searchsorted(indptr, e, side='right') - 1)})")
+    with np.errstate(divide="ignore"):
+        return np.power(beta, dt / unit).astype(np.float32)              # 0 ** 0 = 1: simultaneous events do not decay
+
+
+def user_states(histories, embeddings, beta=0.9, *, timestamps=None, time_unit=None, all_states=False, return_tensor=False,
+                device=None):
+    """User states from browsing histories by the decaying model of "Embedding-based News Recommendation for Millions of Users"
+    (KDD'17): per user, over the events oldest first, ``s = d * s + E[item]``, ``z = d * z + 1``, state = ``s / z`` -- a
+    decay-weighted mean of the embeddings of the articles read, newest weighted most (``dae_user_states``, fp32, fixed order:
+    bit-identical run to run and independent of the order of the users).
+
+    ``histories``: a list of index sequences (one per user, oldest click first; an article may repeat) or an ``(indptr, items)``
+    tuple.  ``embeddings`` [articles x H] takes the containers of ``most_similar``.  ``d`` is ``beta`` in [0, 1] for every event,
+    or, with ``timestamps`` (same layout as the items), ``beta ** ((t_e - t_{e-1}) / time_unit)`` (``decay_factors``; a
+    ``ValueError`` when a user's timestamps decrease).  An item outside ``[0, articles)`` raises ``ValueError``.
+
+    Returns float32 ``[users x H]``: the state after each user's last event (zeros for an empty history); with
+    ``all_states=True`` ``[events x H]``: row e is the state after event e, the one that predicts event e + 1 -- and the row of
+    a user's last event equals that user's row of the default form bit for bit.  ndarray, or a CUDA tensor with
+    ``return_tensor=True``."""
+    import torch
+    indptr, items = _csr_lists(histories)
+    if items.size and items.dtype.kind not in "iu":
+        raise ValueError("histories must hold integer article indices")
+    beta = float(beta)
+    if not 0.0 <= beta <= 1.0:
+        raise ValueError(f"beta must be in [0, 1] (got {beta})")
+    decay = None if timestamps is None else decay_factors(indptr, _csr_lists(timestamps, "timestamps")[1]
+                                                          if isinstance(timestamps, (tuple, list)) else timestamps, beta, time_unit)
+    L.load()
+    dev = torch.device("cuda" if device is None else device)
+    E = _device_matrix(torch, embeddings, dev) if not (isinstance(embeddings, torch.Tensor) and embeddings.is_cuda
+                                                       and embeddings.dtype == torch.float32 and embeddings.dim() == 2
+                                                       and embeddings.stride(1) == 1) else embeddings      # a strided view is read in place
+    Na, H = int(E.shape[0]), int(E.shape[1])
+    if items.size and (int(items.min()) < 0 or int(items.max()) >= Na):
+        raise ValueError(f"history items must be in 0..{Na - 1} (got {int(items.min())}..{int(items.max())})")
+    M, nnz = int(indptr.size - 1), int(items.size)
+    rows = nnz if all_states else M
+    U = torch.empty((rows, H), dtype=torch.float32, device=dev)
+    if rows == 0 or H == 0:
+        return U if return_tensor else U.cpu().numpy()
+    ip_d = torch.from_numpy(indptr).to(dev)
+    it_d = torch.from_numpy(items.astype(np.int32) if nnz else np.zeros(1, dtype=np.int32)).to(dev)
+    dc_d = None if decay is None else torch.from_numpy(decay if nnz else np.zeros(1, dtype=np.float32)).to(dev)
+    with torch.cuda.device(dev):
+        L.call("dae_user_states", L.ptr(E), E.stride(0), Na, H, L.ptr(ip_d), L.ptr(it_d), M, nnz, beta, L.ptr(dc_d),
+               1 if all_states else 0, L.ptr(U), U.stride(0), L.current_stream())
+    if return_tensor:
+        return U
+    return U.cpu().numpy()
+
+
+def recommend(user_vectors, embeddings, k=10, seen=None, norm="", metric="linear kernel", *, return_tensor=False, device=None):
+    """The ``k`` articles (rows of ``embeddings``) with the largest relevance to every user vector (e.g. from ``user_states``)
+    among those the user has not read: ``most_similar(user_vectors, candidates=embeddings, exclude=seen)``.  ``seen``: per
+    user the indices already read (a list of sequences or an ``(indptr, items)`` tuple -- a history as given to ``user_states``
+    will do; order and repeats do not matter), or None.  The default ``metric`` is the paper's relevance, the inner product;
+    ``'cosine'`` and ``norm`` are those of ``most_similar``.  Returns ``(indices, scores)`` as ``most_similar`` does."""
+    return most_similar(user_vectors, k=k, norm=norm, metric=metric, candidates=embeddings, exclude=seen,
+                        return_tensor=return_tensor, device=device)
+
+
+def next_click_metrics(indices, targets):
+    """Scores a recommendation list against one held-out article per query: hit@k (the target is in the list), MRR@k
+    (``1 / rank``) and nDCG@k (``1 / log2(1 + rank)``; one relevant item, so the ideal DCG is 1), rank counted from 1, each 0
+    when the target is not in the list; averaged over the queries with a target >= 0.  An index of -1 matches nothing.  Host
+    code.  Returns ``{'hit', 'mrr', 'ndcg', 'n'}``; the three are NaN when no query counts."""
+    idx = np.asarray(indices)
+    if idx.ndim != 2:
+        raise ValueError("indices must be [n_queries x k]")
+    tgt = np.asarray(targets).ravel().astype(np.int64)
+    if tgt.shape[0] != idx.shape[0]:
+        raise ValueError(f"{tgt.shape[0]} targets for {idx.shape[0]} queries")
+    ok = tgt >= 0
+    n = int(ok.sum())
+    if n == 0 or idx.shape[1] == 0:
+        nan = float("nan")
+        return {"hit": nan if n == 0 else 0.0, "mrr": nan if n == 0 else 0.0, "ndcg": nan if n == 0 else 0.0, "n": n}
+    match = (idx[ok] == tgt[ok][:, None]) & (idx[ok] >= 0)
+    hit = match.any(axis=1)
+    rank = np.where(hit, match.argmax(axis=1) + 1, 1).astype(np.float64)      # the first occurrence
+    return {"hit": float(hit.mean()), "mrr": float(np.where(hit, 1.0 / rank, 0.0).mean()),
+            "ndcg": float(np.where(hit, 1.0 / np.log2(1.0 + rank), 0.0).mean()), "n": n}
+
+
+def popularity_recommend(histories, n_articles, k, seen=None):
+    """The baseline a recommender has to beat: for every user the ``k`` most-clicked articles (over all ``histories``; ties by
+    index ascending) that are not in the user's ``seen`` list (default: the user's own history).  Host code.  Returns
+    int64 ``[users x k]``, -1 where fewer than k articles remain."""
+    indptr, items = _csr_lists(histories)
+    M = indptr.size - 1
+    xp, xi = normalize_exclusions((indptr, items) if seen is None else seen, M, n_articles)
+    order = np.argsort(-np.bincount(items.astype(np.int64), minlength=int(n_articles)), kind="stable")
+    out = np.full((M, int(k)), -1, dtype=np.int64)
+    for u in range(M):
+        mine = xi[xp[u]:xp[u + 1]]
+        head = order[:int(k) + mine.size]                                  # enough to survive the removal of `mine`
+        keep = head[~np.isin(head, mine)][:int(k)]
+        out[u, :keep.size] = keep
+    return out
 
 
 def _label_keys(labels):

@@ -51,6 +51,31 @@ def synthetic_labels(n_rows, *, kind="category", seed=1234):
     return rng.choice(n_story, size=n_rows, p=w / w.sum()).astype(np.int64)
 
 
+def synthetic_sessions(n_users, labels, *, mean_len, seed, n_preferred=2, p_preferred=0.9):
+    """Seeded click logs over the articles ``labels`` describes (one label per article): every user prefers ``n_preferred``
+    label classes drawn uniformly, reads a geometric number of articles (at least 1, mean ``mean_len``), and each click is, with probability
+    ``p_preferred``, a uniformly drawn article of one of the preferred classes, else a uniformly drawn article of the whole
+    corpus.  An article may repeat within a user.  Returns the history CSR ``(indptr int64 [n_users + 1], items int32)``,
+    oldest click first; deterministic per seed."""
+    rng = np.random.default_rng(seed)
+    lab = np.asarray(labels).ravel()
+    classes, inv = np.unique(lab, return_inverse=True)
+    order = np.argsort(inv, kind="stable")                                  # articles grouped by class
+    start = np.zeros(classes.size + 1, dtype=np.int64)
+    start[1:] = np.cumsum(np.bincount(inv, minlength=classes.size))
+    n_pref = min(int(n_preferred), classes.size)
+    pref = np.argsort(rng.random((int(n_users), classes.size)), axis=1)[:, :n_pref]      # distinct classes per user
+    lens = rng.geometric(1.0 / max(float(mean_len), 1.0), int(n_users)).astype(np.int64)      # >= 1, mean mean_len
+    indptr = np.zeros(int(n_users) + 1, dtype=np.int64)
+    indptr[1:] = np.cumsum(lens)
+    nnz = int(indptr[-1])
+    user = np.repeat(np.arange(int(n_users)), lens)
+    cls = pref[user, rng.integers(0, n_pref, nnz)]
+    within = start[cls] + (rng.random(nnz) * (start[cls + 1] - start[cls])).astype(np.int64)
+    items = np.where(rng.random(nnz) < p_preferred, order[within], rng.integers(0, lab.size, nnz))
+    return indptr, items.astype(np.int32)
+
+
 def xavier_uniform(n_features, n_components, const=1, seed=42):
     """U(+-const*sqrt(6/(F+H))) (autoencoder/utils.py:16-26) from a NumPy Generator: the reference's
     tf.random_uniform stream is not reproducible without TensorFlow, so parity runs inject this W0."""

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define DAE_PAD 128
-#define DAE_ABI_VERSION 9   /* 9: dae_pair_hist / dae_pair_hist_workspace / dae_pair_hist_max_bins (label AUROC and pair statistics from fused per-class score histograms); 8: dae_threshold_pairs / dae_threshold_pairs_workspace (near-duplicate search: all pairs over a threshold); 7: dae_topk_similarity / dae_topk_similarity_workspace (fused similarity + top-k retrieval); 6:dae_comm_* / dae_allreduce_grads / dae_dp_exchange / dae_dp_bands (the data-parallel collective in the C ABI, RCCL on the step's stream); 5: dae_storage_format (the fp16 build libdae_hip_f16.so), options x3_terms / op_scale_log2, DAE_WAIT_DW_CREATED = 100; 4: DAE_BF16X3 (split-bf16 mode), dae_gemm_nt_n; 3: dae_buffers.grad_lo, option encode_w32 (and one since removed); 2: dae_step.c_row_idx, plan options, phases 4/5, sharded apply */
+#define DAE_ABI_VERSION 9   /* still 9 with dae_user_states and dae_topk_similarity_ex / dae_topk_similarity_ex_workspace: they are new symbols only (no struct or signature of version 9 changed), which a caller detects by symbol lookup (dlsym); 9: dae_pair_hist / dae_pair_hist_workspace / dae_pair_hist_max_bins (label AUROC and pair statistics from fused per-class score histograms); 8: dae_threshold_pairs / dae_threshold_pairs_workspace (near-duplicate search: all pairs over a threshold); 7: dae_topk_similarity / dae_topk_similarity_workspace (fused similarity + top-k retrieval); 6:dae_comm_* / dae_allreduce_grads / dae_dp_exchange / dae_dp_bands (the data-parallel collective in the C ABI, RCCL on the step's stream); 5: dae_storage_format (the fp16 build libdae_hip_f16.so), options x3_terms / op_scale_log2, DAE_WAIT_DW_CREATED = 100; 4: DAE_BF16X3 (split-bf16 mode), dae_gemm_nt_n; 3: dae_buffers.grad_lo, option encode_w32 (and one since removed); 2: dae_step.c_row_idx, plan options, phases 4/5, sharded apply */
 
 enum { DAE_BF16 = 0, DAE_F32 = 1,
        DAE_BF16X3 = 2 /* dae_config.dtype only: bf16 storage and MFMA, but every stored operand of the three gradient GEMMs is kept as
@@ -430,6 +430,44 @@ int dae_topk_similarity(const float* Q, int64_t ldq, int32_t Nq, const float* C,
                         int32_t D, int32_t norm, int32_t metric, int32_t k, int32_t exclude_self,
                         int32_t* idx, float* score, int64_t ldk, void* workspace, uint64_t workspace_bytes,
                         void* stream);
+
+/* -------------------------------------------------------------------------------------------------
+ * Seen-aware retrieval: dae_topk_similarity with a list of excluded corpus rows per query row (the articles a user has
+ * already read; helpers.most_similar(exclude=...), helpers.recommend).
+ *   Every argument of dae_topk_similarity, and the same scores, order and workspace size, plus an exclusion CSR on the
+ *   device: excl_indptr int64[Nq + 1], excl_items int32[excl_indptr[Nq]]; row i's items are corpus indices, sorted
+ *   ascending and unique (a precondition: the lookup is a binary search).  Candidate j is skipped for query row i when j
+ *   is in row i's list -- before it can take one of the k slots, so a row still gets k results whenever k admissible
+ *   candidates exist (admissible: j < Nc, not excluded, and not i itself with exclude_self); otherwise the tail is
+ *   idx = -1, score = -inf.  Membership is tested only for the candidates that beat the row's current k-th score.
+ *   Both pointers NULL: exactly dae_topk_similarity (which forwards here), bit for bit; exactly one NULL is an argument error.
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_topk_similarity_ex_workspace(int32_t Nq, int32_t Nc, int32_t D, int32_t k);
+int dae_topk_similarity_ex(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc,
+                           int32_t D, int32_t norm, int32_t metric, int32_t k, int32_t exclude_self,
+                           const int64_t* excl_indptr, const int32_t* excl_items, int32_t* idx, float* score,
+                           int64_t ldk, void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
+ * User states from browsing histories: the decaying model of "Embedding-based News Recommendation for Millions of
+ * Users" (KDD'17), a decay-weighted mean of the embeddings of the articles a user has read (helpers.user_states).
+ *   E [Na x lde] fp32 article embeddings (device).  History CSR (device): indptr int64[M + 1], items int32[nnz], each
+ *   user's events oldest first; an article may occur more than once.  Per user, in this order:
+ *       s = 0 (H floats), z = 0;   for every event e:   s = d_e * s + E[items[e]];   z = d_e * z + 1;   state_e = s / z
+ *   d_e: decay == NULL: the scalar beta in [0, 1] for every event; else decay float32[nnz] (device), the factor applied
+ *   to the running state before event e is added (time-based decay, session resets with 0); values are expected in [0, 1].
+ *   A user's first factor is ignored.
+ *   all_states == 0: U [M x ldu], row u = the state after u's last event, zeros for an empty history.
+ *   all_states != 0: U [nnz x ldu], row e = state_e (the state that predicts event e + 1).
+ *   fp32 throughout (one fused multiply-add per step, one IEEE division per output), fixed order, no atomics:
+ *   bit-identical run to run and independent of the order of the users; the all_states row of a user's last event
+ *   equals its all_states == 0 row bit for bit.
+ *   Precondition: every items[e] is in [0, Na).  It is not reported: an index outside is read as the nearest valid row.
+ *   No workspace.  lde, ldu >= H; 16-byte aligned E / U with lde, ldu and H multiples of 4 take the vector path.
+ * ------------------------------------------------------------------------------------------------- */
+int dae_user_states(const float* E, int64_t lde, int32_t Na, int32_t H, const int64_t* indptr, const int32_t* items,
+                    int64_t M, int64_t nnz, float beta, const float* decay, int32_t all_states, float* U, int64_t ldu,
+                    void* stream);
 
 /* -------------------------------------------------------------------------------------------------
  * Near-duplicate search: every pair (i, j) whose score reaches a threshold, without an N x N matrix (the range query

@@ -12,6 +12,7 @@ reference checkout (.MISSING_LARGE_BLOBS:2), so data comes from ``--data <matrix
 examples:
   python main_autoencoder.py --model_name demo --num_epochs 5 --verbose --verbose_step 1
   python main_autoencoder.py --model_name uci --data X.npz --labels y.npy --triplet_strategy batch_hard
+  python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --similarity False
 """
 import argparse
 import os
@@ -91,6 +92,16 @@ def build_parser():
                    help="after training (needs labels): the related-vs-unrelated AUROC, with a bracket that certifies it, and the box-plot "
                         "numbers of the input vectors and of the embeddings, written to similarity_stats_<name>.json (per-class score "
                         "histograms, no N x N matrix: works with --similarity False)")
+    p.add_argument("--sessions", default="",
+                   help="click logs for --recommend: an .npz with `indptr` (int64, users + 1), `items` (train article indices, every user's clicks "
+                        "oldest first) and optionally `timestamps` (one per click), or the word `synthetic` (seeded logs in which a user reads "
+                        "mostly from a few label classes; needs labels)")
+    p.add_argument("--recommend", type=int, default=0,
+                   help="K > 0 (needs --sessions): after training, hold out every user's last click, build decayed user states from the rest "
+                        "on the train embeddings, recommend K unseen articles per user to article_encoded_recommend{K}.npz, and print hit@K / "
+                        "MRR / nDCG beside a most-clicked-unseen popularity baseline (no users x articles matrix: works with --similarity False)")
+    p.add_argument("--session_decay", type=float, default=0.9,
+                   help="decay of --recommend's user states: per click, or per unit of time when the sessions carry timestamps")
     return p
 
 
@@ -106,6 +117,8 @@ def validate(a):
     if a.main_dir == '':
         a.main_dir = a.model_name
     assert a.model_name != '', "--model_name is required"
+    assert a.recommend == 0 or a.sessions != '', "--recommend needs --sessions"
+    assert 0. <= a.session_decay <= 1.
     return a
 
 
@@ -241,6 +254,47 @@ def evaluate_duplicates(a, trY, vlY, emb, emb_v, data_dir):
     return out
 
 
+def evaluate_recommend(a, trY, emb, data_dir):
+    """--sessions S --recommend K: next-click evaluation of the decaying user model.  Every user's last click is held out; the
+    user state is the decay-weighted mean of the train embeddings of the clicks before it (helpers.user_states); the K unseen
+    articles with the largest inner product are recommended (helpers.recommend: no users x articles matrix) and saved as
+    ``indices`` / ``scores`` / ``targets`` in article_encoded_recommend{K}.npz.  hit@K, MRR@K and nDCG@K are printed beside
+    those of the most-clicked-unseen baseline (host code).  Users with fewer than two clicks have no target (-1) and are not
+    counted."""
+    from dae_rnn_news_recommendation_amd import helpers
+    from dae_rnn_news_recommendation_amd.synthetic import synthetic_sessions
+    K, n = a.recommend, emb.shape[0]
+    print('calculate recommend %d' % K)
+    t = None
+    if a.sessions == 'synthetic':
+        assert trY is not None, "--sessions synthetic needs labels"
+        seed = a.seed if a.seed >= 0 else 1234
+        indptr, items = synthetic_sessions(max(n // 2, 1), np.unique(np.asarray(trY), return_inverse=True)[1], mean_len=12, seed=seed)
+    else:
+        with np.load(a.sessions) as f:
+            indptr, items = np.asarray(f['indptr'], dtype=np.int64), np.asarray(f['items'])
+            t = np.asarray(f['timestamps'], dtype=np.float64) if 'timestamps' in f.files else None
+    lens = np.diff(indptr)
+    users = lens.shape[0]
+    has = lens >= 2
+    targets = np.where(has, items[np.maximum(indptr[1:] - 1, 0)] if items.size else -1, -1).astype(np.int64)
+    keep = np.ones(items.shape[0], dtype=bool)
+    keep[indptr[1:][lens >= 1] - 1] = False                               # the history is everything before the last click
+    h_ptr = np.zeros(users + 1, dtype=np.int64)
+    h_ptr[1:] = np.cumsum(np.maximum(lens - 1, 0))
+    hist = (h_ptr, items[keep])
+    states = helpers.user_states(hist, emb, a.session_decay, timestamps=None if t is None else t[keep], return_tensor=True)
+    idx, score = helpers.recommend(states, emb, k=K, seen=hist)
+    np.savez(data_dir + 'article_encoded_recommend%d.npz' % K, indices=idx, scores=score, targets=targets)
+    m = helpers.next_click_metrics(idx, targets)
+    b = helpers.next_click_metrics(helpers.popularity_recommend(hist, n, K), targets)
+    print('  %d users, %d clicks, %d with a held-out click -> article_encoded_recommend%d.npz' % (users, items.shape[0], m['n'], K))
+    print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'decayed user state', m['hit'], m['mrr'], m['ndcg']))
+    print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'most clicked unseen', b['hit'], b['mrr'], b['ndcg']))
+    print('calculate recommend %d done' % K)
+    return idx, score, targets
+
+
 # artefact names of the reference's data directory (main_autoencoder.py:227-244, restored at :162-174)
 def _artefact(kind, a, validate=False):
     suffix = "_validate" if validate else ""
@@ -324,6 +378,8 @@ def main(argv=None):
         evaluate_top_k(a, trX, vlX, trY, vlY, emb, emb_v, model.data_dir)
     if a.dup_threshold > 0 and dp.rank() == 0:
         evaluate_duplicates(a, trY, vlY, emb, emb_v, model.data_dir)
+    if a.recommend > 0 and dp.rank() == 0:
+        evaluate_recommend(a, trY, emb, model.data_dir)
     if model.samples_per_sec:
         print('training throughput: %.0f samples/s over %d epochs; embeddings %s -> %s' %
               (model.samples_per_sec, a.num_epochs, emb.shape, model.data_dir))
