@@ -1,0 +1,278 @@
+// dae_rank.hip -- the rank of one target corpus row per query row among all corpus rows, without the Nq x Nc matrix
+// (dae_rank_similarity): the full-rank twin of dae_topk_similarity_ex, for AUC, mean rank and untruncated MRR / nDCG.
+//
+// The scores and the order are those of dae_topk.hip: rows normalised by row_normalize_kernel into zero-padded fp32 operand
+// images, products by gemm_mainloop<float, 2> over the whole K range in one pass, every (score, index) pair mapped to the
+// 64-bit key score_key(score) << 32 | ~index (score descending, then index ascending, -0 == +0).  What is new is an epilogue
+// that COUNTS the keys above one key per row instead of selecting the k largest.
+//
+//   rank[i] = 1 + #{ j < Nc : j != t, j not in row i's exclusion list, not (exclude_self and j == i), key(S[i, j], j) > key(S[i, t], t) }
+//
+// 1. rank_gather_kernel copies the targets' rows of the corpus image into a third image G [Nqp x Dp] (row i = corpus row t_i).
+// 2. rank_target_kernel, one workgroup per query tile: the same K loop on (query tile qt of Q, tile qt of G); the diagonal of
+//    the 128 x 128 result is S[i, t_i], out of the instruction sequence that produces it in the sweep (the value of an MFMA
+//    output element depends on its two operand rows and the K order alone, not on its place in the tile), so target_score and
+//    the key are bit-equal to what dae_topk_similarity writes for that pair.  Writes the key (8 bytes per row), target_score
+//    and rank = 1 (0 for a row without a target).
+// 3. rank_tiles_kernel: grid = (query tiles) x (corpus slices), 256 threads (4 waves), as topk_tiles_kernel.  Per 128-column
+//    tile the keys above the row's target key are counted straight from the accumulators: a lane holds 32 rows x 2 columns of
+//    the tile; the compare's lane mask is counted per half wave on the scalar unit and lane l of a wave keeps the running
+//    count of the wave's row l for the whole slice.  Columns >= Nc (zero padding: score 0, which would
+//    beat every negative target) and the self pair are masked; the target itself has an equal key and is never counted.
+//    Exclusion lists (sorted CSR rows, as in dae_topk_similarity_ex) only remove competitors: the sweep counts every column,
+//    then the listed ones are taken out again.  Lane l < 32 of wave w owns query row 32 w + l and a cursor into its list; the
+//    items of a list that fall into the current tile are the run behind the cursor.  Only when some row of the query tile has
+//    an item in the tile is the tile written to LDS (over the dead staging ring); the owner lanes read the listed columns'
+//    scores there, compare and count.  The work is one step per list item -- it does not grow with rank.
+//    End of the slice: counters and corrections meet in a [128] LDS array (integer atomics) and one atomic add per row goes
+//    to rank -- integers, so the result is bit-identical run to run and independent of the corpus split and the grid.
+// LDS: 64 KiB ring / tile + 1 KiB keys + 0.5 KiB counts = 65.5 KiB, two workgroups per CU.
+#include "dae_gemm_tile.h"
+
+namespace dae {
+
+constexpr int RANK_SLOTS = 512;            // workgroups in flight on the MI355X: 256 CUs x 2 (the slice count is sized for it)
+constexpr int RANK_TILE_BYTES = BM * BN * 4;
+constexpr int RANK_LDS = RANK_TILE_BYTES + 128 * 8 + 128 * 4;
+constexpr int RANK_TARGET_LDS = lds_bytes_for(2);
+
+// topk_key of dae_topk.hip (duplicated: that file's kernels stay as they are)
+__device__ __forceinline__ uint64_t rank_key(float s, int j) {
+    if (s == 0.f) s = 0.f;                                      // -0 and +0 are one score
+    const uint32_t u = __float_as_uint(s);
+    const uint32_t h = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((uint64_t)h << 32) | (uint32_t)~(uint32_t)j;
+}
+
+__global__ __launch_bounds__(256) void rank_gather_kernel(const float* __restrict__ Ci, const int32_t* __restrict__ targets, int Nq, int Nc,
+                                                          int Dp, float* __restrict__ G) {
+    const int i = blockIdx.x;                                   // < Nqp
+    int t = i < Nq ? targets[i] : 0;
+    t = min(max(t, 0), Nc - 1);                                 // a caller error (see dae_hip.h) must not become a stray read
+    const f32x4* src = reinterpret_cast<const f32x4*>(Ci + (int64_t)t * Dp);
+    f32x4* dst = reinterpret_cast<f32x4*>(G + (int64_t)i * Dp);
+    for (int d = threadIdx.x; d < Dp / 4; d += 256) dst[d] = src[d];
+}
+
+struct RankTargetParams {
+    GemmParams g;                 // one K segment: A = query image, Bt = gathered image
+    int Nq, Nc;
+    const int32_t* targets;       // [Nq]
+    uint64_t* tkey;               // [Nqp]
+    int32_t* rank;                // [Nq]
+    float* target_score;          // [Nq]
+};
+
+__global__ __launch_bounds__(GEMM_THREADS, 2) void rank_target_kernel(RankTargetParams p) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, g = lane >> 5, c = lane & 31;
+    const int qt = blockIdx.x;
+    f32x16 acc[2][2];
+    gemm_mainloop<float, 2>(p.g, qt, qt, 0, p.g.ktiles_total, lds, acc);
+    if (wm != wn) return;                                       // the diagonal lies in the waves (0, 0) and (1, 1), blocks mt == nt
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            // row of a value inside its 32 x 32 block: the accumulator layout of v_mfma_f32_32x32x2_f32; its column is c
+            if ((r & 3) + 8 * (r >> 2) + 4 * g != c) continue;
+            const int gi = qt * BM + wm * 64 + mt * 32 + c;
+            if (gi >= p.Nq) continue;
+            const int t = p.targets[gi];
+            const float s = acc[mt][mt][r];
+            if (t < 0) {
+                p.tkey[gi] = ~0ull;                             // above every key: nothing is counted
+                p.rank[gi] = 0;
+                p.target_score[gi] = -__builtin_inff();
+            } else {
+                p.tkey[gi] = rank_key(s, min(t, p.Nc - 1));
+                p.rank[gi] = 1;
+                p.target_score[gi] = s;
+            }
+        }
+}
+
+struct RankParams {
+    GemmParams g;                 // one K segment: A = query image, Bt = corpus image
+    int Nq, Nc, exclude_self, splits, ctiles;
+    const uint64_t* tkey;         // [Nqp] target keys (rank_target_kernel)
+    int32_t* rank;                // [Nq], holds 1 (0 without a target) on entry
+    const int64_t* excl_indptr;   // [Nq + 1] exclusion CSR (rank_tiles_kernel<true> only): row i's list is
+    const int32_t* excl_items;    // excl_items[excl_indptr[i] .. excl_indptr[i + 1]), ascending and unique
+};
+
+template <bool EXCL>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams p) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    float* tile = reinterpret_cast<float*>(lds);
+    uint64_t* tk = reinterpret_cast<uint64_t*>(lds + RANK_TILE_BYTES);     // the query tile's target keys
+    int* cnt = reinterpret_cast<int*>(tk + 128);                           // keys above the target, per row, this slice
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int split = blockIdx.x % p.splits, qt = blockIdx.x / p.splits;
+    const int ct0 = (int)((int64_t)p.ctiles * split / p.splits), ct1 = (int)((int64_t)p.ctiles * (split + 1) / p.splits);
+    const int wm = wave >> 1, wn = wave & 1, g = lane >> 5, c = lane & 31;
+    if (tid < 128) {
+        const int gi = qt * BM + tid;
+        tk[tid] = gi < p.Nq ? p.tkey[gi] : ~0ull;
+        cnt[tid] = 0;
+    }
+    // ---- the exclusion cursor of this lane's row (lanes 0..31 of every wave) ----
+    const int xrow = wave * 32 + lane, xgi = qt * BM + xrow;
+    const int32_t* X = nullptr;
+    int xpos = 0, xend = 0, xnext = INT32_MAX, xsub = 0;
+    uint64_t xkey = ~0ull;
+    if constexpr (EXCL) {
+        if (lane < 32 && xgi < p.Nq) {
+            xkey = p.tkey[xgi];
+            const int64_t x0 = p.excl_indptr[xgi];
+            X = p.excl_items + x0;
+            xend = (int)(p.excl_indptr[xgi + 1] - x0);
+            if (xkey == ~0ull) xend = 0;                        // no target: nothing to count
+            int lo = 0, hi = xend;                              // first item of the slice
+            while (lo < hi) {
+                const int m = (lo + hi) >> 1;
+                if (X[m] < ct0 * BN) lo = m + 1; else hi = m;
+            }
+            xpos = lo;
+            if (xpos < xend) xnext = X[xpos];
+        }
+    }
+    int n = 0;                                                  // lane l: keys above the target of row wm * 64 + l in this wave's 64 columns
+    __syncthreads();
+    for (int ct = ct0; ct < ct1; ++ct) {
+        f32x16 acc[2][2];
+        gemm_mainloop<float, 2>(p.g, qt, ct, 0, p.g.ktiles_total, lds, acc);
+        // ---- count from the accumulators (tk lies behind the ring).  A register of the tile holds two rows, one per half wave:
+        //      the compare's lane mask is the ballot, its two halves are counted on the scalar unit and added to the rows' lanes ----
+        const int j0 = ct * BN + wn * 64 + c, j1 = j0 + 32;
+        const bool ok0 = j0 < p.Nc, ok1 = j1 < p.Nc;
+        int ln = lane;
+        asm volatile("" : "+v"(ln));                           // per tile: keeps the rows' lane masks and LDS addresses out of the registers that live across the K loop
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int lrow = mt * 32 + (r & 3) + 8 * (r >> 2);          // the row of lanes 0..31 (g = 0); lanes 32..63 hold lrow + 4
+                const int row = wm * 64 + lrow + 4 * (ln >> 5);
+                const uint64_t t = tk[row];
+                const int self = p.exclude_self ? qt * BM + row : -1;
+                const uint64_t b0 = __ballot(ok0 && j0 != self && rank_key(acc[mt][0][r], j0) > t);
+                const uint64_t b1 = __ballot(ok1 && j1 != self && rank_key(acc[mt][1][r], j1) > t);
+                const int lo = __popc((uint32_t)b0) + __popc((uint32_t)b1), hi = __popc((uint32_t)(b0 >> 32)) + __popc((uint32_t)(b1 >> 32));
+                n += (ln == lrow ? lo : 0) + (ln == lrow + 4 ? hi : 0);
+                if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);     // four rows' keys in flight, not all 32 (VGPRs)
+            }
+        if constexpr (!EXCL) __syncthreads();                   // every wave is done with the staging ring
+        if constexpr (EXCL) {
+            const int tile_end = (ct + 1) * BN;
+            // the barrier also says that every wave is done with the staging ring
+            if (__syncthreads_or(xnext < tile_end)) {
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            tile[(wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g) * BN + wn * 64 + nt * 32 + c] = acc[mt][nt][r];
+                __syncthreads();
+                int last = -1;
+                while (xnext < tile_end) {                      // the run of this row's list inside the tile
+                    const int x = xnext;
+                    if (x >= ct * BN && x != last && x < p.Nc && !(p.exclude_self && x == xgi))
+                        xsub += (int)(rank_key(tile[xrow * BN + (x - ct * BN)], x) > xkey);
+                    last = x;
+                    ++xpos;
+                    xnext = xpos < xend ? X[xpos] : INT32_MAX;
+                }
+                __syncthreads();                                // the tile is the next K loop's staging ring
+            }
+        }
+    }
+    // ---- the slice's counts: lanes -> LDS -> one atomic per row ----
+    if (n) atomicAdd(&cnt[wm * 64 + lane], n);
+    if constexpr (EXCL)
+        if (xsub) atomicSub(&cnt[xrow], xsub);
+    __syncthreads();
+    if (tid < 128 && qt * BM + tid < p.Nq && cnt[tid] != 0) atomicAdd(&p.rank[qt * BM + tid], cnt[tid]);
+}
+
+static int rank_splits(int Nq, int Nc) {
+    const int64_t qt = pad128(Nq) / BM, ct = pad128(Nc) / BN;
+    int64_t s = RANK_SLOTS / qt;
+    if (s > ct) s = ct;
+    return s < 1 ? 1 : (int)s;
+}
+static inline uint64_t al256(uint64_t b) { return (b + 255) / 256 * 256; }
+
+}  // namespace dae
+
+using namespace dae;
+
+extern "C" uint64_t dae_rank_similarity_workspace(int32_t Nq, int32_t Nc, int32_t D) {
+    if (Nq <= 0 || Nc <= 0 || D <= 0) return 0;
+    const uint64_t Nqp = pad128(Nq), Ncp = pad128(Nc), Dp = pad128(D);
+    // query image, corpus image, gathered target image, one key per query row
+    return al256(Nqp * Dp * 4) + al256(Ncp * Dp * 4) + al256(Nqp * Dp * 4) + al256(Nqp * 8);
+}
+
+extern "C" int dae_rank_similarity(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                                   int32_t norm, int32_t metric, int32_t exclude_self, const int64_t* excl_indptr,
+                                   const int32_t* excl_items, const int32_t* targets, int32_t* rank, float* target_score,
+                                   void* workspace, uint64_t workspace_bytes, void* stream) {
+    DAE_CHECK_ARG((excl_indptr == nullptr) == (excl_items == nullptr),
+                  "rank_similarity: excl_indptr and excl_items go together (exactly one of them is NULL)");
+    DAE_CHECK_ARG(Q && workspace && Nq > 0 && D > 0 && ldq >= D, "rank_similarity: bad input");
+    DAE_CHECK_ARG(targets && rank && target_score, "rank_similarity: targets / rank / target_score are NULL");
+    DAE_CHECK_ARG(C ? (Nc > 0 && ldc >= D) : Nc == Nq, "rank_similarity: bad corpus (C == NULL means the corpus is Q: pass Nc == Nq)");
+    DAE_CHECK_ARG(norm >= 0 && norm <= 3, "rank_similarity: norm must be 0 (none), 1 (l1), 2 (l2) or 3 (max)");
+    DAE_CHECK_ARG(metric == 0 || metric == 1, "rank_similarity: metric must be 0 (cosine) or 1 (linear kernel)");
+    DAE_CHECK_ARG(!exclude_self || !C, "rank_similarity: exclude_self needs C == NULL (the corpus is Q itself)");
+    const int64_t Nqp = pad128(Nq), Ncp = pad128(Nc), Dp = pad128(D);
+    DAE_CHECK_ARG(Nqp * Dp * 4 < (1ll << 32) && Ncp * Dp * 4 < (1ll << 32), "rank_similarity: an operand image exceeds 4 GiB");
+    DAE_CHECK_ARG(workspace_bytes >= dae_rank_similarity_workspace(Nq, Nc, D),
+                  "rank_similarity: workspace too small (%llu < %llu bytes)", (unsigned long long)workspace_bytes,
+                  (unsigned long long)dae_rank_similarity_workspace(Nq, Nc, D));
+    DAE_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "rank_similarity: workspace must be 256-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int splits = rank_splits(Nq, Nc);
+    char* w = (char*)workspace;
+    float* Qi = (float*)w;           w += al256(Nqp * Dp * 4);
+    float* Ci = C ? (float*)w : Qi;  w += al256(Ncp * Dp * 4);
+    float* Gi = (float*)w;           w += al256(Nqp * Dp * 4);
+    uint64_t* tkey = (uint64_t*)w;
+    const int cosine = metric == 0 ? 1 : 0;
+    if (int rc = launch_row_normalize(Q, ldq, Nq, D, norm, cosine, Qi, Dp, (int)Dp, (int)Nqp, st)) return rc;
+    if (C)
+        if (int rc = launch_row_normalize(C, ldc, Nc, D, norm, cosine, Ci, Dp, (int)Dp, (int)Ncp, st)) return rc;
+    DAE_LAUNCH(rank_gather_kernel, dim3((unsigned)Nqp), dim3(256), 0, st, Ci, targets, (int)Nq, (int)Nc, (int)Dp, Gi);
+    DAE_CHECK_LAUNCH();
+    RankTargetParams tp;
+    memset(&tp, 0, sizeof(tp));
+    tp.g.seg[0].A = (const char*)Qi; tp.g.seg[0].Bt = (const char*)Gi;
+    tp.g.seg[0].lda_b = tp.g.seg[0].ldb_b = Dp * 4;
+    tp.g.seg[0].ktiles = tp.g.ktiles_total = (int)(Dp * 4 / BKB);
+    tp.g.nseg = 1; tp.g.splits = 1; tp.g.out_scale = 1.f;
+    tp.Nq = Nq; tp.Nc = Nc; tp.targets = targets; tp.tkey = tkey; tp.rank = rank; tp.target_score = target_score;
+    static const hipError_t attr_t = hipFuncSetAttribute(reinterpret_cast<const void*>(rank_target_kernel),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, RANK_TARGET_LDS);
+    DAE_CHECK_HIP(attr_t);
+    DAE_LAUNCH(rank_target_kernel, dim3((unsigned)(Nqp / BM)), dim3(GEMM_THREADS), RANK_TARGET_LDS, st, tp);
+    DAE_CHECK_LAUNCH();
+    RankParams p;
+    memset(&p, 0, sizeof(p));
+    p.g = tp.g;
+    p.g.seg[0].Bt = (const char*)Ci;
+    p.Nq = Nq; p.Nc = Nc; p.exclude_self = exclude_self ? 1 : 0; p.splits = splits; p.ctiles = (int)(Ncp / BN);
+    p.tkey = tkey; p.rank = rank; p.excl_indptr = excl_indptr; p.excl_items = excl_items;
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(rank_tiles_kernel<false>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, RANK_LDS);
+    DAE_CHECK_HIP(attr);
+    static const hipError_t attr_x = hipFuncSetAttribute(reinterpret_cast<const void*>(rank_tiles_kernel<true>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, RANK_LDS);
+    DAE_CHECK_HIP(attr_x);
+    if (excl_indptr) DAE_LAUNCH(rank_tiles_kernel<true>, dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), RANK_LDS, st, p);
+    else DAE_LAUNCH(rank_tiles_kernel<false>, dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), RANK_LDS, st, p);
+    DAE_CHECK_LAUNCH();
+    return 0;
+}

@@ -19,7 +19,10 @@ library / a GPU this raises.
 * ``user_states`` -- the decaying user model of "Embedding-based News Recommendation for Millions of Users": a decay-weighted
   mean of the embeddings of the articles a user has read (``dae_user_states``); ``recommend`` -- the top-k articles by
   ``user . article`` that the user has not read yet (``most_similar(exclude=...)``, ``dae_topk_similarity_ex``);
-  ``next_click_metrics`` (host code) scores such a list against one held-out click per user."""
+  ``next_click_metrics`` (host code) scores such a list against one held-out click per user.
+* ``target_ranks`` / ``recommend_ranks`` -- the position of the held-out article among ALL candidates, without the users x
+  articles matrix (``dae_rank_similarity``); ``rank_metrics`` (host code) turns the ranks into AUC, mean / median rank,
+  untruncated MRR / nDCG and hit / MRR / nDCG at any number of cut-offs from one pass."""
 from __future__ import annotations
 
 import numpy as np
@@ -386,6 +389,163 @@ def next_click_metrics(indices, targets):
     rank = np.where(hit, match.argmax(axis=1) + 1, 1).astype(np.float64)      # the first occurrence
     return {"hit": float(hit.mean()), "mrr": float(np.where(hit, 1.0 / rank, 0.0).mean()),
             "ndcg": float(np.where(hit, 1.0 / np.log2(1.0 + rank), 0.0).mean()), "n": n}
+
+
+def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, candidates=None, *, exclude=None, return_tensor=False,
+                 device=None):
+    """The position of one target row of ``candidates`` (default: ``in_df`` itself) per row of ``in_df`` among ALL candidates, by
+    the scores and the order of ``most_similar`` (score descending, ties by index ascending), without the N x N matrix:
+    ``dae_rank_similarity`` counts the candidates ahead of the target inside the GEMM's epilogue.
+
+    Containers, ``norm``, ``metric``, ``exclude_self`` and ``exclude`` are those of ``most_similar``.  ``targets``: one
+    candidate index per row, negative for "no target"; an index >= the number of candidates raises ``ValueError``.
+
+    Returns ``(rank int64 [N], score float32 [N], n_candidates int64 [N])``.  ``rank`` counts from 1 among the candidates that
+    ``most_similar`` with the same arguments could return, and ``score`` is the target's score there bit for bit, so for every
+    k: ``0 < rank <= k`` exactly when the target is in ``most_similar(..., k, exclude=...)``'s row, at position ``rank - 1``.
+    ``rank`` is 0 (``score`` is still the pair's score) for a target that can never be returned: one in its own row's
+    ``exclude`` list, or the row itself under ``exclude_self``; and 0 with score -inf for a row without a target.
+    ``n_candidates`` is the number of candidates competing in that row, the target included: the corpus size minus the row's
+    exclusion items other than the target, minus the row itself when excluded (host code).  ndarrays, or CUDA tensors
+    with ``return_tensor=True``."""
+    import ctypes
+    import torch
+    assert metric in ["cosine", "linear kernel"]                      # helpers.py:34
+    if norm not in _NORMS:
+        raise ValueError(f"'{norm}' is not a supported norm")         # sklearn.preprocessing.normalize's message
+    if exclude_self is None:
+        exclude_self = candidates is None
+    elif exclude_self and candidates is not None:
+        raise ValueError("exclude_self=True needs candidates=None (the self pair exists only when the corpus is in_df itself)")
+    lib = L.load()
+    dev = torch.device("cuda" if device is None else device)
+    Q = _device_matrix(torch, in_df, dev)
+    Cm = None if candidates is None else _device_matrix(torch, candidates, dev)
+    Nq, D = int(Q.shape[0]), int(Q.shape[1])
+    if Cm is not None and int(Cm.shape[1]) != D:
+        raise ValueError(f"candidates have {int(Cm.shape[1])} columns, in_df has {D}")
+    Nc = Nq if Cm is None else int(Cm.shape[0])
+    tgt = targets.detach().cpu().numpy() if isinstance(targets, torch.Tensor) else np.asarray(targets)
+    tgt = tgt.ravel()
+    if tgt.size and tgt.dtype.kind not in "iu":
+        raise ValueError("targets must hold integer indices")
+    tgt = tgt.astype(np.int64)
+    if tgt.shape[0] != Nq:
+        raise ValueError(f"{tgt.shape[0]} targets for {Nq} queries")
+    if tgt.size and int(tgt.max()) >= Nc:
+        raise ValueError(f"targets must be below {Nc} (got {int(tgt.max())})")
+    has = tgt >= 0
+    tgt32 = np.where(has, tgt, -1).astype(np.int32)
+    # what can never be returned, and how many compete (host code)
+    n_cand = np.full(Nq, Nc, dtype=np.int64)
+    barred = np.zeros(Nq, dtype=bool)
+    xp = xi = None
+    if exclude is not None:
+        xp, xi = normalize_exclusions(exclude, Nq, Nc)
+        rows = np.repeat(np.arange(Nq, dtype=np.int64), np.diff(xp))
+        is_t = xi.astype(np.int64) == tgt[rows]
+        barred[rows[is_t]] = True
+        n_cand -= np.diff(xp) - np.bincount(rows[is_t], minlength=Nq)
+        if exclude_self:                                               # the self column, unless the list took it already
+            is_s = xi.astype(np.int64) == rows
+            n_cand -= 1 - np.bincount(rows[is_s & ~is_t], minlength=Nq)
+    elif exclude_self:
+        n_cand -= 1
+    if exclude_self:
+        self_t = tgt == np.arange(Nq)
+        barred |= self_t
+        n_cand[self_t] += 1                                            # the target is counted even there; the row is not ranked anyway
+    rank = torch.empty(Nq, dtype=torch.int32, device=dev)
+    score = torch.empty(Nq, dtype=torch.float32, device=dev)
+    if Nq == 0:
+        out = (rank.long(), score, torch.from_numpy(n_cand).to(dev))
+        return out if return_tensor else tuple(t.cpu().numpy() for t in out)
+    ws_bytes = int(lib.dae_rank_similarity_workspace(Nq, Nc, D))
+    ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
+    off = (-ws.data_ptr()) % 256
+    t_d = torch.from_numpy(tgt32).to(dev)
+    xp_d = xi_d = None
+    if xp is not None:
+        xp_d = torch.from_numpy(xp).to(dev)
+        xi_d = torch.from_numpy(xi if xi.size else np.zeros(1, dtype=np.int32)).to(dev)          # never a NULL pointer
+    with torch.cuda.device(dev):
+        L.call("dae_rank_similarity", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D, _NORMS[norm],
+               _METRICS[metric], 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(t_d), L.ptr(rank), L.ptr(score),
+               ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
+    rank = rank.long()
+    if barred.any():
+        rank[torch.from_numpy(barred).to(dev)] = 0
+    if return_tensor:
+        return rank, score, torch.from_numpy(n_cand).to(dev)
+    return rank.cpu().numpy(), score.cpu().numpy(), n_cand
+
+
+def recommend_ranks(user_vectors, embeddings, targets, seen=None, norm="", metric="linear kernel", *, return_tensor=False, device=None):
+    """The rank of each user's held-out article among all the articles the user has not read: the full-rank twin of
+    ``recommend`` -- ``target_ranks(user_vectors, targets, candidates=embeddings, exclude=seen)``.  Returns ``(rank, score,
+    n_candidates)`` as ``target_ranks`` does; ``rank`` is 0 for a target the user has already seen."""
+    return target_ranks(user_vectors, targets, norm=norm, metric=metric, candidates=embeddings, exclude=seen,
+                        return_tensor=return_tensor, device=device)
+
+
+def rank_metrics(rank, n_candidates, targets, ks=(1, 5, 10, 50, 100)):
+    """Scores full ranks (``target_ranks`` / ``recommend_ranks``) against one held-out article per query.  Host code.
+
+    Over the ``n`` queries with a target >= 0, a rank of 0 (the target can never be recommended) counting as a miss: ``hit@k``,
+    ``mrr@k`` (``1 / rank``) and ``ndcg@k`` (``1 / log2(1 + rank)``) for every k of ``ks`` -- equal to ``next_click_metrics`` on
+    the k-list of ``recommend`` -- and the untruncated ``mrr`` and ``ndcg``.  Over the ``n_ranked`` queries with rank > 0:
+    ``mean_rank``, ``median_rank`` and ``auc``, the mean of ``(n_candidates - rank) / (n_candidates - 1)`` (the share of the other
+    candidates the target beats; queries with a single candidate are skipped).  A value is NaN where no query counts."""
+    r = np.asarray(rank).ravel().astype(np.int64)
+    nc = np.asarray(n_candidates).ravel().astype(np.int64)
+    tgt = np.asarray(targets).ravel().astype(np.int64)
+    if not (r.shape[0] == nc.shape[0] == tgt.shape[0]):
+        raise ValueError(f"{r.shape[0]} ranks, {nc.shape[0]} candidate counts and {tgt.shape[0]} targets")
+    ok = tgt >= 0
+    r, nc = r[ok], nc[ok]
+    n = int(ok.sum())
+    nan = float("nan")
+    out = {"n": n, "n_ranked": int((r > 0).sum())}
+    rf = np.where(r > 0, r, 1).astype(np.float64)
+    for k in ks:
+        k = int(k)
+        hit = (r > 0) & (r <= k)
+        out[f"hit@{k}"] = float(hit.mean()) if n else nan
+        out[f"mrr@{k}"] = float(np.where(hit, 1.0 / rf, 0.0).mean()) if n else nan
+        out[f"ndcg@{k}"] = float(np.where(hit, 1.0 / np.log2(1.0 + rf), 0.0).mean()) if n else nan
+    out["mrr"] = float(np.where(r > 0, 1.0 / rf, 0.0).mean()) if n else nan
+    out["ndcg"] = float(np.where(r > 0, 1.0 / np.log2(1.0 + rf), 0.0).mean()) if n else nan
+    ranked = r > 0
+    out["mean_rank"] = float(r[ranked].mean()) if ranked.any() else nan
+    out["median_rank"] = float(np.median(r[ranked])) if ranked.any() else nan
+    a = ranked & (nc > 1)
+    out["auc"] = float(((nc[a] - r[a]) / (nc[a] - 1.0)).mean()) if a.any() else nan
+    return out
+
+
+def popularity_ranks(histories, n_articles, targets, seen=None):
+    """Full ranks of the popularity baseline (``popularity_recommend``'s order: click count descending, index ascending, the
+    user's ``seen`` articles -- default: the own history -- skipped).  Host code.  Returns ``(rank int64 [users],
+    n_candidates int64 [users])`` with the conventions of ``target_ranks``: rank 0 without a target or for a seen one."""
+    indptr, items = _csr_lists(histories)
+    M = indptr.size - 1
+    xp, xi = normalize_exclusions((indptr, items) if seen is None else seen, M, n_articles)
+    order = np.argsort(-np.bincount(items.astype(np.int64), minlength=int(n_articles)), kind="stable")
+    pos = np.empty(int(n_articles), dtype=np.int64)
+    pos[order] = np.arange(int(n_articles))
+    tgt = np.asarray(targets).ravel().astype(np.int64)
+    if tgt.shape[0] != M:
+        raise ValueError(f"{tgt.shape[0]} targets for {M} users")
+    rank = np.zeros(M, dtype=np.int64)
+    n_cand = np.full(M, int(n_articles), dtype=np.int64)
+    for u in range(M):
+        mine = xi[xp[u]:xp[u + 1]]
+        t = tgt[u]
+        n_cand[u] -= mine.size - int(t >= 0 and (mine == t).any())
+        if t < 0 or (mine == t).any():
+            continue
+        rank[u] = 1 + pos[t] - int((pos[mine] < pos[t]).sum())
+    return rank, n_cand
 
 
 def popularity_recommend(histories, n_articles, k, seen=None):

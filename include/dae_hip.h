@@ -449,6 +449,33 @@ int dae_topk_similarity_ex(const float* Q, int64_t ldq, int32_t Nq, const float*
                            int64_t ldk, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------------------------------------------------
+ * Full-rank evaluation: the position of one target corpus row per query row among ALL corpus rows, without an Nq x Nc
+ * matrix (AUC, mean / median rank, untruncated MRR / nDCG; helpers.target_ranks, helpers.recommend_ranks).
+ *   Q, ldq, Nq, C, ldc, Nc, D, norm, metric, exclude_self, excl_indptr, excl_items: exactly as dae_topk_similarity_ex, and
+ *   the same scores and order (score descending, then index ascending, -0 == +0); there is no k.  Both excl pointers NULL:
+ *   no lists; exactly one NULL is an argument error.
+ *   targets int32[Nq] (device): the corpus row whose rank is asked for, per query row; a negative value means "no target".
+ *   Output (device, Nq entries each), for a row i with t = targets[i] >= 0:
+ *       rank[i] = 1 + #{ j in [0, Nc) : j != t, j not in row i's list, not (exclude_self and j == i), (S[i, j], j) before (S[i, t], t) }
+ *       target_score[i] = S[i, t]
+ *   i.e. rank[i] is the position (from 1) the target takes in dae_topk_similarity_ex with the same arguments for every
+ *   k >= rank[i], and target_score[i] is that call's score bit for bit.  The list removes competitors only: a target that is
+ *   in its own row's list (or is the row itself under exclude_self) is still ranked among the admissible candidates;
+ *   whether it counts is the caller's decision.  Rows without a target get rank 0, target_score -inf.  Zero-padded rows
+ *   and columns are never counted.  Integer counts: bit-identical run to run, independent of the grid and the corpus split.
+ *   The exclusion work is one step per list item; it does not grow with the rank.
+ *   Precondition: every targets[i] < Nc.  It is not reported: an index outside is read as the last corpus row.
+ *   workspace: dae_rank_similarity_workspace(Nq, Nc, D) bytes, 256-byte aligned: the two normalised operand images, the
+ *   targets' rows gathered into a third image of the queries' size, and 8 bytes per query row -- no Nq x Nc term.  Each
+ *   operand image must stay below 4 GiB.
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_rank_similarity_workspace(int32_t Nq, int32_t Nc, int32_t D);
+int dae_rank_similarity(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                        int32_t norm, int32_t metric, int32_t exclude_self, const int64_t* excl_indptr,
+                        const int32_t* excl_items, const int32_t* targets, int32_t* rank, float* target_score,
+                        void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
  * User states from browsing histories: the decaying model of "Embedding-based News Recommendation for Millions of
  * Users" (KDD'17), a decay-weighted mean of the embeddings of the articles a user has read (helpers.user_states).
  *   E [Na x lde] fp32 article embeddings (device).  History CSR (device): indptr int64[M + 1], items int32[nnz], each

@@ -13,6 +13,7 @@ examples:
   python main_autoencoder.py --model_name demo --num_epochs 5 --verbose --verbose_step 1
   python main_autoencoder.py --model_name uci --data X.npz --labels y.npy --triplet_strategy batch_hard
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --similarity False
+  python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rank_metrics --similarity False
 """
 import argparse
 import os
@@ -100,6 +101,9 @@ def build_parser():
                    help="K > 0 (needs --sessions): after training, hold out every user's last click, build decayed user states from the rest "
                         "on the train embeddings, recommend K unseen articles per user to article_encoded_recommend{K}.npz, and print hit@K / "
                         "MRR / nDCG beside a most-clicked-unseen popularity baseline (no users x articles matrix: works with --similarity False)")
+    p.add_argument("--rank_metrics", default=False, **b,
+                   help="with --recommend K: also the rank of every held-out click among ALL unseen articles (no users x articles matrix), "
+                        "saved to article_encoded_ranks.npz, and AUC, full MRR, mean / median rank and hit@{1, 10, 100} per model")
     p.add_argument("--session_decay", type=float, default=0.9,
                    help="decay of --recommend's user states: per click, or per unit of time when the sessions carry timestamps")
     return p
@@ -119,6 +123,7 @@ def validate(a):
     assert a.model_name != '', "--model_name is required"
     assert a.recommend == 0 or a.sessions != '', "--recommend needs --sessions"
     assert 0. <= a.session_decay <= 1.
+    assert not a.rank_metrics or a.recommend > 0, "--rank_metrics needs --recommend K"
     return a
 
 
@@ -292,7 +297,26 @@ def evaluate_recommend(a, trY, emb, data_dir):
     print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'decayed user state', m['hit'], m['mrr'], m['ndcg']))
     print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'most clicked unseen', b['hit'], b['mrr'], b['ndcg']))
     print('calculate recommend %d done' % K)
+    if a.rank_metrics:
+        evaluate_rank_metrics(states, emb, hist, targets, n, data_dir)
     return idx, score, targets
+
+
+def evaluate_rank_metrics(states, emb, hist, targets, n, data_dir):
+    """--rank_metrics: the rank of every held-out click among all the articles the user has not read (helpers.recommend_ranks:
+    no users x articles matrix), saved as ``rank`` / ``score`` / ``n_candidates`` / ``targets`` in article_encoded_ranks.npz, and
+    one line per model -- the decayed user state and the most-clicked-unseen baseline (host code) -- with AUC, untruncated
+    MRR, mean / median rank and hit@{1, 10, 100}."""
+    from dae_rnn_news_recommendation_amd import helpers
+    print('calculate rank metrics')
+    rank, score, n_cand = helpers.recommend_ranks(states, emb, targets, seen=hist)
+    np.savez(data_dir + 'article_encoded_ranks.npz', rank=rank, score=score, n_candidates=n_cand, targets=targets)
+    b_rank, b_cand = helpers.popularity_ranks(hist, n, targets)
+    for name, m in (('decayed user state', helpers.rank_metrics(rank, n_cand, targets, ks=(1, 10, 100))),
+                    ('most clicked unseen', helpers.rank_metrics(b_rank, b_cand, targets, ks=(1, 10, 100)))):
+        print('  ranks %-20s AUC %.4f  MRR %.4f  mean rank %.1f  median rank %.1f  hit@1 %.4f  hit@10 %.4f  hit@100 %.4f'
+              % (name, m['auc'], m['mrr'], m['mean_rank'], m['median_rank'], m['hit@1'], m['hit@10'], m['hit@100']))
+    print('calculate rank metrics done -> article_encoded_ranks.npz')
 
 
 # artefact names of the reference's data directory (main_autoencoder.py:227-244, restored at :162-174)
