@@ -27,6 +27,13 @@
 //    End of the slice: counters and corrections meet in a [128] LDS array (integer atomics) and one atomic add per row goes
 //    to rank -- integers, so the result is bit-identical run to run and independent of the corpus split and the grid.
 // LDS: 64 KiB ring / tile + 1 KiB keys + 0.5 KiB counts = 65.5 KiB, two workgroups per CU.
+//
+// Candidate windows (dae_rank_similarity_win, rank_tiles_kernel<*, true>): row i's competitors are only the columns
+// win_lo[i] <= j < win_hi[i].  As in dae_topk.hip the query tile's windows, clamped to [0, Nc], go to LDS (+1 KiB) and the
+// workgroups of a query tile split the tiles of the union of its non-empty windows; the two compares join the ballots of the
+// count loop (bounds read from LDS per row, not kept across the K loop), a list item outside the row's window is not taken out
+// again (the sweep never counted it), and a workgroup with an empty slice adds nothing.  rank_tiles_kernel<*, false> is the
+// kernel as it was; rank_gather_kernel and rank_target_kernel do not know about windows.
 #include "dae_gemm_tile.h"
 
 namespace dae {
@@ -34,6 +41,7 @@ namespace dae {
 constexpr int RANK_SLOTS = 512;            // workgroups in flight on the MI355X: 256 CUs x 2 (the slice count is sized for it)
 constexpr int RANK_TILE_BYTES = BM * BN * 4;
 constexpr int RANK_LDS = RANK_TILE_BYTES + 128 * 8 + 128 * 4;
+constexpr int RANK_WIN_LDS = RANK_LDS + 2 * 128 * 4 + 16;   // + the query tile's windows and their union
 constexpr int RANK_TARGET_LDS = lds_bytes_for(2);
 
 // topk_key of dae_topk.hip (duplicated: that file's kernels stay as they are)
@@ -100,9 +108,11 @@ struct RankParams {
     int32_t* rank;                // [Nq], holds 1 (0 without a target) on entry
     const int64_t* excl_indptr;   // [Nq + 1] exclusion CSR (rank_tiles_kernel<true> only): row i's list is
     const int32_t* excl_items;    // excl_items[excl_indptr[i] .. excl_indptr[i + 1]), ascending and unique
+    const int32_t* win_lo;        // [Nq] candidate windows (rank_tiles_kernel<*, true> only): row i's competitors are the
+    const int32_t* win_hi;        // columns win_lo[i] <= j < win_hi[i]
 };
 
-template <bool EXCL>
+template <bool EXCL, bool WIN>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     float* tile = reinterpret_cast<float*>(lds);
@@ -110,12 +120,30 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams 
     int* cnt = reinterpret_cast<int*>(tk + 128);                           // keys above the target, per row, this slice
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int split = blockIdx.x % p.splits, qt = blockIdx.x / p.splits;
-    const int ct0 = (int)((int64_t)p.ctiles * split / p.splits), ct1 = (int)((int64_t)p.ctiles * (split + 1) / p.splits);
+    int ct0 = (int)((int64_t)p.ctiles * split / p.splits), ct1 = (int)((int64_t)p.ctiles * (split + 1) / p.splits);
     const int wm = wave >> 1, wn = wave & 1, g = lane >> 5, c = lane & 31;
     if (tid < 128) {
         const int gi = qt * BM + tid;
         tk[tid] = gi < p.Nq ? p.tkey[gi] : ~0ull;
         cnt[tid] = 0;
+    }
+    int* wlo = reinterpret_cast<int*>(lds + RANK_LDS);          // the query tile's windows (WIN only; behind the counts)
+    int* whi = wlo + 128;
+    if constexpr (WIN) {
+        int* un = whi + 128;                                    // union of the non-empty windows: [un[0], un[1])
+        if (tid == 0) { un[0] = INT32_MAX; un[1] = 0; }
+        __syncthreads();
+        if (tid < 128) {
+            const int gi = qt * BM + tid;
+            int lo = 0, hi = 0;
+            if (gi < p.Nq) { lo = min(max(p.win_lo[gi], 0), p.Nc); hi = min(max(p.win_hi[gi], 0), p.Nc); }
+            if (lo >= hi) lo = hi = 0;                          // empty (and the rows >= Nq): does not widen the union
+            else { atomicMin(&un[0], lo); atomicMax(&un[1], hi); }
+            wlo[tid] = lo; whi[tid] = hi;
+        }
+        __syncthreads();
+        const int t0 = un[1] > 0 ? un[0] / BN : 0, nt = un[1] > 0 ? (un[1] + BN - 1) / BN - t0 : 0;
+        ct0 = t0 + (int)((int64_t)nt * split / p.splits); ct1 = t0 + (int)((int64_t)nt * (split + 1) / p.splits);
     }
     // ---- the exclusion cursor of this lane's row (lanes 0..31 of every wave) ----
     const int xrow = wave * 32 + lane, xgi = qt * BM + xrow;
@@ -157,8 +185,15 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams 
                 const int row = wm * 64 + lrow + 4 * (ln >> 5);
                 const uint64_t t = tk[row];
                 const int self = p.exclude_self ? qt * BM + row : -1;
-                const uint64_t b0 = __ballot(ok0 && j0 != self && rank_key(acc[mt][0][r], j0) > t);
-                const uint64_t b1 = __ballot(ok1 && j1 != self && rank_key(acc[mt][1][r], j1) > t);
+                uint64_t b0, b1;
+                if constexpr (WIN) {                            // the row's bounds come from LDS here: nothing lives across the K loop
+                    const int wl = wlo[row], wh = whi[row];
+                    b0 = __ballot(ok0 && j0 != self && j0 >= wl && j0 < wh && rank_key(acc[mt][0][r], j0) > t);
+                    b1 = __ballot(ok1 && j1 != self && j1 >= wl && j1 < wh && rank_key(acc[mt][1][r], j1) > t);
+                } else {
+                    b0 = __ballot(ok0 && j0 != self && rank_key(acc[mt][0][r], j0) > t);
+                    b1 = __ballot(ok1 && j1 != self && rank_key(acc[mt][1][r], j1) > t);
+                }
                 const int lo = __popc((uint32_t)b0) + __popc((uint32_t)b1), hi = __popc((uint32_t)(b0 >> 32)) + __popc((uint32_t)(b1 >> 32));
                 n += (ln == lrow ? lo : 0) + (ln == lrow + 4 ? hi : 0);
                 if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);     // four rows' keys in flight, not all 32 (VGPRs)
@@ -179,7 +214,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams 
                 int last = -1;
                 while (xnext < tile_end) {                      // the run of this row's list inside the tile
                     const int x = xnext;
-                    if (x >= ct * BN && x != last && x < p.Nc && !(p.exclude_self && x == xgi))
+                    bool inw = true;                            // outside the row's window the sweep did not count it
+                    if constexpr (WIN) inw = x >= wlo[xrow] && x < whi[xrow];
+                    if (x >= ct * BN && x != last && x < p.Nc && !(p.exclude_self && x == xgi) && inw)
                         xsub += (int)(rank_key(tile[xrow * BN + (x - ct * BN)], x) > xkey);
                     last = x;
                     ++xpos;
@@ -216,12 +253,18 @@ extern "C" uint64_t dae_rank_similarity_workspace(int32_t Nq, int32_t Nc, int32_
     return al256(Nqp * Dp * 4) + al256(Ncp * Dp * 4) + al256(Nqp * Dp * 4) + al256(Nqp * 8);
 }
 
-extern "C" int dae_rank_similarity(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
-                                   int32_t norm, int32_t metric, int32_t exclude_self, const int64_t* excl_indptr,
-                                   const int32_t* excl_items, const int32_t* targets, int32_t* rank, float* target_score,
-                                   void* workspace, uint64_t workspace_bytes, void* stream) {
+extern "C" uint64_t dae_rank_similarity_win_workspace(int32_t Nq, int32_t Nc, int32_t D) {
+    return dae_rank_similarity_workspace(Nq, Nc, D);            // the windows are read in place
+}
+
+extern "C" int dae_rank_similarity_win(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                                       int32_t norm, int32_t metric, int32_t exclude_self, const int64_t* excl_indptr,
+                                       const int32_t* excl_items, const int32_t* win_lo, const int32_t* win_hi, const int32_t* targets,
+                                       int32_t* rank, float* target_score, void* workspace, uint64_t workspace_bytes, void* stream) {
     DAE_CHECK_ARG((excl_indptr == nullptr) == (excl_items == nullptr),
                   "rank_similarity: excl_indptr and excl_items go together (exactly one of them is NULL)");
+    DAE_CHECK_ARG((win_lo == nullptr) == (win_hi == nullptr),
+                  "rank_similarity: win_lo and win_hi go together (exactly one of them is NULL)");
     DAE_CHECK_ARG(Q && workspace && Nq > 0 && D > 0 && ldq >= D, "rank_similarity: bad input");
     DAE_CHECK_ARG(targets && rank && target_score, "rank_similarity: targets / rank / target_score are NULL");
     DAE_CHECK_ARG(C ? (Nc > 0 && ldc >= D) : Nc == Nq, "rank_similarity: bad corpus (C == NULL means the corpus is Q: pass Nc == Nq)");
@@ -264,15 +307,37 @@ extern "C" int dae_rank_similarity(const float* Q, int64_t ldq, int32_t Nq, cons
     p.g = tp.g;
     p.g.seg[0].Bt = (const char*)Ci;
     p.Nq = Nq; p.Nc = Nc; p.exclude_self = exclude_self ? 1 : 0; p.splits = splits; p.ctiles = (int)(Ncp / BN);
-    p.tkey = tkey; p.rank = rank; p.excl_indptr = excl_indptr; p.excl_items = excl_items;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(rank_tiles_kernel<false>),
+    p.tkey = tkey; p.rank = rank; p.excl_indptr = excl_indptr; p.excl_items = excl_items; p.win_lo = win_lo; p.win_hi = win_hi;
+    if (win_lo) {
+        static const hipError_t attr_w = hipFuncSetAttribute(reinterpret_cast<const void*>(rank_tiles_kernel<false, true>),
+                                                             hipFuncAttributeMaxDynamicSharedMemorySize, RANK_WIN_LDS);
+        DAE_CHECK_HIP(attr_w);
+        static const hipError_t attr_xw = hipFuncSetAttribute(reinterpret_cast<const void*>(rank_tiles_kernel<true, true>),
+                                                              hipFuncAttributeMaxDynamicSharedMemorySize, RANK_WIN_LDS);
+        DAE_CHECK_HIP(attr_xw);
+        if (excl_indptr)
+            DAE_LAUNCH((rank_tiles_kernel<true, true>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), RANK_WIN_LDS, st, p);
+        else
+            DAE_LAUNCH((rank_tiles_kernel<false, true>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), RANK_WIN_LDS, st, p);
+        DAE_CHECK_LAUNCH();
+        return 0;
+    }
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(rank_tiles_kernel<false, false>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, RANK_LDS);
     DAE_CHECK_HIP(attr);
-    static const hipError_t attr_x = hipFuncSetAttribute(reinterpret_cast<const void*>(rank_tiles_kernel<true>),
+    static const hipError_t attr_x = hipFuncSetAttribute(reinterpret_cast<const void*>(rank_tiles_kernel<true, false>),
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, RANK_LDS);
     DAE_CHECK_HIP(attr_x);
-    if (excl_indptr) DAE_LAUNCH(rank_tiles_kernel<true>, dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), RANK_LDS, st, p);
-    else DAE_LAUNCH(rank_tiles_kernel<false>, dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), RANK_LDS, st, p);
+    if (excl_indptr) DAE_LAUNCH((rank_tiles_kernel<true, false>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), RANK_LDS, st, p);
+    else DAE_LAUNCH((rank_tiles_kernel<false, false>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), RANK_LDS, st, p);
     DAE_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int dae_rank_similarity(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                                   int32_t norm, int32_t metric, int32_t exclude_self, const int64_t* excl_indptr,
+                                   const int32_t* excl_items, const int32_t* targets, int32_t* rank, float* target_score,
+                                   void* workspace, uint64_t workspace_bytes, void* stream) {
+    return dae_rank_similarity_win(Q, ldq, Nq, C, ldc, Nc, D, norm, metric, exclude_self, excl_indptr, excl_items, nullptr, nullptr,
+                                   targets, rank, target_score, workspace, workspace_bytes, stream);
 }

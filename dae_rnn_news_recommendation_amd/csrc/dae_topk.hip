@@ -24,6 +24,13 @@
 // LDS: 64 KiB tile / staging + 1 KiB thresholds + 0.5 KiB list lengths + 4 x 2 KiB merge scratch = 73.5 KiB, two
 // workgroups per CU.  Phase B, topk_merge_kernel: one workgroup per query row merges the `splits` sorted lists the same
 // way (each entry's rank = its position + the entries above it in the other lists) and writes idx / score.
+//
+// Candidate windows (dae_topk_similarity_win, topk_tiles_kernel<*, true>): row i admits only the columns win_lo[i] <= j <
+// win_hi[i].  The query tile's 128 (lo, hi) pairs, clamped to [0, Nc], go to LDS (+1 KiB: 74.5 KiB, still two workgroups per
+// CU); the workgroups of a query tile split the tiles of the UNION of its non-empty windows among them instead of [0, ctiles),
+// a row whose window misses the current tile is passed over, and the two compares join ok0 / ok1, so a column outside the
+// window never reaches the ballot, the exclusion search or the merge.  A workgroup with an empty slice writes part_n = 0.
+// topk_tiles_kernel<*, false> is the kernel as it was.
 #include "dae_gemm_tile.h"
 
 namespace dae {
@@ -33,6 +40,7 @@ constexpr int TOPK_SLOTS = 512;            // workgroups in flight on the MI355X
 constexpr int TOPK_MAX_SPLITS = 32;        // bounds phase B's LDS (32 lists x 128 keys x 8 B)
 constexpr int TOPK_TILE_BYTES = BM * BN * 4;
 constexpr int TOPK_LDS = TOPK_TILE_BYTES + 128 * 8 + 128 * 4 + 4 * 2 * TOPK_MAX * 8;
+constexpr int TOPK_WIN_LDS = TOPK_LDS + 2 * 128 * 4 + 16;   // + the query tile's windows and their union
 
 __device__ __forceinline__ uint64_t topk_key(float s, int j) {
     if (s == 0.f) s = 0.f;                                      // -0 and +0 are one score
@@ -58,6 +66,8 @@ struct TopkParams {
     int* part_n;                  // [splits][Nqp] valid keys per list
     const int64_t* excl_indptr;   // [Nq + 1] exclusion CSR (topk_tiles_kernel<true> only): row i's list is
     const int32_t* excl_items;    // excl_items[excl_indptr[i] .. excl_indptr[i + 1]), ascending and unique
+    const int32_t* win_lo;        // [Nq] candidate windows (topk_tiles_kernel<*, true> only): row i admits the columns
+    const int32_t* win_hi;        // win_lo[i] <= j < win_hi[i]
 };
 
 // is j in the ascending list X[0, n)?
@@ -70,7 +80,7 @@ __device__ __forceinline__ bool excl_has(const int32_t* X, int n, int j) {
     return lo < n && X[lo] == j;
 }
 
-template <bool EXCL>
+template <bool EXCL, bool WIN>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     float* tile = reinterpret_cast<float*>(lds);
@@ -80,9 +90,27 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams 
     uint64_t* Ls = reinterpret_cast<uint64_t*>(len + 128) + wave * 2 * TOPK_MAX;     // this wave's copy of the list being merged
     uint64_t* Cs = Ls + TOPK_MAX;                                                    // and its candidates
     const int split = blockIdx.x % p.splits, qt = blockIdx.x / p.splits;
-    const int ct0 = (int)((int64_t)p.ctiles * split / p.splits), ct1 = (int)((int64_t)p.ctiles * (split + 1) / p.splits);
+    int ct0 = (int)((int64_t)p.ctiles * split / p.splits), ct1 = (int)((int64_t)p.ctiles * (split + 1) / p.splits);
     const int k = p.k;
     if (tid < 128) { th[tid] = 0; len[tid] = 0; }
+    int* wlo = reinterpret_cast<int*>(lds + TOPK_LDS);          // the query tile's windows (WIN only; behind the merge scratch)
+    int* whi = wlo + 128;
+    if constexpr (WIN) {
+        int* un = whi + 128;                                    // union of the non-empty windows: [un[0], un[1])
+        if (tid == 0) { un[0] = INT32_MAX; un[1] = 0; }
+        __syncthreads();
+        if (tid < 128) {
+            const int gi = qt * BM + tid;
+            int lo = 0, hi = 0;
+            if (gi < p.Nq) { lo = min(max(p.win_lo[gi], 0), p.Nc); hi = min(max(p.win_hi[gi], 0), p.Nc); }
+            if (lo >= hi) lo = hi = 0;                          // empty (and the rows >= Nq): does not widen the union
+            else { atomicMin(&un[0], lo); atomicMax(&un[1], hi); }
+            wlo[tid] = lo; whi[tid] = hi;
+        }
+        __syncthreads();
+        const int t0 = un[1] > 0 ? un[0] / BN : 0, nt = un[1] > 0 ? (un[1] + BN - 1) / BN - t0 : 0;
+        ct0 = t0 + (int)((int64_t)nt * split / p.splits); ct1 = t0 + (int)((int64_t)nt * (split + 1) / p.splits);
+    }
     const int wm = wave >> 1, wn = wave & 1, g = lane >> 5, c = lane & 31;
     const uint64_t below = (1ull << lane) - 1ull;
     for (int ct = ct0; ct < ct1; ++ct) {
@@ -101,8 +129,14 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams 
         for (int rr = 0; rr < 32; ++rr) {
             const int row = wave * 32 + rr, gi = qt * BM + row;
             if (gi >= p.Nq) break;
+            int wl = 0, wh = INT32_MAX;
+            if constexpr (WIN) {
+                wl = wlo[row]; wh = whi[row];
+                if (wh <= ct * BN || wl >= (ct + 1) * BN) continue;      // the row's window misses this tile (wave-uniform)
+            }
             const uint64_t t = th[row];
-            const bool ok0 = j0 < p.Nc && !(p.exclude_self && j0 == gi), ok1 = j1 < p.Nc && !(p.exclude_self && j1 == gi);
+            const bool ok0 = j0 < p.Nc && !(p.exclude_self && j0 == gi) && (!WIN || (j0 >= wl && j0 < wh)),
+                       ok1 = j1 < p.Nc && !(p.exclude_self && j1 == gi) && (!WIN || (j1 >= wl && j1 < wh));
             const uint64_t c0 = ok0 ? topk_key(tile[row * BN + lane], j0) : 0, c1 = ok1 ? topk_key(tile[row * BN + 64 + lane], j1) : 0;
             bool in0 = c0 > t, in1 = c1 > t;
             uint64_t b0 = __ballot(in0), b1 = __ballot(in1);
@@ -214,12 +248,18 @@ extern "C" uint64_t dae_topk_similarity_ex_workspace(int32_t Nq, int32_t Nc, int
     return dae_topk_similarity_workspace(Nq, Nc, D, k);         // the exclusion lists are read in place
 }
 
-extern "C" int dae_topk_similarity_ex(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
-                                      int32_t norm, int32_t metric, int32_t k, int32_t exclude_self, const int64_t* excl_indptr,
-                                      const int32_t* excl_items, int32_t* idx, float* score, int64_t ldk, void* workspace,
-                                      uint64_t workspace_bytes, void* stream) {
+extern "C" uint64_t dae_topk_similarity_win_workspace(int32_t Nq, int32_t Nc, int32_t D, int32_t k) {
+    return dae_topk_similarity_workspace(Nq, Nc, D, k);         // the windows are read in place
+}
+
+extern "C" int dae_topk_similarity_win(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                                       int32_t norm, int32_t metric, int32_t k, int32_t exclude_self, const int64_t* excl_indptr,
+                                       const int32_t* excl_items, const int32_t* win_lo, const int32_t* win_hi, int32_t* idx,
+                                       float* score, int64_t ldk, void* workspace, uint64_t workspace_bytes, void* stream) {
     DAE_CHECK_ARG((excl_indptr == nullptr) == (excl_items == nullptr),
                   "topk_similarity: excl_indptr and excl_items go together (exactly one of them is NULL)");
+    DAE_CHECK_ARG((win_lo == nullptr) == (win_hi == nullptr),
+                  "topk_similarity: win_lo and win_hi go together (exactly one of them is NULL)");
     DAE_CHECK_ARG(Q && idx && score && workspace && Nq > 0 && D > 0 && ldq >= D, "topk_similarity: bad input");
     DAE_CHECK_ARG(C ? (Nc > 0 && ldc >= D) : Nc == Nq, "topk_similarity: bad corpus (C == NULL means the corpus is Q: pass Nc == Nq)");
     DAE_CHECK_ARG(norm >= 0 && norm <= 3, "topk_similarity: norm must be 0 (none), 1 (l1), 2 (l2) or 3 (max)");
@@ -252,19 +292,43 @@ extern "C" int dae_topk_similarity_ex(const float* Q, int64_t ldq, int32_t Nq, c
     p.g.nseg = 1; p.g.splits = 1; p.g.out_scale = 1.f;
     p.Nq = Nq; p.Nc = Nc; p.Nqp = (int)Nqp; p.k = k; p.exclude_self = exclude_self ? 1 : 0; p.splits = splits;
     p.ctiles = (int)(Ncp / BN); p.part = part; p.part_n = part_n;
-    p.excl_indptr = excl_indptr; p.excl_items = excl_items;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_tiles_kernel<false>),
+    p.excl_indptr = excl_indptr; p.excl_items = excl_items; p.win_lo = win_lo; p.win_hi = win_hi;
+    if (win_lo) {
+        static const hipError_t attr_w = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_tiles_kernel<false, true>),
+                                                             hipFuncAttributeMaxDynamicSharedMemorySize, TOPK_WIN_LDS);
+        DAE_CHECK_HIP(attr_w);
+        static const hipError_t attr_xw = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_tiles_kernel<true, true>),
+                                                              hipFuncAttributeMaxDynamicSharedMemorySize, TOPK_WIN_LDS);
+        DAE_CHECK_HIP(attr_xw);
+        if (excl_indptr)
+            DAE_LAUNCH((topk_tiles_kernel<true, true>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), TOPK_WIN_LDS, st, p);
+        else
+            DAE_LAUNCH((topk_tiles_kernel<false, true>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), TOPK_WIN_LDS, st, p);
+        DAE_CHECK_LAUNCH();
+        DAE_LAUNCH(topk_merge_kernel, dim3(Nq), dim3(256), 0, st, part, part_n, (int)Nqp, splits, k, idx, score, ldk);
+        DAE_CHECK_LAUNCH();
+        return 0;
+    }
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_tiles_kernel<false, false>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, TOPK_LDS);
     DAE_CHECK_HIP(attr);
-    static const hipError_t attr_x = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_tiles_kernel<true>),
+    static const hipError_t attr_x = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_tiles_kernel<true, false>),
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, TOPK_LDS);
     DAE_CHECK_HIP(attr_x);
-    if (excl_indptr) DAE_LAUNCH(topk_tiles_kernel<true>, dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), TOPK_LDS, st, p);
-    else DAE_LAUNCH(topk_tiles_kernel<false>, dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), TOPK_LDS, st, p);
+    if (excl_indptr) DAE_LAUNCH((topk_tiles_kernel<true, false>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), TOPK_LDS, st, p);
+    else DAE_LAUNCH((topk_tiles_kernel<false, false>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), TOPK_LDS, st, p);
     DAE_CHECK_LAUNCH();
     DAE_LAUNCH(topk_merge_kernel, dim3(Nq), dim3(256), 0, st, part, part_n, (int)Nqp, splits, k, idx, score, ldk);
     DAE_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int dae_topk_similarity_ex(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                                      int32_t norm, int32_t metric, int32_t k, int32_t exclude_self, const int64_t* excl_indptr,
+                                      const int32_t* excl_items, int32_t* idx, float* score, int64_t ldk, void* workspace,
+                                      uint64_t workspace_bytes, void* stream) {
+    return dae_topk_similarity_win(Q, ldq, Nq, C, ldc, Nc, D, norm, metric, k, exclude_self, excl_indptr, excl_items, nullptr, nullptr,
+                                   idx, score, ldk, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dae_topk_similarity(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,

@@ -224,8 +224,82 @@ def normalize_exclusions(exclude, n_rows, n_candidates):
     return out_ptr, np.zeros(0, dtype=np.int32)
 
 
-def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candidates=None, *, exclude=None, return_tensor=False,
-                 device=None):
+def _n_rows(data):
+    """The number of rows of a container ``_device_matrix`` takes, without touching it."""
+    shape = getattr(data, "shape", None)
+    return int(shape[0]) if shape is not None and len(shape) else len(data)
+
+
+def normalize_window(window, n_rows, n_candidates):
+    """The candidate windows of ``most_similar`` / ``recommend`` / ``target_ranks`` in the form ``dae_topk_similarity_win``
+    reads: ``(lo int32 [n_rows], hi int32 [n_rows])``.  ``window``: a pair ``(lo, hi)`` of integer sequences, one entry per query
+    row; row i admits the candidates ``lo[i] <= j < hi[i]`` (``lo == hi``: none).  ``ValueError`` for anything else: a wrong
+    length, non-integers, ``lo < 0``, ``hi > n_candidates`` or ``lo > hi``.  Host code."""
+    if not (isinstance(window, (tuple, list)) and len(window) == 2):
+        raise ValueError("window must be a pair (lo, hi) of integer sequences, one entry per query row")
+    out = []
+    for name, w in zip(("lo", "hi"), window):
+        if hasattr(w, "detach"):
+            w = w.detach().cpu().numpy()
+        w = np.asarray(w).ravel()
+        if w.shape[0] != int(n_rows):
+            raise ValueError(f"window {name} has {w.shape[0]} entries for {int(n_rows)} queries")
+        if w.size and w.dtype.kind not in "iu":
+            raise ValueError("window must hold integer indices")
+        out.append(w.astype(np.int64))
+    lo, hi = out
+    if lo.size and int(lo.min()) < 0:
+        raise ValueError(f"window lo must not be negative (got {int(lo.min())})")
+    if hi.size and int(hi.max()) > int(n_candidates):
+        raise ValueError(f"window hi must not exceed the {int(n_candidates)} candidates (got {int(hi.max())})")
+    if (lo > hi).any():
+        i = int(np.flatnonzero(lo > hi)[0])
+        raise ValueError(f"window lo must not exceed hi (row {i}: {int(lo[i])} > {int(hi[i])})")
+    return np.ascontiguousarray(lo.astype(np.int32)), np.ascontiguousarray(hi.astype(np.int32))
+
+
+def _window_order(lo, hi):
+    """The stable order of the query rows by ``(lo, hi)``, or None when they are in that order already: neighbours with similar
+    windows make the union of a 128-row query tile narrow, and the union is what the kernel walks."""
+    perm = np.lexsort((hi, lo))
+    return None if (perm == np.arange(perm.size)).all() else perm
+
+
+def _permute_csr(indptr, items, perm):
+    """The CSR ``(indptr, items)`` with its rows in the order ``perm``."""
+    n = np.diff(indptr)[perm]
+    out_ptr = np.zeros(perm.size + 1, dtype=np.int64)
+    out_ptr[1:] = np.cumsum(n)
+    take = np.repeat(indptr[:-1][perm] - out_ptr[:-1], n) + np.arange(int(out_ptr[-1]), dtype=np.int64)
+    return out_ptr, items[take]
+
+
+def candidate_windows(query_times, publish_times, max_age=None):
+    """Candidate windows of a news feed for a corpus in publication order: for a query at time ``t`` the articles with
+    ``t - max_age < publish <= t`` (``max_age=None`` or ``inf``: everything published by ``t``), as the column range
+    ``lo = searchsorted(publish, t - max_age, 'right')``, ``hi = searchsorted(publish, t, 'right')``.  A query before the first
+    publication gets an empty window.  Returns ``(lo int32 [Nq], hi int32 [Nq])`` for ``window=``.  ``ValueError`` when
+    ``publish_times`` decrease (order the corpus first), for non-finite times and for a negative ``max_age``.  Host code."""
+    t = np.asarray(query_times, dtype=np.float64).ravel()
+    pub = np.asarray(publish_times, dtype=np.float64).ravel()
+    if not (np.isfinite(t).all() and np.isfinite(pub).all()):
+        raise ValueError("query_times and publish_times must be finite")
+    if (np.diff(pub) < 0).any():
+        raise ValueError("publish_times decrease: a window is a column range only for a corpus in publication order -- reorder "
+                         "the articles by np.argsort(publish_times, kind='stable') first")
+    hi = np.searchsorted(pub, t, side="right")
+    if max_age is None:
+        lo = np.zeros_like(hi)
+    else:
+        age = float(max_age)
+        if not age >= 0.0:
+            raise ValueError(f"max_age must not be negative (got {max_age})")
+        lo = np.searchsorted(pub, t - age, side="right")                 # age == inf: t - age = -inf, lo = 0
+    return lo.astype(np.int32), hi.astype(np.int32)
+
+
+def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candidates=None, *, exclude=None, window=None,
+                 return_tensor=False, device=None):
     """The ``k`` most similar rows of ``candidates`` (default: ``in_df`` itself) for every row of ``in_df``, by the scores
     ``pairwise_similarity`` would give (same ``norm`` / ``metric``, same exact-fp32 products), without the N x N matrix:
     ``dae_topk_similarity`` keeps a running top-k per row inside the GEMM's epilogue.
@@ -239,7 +313,13 @@ def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candi
     ``exclude`` (default None: nothing) names, per query row, candidates that must not be returned -- a list of index sequences
     or an ``(indptr, items)`` tuple; it is sorted, de-duplicated and stripped of indices outside the corpus here
     (``normalize_exclusions``).  An excluded candidate is skipped before it can take one of the k slots
-    (``dae_topk_similarity_ex``), so a row still gets k results when k others exist.  Allowed together with ``exclude_self``."""
+    (``dae_topk_similarity_ex``), so a row still gets k results when k others exist.  Allowed together with ``exclude_self``.
+
+    ``window`` (default None: every candidate) is a pair ``(lo, hi)`` of integer sequences, one entry per query row: row i
+    admits only the candidates ``lo[i] <= j < hi[i]`` (``normalize_window``; e.g. from ``candidate_windows``), on top of
+    ``exclude`` and ``exclude_self`` (``dae_topk_similarity_win``).  An empty window gives a row of -1 / -inf.  The kernel walks
+    the union of the windows of 128 neighbouring rows, so with ``candidates`` the rows are handed over in the stable order of
+    ``(lo, hi)`` and the result is put back in the caller's order; the order is total, so the result does not depend on it."""
     import torch
     assert metric in ["cosine", "linear kernel"]                      # helpers.py:34
     if norm not in _NORMS:
@@ -248,6 +328,8 @@ def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candi
         exclude_self = candidates is None
     elif exclude_self and candidates is not None:
         raise ValueError("exclude_self=True needs candidates=None (the self pair exists only when the corpus is in_df itself)")
+    if window is not None:
+        window = normalize_window(window, _n_rows(in_df), _n_rows(in_df if candidates is None else candidates))
     lib = L.load()
     dev = torch.device("cuda" if device is None else device)
     Q = _device_matrix(torch, in_df, dev)
@@ -263,6 +345,32 @@ def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candi
     ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
     off = (-ws.data_ptr()) % 256
     import ctypes
+    if window is not None:
+        wlo, whi = window
+        perm = None if Cm is None else _window_order(wlo, whi)        # the corpus is Q itself: its rows stay where they are
+        xp_d = xi_d = None
+        if exclude is not None:
+            xp, xi = normalize_exclusions(exclude, Nq, Nc)
+            if perm is not None:
+                xp, xi = _permute_csr(xp, xi, perm)
+            xp_d = torch.from_numpy(xp).to(dev)
+            xi_d = torch.from_numpy(xi if xi.size else np.zeros(1, dtype=np.int32)).to(dev)      # never a NULL pointer
+        perm_d = None
+        if perm is not None:
+            perm_d = torch.from_numpy(perm).to(dev)
+            Q, wlo, whi = Q[perm_d].contiguous(), wlo[perm], whi[perm]
+        lo_d, hi_d = torch.from_numpy(np.ascontiguousarray(wlo)).to(dev), torch.from_numpy(np.ascontiguousarray(whi)).to(dev)
+        if Nq > 0:
+            with torch.cuda.device(dev):
+                L.call("dae_topk_similarity_win", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
+                       _NORMS[norm], _METRICS[metric], k, 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(lo_d), L.ptr(hi_d),
+                       L.ptr(idx), L.ptr(score), idx.stride(0), ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
+        if perm_d is not None:
+            idx, score = torch.empty_like(idx).index_copy_(0, perm_d, idx), torch.empty_like(score).index_copy_(0, perm_d, score)
+        idx = idx.long()
+        if return_tensor:
+            return idx, score
+        return idx.cpu().numpy(), score.cpu().numpy()
     with torch.cuda.device(dev):
         if exclude is None:
             L.call("dae_topk_similarity", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D, _NORMS[norm],
@@ -358,13 +466,19 @@ def user_states(histories, embeddings, beta=0.9, *, timestamps=None, time_unit=N
     return U.cpu().numpy()
 
 
-def recommend(user_vectors, embeddings, k=10, seen=None, norm="", metric="linear kernel", *, return_tensor=False, device=None):
+def recommend(user_vectors, embeddings, k=10, seen=None, norm="", metric="linear kernel", *, window=None, return_tensor=False,
+              device=None):
     """The ``k`` articles (rows of ``embeddings``) with the largest relevance to every user vector (e.g. from ``user_states``)
     among those the user has not read: ``most_similar(user_vectors, candidates=embeddings, exclude=seen)``.  ``seen``: per
     user the indices already read (a list of sequences or an ``(indptr, items)`` tuple -- a history as given to ``user_states``
     will do; order and repeats do not matter), or None.  The default ``metric`` is the paper's relevance, the inner product;
-    ``'cosine'`` and ``norm`` are those of ``most_similar``.  Returns ``(indices, scores)`` as ``most_similar`` does."""
-    return most_similar(user_vectors, k=k, norm=norm, metric=metric, candidates=embeddings, exclude=seen,
+    ``'cosine'`` and ``norm`` are those of ``most_similar``, and so is ``window``: per user the range of articles that may be
+    shown at all (``candidate_windows``: those published by the time of the click, and not too long before).  Returns
+    ``(indices, scores)`` as ``most_similar`` does."""
+    if window is None:
+        return most_similar(user_vectors, k=k, norm=norm, metric=metric, candidates=embeddings, exclude=seen,
+                            return_tensor=return_tensor, device=device)
+    return most_similar(user_vectors, k=k, norm=norm, metric=metric, candidates=embeddings, exclude=seen, window=window,
                         return_tensor=return_tensor, device=device)
 
 
@@ -391,8 +505,8 @@ def next_click_metrics(indices, targets):
             "ndcg": float(np.where(hit, 1.0 / np.log2(1.0 + rank), 0.0).mean()), "n": n}
 
 
-def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, candidates=None, *, exclude=None, return_tensor=False,
-                 device=None):
+def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, candidates=None, *, exclude=None, window=None,
+                 return_tensor=False, device=None):
     """The position of one target row of ``candidates`` (default: ``in_df`` itself) per row of ``in_df`` among ALL candidates, by
     the scores and the order of ``most_similar`` (score descending, ties by index ascending), without the N x N matrix:
     ``dae_rank_similarity`` counts the candidates ahead of the target inside the GEMM's epilogue.
@@ -407,7 +521,13 @@ def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, ca
     ``exclude`` list, or the row itself under ``exclude_self``; and 0 with score -inf for a row without a target.
     ``n_candidates`` is the number of candidates competing in that row, the target included: the corpus size minus the row's
     exclusion items other than the target, minus the row itself when excluded (host code).  ndarrays, or CUDA tensors
-    with ``return_tensor=True``."""
+    with ``return_tensor=True``.
+
+    With ``window`` (a pair ``(lo, hi)`` as in ``most_similar``; ``dae_rank_similarity_win``) the competitors are the
+    candidates inside the row's window, and the sentence about k above holds for ``most_similar(..., window=window)``: a target
+    outside its row's window can never be returned and gets ``rank`` 0 (its ``score`` is still the pair's score), and
+    ``n_candidates`` is the window's size minus the row's exclusion items inside the window other than the target, minus the
+    row itself when it is excluded and lies inside."""
     import ctypes
     import torch
     assert metric in ["cosine", "linear kernel"]                      # helpers.py:34
@@ -417,6 +537,8 @@ def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, ca
         exclude_self = candidates is None
     elif exclude_self and candidates is not None:
         raise ValueError("exclude_self=True needs candidates=None (the self pair exists only when the corpus is in_df itself)")
+    if window is not None:
+        window = normalize_window(window, _n_rows(in_df), _n_rows(in_df if candidates is None else candidates))
     lib = L.load()
     dev = torch.device("cuda" if device is None else device)
     Q = _device_matrix(torch, in_df, dev)
@@ -440,7 +562,26 @@ def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, ca
     n_cand = np.full(Nq, Nc, dtype=np.int64)
     barred = np.zeros(Nq, dtype=bool)
     xp = xi = None
-    if exclude is not None:
+    if window is not None:
+        wlo, whi = (w.astype(np.int64) for w in window)
+        n_cand = whi - wlo
+        barred = has & ~((tgt >= wlo) & (tgt < whi))                   # outside its own window: never returned
+        me = np.arange(Nq, dtype=np.int64)
+        self_in = (me >= wlo) & (me < whi) if exclude_self else np.zeros(Nq, dtype=bool)
+        if exclude is not None:
+            xp, xi = normalize_exclusions(exclude, Nq, Nc)
+            rows = np.repeat(me, np.diff(xp))
+            it = xi.astype(np.int64)
+            is_t = it == tgt[rows]
+            barred[rows[is_t]] = True
+            inside = (it >= wlo[rows]) & (it < whi[rows])
+            n_cand -= np.bincount(rows[inside & ~is_t], minlength=Nq)
+            self_in &= np.bincount(rows[(it == rows) & ~is_t], minlength=Nq) == 0      # unless the list took the self column already
+        if exclude_self:
+            self_t = tgt == me
+            barred |= self_t
+            n_cand -= (self_in & ~self_t).astype(np.int64)             # the target is counted even there; the row is not ranked anyway
+    elif exclude is not None:
         xp, xi = normalize_exclusions(exclude, Nq, Nc)
         rows = np.repeat(np.arange(Nq, dtype=np.int64), np.diff(xp))
         is_t = xi.astype(np.int64) == tgt[rows]
@@ -451,7 +592,7 @@ def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, ca
             n_cand -= 1 - np.bincount(rows[is_s & ~is_t], minlength=Nq)
     elif exclude_self:
         n_cand -= 1
-    if exclude_self:
+    if exclude_self and window is None:
         self_t = tgt == np.arange(Nq)
         barred |= self_t
         n_cand[self_t] += 1                                            # the target is counted even there; the row is not ranked anyway
@@ -468,10 +609,28 @@ def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, ca
     if xp is not None:
         xp_d = torch.from_numpy(xp).to(dev)
         xi_d = torch.from_numpy(xi if xi.size else np.zeros(1, dtype=np.int32)).to(dev)          # never a NULL pointer
-    with torch.cuda.device(dev):
-        L.call("dae_rank_similarity", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D, _NORMS[norm],
-               _METRICS[metric], 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(t_d), L.ptr(rank), L.ptr(score),
-               ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
+    if window is not None:
+        wlo, whi = window
+        perm = None if Cm is None else _window_order(wlo, whi)        # the corpus is Q itself: its rows stay where they are
+        if perm is not None:
+            perm_d = torch.from_numpy(perm).to(dev)
+            Q, wlo, whi, t_d = Q[perm_d].contiguous(), wlo[perm], whi[perm], t_d[perm_d].contiguous()
+            if xp is not None:
+                pp, pi = _permute_csr(xp, xi, perm)
+                xp_d = torch.from_numpy(pp).to(dev)
+                xi_d = torch.from_numpy(pi if pi.size else np.zeros(1, dtype=np.int32)).to(dev)
+        lo_d, hi_d = torch.from_numpy(np.ascontiguousarray(wlo)).to(dev), torch.from_numpy(np.ascontiguousarray(whi)).to(dev)
+        with torch.cuda.device(dev):
+            L.call("dae_rank_similarity_win", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
+                   _NORMS[norm], _METRICS[metric], 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(lo_d), L.ptr(hi_d),
+                   L.ptr(t_d), L.ptr(rank), L.ptr(score), ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
+        if perm is not None:
+            rank, score = torch.empty_like(rank).index_copy_(0, perm_d, rank), torch.empty_like(score).index_copy_(0, perm_d, score)
+    else:
+        with torch.cuda.device(dev):
+            L.call("dae_rank_similarity", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D, _NORMS[norm],
+                   _METRICS[metric], 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(t_d), L.ptr(rank), L.ptr(score),
+                   ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
     rank = rank.long()
     if barred.any():
         rank[torch.from_numpy(barred).to(dev)] = 0
@@ -480,11 +639,16 @@ def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, ca
     return rank.cpu().numpy(), score.cpu().numpy(), n_cand
 
 
-def recommend_ranks(user_vectors, embeddings, targets, seen=None, norm="", metric="linear kernel", *, return_tensor=False, device=None):
+def recommend_ranks(user_vectors, embeddings, targets, seen=None, norm="", metric="linear kernel", *, window=None, return_tensor=False,
+                    device=None):
     """The rank of each user's held-out article among all the articles the user has not read: the full-rank twin of
     ``recommend`` -- ``target_ranks(user_vectors, targets, candidates=embeddings, exclude=seen)``.  Returns ``(rank, score,
-    n_candidates)`` as ``target_ranks`` does; ``rank`` is 0 for a target the user has already seen."""
-    return target_ranks(user_vectors, targets, norm=norm, metric=metric, candidates=embeddings, exclude=seen,
+    n_candidates)`` as ``target_ranks`` does; ``rank`` is 0 for a target the user has already seen, and, with ``window`` (as in
+    ``recommend``), for one outside the user's window."""
+    if window is None:
+        return target_ranks(user_vectors, targets, norm=norm, metric=metric, candidates=embeddings, exclude=seen,
+                            return_tensor=return_tensor, device=device)
+    return target_ranks(user_vectors, targets, norm=norm, metric=metric, candidates=embeddings, exclude=seen, window=window,
                         return_tensor=return_tensor, device=device)
 
 
@@ -523,12 +687,16 @@ def rank_metrics(rank, n_candidates, targets, ks=(1, 5, 10, 50, 100)):
     return out
 
 
-def popularity_ranks(histories, n_articles, targets, seen=None):
+def popularity_ranks(histories, n_articles, targets, seen=None, *, window=None):
     """Full ranks of the popularity baseline (``popularity_recommend``'s order: click count descending, index ascending, the
     user's ``seen`` articles -- default: the own history -- skipped).  Host code.  Returns ``(rank int64 [users],
-    n_candidates int64 [users])`` with the conventions of ``target_ranks``: rank 0 without a target or for a seen one."""
+    n_candidates int64 [users])`` with the conventions of ``target_ranks``: rank 0 without a target or for a seen one.  With
+    ``window`` (a pair ``(lo, hi)`` per user, as in ``recommend``) only the articles ``lo <= a < hi`` compete, in the same order,
+    and a target outside the window has rank 0."""
     indptr, items = _csr_lists(histories)
     M = indptr.size - 1
+    if window is not None:
+        window = normalize_window(window, M, n_articles)
     xp, xi = normalize_exclusions((indptr, items) if seen is None else seen, M, n_articles)
     order = np.argsort(-np.bincount(items.astype(np.int64), minlength=int(n_articles)), kind="stable")
     pos = np.empty(int(n_articles), dtype=np.int64)
@@ -538,6 +706,17 @@ def popularity_ranks(histories, n_articles, targets, seen=None):
         raise ValueError(f"{tgt.shape[0]} targets for {M} users")
     rank = np.zeros(M, dtype=np.int64)
     n_cand = np.full(M, int(n_articles), dtype=np.int64)
+    if window is not None:
+        for u in range(M):
+            lo, hi = int(window[0][u]), int(window[1][u])
+            mine = xi[xp[u]:xp[u + 1]]
+            mine = mine[(mine >= lo) & (mine < hi)]
+            t = tgt[u]
+            n_cand[u] = hi - lo - (mine.size - int(t >= 0 and (mine == t).any()))
+            if t < 0 or not lo <= t < hi or (mine == t).any():
+                continue
+            rank[u] = 1 + int((pos[lo:hi] < pos[t]).sum()) - int((pos[mine] < pos[t]).sum())
+        return rank, n_cand
     for u in range(M):
         mine = xi[xp[u]:xp[u + 1]]
         t = tgt[u]
@@ -548,15 +727,26 @@ def popularity_ranks(histories, n_articles, targets, seen=None):
     return rank, n_cand
 
 
-def popularity_recommend(histories, n_articles, k, seen=None):
+def popularity_recommend(histories, n_articles, k, seen=None, *, window=None):
     """The baseline a recommender has to beat: for every user the ``k`` most-clicked articles (over all ``histories``; ties by
     index ascending) that are not in the user's ``seen`` list (default: the user's own history).  Host code.  Returns
-    int64 ``[users x k]``, -1 where fewer than k articles remain."""
+    int64 ``[users x k]``, -1 where fewer than k articles remain.  With ``window`` (a pair ``(lo, hi)`` per user, as in
+    ``recommend``) only the articles ``lo <= a < hi`` are eligible, in the same order."""
     indptr, items = _csr_lists(histories)
     M = indptr.size - 1
+    if window is not None:
+        window = normalize_window(window, M, n_articles)
     xp, xi = normalize_exclusions((indptr, items) if seen is None else seen, M, n_articles)
     order = np.argsort(-np.bincount(items.astype(np.int64), minlength=int(n_articles)), kind="stable")
     out = np.full((M, int(k)), -1, dtype=np.int64)
+    if window is not None:
+        for u in range(M):
+            lo, hi = int(window[0][u]), int(window[1][u])
+            mine = xi[xp[u]:xp[u + 1]]
+            cand = order[(order >= lo) & (order < hi)]                     # the window's articles, most clicked first
+            keep = cand[~np.isin(cand, mine)][:int(k)]
+            out[u, :keep.size] = keep
+        return out
     for u in range(M):
         mine = xi[xp[u]:xp[u + 1]]
         head = order[:int(k) + mine.size]                                  # enough to survive the removal of `mine`

@@ -76,6 +76,30 @@ def synthetic_sessions(n_users, labels, *, mean_len, seed, n_preferred=2, p_pref
     return indptr, items.astype(np.int32)
 
 
+def synthetic_timed_sessions(n_users, labels, *, mean_len, seed, span_hours=720.0, mean_delay_hours=6.0, n_preferred=2,
+                             p_preferred=0.9):
+    """``synthetic_sessions`` on a timeline: the articles are published at seeded uniform times over ``span_hours``, in the order
+    of their index (``publish_times`` does not decrease, so the corpus is in publication order and a window of time is a range
+    of indices), and a user clicks the articles of the session in publication order, each an exponential delay of mean
+    ``mean_delay_hours`` after it appeared but never before the previous click: ``t = running max of (publish[item] + delay)``.
+    So most clicks fall within a few ``mean_delay_hours`` of publication, every click is at or after its article's publication,
+    and a user's timestamps do not decrease.  Returns ``(indptr int64 [n_users + 1], items int32, timestamps float64 [clicks],
+    publish_times float64 [articles])`` in hours, oldest click first; deterministic per seed."""
+    indptr, items = synthetic_sessions(n_users, labels, mean_len=mean_len, seed=seed, n_preferred=n_preferred, p_preferred=p_preferred)
+    rng = np.random.default_rng([int(seed), 0x71AE])
+    n_articles = np.asarray(labels).ravel().size
+    publish = np.sort(rng.random(n_articles) * float(span_hours))
+    delay = rng.exponential(float(mean_delay_hours), items.size)
+    items = items.copy()
+    times = np.empty(items.size, dtype=np.float64)
+    for u in range(int(n_users)):
+        a, b = int(indptr[u]), int(indptr[u + 1])
+        it = np.sort(items[a:b], kind="stable")                             # index order is publication order
+        items[a:b] = it
+        times[a:b] = np.maximum.accumulate(publish[it] + delay[a:b])
+    return indptr, items, times, publish
+
+
 def xavier_uniform(n_features, n_components, const=1, seed=42):
     """U(+-const*sqrt(6/(F+H))) (autoencoder/utils.py:16-26) from a NumPy Generator: the reference's
     tf.random_uniform stream is not reproducible without TensorFlow, so parity runs inject this W0."""

@@ -476,6 +476,35 @@ int dae_rank_similarity(const float* Q, int64_t ldq, int32_t Nq, const float* C,
                         void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------------------------------------------------
+ * Candidate windows: dae_topk_similarity_ex and dae_rank_similarity with one contiguous range of admissible corpus rows
+ * per query row (a news feed: the articles that existed when the user clicked, and only the recent ones; with the corpus
+ * ordered by publication time that is a column range; helpers.most_similar / recommend / target_ranks(window=...)).
+ *   Every argument of the plain call, and the same scores, 64-bit key order, tails, determinism, grid-independence and
+ *   workspace size, plus win_lo, win_hi: int32[Nq] on the device.  Candidate j is admissible for query row i only if
+ *   win_lo[i] <= j < win_hi[i] -- in addition to j < Nc, not in row i's list, and not i itself under exclude_self.
+ *   win_lo[i] >= win_hi[i] is an empty window: the top-k row is idx = -1, score = -inf throughout.  Values are clamped
+ *   to [0, Nc] in the kernel.  The workgroups of a 128-row query tile walk only the 128-column corpus tiles that the union
+ *   of the tile's non-empty windows touches, so rows with similar windows should be neighbours (the helpers sort them).
+ *   dae_rank_similarity_win: the window removes competitors only, exactly as the exclusion list does -- a target outside
+ *   its own row's window is still scored and ranked among the admissible candidates; whether it counts is the caller's
+ *   decision.  A list item outside the window is neither counted nor taken out again.
+ *   Both window pointers NULL: exactly the plain call (which forwards here), bit for bit; exactly one NULL is an argument
+ *   error.  All other argument checks are those of the plain calls, with their messages.
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_topk_similarity_win_workspace(int32_t Nq, int32_t Nc, int32_t D, int32_t k);
+int dae_topk_similarity_win(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc,
+                            int32_t D, int32_t norm, int32_t metric, int32_t k, int32_t exclude_self,
+                            const int64_t* excl_indptr, const int32_t* excl_items, const int32_t* win_lo,
+                            const int32_t* win_hi, int32_t* idx, float* score, int64_t ldk, void* workspace,
+                            uint64_t workspace_bytes, void* stream);
+uint64_t dae_rank_similarity_win_workspace(int32_t Nq, int32_t Nc, int32_t D);
+int dae_rank_similarity_win(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                            int32_t norm, int32_t metric, int32_t exclude_self, const int64_t* excl_indptr,
+                            const int32_t* excl_items, const int32_t* win_lo, const int32_t* win_hi,
+                            const int32_t* targets, int32_t* rank, float* target_score, void* workspace,
+                            uint64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
  * User states from browsing histories: the decaying model of "Embedding-based News Recommendation for Millions of
  * Users" (KDD'17), a decay-weighted mean of the embeddings of the articles a user has read (helpers.user_states).
  *   E [Na x lde] fp32 article embeddings (device).  History CSR (device): indptr int64[M + 1], items int32[nnz], each

@@ -14,6 +14,7 @@ examples:
   python main_autoencoder.py --model_name uci --data X.npz --labels y.npy --triplet_strategy batch_hard
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rank_metrics --similarity False
+  python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rank_metrics --max_age 48 --similarity False
 """
 import argparse
 import os
@@ -106,6 +107,11 @@ def build_parser():
                         "saved to article_encoded_ranks.npz, and AUC, full MRR, mean / median rank and hit@{1, 10, 100} per model")
     p.add_argument("--session_decay", type=float, default=0.9,
                    help="decay of --recommend's user states: per click, or per unit of time when the sessions carry timestamps")
+    p.add_argument("--max_age", type=float, default=0.,
+                   help="HOURS > 0 (only with --sessions synthetic --recommend K): the sessions get a timeline (articles in publication "
+                        "order, clicks after publication), and every user is recommended, ranked and compared with the baseline only among "
+                        "the articles published by the time of the held-out click and at most HOURS before it (`inf`: any age); the files "
+                        "are article_encoded_recommend{K}_window.npz / article_encoded_ranks_window.npz.  0: off")
     return p
 
 
@@ -124,6 +130,8 @@ def validate(a):
     assert a.recommend == 0 or a.sessions != '', "--recommend needs --sessions"
     assert 0. <= a.session_decay <= 1.
     assert not a.rank_metrics or a.recommend > 0, "--rank_metrics needs --recommend K"
+    assert a.max_age >= 0., "--max_age is a number of hours"
+    assert a.max_age == 0. or (a.sessions == 'synthetic' and a.recommend > 0), "--max_age needs --sessions synthetic --recommend K"
     return a
 
 
@@ -265,12 +273,19 @@ def evaluate_recommend(a, trY, emb, data_dir):
     articles with the largest inner product are recommended (helpers.recommend: no users x articles matrix) and saved as
     ``indices`` / ``scores`` / ``targets`` in article_encoded_recommend{K}.npz.  hit@K, MRR@K and nDCG@K are printed beside
     those of the most-clicked-unseen baseline (host code).  Users with fewer than two clicks have no target (-1) and are not
-    counted."""
+    counted.
+
+    With --max_age HOURS the sessions carry a timeline (synthetic_timed_sessions), the user states decay per hour, and the time
+    of the held-out click gives every user a candidate window (helpers.candidate_windows): the model and the baseline recommend
+    only among the articles published by then and at most HOURS earlier.  The file is article_encoded_recommend{K}_window.npz
+    and also holds ``window_lo`` / ``window_hi`` / ``max_age`` / ``mean_window``."""
     from dae_rnn_news_recommendation_amd import helpers
     from dae_rnn_news_recommendation_amd.synthetic import synthetic_sessions
     K, n = a.recommend, emb.shape[0]
     print('calculate recommend %d' % K)
     t = None
+    if a.max_age > 0:
+        return evaluate_recommend_window(a, trY, emb, data_dir)
     if a.sessions == 'synthetic':
         assert trY is not None, "--sessions synthetic needs labels"
         seed = a.seed if a.seed >= 0 else 1234
@@ -302,13 +317,62 @@ def evaluate_recommend(a, trY, emb, data_dir):
     return idx, score, targets
 
 
-def evaluate_rank_metrics(states, emb, hist, targets, n, data_dir):
+def evaluate_recommend_window(a, trY, emb, data_dir):
+    """--max_age HOURS: evaluate_recommend inside per-user candidate windows (see there)."""
+    from dae_rnn_news_recommendation_amd import helpers
+    from dae_rnn_news_recommendation_amd.synthetic import synthetic_timed_sessions
+    K, n = a.recommend, emb.shape[0]
+    assert trY is not None, "--sessions synthetic needs labels"
+    seed = a.seed if a.seed >= 0 else 1234
+    indptr, items, t, publish = synthetic_timed_sessions(max(n // 2, 1), np.unique(np.asarray(trY), return_inverse=True)[1],
+                                                         mean_len=12, seed=seed)
+    lens = np.diff(indptr)
+    users = lens.shape[0]
+    has = lens >= 2
+    last = np.maximum(indptr[1:] - 1, 0)
+    targets = np.where(has, items[last], -1).astype(np.int64)
+    keep = np.ones(items.shape[0], dtype=bool)
+    keep[indptr[1:][lens >= 1] - 1] = False                               # the history is everything before the last click
+    h_ptr = np.zeros(users + 1, dtype=np.int64)
+    h_ptr[1:] = np.cumsum(np.maximum(lens - 1, 0))
+    hist = (h_ptr, items[keep])
+    window = helpers.candidate_windows(t[last], publish, None if np.isinf(a.max_age) else a.max_age)
+    mean_window = float((window[1] - window[0]).mean())
+    states = helpers.user_states(hist, emb, a.session_decay, timestamps=t[keep], return_tensor=True)
+    idx, score = helpers.recommend(states, emb, k=K, seen=hist, window=window)
+    np.savez(data_dir + 'article_encoded_recommend%d_window.npz' % K, indices=idx, scores=score, targets=targets, window_lo=window[0],
+             window_hi=window[1], max_age=a.max_age, mean_window=mean_window)
+    m = helpers.next_click_metrics(idx, targets)
+    b = helpers.next_click_metrics(helpers.popularity_recommend(hist, n, K, window=window), targets)
+    print('  %d users, %d clicks, %d with a held-out click, max age %g h, mean window %.1f of %d articles -> '
+          'article_encoded_recommend%d_window.npz' % (users, items.shape[0], m['n'], a.max_age, mean_window, n, K))
+    print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'decayed user state', m['hit'], m['mrr'], m['ndcg']))
+    print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'most clicked unseen', b['hit'], b['mrr'], b['ndcg']))
+    print('calculate recommend %d done' % K)
+    if a.rank_metrics:
+        evaluate_rank_metrics(states, emb, hist, targets, n, data_dir, window=window, max_age=a.max_age)
+    return idx, score, targets
+
+
+def evaluate_rank_metrics(states, emb, hist, targets, n, data_dir, window=None, max_age=0.):
     """--rank_metrics: the rank of every held-out click among all the articles the user has not read (helpers.recommend_ranks:
     no users x articles matrix), saved as ``rank`` / ``score`` / ``n_candidates`` / ``targets`` in article_encoded_ranks.npz, and
     one line per model -- the decayed user state and the most-clicked-unseen baseline (host code) -- with AUC, untruncated
-    MRR, mean / median rank and hit@{1, 10, 100}."""
+    MRR, mean / median rank and hit@{1, 10, 100}.  With ``window`` (--max_age) both models rank inside the users' candidate
+    windows and the file is article_encoded_ranks_window.npz, with the window's parameters."""
     from dae_rnn_news_recommendation_amd import helpers
     print('calculate rank metrics')
+    if window is not None:
+        rank, score, n_cand = helpers.recommend_ranks(states, emb, targets, seen=hist, window=window)
+        np.savez(data_dir + 'article_encoded_ranks_window.npz', rank=rank, score=score, n_candidates=n_cand, targets=targets,
+                 window_lo=window[0], window_hi=window[1], max_age=max_age, mean_window=float((window[1] - window[0]).mean()))
+        b_rank, b_cand = helpers.popularity_ranks(hist, n, targets, window=window)
+        for name, m in (('decayed user state', helpers.rank_metrics(rank, n_cand, targets, ks=(1, 10, 100))),
+                        ('most clicked unseen', helpers.rank_metrics(b_rank, b_cand, targets, ks=(1, 10, 100)))):
+            print('  ranks %-20s AUC %.4f  MRR %.4f  mean rank %.1f  median rank %.1f  hit@1 %.4f  hit@10 %.4f  hit@100 %.4f'
+                  % (name, m['auc'], m['mrr'], m['mean_rank'], m['median_rank'], m['hit@1'], m['hit@10'], m['hit@100']))
+        print('calculate rank metrics done -> article_encoded_ranks_window.npz')
+        return
     rank, score, n_cand = helpers.recommend_ranks(states, emb, targets, seen=hist)
     np.savez(data_dir + 'article_encoded_ranks.npz', rank=rank, score=score, n_candidates=n_cand, targets=targets)
     b_rank, b_cand = helpers.popularity_ranks(hist, n, targets)
