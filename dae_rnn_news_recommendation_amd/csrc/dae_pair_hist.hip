@@ -17,7 +17,7 @@
 // LDS counters go to the global uint64[2][bins] histogram by atomic adds -- integers, so the result is bit-identical run to
 // run and independent of the grid -- and the lanes' running values are reduced over the wave and the workgroup into one
 // record per workgroup; the host folds the records in index order (the fp64 sums are therefore bit-identical run to run).
-#include "dae_gemm_tile.h"
+#include "dae_score_sweep.h"
 
 #include <cmath>
 #include <vector>
@@ -29,17 +29,6 @@ constexpr int PAIR_HIST_RING = lds_bytes_for(2);
 constexpr int PAIR_HIST_MAX_GRID = 1024;     // records in the workspace; the grid is 2 x CUs (512 on the MI355X), capped here
 constexpr int PAIR_HIST_FLUSH_TILES = 1 << 17;
 constexpr int PAIR_NORM_BLOCKS = 256;
-
-__device__ __forceinline__ uint32_t hist_score_key(float f) {     // score_key of dae_similarity.hip: a < b <=> key(a) < key(b)
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-static inline float hist_key_score(uint32_t k) {
-    const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
 
 struct PairHistRecord {           // one per workgroup
     double sum[2];                // related, unrelated
@@ -80,14 +69,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void pair_hist_tiles_kernel(PairHi
     int done = 0;
     for (long long t = blockIdx.x; t < p.tiles; t += gridDim.x) {
         int qt, ct;
-        if (p.self) {                                           // t = qt (qt + 1) / 2 + ct, ct <= qt
-            long long q = (long long)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-            while (q * (q + 1) / 2 > t) --q;
-            while ((q + 1) * (q + 2) / 2 <= t) ++q;
-            qt = (int)q; ct = (int)(t - q * (q + 1) / 2);
-        } else {
-            qt = (int)(t / p.ctiles); ct = (int)(t % p.ctiles);
-        }
+        if (p.self) tri_tile(t, qt, ct);
+        else { qt = (int)(t / p.ctiles); ct = (int)(t % p.ctiles); }
         f32x16 acc[2][2];
         gemm_mainloop<float, 2>(p.g, qt, ct, 0, p.g.ktiles_total, lds, acc);
         __syncthreads();                                        // every wave is done with the staging ring
@@ -96,7 +79,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void pair_hist_tiles_kernel(PairHi
             lab[tid] = tid < 128 ? (i < p.Nq ? p.labels_q[i] : -1) : (i < p.Nc ? p.labels_c[i] : -1);
         }
         __syncthreads();
-        const int li0 = wm * 64 + 4 * g, lj0 = 128 + wn * 64 + c;
+        const int li0 = wm * 64 + 4 * g, lj0 = 128 + wn * 64 + c;          // the lane's first value
         const int32_t lc0 = lab[lj0], lc1 = lab[lj0 + 32];
         const bool tri = p.self && qt == ct;                    // the diagonal tile: only j < i counts
         const int i0 = qt * BM + li0, j0 = ct * BN + wn * 64 + c;
@@ -104,19 +87,18 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void pair_hist_tiles_kernel(PairHi
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                // row / column of a value: the accumulator layout of v_mfma_f32_32x32x2_f32, as in dae_pairs.hip
-                const int li = li0 + mt * 32 + (r & 3) + 8 * (r >> 2);
+                const int li = li0 + acc_row(mt, r, 0);
                 const int32_t lq = lab[li];
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) {
                     const int32_t lc = nt ? lc1 : lc0;
-                    const int i = i0 + mt * 32 + (r & 3) + 8 * (r >> 2), j = j0 + nt * 32;
+                    const int i = i0 + acc_row(mt, r, 0), j = j0 + acc_col(nt, 0);
                     if ((lq | lc) < 0 || (tri && j >= i)) continue;
                     const float s = acc[mt][nt][r];
                     if (s != s) { ++n_nan; continue; }
                     float x = floorf(__fdiv_rn(__fmul_rn(__fsub_rn(s, p.lo), p.fbins), p.span));
                     x = fminf(fmaxf(x, 0.f), p.fbins - 1.f);
-                    const uint32_t k = hist_score_key(s);
+                    const uint32_t k = score_key(s);
                     if (lq == lc) {
                         atomicAdd(&hist[(int)x], 1u);
                         kmin_r = min(kmin_r, k); kmax_r = max(kmax_r, k); sum_r += (double)s;
@@ -178,8 +160,6 @@ __global__ __launch_bounds__(256) void row_norm2_max_kernel(const float* __restr
     if (threadIdx.x == 0) part[blockIdx.x] = best;
 }
 
-static inline uint64_t al256(uint64_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace dae
 
 using namespace dae;
@@ -188,9 +168,9 @@ extern "C" int32_t dae_pair_hist_max_bins(void) { return PAIR_HIST_MAX_BINS; }
 
 extern "C" uint64_t dae_pair_hist_workspace(int32_t Nq, int32_t Nc, int32_t D, int32_t bins) {
     if (Nq <= 0 || Nc <= 0 || D <= 0 || bins <= 0) return 0;
-    const uint64_t Nqp = pad128(Nq), Ncp = pad128(Nc), Dp = pad128(D);
+    const uint64_t Nqp = pad128(Nq), Ncp = pad128(Nc);
     // operand images, labels, global histogram, per-workgroup records, norm partials of the automatic range
-    return al256(Nqp * Dp * 4) + al256(Ncp * Dp * 4) + al256(Nqp * 4) + al256(Ncp * 4) + al256(2 * (uint64_t)bins * 8) +
+    return sweep_images_bytes(Nq, Nc, D) + al256(Nqp * 4) + al256(Ncp * 4) + al256(2 * (uint64_t)bins * 8) +
            al256(PAIR_HIST_MAX_GRID * sizeof(PairHistRecord)) + al256(2 * PAIR_NORM_BLOCKS * 8);
 }
 
@@ -203,35 +183,28 @@ extern "C" int dae_pair_hist(const float* Q, int64_t ldq, int32_t Nq, const int3
     DAE_CHECK_ARG(ldq >= D, "pair_hist: ldq (%lld) must be >= D (%d)", (long long)ldq, D);
     DAE_CHECK_ARG(C ? (Nc > 0 && ldc >= D && labels_c_host) : Nc == Nq,
                   "pair_hist: bad corpus (C == NULL means the corpus is Q: pass Nc == Nq; with C, labels_c is needed)");
-    DAE_CHECK_ARG(norm >= 0 && norm <= 3, "pair_hist: norm must be 0 (none), 1 (l1), 2 (l2) or 3 (max)");
-    DAE_CHECK_ARG(metric == 0 || metric == 1, "pair_hist: metric must be 0 (cosine) or 1 (linear kernel)");
     DAE_CHECK_ARG(bins >= 2 && bins <= PAIR_HIST_MAX_BINS, "pair_hist: bins must be in 2..%d (got %d)", PAIR_HIST_MAX_BINS, bins);
     DAE_CHECK_ARG(std::isfinite(lo) && std::isfinite(hi), "pair_hist: lo / hi must be finite (lo >= hi asks for the automatic range)");
     DAE_CHECK_ARG(lo >= hi || std::isfinite(hi - lo), "pair_hist: hi - lo overflows fp32");
-    const int64_t Nqp = pad128(Nq), Ncp = pad128(Nc), Dp = pad128(D);
-    DAE_CHECK_ARG(Nqp * Dp * 4 < (1ll << 32) && Ncp * Dp * 4 < (1ll << 32), "pair_hist: an operand image exceeds 4 GiB");
-    const uint64_t need = dae_pair_hist_workspace(Nq, Nc, D, bins);
-    DAE_CHECK_ARG(workspace_bytes >= need, "pair_hist: workspace too small (%llu < %llu bytes)", (unsigned long long)workspace_bytes,
-                  (unsigned long long)need);
-    DAE_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "pair_hist: workspace must be 256-byte aligned");
     const int self = C ? 0 : 1;
-    const int64_t qtiles = Nqp / BM, ctiles = Ncp / BN;
+    const int64_t Nqp = pad128(Nq), Ncp = pad128(Nc), qtiles = Nqp / BM, ctiles = Ncp / BN;
     const int64_t tiles = self ? qtiles * (qtiles + 1) / 2 : qtiles * ctiles;
     DAE_CHECK_ARG(tiles < (1ll << 31), "pair_hist: %lld tiles exceed the enumeration", (long long)tiles);
     hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)workspace;
-    float* Qi = (float*)w;                      w += al256(Nqp * Dp * 4);
-    float* Ci = C ? (float*)w : Qi;             w += al256(Ncp * Dp * 4);
+    SweepOperands o;
+    if (int rc = sweep_prepare("pair_hist", Q, ldq, Nq, C, ldc, Nc, D, norm, metric, workspace, workspace_bytes,
+                               dae_pair_hist_workspace(Nq, Nc, D, bins), st, o))
+        return rc;
+    for (int k = 0; k < 16; ++k) out16_host[k] = std::nan("");
+    const float *Qi = o.Qi, *Ci = o.Ci;
+    const int64_t Dp = o.Dp;
+    const int cosine = metric == 0 ? 1 : 0;
+    char* w = o.rest;
     int32_t* lq = (int32_t*)w;                  w += al256(Nqp * 4);
     int32_t* lc = C ? (int32_t*)w : lq;         w += al256(Ncp * 4);
     unsigned long long* hist = (unsigned long long*)w;   w += al256(2 * (uint64_t)bins * 8);
     PairHistRecord* rec = (PairHistRecord*)w;   w += al256(PAIR_HIST_MAX_GRID * sizeof(PairHistRecord));
     double* npart = (double*)w;
-    for (int k = 0; k < 16; ++k) out16_host[k] = std::nan("");
-    const int cosine = metric == 0 ? 1 : 0;
-    if (int rc = launch_row_normalize(Q, ldq, Nq, D, norm, cosine, Qi, Dp, (int)Dp, (int)Nqp, st)) return rc;
-    if (C)
-        if (int rc = launch_row_normalize(C, ldc, Nc, D, norm, cosine, Ci, Dp, (int)Dp, (int)Ncp, st)) return rc;
     DAE_CHECK_HIP(hipMemcpyAsync(lq, labels_q_host, (size_t)Nq * 4, hipMemcpyHostToDevice, st));
     if (C) DAE_CHECK_HIP(hipMemcpyAsync(lc, labels_c_host, (size_t)Nc * 4, hipMemcpyHostToDevice, st));
     DAE_CHECK_HIP(hipMemsetAsync(hist, 0, 2 * (size_t)bins * 8, st));
@@ -270,19 +243,12 @@ extern "C" int dae_pair_hist(const float* Q, int64_t ldq, int32_t Nq, const int3
     if (grid > tiles) grid = tiles;
     PairHistParams p;
     memset(&p, 0, sizeof(p));
-    p.g.seg[0].A = (const char*)Qi; p.g.seg[0].Bt = (const char*)Ci;
-    p.g.seg[0].lda_b = p.g.seg[0].ldb_b = Dp * 4;
-    p.g.seg[0].ktiles = p.g.ktiles_total = (int)(Dp * 4 / BKB);
-    p.g.nseg = 1; p.g.splits = 1; p.g.out_scale = 1.f;
+    p.g = o.g;
     p.Nq = Nq; p.Nc = Nc; p.self = self; p.ctiles = (int)ctiles; p.bins = bins; p.tiles = tiles;
     p.lo = lo; p.span = hi - lo; p.fbins = (float)bins;
     p.labels_q = lq; p.labels_c = lc; p.hist = hist; p.rec = rec;
-    const int lds_bytes = PAIR_HIST_RING + 2 * bins * 4;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(pair_hist_tiles_kernel),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, PAIR_HIST_RING + 2 * PAIR_HIST_MAX_BINS * 4);
-    DAE_CHECK_HIP(attr);
-    DAE_LAUNCH(pair_hist_tiles_kernel, dim3((unsigned)grid), dim3(GEMM_THREADS), lds_bytes, st, p);
-    DAE_CHECK_LAUNCH();
+    if (int rc = sweep_launch<pair_hist_tiles_kernel>(grid, PAIR_HIST_RING + 2 * PAIR_HIST_MAX_BINS * 4, PAIR_HIST_RING + 2 * bins * 4, st, p))
+        return rc;
     std::vector<PairHistRecord> r((size_t)grid);
     DAE_CHECK_HIP(hipMemcpyAsync(hist_host, hist, 2 * (size_t)bins * 8, hipMemcpyDeviceToHost, st));
     DAE_CHECK_HIP(hipMemcpyAsync(r.data(), rec, (size_t)grid * sizeof(PairHistRecord), hipMemcpyDeviceToHost, st));
@@ -304,8 +270,8 @@ extern "C" int dae_pair_hist(const float* Q, int64_t ldq, int32_t Nq, const int3
     for (int k = 0; k < 2; ++k)
         if (n[k]) {
             out16_host[3 + k] = sum[k];
-            out16_host[5 + 2 * k] = (double)hist_key_score(kmin[k]);
-            out16_host[6 + 2 * k] = (double)hist_key_score(kmax[k]);
+            out16_host[5 + 2 * k] = (double)key_score(kmin[k]);
+            out16_host[6 + 2 * k] = (double)key_score(kmax[k]);
         }
     out16_host[9] = (double)lo; out16_host[10] = (double)hi;
     out16_host[11] = (double)grid; out16_host[12] = (double)tiles;

@@ -17,7 +17,7 @@
 // buffer is too small.  Append order depends on scheduling: when the count fits, rocprim::radix_sort_pairs orders the records by
 // key (i ascending, then j ascending) and pairs_unpack_kernel splits the keys into rows / cols, which makes the result
 // bit-identical run to run and independent of the grid.
-#include "dae_gemm_tile.h"
+#include "dae_score_sweep.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -40,23 +40,16 @@ struct PairsParams {
 __global__ __launch_bounds__(GEMM_THREADS, 2) void pairs_tiles_kernel(PairsParams p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     int qt, ct;
-    if (p.self) {                                               // t = qt (qt + 1) / 2 + ct, ct <= qt
-        const long long t = blockIdx.x;
-        long long q = (long long)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-        while (q * (q + 1) / 2 > t) --q;
-        while ((q + 1) * (q + 2) / 2 <= t) ++q;
-        qt = (int)q; ct = (int)(t - q * (q + 1) / 2);
-    } else {
-        qt = blockIdx.x / p.ctiles; ct = blockIdx.x % p.ctiles;
-    }
+    if (p.self) tri_tile(blockIdx.x, qt, ct);
+    else { qt = blockIdx.x / p.ctiles; ct = blockIdx.x % p.ctiles; }
     f32x16 acc[2][2];
     gemm_mainloop<float, 2>(p.g, qt, ct, 0, p.g.ktiles_total, lds, acc);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, g = lane >> 5, c = lane & 31;
-    const int i0 = qt * BM + wm * 64 + 4 * g, j0 = ct * BN + wn * 64 + c;
+    const int i0 = qt * BM + wm * 64 + 4 * g, j0 = ct * BN + wn * 64 + c;      // the lane's first value
     const float T = p.threshold;
-    // bit (mt * 2 + nt) * 16 + r of `hits`: the lane's value acc[mt][nt][r] qualifies.  Row / column of a value: the accumulator
-    // layout of v_mfma_f32_32x32x2_f32, as in dae_topk.hip.  (A mask in two VGPRs rather than 64 conditions kept in SGPR pairs.)
+    // bit (mt * 2 + nt) * 16 + r of `hits`: the lane's value acc[mt][nt][r] qualifies.  Row / column of a value: acc_row /
+    // acc_col of dae_score_sweep.h.  (A mask in two VGPRs rather than 64 conditions kept in SGPR pairs.)
     uint64_t hits = 0;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
@@ -64,7 +57,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void pairs_tiles_kernel(PairsParam
         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int i = i0 + mt * 32 + (r & 3) + 8 * (r >> 2), j = j0 + nt * 32;
+                const int i = i0 + acc_row(mt, r, 0), j = j0 + acc_col(nt, 0);
                 const bool hit = acc[mt][nt][r] >= T && i < p.Nq && j < p.Nc && (!p.self || j < i);
                 hits |= (uint64_t)hit << ((mt * 2 + nt) * 16 + r);
             }
@@ -87,7 +80,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void pairs_tiles_kernel(PairsParam
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 if ((hits >> ((mt * 2 + nt) * 16 + r)) & 1) {
-                    const int i = i0 + mt * 32 + (r & 3) + 8 * (r >> 2), j = j0 + nt * 32;
+                    const int i = i0 + acc_row(mt, r, 0), j = j0 + acc_col(nt, 0);
                     if (slot < p.capacity) {
                         p.keys[slot] = ((uint64_t)(uint32_t)i << 32) | (uint32_t)j;
                         p.vals[slot] = acc[mt][nt][r];
@@ -119,7 +112,6 @@ static size_t pairs_sort_temp_bytes(size_t n, int Nq) {
     (void)rocprim::radix_sort_pairs(nullptr, bytes, k, k, v, v, n, 0, pairs_end_bit(Nq), (hipStream_t)0);
     return bytes;
 }
-static inline uint64_t al256(uint64_t b) { return (b + 255) / 256 * 256; }
 
 }  // namespace dae
 
@@ -127,9 +119,8 @@ using namespace dae;
 
 extern "C" uint64_t dae_threshold_pairs_workspace(int32_t Nq, int32_t Nc, int32_t D, uint64_t capacity) {
     if (Nq <= 0 || Nc <= 0 || D <= 0) return 0;
-    const uint64_t Nqp = pad128(Nq), Ncp = pad128(Nc), Dp = pad128(D);
     // operand images, unsorted keys + scores, sorted keys, sort scratch, cursor
-    return al256(Nqp * Dp * 4) + al256(Ncp * Dp * 4) + 2 * al256(capacity * 8) + al256(capacity * 4) +
+    return sweep_images_bytes(Nq, Nc, D) + 2 * al256(capacity * 8) + al256(capacity * 4) +
            al256(capacity ? pairs_sort_temp_bytes((size_t)capacity, Nq) : 0) + 256;
 }
 
@@ -138,49 +129,31 @@ extern "C" int dae_threshold_pairs(const float* Q, int64_t ldq, int32_t Nq, cons
                                    uint64_t capacity, uint64_t* count_host, void* workspace, uint64_t workspace_bytes, void* stream) {
     DAE_CHECK_ARG(Q && count_host && workspace && Nq > 0 && D > 0, "threshold_pairs: bad input");
     DAE_CHECK_ARG(ldq >= D, "threshold_pairs: ldq (%lld) must be >= D (%d)", (long long)ldq, D);
-    DAE_CHECK_ARG(C ? (Nc > 0 && ldc >= D) : Nc == Nq, "threshold_pairs: bad corpus (C == NULL means the corpus is Q: pass Nc == Nq)");
-    DAE_CHECK_ARG(norm >= 0 && norm <= 3, "threshold_pairs: norm must be 0 (none), 1 (l1), 2 (l2) or 3 (max)");
-    DAE_CHECK_ARG(metric == 0 || metric == 1, "threshold_pairs: metric must be 0 (cosine) or 1 (linear kernel)");
     DAE_CHECK_ARG(!std::isnan(threshold), "threshold_pairs: threshold is NaN");
     DAE_CHECK_ARG(capacity == 0 || (rows && cols && scores), "threshold_pairs: rows / cols / scores are NULL with capacity %llu",
                   (unsigned long long)capacity);
-    const int64_t Nqp = pad128(Nq), Ncp = pad128(Nc), Dp = pad128(D);
-    DAE_CHECK_ARG(Nqp * Dp * 4 < (1ll << 32) && Ncp * Dp * 4 < (1ll << 32), "threshold_pairs: an operand image exceeds 4 GiB");
-    const uint64_t need = dae_threshold_pairs_workspace(Nq, Nc, D, capacity);
-    DAE_CHECK_ARG(workspace_bytes >= need, "threshold_pairs: workspace too small (%llu < %llu bytes)",
-                  (unsigned long long)workspace_bytes, (unsigned long long)need);
-    DAE_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "threshold_pairs: workspace must be 256-byte aligned");
     hipStream_t st = (hipStream_t)stream;
+    SweepOperands o;
+    if (int rc = sweep_prepare("threshold_pairs", Q, ldq, Nq, C, ldc, Nc, D, norm, metric, workspace, workspace_bytes,
+                               dae_threshold_pairs_workspace(Nq, Nc, D, capacity), st, o))
+        return rc;
     const size_t temp_bytes = capacity ? pairs_sort_temp_bytes((size_t)capacity, Nq) : 0;
-    char* w = (char*)workspace;
-    float* Qi = (float*)w;                w += al256(Nqp * Dp * 4);
-    float* Ci = C ? (float*)w : Qi;       w += al256(Ncp * Dp * 4);
+    char* w = o.rest;
     uint64_t* keys = (uint64_t*)w;        w += al256(capacity * 8);
     uint64_t* keys_s = (uint64_t*)w;      w += al256(capacity * 8);
     float* vals = (float*)w;              w += al256(capacity * 4);
     void* temp = w;                       w += al256(temp_bytes);
     unsigned long long* cursor = (unsigned long long*)w;
-    const int cosine = metric == 0 ? 1 : 0;
-    if (int rc = launch_row_normalize(Q, ldq, Nq, D, norm, cosine, Qi, Dp, (int)Dp, (int)Nqp, st)) return rc;
-    if (C)
-        if (int rc = launch_row_normalize(C, ldc, Nc, D, norm, cosine, Ci, Dp, (int)Dp, (int)Ncp, st)) return rc;
     DAE_CHECK_HIP(hipMemsetAsync(cursor, 0, 8, st));
     PairsParams p;
     memset(&p, 0, sizeof(p));
-    p.g.seg[0].A = (const char*)Qi; p.g.seg[0].Bt = (const char*)Ci;
-    p.g.seg[0].lda_b = p.g.seg[0].ldb_b = Dp * 4;
-    p.g.seg[0].ktiles = p.g.ktiles_total = (int)(Dp * 4 / BKB);
-    p.g.nseg = 1; p.g.splits = 1; p.g.out_scale = 1.f;
-    p.Nq = Nq; p.Nc = Nc; p.self = C ? 0 : 1; p.ctiles = (int)(Ncp / BN); p.threshold = threshold;
+    p.g = o.g;
+    p.Nq = Nq; p.Nc = Nc; p.self = C ? 0 : 1; p.ctiles = (int)(o.Ncp / BN); p.threshold = threshold;
     p.capacity = capacity; p.cursor = cursor; p.keys = keys; p.vals = vals;
-    const int64_t qtiles = Nqp / BM;
+    const int64_t qtiles = o.Nqp / BM;
     const int64_t tiles = p.self ? qtiles * (qtiles + 1) / 2 : qtiles * p.ctiles;
     DAE_CHECK_ARG(tiles < (1ll << 31), "threshold_pairs: %lld tiles exceed the grid", (long long)tiles);
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(pairs_tiles_kernel),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, PAIRS_LDS);
-    DAE_CHECK_HIP(attr);
-    DAE_LAUNCH(pairs_tiles_kernel, dim3((unsigned)tiles), dim3(GEMM_THREADS), PAIRS_LDS, st, p);
-    DAE_CHECK_LAUNCH();
+    if (int rc = sweep_launch<pairs_tiles_kernel>(tiles, PAIRS_LDS, PAIRS_LDS, st, p)) return rc;
     unsigned long long count = 0;
     DAE_CHECK_HIP(hipMemcpyAsync(&count, cursor, 8, hipMemcpyDeviceToHost, st));
     DAE_CHECK_HIP(hipStreamSynchronize(st));

@@ -3,8 +3,8 @@
 //
 // The scores and the order are those of dae_topk.hip: rows normalised by row_normalize_kernel into zero-padded fp32 operand
 // images, products by gemm_mainloop<float, 2> over the whole K range in one pass, every (score, index) pair mapped to the
-// 64-bit key score_key(score) << 32 | ~index (score descending, then index ascending, -0 == +0).  What is new is an epilogue
-// that COUNTS the keys above one key per row instead of selecting the k largest.
+// 64-bit key pair_key (dae_score_sweep.h) = score_key(score) << 32 | ~index (score descending, then index ascending,
+// -0 == +0).  What is new is an epilogue that COUNTS the keys above one key per row instead of selecting the k largest.
 //
 //   rank[i] = 1 + #{ j < Nc : j != t, j not in row i's exclusion list, not (exclude_self and j == i), key(S[i, j], j) > key(S[i, t], t) }
 //
@@ -29,12 +29,12 @@
 // LDS: 64 KiB ring / tile + 1 KiB keys + 0.5 KiB counts = 65.5 KiB, two workgroups per CU.
 //
 // Candidate windows (dae_rank_similarity_win, rank_tiles_kernel<*, true>): row i's competitors are only the columns
-// win_lo[i] <= j < win_hi[i].  As in dae_topk.hip the query tile's windows, clamped to [0, Nc], go to LDS (+1 KiB) and the
-// workgroups of a query tile split the tiles of the union of its non-empty windows; the two compares join the ballots of the
+// win_lo[i] <= j < win_hi[i].  By window_prologue (dae_score_sweep.h) the query tile's windows, clamped to [0, Nc], go to LDS
+// (+1 KiB) and the workgroups of a query tile split the tiles of the union of its non-empty windows; the two compares join the ballots of the
 // count loop (bounds read from LDS per row, not kept across the K loop), a list item outside the row's window is not taken out
 // again (the sweep never counted it), and a workgroup with an empty slice adds nothing.  rank_tiles_kernel<*, false> is the
 // kernel as it was; rank_gather_kernel and rank_target_kernel do not know about windows.
-#include "dae_gemm_tile.h"
+#include "dae_score_sweep.h"
 
 namespace dae {
 
@@ -43,14 +43,6 @@ constexpr int RANK_TILE_BYTES = BM * BN * 4;
 constexpr int RANK_LDS = RANK_TILE_BYTES + 128 * 8 + 128 * 4;
 constexpr int RANK_WIN_LDS = RANK_LDS + 2 * 128 * 4 + 16;   // + the query tile's windows and their union
 constexpr int RANK_TARGET_LDS = lds_bytes_for(2);
-
-// topk_key of dae_topk.hip (duplicated: that file's kernels stay as they are)
-__device__ __forceinline__ uint64_t rank_key(float s, int j) {
-    if (s == 0.f) s = 0.f;                                      // -0 and +0 are one score
-    const uint32_t u = __float_as_uint(s);
-    const uint32_t h = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((uint64_t)h << 32) | (uint32_t)~(uint32_t)j;
-}
 
 __global__ __launch_bounds__(256) void rank_gather_kernel(const float* __restrict__ Ci, const int32_t* __restrict__ targets, int Nq, int Nc,
                                                           int Dp, float* __restrict__ G) {
@@ -83,9 +75,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_target_kernel(RankTarget
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            // row of a value inside its 32 x 32 block: the accumulator layout of v_mfma_f32_32x32x2_f32; its column is c
-            if ((r & 3) + 8 * (r >> 2) + 4 * g != c) continue;
-            const int gi = qt * BM + wm * 64 + mt * 32 + c;
+            if (acc_row(0, r, g) != c) continue;                // block (mt, mt): the value of row == column
+            const int gi = qt * BM + wm * 64 + acc_col(mt, c);
             if (gi >= p.Nq) continue;
             const int t = p.targets[gi];
             const float s = acc[mt][mt][r];
@@ -94,7 +85,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_target_kernel(RankTarget
                 p.rank[gi] = 0;
                 p.target_score[gi] = -__builtin_inff();
             } else {
-                p.tkey[gi] = rank_key(s, min(t, p.Nc - 1));
+                p.tkey[gi] = pair_key(s, min(t, p.Nc - 1));
                 p.rank[gi] = 1;
                 p.target_score[gi] = s;
             }
@@ -129,22 +120,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams 
     }
     int* wlo = reinterpret_cast<int*>(lds + RANK_LDS);          // the query tile's windows (WIN only; behind the counts)
     int* whi = wlo + 128;
-    if constexpr (WIN) {
-        int* un = whi + 128;                                    // union of the non-empty windows: [un[0], un[1])
-        if (tid == 0) { un[0] = INT32_MAX; un[1] = 0; }
-        __syncthreads();
-        if (tid < 128) {
-            const int gi = qt * BM + tid;
-            int lo = 0, hi = 0;
-            if (gi < p.Nq) { lo = min(max(p.win_lo[gi], 0), p.Nc); hi = min(max(p.win_hi[gi], 0), p.Nc); }
-            if (lo >= hi) lo = hi = 0;                          // empty (and the rows >= Nq): does not widen the union
-            else { atomicMin(&un[0], lo); atomicMax(&un[1], hi); }
-            wlo[tid] = lo; whi[tid] = hi;
-        }
-        __syncthreads();
-        const int t0 = un[1] > 0 ? un[0] / BN : 0, nt = un[1] > 0 ? (un[1] + BN - 1) / BN - t0 : 0;
-        ct0 = t0 + (int)((int64_t)nt * split / p.splits); ct1 = t0 + (int)((int64_t)nt * (split + 1) / p.splits);
-    }
+    if constexpr (WIN) window_prologue(p.win_lo, p.win_hi, p.Nq, p.Nc, qt, split, p.splits, wlo, whi, whi + 128, ct0, ct1);
     // ---- the exclusion cursor of this lane's row (lanes 0..31 of every wave) ----
     const int xrow = wave * 32 + lane, xgi = qt * BM + xrow;
     const int32_t* X = nullptr;
@@ -157,12 +133,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams 
             X = p.excl_items + x0;
             xend = (int)(p.excl_indptr[xgi + 1] - x0);
             if (xkey == ~0ull) xend = 0;                        // no target: nothing to count
-            int lo = 0, hi = xend;                              // first item of the slice
-            while (lo < hi) {
-                const int m = (lo + hi) >> 1;
-                if (X[m] < ct0 * BN) lo = m + 1; else hi = m;
-            }
-            xpos = lo;
+            xpos = lower_bound_i32(X, xend, ct0 * BN);          // first item of the slice
             if (xpos < xend) xnext = X[xpos];
         }
     }
@@ -181,18 +152,18 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams 
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int lrow = mt * 32 + (r & 3) + 8 * (r >> 2);          // the row of lanes 0..31 (g = 0); lanes 32..63 hold lrow + 4
+                const int lrow = acc_row(mt, r, 0);                         // the row of lanes 0..31 (g = 0); lanes 32..63 hold lrow + 4
                 const int row = wm * 64 + lrow + 4 * (ln >> 5);
                 const uint64_t t = tk[row];
                 const int self = p.exclude_self ? qt * BM + row : -1;
                 uint64_t b0, b1;
                 if constexpr (WIN) {                            // the row's bounds come from LDS here: nothing lives across the K loop
                     const int wl = wlo[row], wh = whi[row];
-                    b0 = __ballot(ok0 && j0 != self && j0 >= wl && j0 < wh && rank_key(acc[mt][0][r], j0) > t);
-                    b1 = __ballot(ok1 && j1 != self && j1 >= wl && j1 < wh && rank_key(acc[mt][1][r], j1) > t);
+                    b0 = __ballot(ok0 && j0 != self && j0 >= wl && j0 < wh && pair_key(acc[mt][0][r], j0) > t);
+                    b1 = __ballot(ok1 && j1 != self && j1 >= wl && j1 < wh && pair_key(acc[mt][1][r], j1) > t);
                 } else {
-                    b0 = __ballot(ok0 && j0 != self && rank_key(acc[mt][0][r], j0) > t);
-                    b1 = __ballot(ok1 && j1 != self && rank_key(acc[mt][1][r], j1) > t);
+                    b0 = __ballot(ok0 && j0 != self && pair_key(acc[mt][0][r], j0) > t);
+                    b1 = __ballot(ok1 && j1 != self && pair_key(acc[mt][1][r], j1) > t);
                 }
                 const int lo = __popc((uint32_t)b0) + __popc((uint32_t)b1), hi = __popc((uint32_t)(b0 >> 32)) + __popc((uint32_t)(b1 >> 32));
                 n += (ln == lrow ? lo : 0) + (ln == lrow + 4 ? hi : 0);
@@ -203,13 +174,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams 
             const int tile_end = (ct + 1) * BN;
             // the barrier also says that every wave is done with the staging ring
             if (__syncthreads_or(xnext < tile_end)) {
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            tile[(wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g) * BN + wn * 64 + nt * 32 + c] = acc[mt][nt][r];
+                acc_to_tile(acc, tile, wm, wn, g, c);
                 __syncthreads();
                 int last = -1;
                 while (xnext < tile_end) {                      // the run of this row's list inside the tile
@@ -217,7 +182,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams 
                     bool inw = true;                            // outside the row's window the sweep did not count it
                     if constexpr (WIN) inw = x >= wlo[xrow] && x < whi[xrow];
                     if (x >= ct * BN && x != last && x < p.Nc && !(p.exclude_self && x == xgi) && inw)
-                        xsub += (int)(rank_key(tile[xrow * BN + (x - ct * BN)], x) > xkey);
+                        xsub += (int)(pair_key(tile[xrow * BN + (x - ct * BN)], x) > xkey);
                     last = x;
                     ++xpos;
                     xnext = xpos < xend ? X[xpos] : INT32_MAX;
@@ -234,13 +199,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams 
     if (tid < 128 && qt * BM + tid < p.Nq && cnt[tid] != 0) atomicAdd(&p.rank[qt * BM + tid], cnt[tid]);
 }
 
-static int rank_splits(int Nq, int Nc) {
-    const int64_t qt = pad128(Nq) / BM, ct = pad128(Nc) / BN;
-    int64_t s = RANK_SLOTS / qt;
-    if (s > ct) s = ct;
-    return s < 1 ? 1 : (int)s;
-}
-static inline uint64_t al256(uint64_t b) { return (b + 255) / 256 * 256; }
+static int rank_splits(int Nq, int Nc) { return sweep_splits(Nq, Nc, RANK_SLOTS, RANK_SLOTS); }      // no cap of its own
 
 }  // namespace dae
 
@@ -248,9 +207,9 @@ using namespace dae;
 
 extern "C" uint64_t dae_rank_similarity_workspace(int32_t Nq, int32_t Nc, int32_t D) {
     if (Nq <= 0 || Nc <= 0 || D <= 0) return 0;
-    const uint64_t Nqp = pad128(Nq), Ncp = pad128(Nc), Dp = pad128(D);
+    const uint64_t Nqp = pad128(Nq), Dp = pad128(D);
     // query image, corpus image, gathered target image, one key per query row
-    return al256(Nqp * Dp * 4) + al256(Ncp * Dp * 4) + al256(Nqp * Dp * 4) + al256(Nqp * 8);
+    return sweep_images_bytes(Nq, Nc, D) + al256(Nqp * Dp * 4) + al256(Nqp * 8);
 }
 
 extern "C" uint64_t dae_rank_similarity_win_workspace(int32_t Nq, int32_t Nc, int32_t D) {
@@ -267,71 +226,33 @@ extern "C" int dae_rank_similarity_win(const float* Q, int64_t ldq, int32_t Nq, 
                   "rank_similarity: win_lo and win_hi go together (exactly one of them is NULL)");
     DAE_CHECK_ARG(Q && workspace && Nq > 0 && D > 0 && ldq >= D, "rank_similarity: bad input");
     DAE_CHECK_ARG(targets && rank && target_score, "rank_similarity: targets / rank / target_score are NULL");
-    DAE_CHECK_ARG(C ? (Nc > 0 && ldc >= D) : Nc == Nq, "rank_similarity: bad corpus (C == NULL means the corpus is Q: pass Nc == Nq)");
-    DAE_CHECK_ARG(norm >= 0 && norm <= 3, "rank_similarity: norm must be 0 (none), 1 (l1), 2 (l2) or 3 (max)");
-    DAE_CHECK_ARG(metric == 0 || metric == 1, "rank_similarity: metric must be 0 (cosine) or 1 (linear kernel)");
     DAE_CHECK_ARG(!exclude_self || !C, "rank_similarity: exclude_self needs C == NULL (the corpus is Q itself)");
-    const int64_t Nqp = pad128(Nq), Ncp = pad128(Nc), Dp = pad128(D);
-    DAE_CHECK_ARG(Nqp * Dp * 4 < (1ll << 32) && Ncp * Dp * 4 < (1ll << 32), "rank_similarity: an operand image exceeds 4 GiB");
-    DAE_CHECK_ARG(workspace_bytes >= dae_rank_similarity_workspace(Nq, Nc, D),
-                  "rank_similarity: workspace too small (%llu < %llu bytes)", (unsigned long long)workspace_bytes,
-                  (unsigned long long)dae_rank_similarity_workspace(Nq, Nc, D));
-    DAE_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "rank_similarity: workspace must be 256-byte aligned");
     hipStream_t st = (hipStream_t)stream;
+    SweepOperands o;
+    if (int rc = sweep_prepare("rank_similarity", Q, ldq, Nq, C, ldc, Nc, D, norm, metric, workspace, workspace_bytes,
+                               dae_rank_similarity_workspace(Nq, Nc, D), st, o))
+        return rc;
     const int splits = rank_splits(Nq, Nc);
-    char* w = (char*)workspace;
-    float* Qi = (float*)w;           w += al256(Nqp * Dp * 4);
-    float* Ci = C ? (float*)w : Qi;  w += al256(Ncp * Dp * 4);
-    float* Gi = (float*)w;           w += al256(Nqp * Dp * 4);
-    uint64_t* tkey = (uint64_t*)w;
-    const int cosine = metric == 0 ? 1 : 0;
-    if (int rc = launch_row_normalize(Q, ldq, Nq, D, norm, cosine, Qi, Dp, (int)Dp, (int)Nqp, st)) return rc;
-    if (C)
-        if (int rc = launch_row_normalize(C, ldc, Nc, D, norm, cosine, Ci, Dp, (int)Dp, (int)Ncp, st)) return rc;
-    DAE_LAUNCH(rank_gather_kernel, dim3((unsigned)Nqp), dim3(256), 0, st, Ci, targets, (int)Nq, (int)Nc, (int)Dp, Gi);
+    float* Gi = (float*)o.rest;
+    uint64_t* tkey = (uint64_t*)(o.rest + al256(o.Nqp * o.Dp * 4));
+    DAE_LAUNCH(rank_gather_kernel, dim3((unsigned)o.Nqp), dim3(256), 0, st, o.Ci, targets, (int)Nq, (int)Nc, (int)o.Dp, Gi);
     DAE_CHECK_LAUNCH();
     RankTargetParams tp;
     memset(&tp, 0, sizeof(tp));
-    tp.g.seg[0].A = (const char*)Qi; tp.g.seg[0].Bt = (const char*)Gi;
-    tp.g.seg[0].lda_b = tp.g.seg[0].ldb_b = Dp * 4;
-    tp.g.seg[0].ktiles = tp.g.ktiles_total = (int)(Dp * 4 / BKB);
-    tp.g.nseg = 1; tp.g.splits = 1; tp.g.out_scale = 1.f;
+    tp.g = o.g;
+    tp.g.seg[0].Bt = (const char*)Gi;
     tp.Nq = Nq; tp.Nc = Nc; tp.targets = targets; tp.tkey = tkey; tp.rank = rank; tp.target_score = target_score;
-    static const hipError_t attr_t = hipFuncSetAttribute(reinterpret_cast<const void*>(rank_target_kernel),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, RANK_TARGET_LDS);
-    DAE_CHECK_HIP(attr_t);
-    DAE_LAUNCH(rank_target_kernel, dim3((unsigned)(Nqp / BM)), dim3(GEMM_THREADS), RANK_TARGET_LDS, st, tp);
-    DAE_CHECK_LAUNCH();
+    if (int rc = sweep_launch<rank_target_kernel>(o.Nqp / BM, RANK_TARGET_LDS, RANK_TARGET_LDS, st, tp)) return rc;
     RankParams p;
     memset(&p, 0, sizeof(p));
-    p.g = tp.g;
-    p.g.seg[0].Bt = (const char*)Ci;
-    p.Nq = Nq; p.Nc = Nc; p.exclude_self = exclude_self ? 1 : 0; p.splits = splits; p.ctiles = (int)(Ncp / BN);
+    p.g = o.g;
+    p.Nq = Nq; p.Nc = Nc; p.exclude_self = exclude_self ? 1 : 0; p.splits = splits; p.ctiles = (int)(o.Ncp / BN);
     p.tkey = tkey; p.rank = rank; p.excl_indptr = excl_indptr; p.excl_items = excl_items; p.win_lo = win_lo; p.win_hi = win_hi;
-    if (win_lo) {
-        static const hipError_t attr_w = hipFuncSetAttribute(reinterpret_cast<const void*>(rank_tiles_kernel<false, true>),
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, RANK_WIN_LDS);
-        DAE_CHECK_HIP(attr_w);
-        static const hipError_t attr_xw = hipFuncSetAttribute(reinterpret_cast<const void*>(rank_tiles_kernel<true, true>),
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize, RANK_WIN_LDS);
-        DAE_CHECK_HIP(attr_xw);
-        if (excl_indptr)
-            DAE_LAUNCH((rank_tiles_kernel<true, true>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), RANK_WIN_LDS, st, p);
-        else
-            DAE_LAUNCH((rank_tiles_kernel<false, true>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), RANK_WIN_LDS, st, p);
-        DAE_CHECK_LAUNCH();
-        return 0;
-    }
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(rank_tiles_kernel<false, false>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, RANK_LDS);
-    DAE_CHECK_HIP(attr);
-    static const hipError_t attr_x = hipFuncSetAttribute(reinterpret_cast<const void*>(rank_tiles_kernel<true, false>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, RANK_LDS);
-    DAE_CHECK_HIP(attr_x);
-    if (excl_indptr) DAE_LAUNCH((rank_tiles_kernel<true, false>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), RANK_LDS, st, p);
-    else DAE_LAUNCH((rank_tiles_kernel<false, false>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), RANK_LDS, st, p);
-    DAE_CHECK_LAUNCH();
-    return 0;
+    const int64_t grid = o.Nqp / BM * splits;
+    if (win_lo) return excl_indptr ? sweep_launch<rank_tiles_kernel<true, true>>(grid, RANK_WIN_LDS, RANK_WIN_LDS, st, p)
+                                   : sweep_launch<rank_tiles_kernel<false, true>>(grid, RANK_WIN_LDS, RANK_WIN_LDS, st, p);
+    return excl_indptr ? sweep_launch<rank_tiles_kernel<true, false>>(grid, RANK_LDS, RANK_LDS, st, p)
+                       : sweep_launch<rank_tiles_kernel<false, false>>(grid, RANK_LDS, RANK_LDS, st, p);
 }
 
 extern "C" int dae_rank_similarity(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,

@@ -1,0 +1,152 @@
+// dae_score_sweep.h -- what the "without the N x N matrix" kernels share: dae_topk.hip, dae_rank.hip, dae_pairs.hip and
+// dae_pair_hist.hip sweep the 128 x 128 score tiles of gemm_mainloop<float, 2> over two normalised operand images and differ
+// only in the epilogue.  Here: the order-preserving keys, the accumulator layout, the tile enumerations, the candidate-window
+// prologue, and the host prologue (argument checks, workspace carve, normalisation, GemmParams) and launch of every entry.
+#pragma once
+#include "dae_gemm_tile.h"
+
+namespace dae {
+
+// ---- keys ----
+// monotone 32-bit key of a score: a < b  <=>  key(a) < key(b); -0 < +0 adjacent
+__device__ __forceinline__ uint32_t score_key(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__host__ __device__ __forceinline__ float key_score(uint32_t k) {
+    return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+// 64-bit key of a (score, index) pair: a larger key is a better pair, i.e. score descending, then index ascending -- a total
+// order.  Key 0 lies below every finite score, ~0 above every pair.
+__device__ __forceinline__ uint64_t pair_key(float s, int j) {
+    if (s == 0.f) s = 0.f;                                      // -0 and +0 are one score
+    return ((uint64_t)score_key(s) << 32) | (uint32_t)~(uint32_t)j;
+}
+__device__ __forceinline__ float pair_key_score(uint64_t x) { return key_score((uint32_t)(x >> 32)); }
+__device__ __forceinline__ int32_t pair_key_index(uint64_t x) { return (int32_t)~(uint32_t)x; }
+
+// ---- the accumulator layout of v_mfma_f32_32x32x2_f32 ----
+// Wave (wm, wn) of gemm_mainloop<float, 2> holds the 64 x 64 quadrant (wm * 64, wn * 64) of the tile as acc[mt][nt][r]: 2 x 2
+// blocks of 32 x 32, and inside a block lane (g = lane >> 5, c = lane & 31) holds in register r the value of row
+// (r & 3) + 8 * (r >> 2) + 4 * g, column c.  Row and column below are relative to the quadrant.  A lane's 64 values are thus its
+// first one's place, (4 * g, c), plus the compile-time offsets acc_row(mt, r, 0) and acc_col(nt, 0).
+__device__ __forceinline__ int acc_row(int mt, int r, int g) { return mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g; }
+__device__ __forceinline__ int acc_col(int nt, int c) { return nt * 32 + c; }
+
+// the accumulators as a [128][128] fp32 tile in LDS (over the dead staging ring: the caller's barriers frame it)
+__device__ __forceinline__ void acc_to_tile(const f32x16 (&acc)[2][2], float* tile, int wm, int wn, int g, int c) {
+    float* first = tile + (wm * 64 + 4 * g) * BN + wn * 64 + c;  // the lane's first value
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) first[acc_row(mt, r, 0) * BN + acc_col(nt, 0)] = acc[mt][nt][r];
+}
+
+// ---- tile enumerations ----
+// tile (qt, ct), ct <= qt, of the lower triangle: t = qt (qt + 1) / 2 + ct
+__device__ __forceinline__ void tri_tile(long long t, int& qt, int& ct) {
+    long long q = (long long)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while (q * (q + 1) / 2 > t) --q;
+    while ((q + 1) * (q + 2) / 2 <= t) ++q;
+    qt = (int)q; ct = (int)(t - q * (q + 1) / 2);
+}
+
+// first position of the ascending list X[0, n) whose item is >= v
+__device__ __forceinline__ int lower_bound_i32(const int32_t* X, int n, int v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int m = (lo + hi) >> 1;
+        if (X[m] < v) lo = m + 1; else hi = m;
+    }
+    return lo;
+}
+
+// Candidate windows: row i admits only the columns win_lo[i] <= j < win_hi[i].  The 128 (lo, hi) pairs of query tile qt, clamped
+// to [0, Nc], go to LDS (wlo / whi; an empty window and the rows >= Nq become (0, 0)); un[0..1] receives the union of the
+// non-empty ones, and [ct0, ct1) the share of workgroup `split` of `splits` in the union's corpus tiles (empty without a union).
+__device__ __forceinline__ void window_prologue(const int32_t* win_lo, const int32_t* win_hi, int Nq, int Nc, int qt, int split, int splits,
+                                                int* wlo, int* whi, int* un, int& ct0, int& ct1) {
+    const int tid = threadIdx.x;
+    if (tid == 0) { un[0] = INT32_MAX; un[1] = 0; }
+    __syncthreads();
+    if (tid < 128) {
+        const int gi = qt * BM + tid;
+        int lo = 0, hi = 0;
+        if (gi < Nq) { lo = min(max(win_lo[gi], 0), Nc); hi = min(max(win_hi[gi], 0), Nc); }
+        if (lo >= hi) lo = hi = 0;                              // does not widen the union
+        else { atomicMin(&un[0], lo); atomicMax(&un[1], hi); }
+        wlo[tid] = lo; whi[tid] = hi;
+    }
+    __syncthreads();
+    const int t0 = un[1] > 0 ? un[0] / BN : 0, nt = un[1] > 0 ? (un[1] + BN - 1) / BN - t0 : 0;
+    ct0 = t0 + (int)((int64_t)nt * split / splits); ct1 = t0 + (int)((int64_t)nt * (split + 1) / splits);
+}
+
+// ---- host ----
+static inline uint64_t al256(uint64_t b) { return (b + 255) / 256 * 256; }
+
+// the two operand images every *_workspace starts with
+static inline uint64_t sweep_images_bytes(int Nq, int Nc, int D) {
+    const uint64_t Dp = pad128(D);
+    return al256(pad128(Nq) * Dp * 4) + al256(pad128(Nc) * Dp * 4);
+}
+
+// corpus slices per query tile: `slots` workgroups in flight, at most one slice per corpus tile and at most `cap`
+static inline int sweep_splits(int Nq, int Nc, int slots, int cap) {
+    const int64_t qt = pad128(Nq) / BM, ct = pad128(Nc) / BN;
+    int64_t s = slots / qt;
+    if (s > ct) s = ct;
+    if (s > cap) s = cap;
+    return s < 1 ? 1 : (int)s;
+}
+
+struct SweepOperands {
+    float *Qi, *Ci;               // normalised, zero-padded images [Nqp x Dp], [Ncp x Dp] (Ci == Qi when the corpus is Q)
+    int64_t Nqp, Ncp, Dp;
+    GemmParams g;                 // one K segment: A = Qi, Bt = Ci
+    char* rest;                   // the workspace behind the images
+};
+
+// The prologue of every entry point: the argument checks they share (messages prefixed with `who`; `need` is the entry's
+// *_workspace), the images carved from the workspace and filled by row_normalize_kernel, and the K loop's parameters.
+static inline int sweep_prepare(const char* who, const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                                int32_t norm, int32_t metric, void* workspace, uint64_t workspace_bytes, uint64_t need, hipStream_t st,
+                                SweepOperands& o) {
+    DAE_CHECK_ARG(C ? (Nc > 0 && ldc >= D) : Nc == Nq, "%s: bad corpus (C == NULL means the corpus is Q: pass Nc == Nq)", who);
+    DAE_CHECK_ARG(norm >= 0 && norm <= 3, "%s: norm must be 0 (none), 1 (l1), 2 (l2) or 3 (max)", who);
+    DAE_CHECK_ARG(metric == 0 || metric == 1, "%s: metric must be 0 (cosine) or 1 (linear kernel)", who);
+    o.Nqp = pad128(Nq); o.Ncp = pad128(Nc); o.Dp = pad128(D);
+    DAE_CHECK_ARG(o.Nqp * o.Dp * 4 < (1ll << 32) && o.Ncp * o.Dp * 4 < (1ll << 32), "%s: an operand image exceeds 4 GiB", who);
+    DAE_CHECK_ARG(workspace_bytes >= need, "%s: workspace too small (%llu < %llu bytes)", who, (unsigned long long)workspace_bytes,
+                  (unsigned long long)need);
+    DAE_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "%s: workspace must be 256-byte aligned", who);
+    char* w = (char*)workspace;
+    o.Qi = (float*)w;           w += al256(o.Nqp * o.Dp * 4);
+    o.Ci = C ? (float*)w : o.Qi;  w += al256(o.Ncp * o.Dp * 4);
+    o.rest = w;
+    const int cosine = metric == 0 ? 1 : 0;
+    if (int rc = launch_row_normalize(Q, ldq, Nq, D, norm, cosine, o.Qi, o.Dp, (int)o.Dp, (int)o.Nqp, st)) return rc;
+    if (C)
+        if (int rc = launch_row_normalize(C, ldc, Nc, D, norm, cosine, o.Ci, o.Dp, (int)o.Dp, (int)o.Ncp, st)) return rc;
+    memset(&o.g, 0, sizeof(o.g));
+    o.g.seg[0].A = (const char*)o.Qi; o.g.seg[0].Bt = (const char*)o.Ci;
+    o.g.seg[0].lda_b = o.g.seg[0].ldb_b = o.Dp * 4;
+    o.g.seg[0].ktiles = o.g.ktiles_total = (int)(o.Dp * 4 / BKB);
+    o.g.nseg = 1; o.g.splits = 1; o.g.out_scale = 1.f;
+    return 0;
+}
+
+// launches kernel K (GEMM_THREADS threads, `lds` bytes of dynamic LDS, one parameter block) through DAE_LAUNCH; the first launch
+// of every instantiation raises the kernel's dynamic-LDS limit to `lds_max`
+template <auto K, typename P>
+static inline int sweep_launch(int64_t grid, int lds_max, int lds, hipStream_t st, const P& p) {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    DAE_CHECK_HIP(attr);
+    DAE_LAUNCH(K, dim3((unsigned)grid), dim3(GEMM_THREADS), lds, st, p);
+    DAE_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // namespace dae

@@ -5,8 +5,7 @@
 // called six times per run by main_autoencoder.py:307-317 on the 8000 x 500 embeddings and the 8000 x 10000 BoW / TF-IDF
 // matrices.  Rows are normalised once into a zero-padded fp32 image, the product is the exact-fp32 MFMA GEMM of
 // dae_gemm.hip (both operands = the same K-contiguous image), the diagonal is cleared in place.
-#include "dae_common.h"
-#include "dae_kernels.h"
+#include "dae_score_sweep.h"      // score_key / key_score, al256
 
 namespace dae {
 
@@ -98,7 +97,7 @@ extern "C" int dae_pairwise_similarity(const float* X, int64_t ldx, int32_t N, i
 // Replaces the numeric part of helpers.visualize_pairwise_similarity (helpers.py:79-135): pairs (i, j), j < i, whose two labels
 // are both >= 0 are "related" when the labels are equal and "unrelated" otherwise; the reference hands the two score lists
 // to sklearn's roc_curve / auc (on Python lists of 3.2e7 elements) and draws a box plot of them.  Here:
-//   1. one pass over the strict lower triangle splits the scores into two key arrays (order-preserving uint32 keys);
+//   1. one pass over the strict lower triangle splits the scores into two key arrays (score_key of dae_score_sweep.h);
 //   2. rocPRIM device radix sort of each array (library sort, like hipBLASLt for a plain GEMM);
 //   3. AUROC = P(related > unrelated) + 0.5 P(equal): every related key is located in the sorted unrelated keys by two
 //      binary searches, (lower + upper) summed in 64-bit integers -- exact, tie-aware, order-independent;
@@ -110,14 +109,6 @@ extern "C" int dae_pairwise_similarity(const float* X, int64_t ldx, int32_t N, i
 #include <vector>
 
 namespace dae {
-
-__device__ __forceinline__ uint32_t score_key(float f) {      // monotone: a < b  <=>  key(a) < key(b); -0 < +0 adjacent
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_score(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 // one workgroup per row i: columns j < i.  Appends with one atomic per wave and class (ballot-aggregated).
 __global__ __launch_bounds__(256) void split_pairs_kernel(const float* __restrict__ S, int64_t lds, const int32_t* __restrict__ labels,
@@ -196,7 +187,6 @@ static size_t sort_temp_bytes(size_t n) {
     (void)rocprim::radix_sort_keys(nullptr, bytes, p, p, n, 0, 32, (hipStream_t)0);
     return bytes;
 }
-static inline uint64_t al256(uint64_t b) { return (b + 255) / 256 * 256; }
 
 }  // namespace dae
 

@@ -31,7 +31,7 @@
 // a row whose window misses the current tile is passed over, and the two compares join ok0 / ok1, so a column outside the
 // window never reaches the ballot, the exclusion search or the merge.  A workgroup with an empty slice writes part_n = 0.
 // topk_tiles_kernel<*, false> is the kernel as it was.
-#include "dae_gemm_tile.h"
+#include "dae_score_sweep.h"
 
 namespace dae {
 
@@ -41,13 +41,6 @@ constexpr int TOPK_MAX_SPLITS = 32;        // bounds phase B's LDS (32 lists x 1
 constexpr int TOPK_TILE_BYTES = BM * BN * 4;
 constexpr int TOPK_LDS = TOPK_TILE_BYTES + 128 * 8 + 128 * 4 + 4 * 2 * TOPK_MAX * 8;
 constexpr int TOPK_WIN_LDS = TOPK_LDS + 2 * 128 * 4 + 16;   // + the query tile's windows and their union
-
-__device__ __forceinline__ uint64_t topk_key(float s, int j) {
-    if (s == 0.f) s = 0.f;                                      // -0 and +0 are one score
-    const uint32_t u = __float_as_uint(s);
-    const uint32_t h = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((uint64_t)h << 32) | (uint32_t)~(uint32_t)j;
-}
 
 // number of keys of the descending list L[0, n) above x
 __device__ __forceinline__ int keys_above(const uint64_t* L, int n, uint64_t x) {
@@ -72,11 +65,7 @@ struct TopkParams {
 
 // is j in the ascending list X[0, n)?
 __device__ __forceinline__ bool excl_has(const int32_t* X, int n, int j) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int m = (lo + hi) >> 1;
-        if (X[m] < j) lo = m + 1; else hi = m;
-    }
+    const int lo = lower_bound_i32(X, n, j);
     return lo < n && X[lo] == j;
 }
 
@@ -95,35 +84,14 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams 
     if (tid < 128) { th[tid] = 0; len[tid] = 0; }
     int* wlo = reinterpret_cast<int*>(lds + TOPK_LDS);          // the query tile's windows (WIN only; behind the merge scratch)
     int* whi = wlo + 128;
-    if constexpr (WIN) {
-        int* un = whi + 128;                                    // union of the non-empty windows: [un[0], un[1])
-        if (tid == 0) { un[0] = INT32_MAX; un[1] = 0; }
-        __syncthreads();
-        if (tid < 128) {
-            const int gi = qt * BM + tid;
-            int lo = 0, hi = 0;
-            if (gi < p.Nq) { lo = min(max(p.win_lo[gi], 0), p.Nc); hi = min(max(p.win_hi[gi], 0), p.Nc); }
-            if (lo >= hi) lo = hi = 0;                          // empty (and the rows >= Nq): does not widen the union
-            else { atomicMin(&un[0], lo); atomicMax(&un[1], hi); }
-            wlo[tid] = lo; whi[tid] = hi;
-        }
-        __syncthreads();
-        const int t0 = un[1] > 0 ? un[0] / BN : 0, nt = un[1] > 0 ? (un[1] + BN - 1) / BN - t0 : 0;
-        ct0 = t0 + (int)((int64_t)nt * split / p.splits); ct1 = t0 + (int)((int64_t)nt * (split + 1) / p.splits);
-    }
+    if constexpr (WIN) window_prologue(p.win_lo, p.win_hi, p.Nq, p.Nc, qt, split, p.splits, wlo, whi, whi + 128, ct0, ct1);
     const int wm = wave >> 1, wn = wave & 1, g = lane >> 5, c = lane & 31;
     const uint64_t below = (1ull << lane) - 1ull;
     for (int ct = ct0; ct < ct1; ++ct) {
         f32x16 acc[2][2];
         gemm_mainloop<float, 2>(p.g, qt, ct, 0, p.g.ktiles_total, lds, acc);
         __syncthreads();                                        // every wave is done with the staging ring
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    tile[(wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g) * BN + wn * 64 + nt * 32 + c] = acc[mt][nt][r];
+        acc_to_tile(acc, tile, wm, wn, g, c);
         __syncthreads();
         const int j0 = ct * BN + lane, j1 = j0 + 64;
         for (int rr = 0; rr < 32; ++rr) {
@@ -137,7 +105,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams 
             const uint64_t t = th[row];
             const bool ok0 = j0 < p.Nc && !(p.exclude_self && j0 == gi) && (!WIN || (j0 >= wl && j0 < wh)),
                        ok1 = j1 < p.Nc && !(p.exclude_self && j1 == gi) && (!WIN || (j1 >= wl && j1 < wh));
-            const uint64_t c0 = ok0 ? topk_key(tile[row * BN + lane], j0) : 0, c1 = ok1 ? topk_key(tile[row * BN + 64 + lane], j1) : 0;
+            const uint64_t c0 = ok0 ? pair_key(tile[row * BN + lane], j0) : 0, c1 = ok1 ? pair_key(tile[row * BN + 64 + lane], j1) : 0;
             bool in0 = c0 > t, in1 = c1 > t;
             uint64_t b0 = __ballot(in0), b1 = __ballot(in1);
             if ((b0 | b1) == 0) continue;
@@ -217,22 +185,14 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* __restr
         for (int t = 0; t < splits; ++t)
             if (t != s) rank += keys_above(keys + off[t], off[t + 1] - off[t], x);
         if (rank < k) {
-            const uint32_t h = (uint32_t)(x >> 32);
-            oi[rank] = (int32_t)~(uint32_t)x;
-            os[rank] = __uint_as_float((h & 0x80000000u) ? (h & 0x7fffffffu) : ~h);
+            oi[rank] = pair_key_index(x);
+            os[rank] = pair_key_score(x);
         }
     }
     for (int r = total + tid; r < k; r += 256) { oi[r] = -1; os[r] = -__builtin_inff(); }
 }
 
-static int topk_splits(int Nq, int Nc) {
-    const int64_t qt = pad128(Nq) / BM, ct = pad128(Nc) / BN;
-    int64_t s = TOPK_SLOTS / qt;
-    if (s > ct) s = ct;
-    if (s > TOPK_MAX_SPLITS) s = TOPK_MAX_SPLITS;
-    return s < 1 ? 1 : (int)s;
-}
-static inline uint64_t al256(uint64_t b) { return (b + 255) / 256 * 256; }
+static int topk_splits(int Nq, int Nc) { return sweep_splits(Nq, Nc, TOPK_SLOTS, TOPK_MAX_SPLITS); }
 
 }  // namespace dae
 
@@ -240,8 +200,8 @@ using namespace dae;
 
 extern "C" uint64_t dae_topk_similarity_workspace(int32_t Nq, int32_t Nc, int32_t D, int32_t k) {
     if (Nq <= 0 || Nc <= 0 || D <= 0 || k <= 0) return 0;
-    const uint64_t Nqp = pad128(Nq), Ncp = pad128(Nc), Dp = pad128(D), s = topk_splits(Nq, Nc);
-    return al256(Nqp * Dp * 4) + al256(Ncp * Dp * 4) + al256(s * Nqp * (uint64_t)k * 8) + al256(s * Nqp * 4);
+    const uint64_t Nqp = pad128(Nq), s = topk_splits(Nq, Nc);
+    return sweep_images_bytes(Nq, Nc, D) + al256(s * Nqp * (uint64_t)k * 8) + al256(s * Nqp * 4);
 }
 
 extern "C" uint64_t dae_topk_similarity_ex_workspace(int32_t Nq, int32_t Nc, int32_t D, int32_t k) {
@@ -261,64 +221,30 @@ extern "C" int dae_topk_similarity_win(const float* Q, int64_t ldq, int32_t Nq, 
     DAE_CHECK_ARG((win_lo == nullptr) == (win_hi == nullptr),
                   "topk_similarity: win_lo and win_hi go together (exactly one of them is NULL)");
     DAE_CHECK_ARG(Q && idx && score && workspace && Nq > 0 && D > 0 && ldq >= D, "topk_similarity: bad input");
-    DAE_CHECK_ARG(C ? (Nc > 0 && ldc >= D) : Nc == Nq, "topk_similarity: bad corpus (C == NULL means the corpus is Q: pass Nc == Nq)");
-    DAE_CHECK_ARG(norm >= 0 && norm <= 3, "topk_similarity: norm must be 0 (none), 1 (l1), 2 (l2) or 3 (max)");
-    DAE_CHECK_ARG(metric == 0 || metric == 1, "topk_similarity: metric must be 0 (cosine) or 1 (linear kernel)");
     DAE_CHECK_ARG(k >= 1 && k <= TOPK_MAX, "topk_similarity: k must be in 1..%d (got %d)", TOPK_MAX, k);
     DAE_CHECK_ARG(!exclude_self || !C, "topk_similarity: exclude_self needs C == NULL (the corpus is Q itself)");
     DAE_CHECK_ARG(ldk >= k, "topk_similarity: ldk (%lld) must be >= k (%d)", (long long)ldk, k);
-    const int64_t Nqp = pad128(Nq), Ncp = pad128(Nc), Dp = pad128(D);
-    DAE_CHECK_ARG(Nqp * Dp * 4 < (1ll << 32) && Ncp * Dp * 4 < (1ll << 32), "topk_similarity: an operand image exceeds 4 GiB");
-    DAE_CHECK_ARG(workspace_bytes >= dae_topk_similarity_workspace(Nq, Nc, D, k),
-                  "topk_similarity: workspace too small (%llu < %llu bytes)", (unsigned long long)workspace_bytes,
-                  (unsigned long long)dae_topk_similarity_workspace(Nq, Nc, D, k));
-    DAE_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "topk_similarity: workspace must be 256-byte aligned");
     hipStream_t st = (hipStream_t)stream;
+    SweepOperands o;
+    if (int rc = sweep_prepare("topk_similarity", Q, ldq, Nq, C, ldc, Nc, D, norm, metric, workspace, workspace_bytes,
+                               dae_topk_similarity_workspace(Nq, Nc, D, k), st, o))
+        return rc;
     const int splits = topk_splits(Nq, Nc);
-    char* w = (char*)workspace;
-    float* Qi = (float*)w;           w += al256(Nqp * Dp * 4);
-    float* Ci = C ? (float*)w : Qi;  w += al256(Ncp * Dp * 4);
-    uint64_t* part = (uint64_t*)w;   w += al256((uint64_t)splits * Nqp * k * 8);
-    int* part_n = (int*)w;
-    const int cosine = metric == 0 ? 1 : 0;
-    if (int rc = launch_row_normalize(Q, ldq, Nq, D, norm, cosine, Qi, Dp, (int)Dp, (int)Nqp, st)) return rc;
-    if (C)
-        if (int rc = launch_row_normalize(C, ldc, Nc, D, norm, cosine, Ci, Dp, (int)Dp, (int)Ncp, st)) return rc;
     TopkParams p;
     memset(&p, 0, sizeof(p));
-    p.g.seg[0].A = (const char*)Qi; p.g.seg[0].Bt = (const char*)Ci;
-    p.g.seg[0].lda_b = p.g.seg[0].ldb_b = Dp * 4;
-    p.g.seg[0].ktiles = p.g.ktiles_total = (int)(Dp * 4 / BKB);
-    p.g.nseg = 1; p.g.splits = 1; p.g.out_scale = 1.f;
-    p.Nq = Nq; p.Nc = Nc; p.Nqp = (int)Nqp; p.k = k; p.exclude_self = exclude_self ? 1 : 0; p.splits = splits;
-    p.ctiles = (int)(Ncp / BN); p.part = part; p.part_n = part_n;
+    p.g = o.g;
+    p.Nq = Nq; p.Nc = Nc; p.Nqp = (int)o.Nqp; p.k = k; p.exclude_self = exclude_self ? 1 : 0; p.splits = splits;
+    p.ctiles = (int)(o.Ncp / BN);
+    p.part = (uint64_t*)o.rest; p.part_n = (int*)(o.rest + al256((uint64_t)splits * o.Nqp * k * 8));
     p.excl_indptr = excl_indptr; p.excl_items = excl_items; p.win_lo = win_lo; p.win_hi = win_hi;
-    if (win_lo) {
-        static const hipError_t attr_w = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_tiles_kernel<false, true>),
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, TOPK_WIN_LDS);
-        DAE_CHECK_HIP(attr_w);
-        static const hipError_t attr_xw = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_tiles_kernel<true, true>),
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize, TOPK_WIN_LDS);
-        DAE_CHECK_HIP(attr_xw);
-        if (excl_indptr)
-            DAE_LAUNCH((topk_tiles_kernel<true, true>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), TOPK_WIN_LDS, st, p);
-        else
-            DAE_LAUNCH((topk_tiles_kernel<false, true>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), TOPK_WIN_LDS, st, p);
-        DAE_CHECK_LAUNCH();
-        DAE_LAUNCH(topk_merge_kernel, dim3(Nq), dim3(256), 0, st, part, part_n, (int)Nqp, splits, k, idx, score, ldk);
-        DAE_CHECK_LAUNCH();
-        return 0;
-    }
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_tiles_kernel<false, false>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, TOPK_LDS);
-    DAE_CHECK_HIP(attr);
-    static const hipError_t attr_x = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_tiles_kernel<true, false>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, TOPK_LDS);
-    DAE_CHECK_HIP(attr_x);
-    if (excl_indptr) DAE_LAUNCH((topk_tiles_kernel<true, false>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), TOPK_LDS, st, p);
-    else DAE_LAUNCH((topk_tiles_kernel<false, false>), dim3((unsigned)(Nqp / BM) * splits), dim3(GEMM_THREADS), TOPK_LDS, st, p);
-    DAE_CHECK_LAUNCH();
-    DAE_LAUNCH(topk_merge_kernel, dim3(Nq), dim3(256), 0, st, part, part_n, (int)Nqp, splits, k, idx, score, ldk);
+    const int64_t grid = o.Nqp / BM * splits;
+    int rc;
+    if (win_lo) rc = excl_indptr ? sweep_launch<topk_tiles_kernel<true, true>>(grid, TOPK_WIN_LDS, TOPK_WIN_LDS, st, p)
+                                 : sweep_launch<topk_tiles_kernel<false, true>>(grid, TOPK_WIN_LDS, TOPK_WIN_LDS, st, p);
+    else rc = excl_indptr ? sweep_launch<topk_tiles_kernel<true, false>>(grid, TOPK_LDS, TOPK_LDS, st, p)
+                          : sweep_launch<topk_tiles_kernel<false, false>>(grid, TOPK_LDS, TOPK_LDS, st, p);
+    if (rc) return rc;
+    DAE_LAUNCH(topk_merge_kernel, dim3(Nq), dim3(256), 0, st, p.part, p.part_n, p.Nqp, splits, k, idx, score, ldk);
     DAE_CHECK_LAUNCH();
     return 0;
 }

@@ -187,6 +187,41 @@ def _device_matrix(torch, data, dev):
     return X.contiguous()
 
 
+def _sweep_inputs(in_df, candidates, norm, metric, device):
+    """What ``most_similar``, ``target_ranks``, ``similar_pairs`` and ``label_similarity_stats`` start with: ``norm`` / ``metric``
+    checked, the library, the device, and the two operands as device matrices (``Cm`` None: the corpus is ``in_df`` itself).
+    Returns ``(lib, dev, Q, Cm, Nq, Nc, D)``."""
+    import torch
+    assert metric in ["cosine", "linear kernel"]                      # helpers.py:34
+    if norm not in _NORMS:
+        raise ValueError(f"'{norm}' is not a supported norm")         # sklearn.preprocessing.normalize's message
+    lib = L.load()
+    dev = torch.device("cuda" if device is None else device)
+    Q = _device_matrix(torch, in_df, dev)
+    Cm = None if candidates is None else _device_matrix(torch, candidates, dev)
+    Nq, D = int(Q.shape[0]), int(Q.shape[1])
+    if Cm is not None and int(Cm.shape[1]) != D:
+        raise ValueError(f"candidates have {int(Cm.shape[1])} columns, in_df has {D}")
+    return lib, dev, Q, Cm, Nq, Nq if Cm is None else int(Cm.shape[0]), D
+
+
+def _workspace(dev, nbytes):
+    """A 256-byte aligned device workspace of ``nbytes`` as ``(c_void_p, tensor)``; the tensor keeps it alive."""
+    import ctypes
+    import torch
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    return ctypes.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256), ws
+
+
+def _upload_exclusions(xp, xi, dev):
+    """The exclusion CSR of ``normalize_exclusions`` on the device (``(None, None)`` without one).  The library tells "no lists" from
+    "empty lists" by the pointers, so an empty item array is still uploaded as one element: never a NULL pointer."""
+    import torch
+    if xp is None:
+        return None, None
+    return torch.from_numpy(xp).to(dev), torch.from_numpy(xi if xi.size else np.zeros(1, dtype=np.int32)).to(dev)
+
+
 def _csr_lists(lists, what="histories"):
     """``(indptr int64 [n + 1], items int64 [nnz])`` of a list of index sequences, or of an ``(indptr, items)`` pair -- a *tuple* of
     two arrays; a list is always taken as one sequence per row."""
@@ -321,68 +356,38 @@ def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candi
     the union of the windows of 128 neighbouring rows, so with ``candidates`` the rows are handed over in the stable order of
     ``(lo, hi)`` and the result is put back in the caller's order; the order is total, so the result does not depend on it."""
     import torch
-    assert metric in ["cosine", "linear kernel"]                      # helpers.py:34
-    if norm not in _NORMS:
-        raise ValueError(f"'{norm}' is not a supported norm")         # sklearn.preprocessing.normalize's message
     if exclude_self is None:
         exclude_self = candidates is None
     elif exclude_self and candidates is not None:
         raise ValueError("exclude_self=True needs candidates=None (the self pair exists only when the corpus is in_df itself)")
     if window is not None:
         window = normalize_window(window, _n_rows(in_df), _n_rows(in_df if candidates is None else candidates))
-    lib = L.load()
-    dev = torch.device("cuda" if device is None else device)
-    Q = _device_matrix(torch, in_df, dev)
-    Cm = None if candidates is None else _device_matrix(torch, candidates, dev)
-    Nq, D = int(Q.shape[0]), int(Q.shape[1])
-    if Cm is not None and int(Cm.shape[1]) != D:
-        raise ValueError(f"candidates have {int(Cm.shape[1])} columns, in_df has {D}")
-    Nc = Nq if Cm is None else int(Cm.shape[0])
+    lib, dev, Q, Cm, Nq, Nc, D = _sweep_inputs(in_df, candidates, norm, metric, device)
     k = int(k)
     idx = torch.empty((Nq, max(k, 1)), dtype=torch.int32, device=dev)
     score = torch.empty((Nq, max(k, 1)), dtype=torch.float32, device=dev)
     ws_bytes = int(lib.dae_topk_similarity_workspace(Nq, Nc, D, k))
-    ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
-    import ctypes
+    ws_p, ws = _workspace(dev, ws_bytes)
+    xp = xi = perm = perm_d = lo_d = hi_d = None
+    if exclude is not None:
+        xp, xi = normalize_exclusions(exclude, Nq, Nc)
     if window is not None:
         wlo, whi = window
         perm = None if Cm is None else _window_order(wlo, whi)        # the corpus is Q itself: its rows stay where they are
-        xp_d = xi_d = None
-        if exclude is not None:
-            xp, xi = normalize_exclusions(exclude, Nq, Nc)
-            if perm is not None:
-                xp, xi = _permute_csr(xp, xi, perm)
-            xp_d = torch.from_numpy(xp).to(dev)
-            xi_d = torch.from_numpy(xi if xi.size else np.zeros(1, dtype=np.int32)).to(dev)      # never a NULL pointer
-        perm_d = None
         if perm is not None:
             perm_d = torch.from_numpy(perm).to(dev)
             Q, wlo, whi = Q[perm_d].contiguous(), wlo[perm], whi[perm]
+            if xp is not None:
+                xp, xi = _permute_csr(xp, xi, perm)
         lo_d, hi_d = torch.from_numpy(np.ascontiguousarray(wlo)).to(dev), torch.from_numpy(np.ascontiguousarray(whi)).to(dev)
-        if Nq > 0:
-            with torch.cuda.device(dev):
-                L.call("dae_topk_similarity_win", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
-                       _NORMS[norm], _METRICS[metric], k, 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(lo_d), L.ptr(hi_d),
-                       L.ptr(idx), L.ptr(score), idx.stride(0), ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
-        if perm_d is not None:
-            idx, score = torch.empty_like(idx).index_copy_(0, perm_d, idx), torch.empty_like(score).index_copy_(0, perm_d, score)
-        idx = idx.long()
-        if return_tensor:
-            return idx, score
-        return idx.cpu().numpy(), score.cpu().numpy()
-    with torch.cuda.device(dev):
-        if exclude is None:
-            L.call("dae_topk_similarity", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D, _NORMS[norm],
-                   _METRICS[metric], k, 1 if exclude_self else 0, L.ptr(idx), L.ptr(score), idx.stride(0),
-                   ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
-        else:
-            xp, xi = normalize_exclusions(exclude, Nq, Nc)
-            xp_d = torch.from_numpy(xp).to(dev)
-            xi_d = torch.from_numpy(xi if xi.size else np.zeros(1, dtype=np.int32)).to(dev)      # never a NULL pointer
-            L.call("dae_topk_similarity_ex", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
-                   _NORMS[norm], _METRICS[metric], k, 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(idx), L.ptr(score),
-                   idx.stride(0), ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
+    xp_d, xi_d = _upload_exclusions(xp, xi, dev)
+    if Nq > 0 or window is None:                                      # without rows only the windowed call is skipped
+        with torch.cuda.device(dev):
+            L.call("dae_topk_similarity_win", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
+                   _NORMS[norm], _METRICS[metric], k, 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(lo_d), L.ptr(hi_d),
+                   L.ptr(idx), L.ptr(score), idx.stride(0), ws_p, ws_bytes, L.current_stream())
+    if perm_d is not None:
+        idx, score = torch.empty_like(idx).index_copy_(0, perm_d, idx), torch.empty_like(score).index_copy_(0, perm_d, score)
     idx = idx.long()
     if return_tensor:
         return idx, score
@@ -475,9 +480,6 @@ def recommend(user_vectors, embeddings, k=10, seen=None, norm="", metric="linear
     ``'cosine'`` and ``norm`` are those of ``most_similar``, and so is ``window``: per user the range of articles that may be
     shown at all (``candidate_windows``: those published by the time of the click, and not too long before).  Returns
     ``(indices, scores)`` as ``most_similar`` does."""
-    if window is None:
-        return most_similar(user_vectors, k=k, norm=norm, metric=metric, candidates=embeddings, exclude=seen,
-                            return_tensor=return_tensor, device=device)
     return most_similar(user_vectors, k=k, norm=norm, metric=metric, candidates=embeddings, exclude=seen, window=window,
                         return_tensor=return_tensor, device=device)
 
@@ -505,6 +507,34 @@ def next_click_metrics(indices, targets):
             "ndcg": float(np.where(hit, 1.0 / np.log2(1.0 + rank), 0.0).mean()), "n": n}
 
 
+def _competitors(tgt, Nq, Nc, exclude_self, xp, xi, window):
+    """The host bookkeeping of ``target_ranks``: ``(n_cand int64 [Nq], barred bool [Nq])`` -- how many candidates compete in each
+    row, the target included, and which targets can never be returned.  ``tgt``: int64 targets (negative: none); ``xp, xi``: the
+    lists of ``normalize_exclusions`` or None; ``window``: the pair of ``normalize_window``, None meaning ``(0, Nc)`` for every row."""
+    tgt = np.asarray(tgt, dtype=np.int64)
+    me = np.arange(Nq, dtype=np.int64)
+    if window is None:
+        wlo, whi = np.zeros(Nq, dtype=np.int64), np.full(Nq, Nc, dtype=np.int64)
+    else:
+        wlo, whi = (np.asarray(w).astype(np.int64) for w in window)
+    n_cand = whi - wlo
+    barred = (tgt >= 0) & ~((tgt >= wlo) & (tgt < whi))              # outside its own window: never returned
+    self_in = (me >= wlo) & (me < whi) if exclude_self else np.zeros(Nq, dtype=bool)
+    if xp is not None:
+        rows = np.repeat(me, np.diff(xp))
+        it = xi.astype(np.int64)
+        is_t = it == tgt[rows]
+        barred[rows[is_t]] = True
+        inside = (it >= wlo[rows]) & (it < whi[rows])
+        n_cand -= np.bincount(rows[inside & ~is_t], minlength=Nq)
+        self_in &= np.bincount(rows[(it == rows) & ~is_t], minlength=Nq) == 0      # unless the list took the self column already
+    if exclude_self:
+        self_t = tgt == me
+        barred |= self_t
+        n_cand -= (self_in & ~self_t).astype(np.int64)                # the target is counted even there; the row is not ranked anyway
+    return n_cand, barred
+
+
 def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, candidates=None, *, exclude=None, window=None,
                  return_tensor=False, device=None):
     """The position of one target row of ``candidates`` (default: ``in_df`` itself) per row of ``in_df`` among ALL candidates, by
@@ -528,25 +558,14 @@ def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, ca
     outside its row's window can never be returned and gets ``rank`` 0 (its ``score`` is still the pair's score), and
     ``n_candidates`` is the window's size minus the row's exclusion items inside the window other than the target, minus the
     row itself when it is excluded and lies inside."""
-    import ctypes
     import torch
-    assert metric in ["cosine", "linear kernel"]                      # helpers.py:34
-    if norm not in _NORMS:
-        raise ValueError(f"'{norm}' is not a supported norm")         # sklearn.preprocessing.normalize's message
     if exclude_self is None:
         exclude_self = candidates is None
     elif exclude_self and candidates is not None:
         raise ValueError("exclude_self=True needs candidates=None (the self pair exists only when the corpus is in_df itself)")
     if window is not None:
         window = normalize_window(window, _n_rows(in_df), _n_rows(in_df if candidates is None else candidates))
-    lib = L.load()
-    dev = torch.device("cuda" if device is None else device)
-    Q = _device_matrix(torch, in_df, dev)
-    Cm = None if candidates is None else _device_matrix(torch, candidates, dev)
-    Nq, D = int(Q.shape[0]), int(Q.shape[1])
-    if Cm is not None and int(Cm.shape[1]) != D:
-        raise ValueError(f"candidates have {int(Cm.shape[1])} columns, in_df has {D}")
-    Nc = Nq if Cm is None else int(Cm.shape[0])
+    lib, dev, Q, Cm, Nq, Nc, D = _sweep_inputs(in_df, candidates, norm, metric, device)
     tgt = targets.detach().cpu().numpy() if isinstance(targets, torch.Tensor) else np.asarray(targets)
     tgt = tgt.ravel()
     if tgt.size and tgt.dtype.kind not in "iu":
@@ -556,59 +575,19 @@ def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, ca
         raise ValueError(f"{tgt.shape[0]} targets for {Nq} queries")
     if tgt.size and int(tgt.max()) >= Nc:
         raise ValueError(f"targets must be below {Nc} (got {int(tgt.max())})")
-    has = tgt >= 0
-    tgt32 = np.where(has, tgt, -1).astype(np.int32)
-    # what can never be returned, and how many compete (host code)
-    n_cand = np.full(Nq, Nc, dtype=np.int64)
-    barred = np.zeros(Nq, dtype=bool)
     xp = xi = None
-    if window is not None:
-        wlo, whi = (w.astype(np.int64) for w in window)
-        n_cand = whi - wlo
-        barred = has & ~((tgt >= wlo) & (tgt < whi))                   # outside its own window: never returned
-        me = np.arange(Nq, dtype=np.int64)
-        self_in = (me >= wlo) & (me < whi) if exclude_self else np.zeros(Nq, dtype=bool)
-        if exclude is not None:
-            xp, xi = normalize_exclusions(exclude, Nq, Nc)
-            rows = np.repeat(me, np.diff(xp))
-            it = xi.astype(np.int64)
-            is_t = it == tgt[rows]
-            barred[rows[is_t]] = True
-            inside = (it >= wlo[rows]) & (it < whi[rows])
-            n_cand -= np.bincount(rows[inside & ~is_t], minlength=Nq)
-            self_in &= np.bincount(rows[(it == rows) & ~is_t], minlength=Nq) == 0      # unless the list took the self column already
-        if exclude_self:
-            self_t = tgt == me
-            barred |= self_t
-            n_cand -= (self_in & ~self_t).astype(np.int64)             # the target is counted even there; the row is not ranked anyway
-    elif exclude is not None:
+    if exclude is not None:
         xp, xi = normalize_exclusions(exclude, Nq, Nc)
-        rows = np.repeat(np.arange(Nq, dtype=np.int64), np.diff(xp))
-        is_t = xi.astype(np.int64) == tgt[rows]
-        barred[rows[is_t]] = True
-        n_cand -= np.diff(xp) - np.bincount(rows[is_t], minlength=Nq)
-        if exclude_self:                                               # the self column, unless the list took it already
-            is_s = xi.astype(np.int64) == rows
-            n_cand -= 1 - np.bincount(rows[is_s & ~is_t], minlength=Nq)
-    elif exclude_self:
-        n_cand -= 1
-    if exclude_self and window is None:
-        self_t = tgt == np.arange(Nq)
-        barred |= self_t
-        n_cand[self_t] += 1                                            # the target is counted even there; the row is not ranked anyway
+    n_cand, barred = _competitors(tgt, Nq, Nc, exclude_self, xp, xi, window)
     rank = torch.empty(Nq, dtype=torch.int32, device=dev)
     score = torch.empty(Nq, dtype=torch.float32, device=dev)
     if Nq == 0:
         out = (rank.long(), score, torch.from_numpy(n_cand).to(dev))
         return out if return_tensor else tuple(t.cpu().numpy() for t in out)
     ws_bytes = int(lib.dae_rank_similarity_workspace(Nq, Nc, D))
-    ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
-    t_d = torch.from_numpy(tgt32).to(dev)
-    xp_d = xi_d = None
-    if xp is not None:
-        xp_d = torch.from_numpy(xp).to(dev)
-        xi_d = torch.from_numpy(xi if xi.size else np.zeros(1, dtype=np.int32)).to(dev)          # never a NULL pointer
+    ws_p, ws = _workspace(dev, ws_bytes)
+    t_d = torch.from_numpy(np.where(tgt >= 0, tgt, -1).astype(np.int32)).to(dev)
+    perm = perm_d = lo_d = hi_d = None
     if window is not None:
         wlo, whi = window
         perm = None if Cm is None else _window_order(wlo, whi)        # the corpus is Q itself: its rows stay where they are
@@ -616,21 +595,15 @@ def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, ca
             perm_d = torch.from_numpy(perm).to(dev)
             Q, wlo, whi, t_d = Q[perm_d].contiguous(), wlo[perm], whi[perm], t_d[perm_d].contiguous()
             if xp is not None:
-                pp, pi = _permute_csr(xp, xi, perm)
-                xp_d = torch.from_numpy(pp).to(dev)
-                xi_d = torch.from_numpy(pi if pi.size else np.zeros(1, dtype=np.int32)).to(dev)
+                xp, xi = _permute_csr(xp, xi, perm)
         lo_d, hi_d = torch.from_numpy(np.ascontiguousarray(wlo)).to(dev), torch.from_numpy(np.ascontiguousarray(whi)).to(dev)
-        with torch.cuda.device(dev):
-            L.call("dae_rank_similarity_win", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
-                   _NORMS[norm], _METRICS[metric], 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(lo_d), L.ptr(hi_d),
-                   L.ptr(t_d), L.ptr(rank), L.ptr(score), ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
-        if perm is not None:
-            rank, score = torch.empty_like(rank).index_copy_(0, perm_d, rank), torch.empty_like(score).index_copy_(0, perm_d, score)
-    else:
-        with torch.cuda.device(dev):
-            L.call("dae_rank_similarity", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D, _NORMS[norm],
-                   _METRICS[metric], 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(t_d), L.ptr(rank), L.ptr(score),
-                   ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
+    xp_d, xi_d = _upload_exclusions(xp, xi, dev)
+    with torch.cuda.device(dev):
+        L.call("dae_rank_similarity_win", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
+               _NORMS[norm], _METRICS[metric], 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(lo_d), L.ptr(hi_d),
+               L.ptr(t_d), L.ptr(rank), L.ptr(score), ws_p, ws_bytes, L.current_stream())
+    if perm_d is not None:
+        rank, score = torch.empty_like(rank).index_copy_(0, perm_d, rank), torch.empty_like(score).index_copy_(0, perm_d, score)
     rank = rank.long()
     if barred.any():
         rank[torch.from_numpy(barred).to(dev)] = 0
@@ -645,9 +618,6 @@ def recommend_ranks(user_vectors, embeddings, targets, seen=None, norm="", metri
     ``recommend`` -- ``target_ranks(user_vectors, targets, candidates=embeddings, exclude=seen)``.  Returns ``(rank, score,
     n_candidates)`` as ``target_ranks`` does; ``rank`` is 0 for a target the user has already seen, and, with ``window`` (as in
     ``recommend``), for one outside the user's window."""
-    if window is None:
-        return target_ranks(user_vectors, targets, norm=norm, metric=metric, candidates=embeddings, exclude=seen,
-                            return_tensor=return_tensor, device=device)
     return target_ranks(user_vectors, targets, norm=norm, metric=metric, candidates=embeddings, exclude=seen, window=window,
                         return_tensor=return_tensor, device=device)
 
@@ -801,20 +771,10 @@ def similar_pairs(in_df, threshold, norm="", metric="cosine", candidates=None, *
     tensors with ``return_tensor=True``."""
     import ctypes
     import torch
-    assert metric in ["cosine", "linear kernel"]                      # helpers.py:34
-    if norm not in _NORMS:
-        raise ValueError(f"'{norm}' is not a supported norm")         # sklearn.preprocessing.normalize's message
     threshold = float(threshold)
     if threshold != threshold:
         raise ValueError("threshold is NaN")
-    lib = L.load()
-    dev = torch.device("cuda" if device is None else device)
-    Q = _device_matrix(torch, in_df, dev)
-    Cm = None if candidates is None else _device_matrix(torch, candidates, dev)
-    Nq, D = int(Q.shape[0]), int(Q.shape[1])
-    if Cm is not None and int(Cm.shape[1]) != D:
-        raise ValueError(f"candidates have {int(Cm.shape[1])} columns, in_df has {D}")
-    Nc = Nq if Cm is None else int(Cm.shape[0])
+    lib, dev, Q, Cm, Nq, Nc, D = _sweep_inputs(in_df, candidates, norm, metric, device)
     capacity = max(65536, 8 * Nq)
     if max_pairs is not None:
         capacity = min(capacity, max(int(max_pairs), 0))
@@ -824,13 +784,11 @@ def similar_pairs(in_df, threshold, norm="", metric="cosine", candidates=None, *
         cols = torch.empty(capacity, dtype=torch.int32, device=dev)
         score = torch.empty(capacity, dtype=torch.float32, device=dev)
         ws_bytes = int(lib.dae_threshold_pairs_workspace(Nq, Nc, D, capacity))
-        ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
-        off = (-ws.data_ptr()) % 256
+        ws_p, ws = _workspace(dev, ws_bytes)
         with torch.cuda.device(dev):
             L.call("dae_threshold_pairs", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
                    _NORMS[norm], _METRICS[metric], threshold, L.ptr(rows) if capacity else None, L.ptr(cols) if capacity else None,
-                   L.ptr(score) if capacity else None, capacity, ctypes.byref(count), ctypes.c_void_p(ws.data_ptr() + off),
-                   ws_bytes, L.current_stream())
+                   L.ptr(score) if capacity else None, capacity, ctypes.byref(count), ws_p, ws_bytes, L.current_stream())
         del ws
         n = int(count.value)
         if max_pairs is not None and n > int(max_pairs):
@@ -1056,9 +1014,6 @@ def label_similarity_stats(in_df, labels, norm="", metric="cosine", candidates=N
     import ctypes
     import json
     import torch
-    assert metric in ["cosine", "linear kernel"]                      # helpers.py:34
-    if norm not in _NORMS:
-        raise ValueError(f"'{norm}' is not a supported norm")         # sklearn.preprocessing.normalize's message
     lib = L.load()
     bins = int(bins)
     if not 2 <= bins <= int(lib.dae_pair_hist_max_bins()):
@@ -1071,18 +1026,11 @@ def label_similarity_stats(in_df, labels, norm="", metric="cosine", candidates=N
         lo, hi = float(score_range[0]), float(score_range[1])
         if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
             raise ValueError("score_range must be finite with lo < hi")
-    dev = torch.device("cuda" if device is None else device)
-    Q = _device_matrix(torch, in_df, dev)
-    Cm = None if candidates is None else _device_matrix(torch, candidates, dev)
-    Nq, D = int(Q.shape[0]), int(Q.shape[1])
-    if Cm is not None and int(Cm.shape[1]) != D:
-        raise ValueError(f"candidates have {int(Cm.shape[1])} columns, in_df has {D}")
-    Nc = Nq if Cm is None else int(Cm.shape[0])
+    lib, dev, Q, Cm, Nq, Nc, D = _sweep_inputs(in_df, candidates, norm, metric, device)
     lq = _label_ids(labels, Nq)
     lc = None if Cm is None else _label_ids(candidate_labels, Nc)
     ws_bytes = int(lib.dae_pair_hist_workspace(Nq, Nc, D, bins))
-    ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
+    ws_p, ws = _workspace(dev, ws_bytes)
 
     def run(lo, hi):
         hist = np.zeros((2, bins), dtype=np.uint64)
@@ -1091,7 +1039,7 @@ def label_similarity_stats(in_df, labels, norm="", metric="cosine", candidates=N
             L.call("dae_pair_hist", L.ptr(Q), Q.stride(0), Nq, lq.ctypes.data_as(ctypes.c_void_p), L.ptr(Cm),
                    0 if Cm is None else Cm.stride(0), Nc, None if lc is None else lc.ctypes.data_as(ctypes.c_void_p), D, _NORMS[norm],
                    _METRICS[metric], lo, hi, bins, hist.ctypes.data_as(ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p),
-                   ctypes.c_void_p(ws.data_ptr() + off), ws_bytes, L.current_stream())
+                   ws_p, ws_bytes, L.current_stream())
         v = [float(x) for x in out]
         have_r, have_u = v[0] > 0, v[1] > 0
         st = stats_from_histograms(hist[0], hist[1], (v[9], v[10]),
