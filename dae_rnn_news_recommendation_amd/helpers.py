@@ -22,7 +22,10 @@ library / a GPU this raises.
   ``next_click_metrics`` (host code) scores such a list against one held-out click per user.
 * ``target_ranks`` / ``recommend_ranks`` -- the position of the held-out article among ALL candidates, without the users x
   articles matrix (``dae_rank_similarity``); ``rank_metrics`` (host code) turns the ranks into AUC, mean / median rank,
-  untruncated MRR / nDCG and hit / MRR / nDCG at any number of cut-offs from one pass."""
+  untruncated MRR / nDCG and hit / MRR / nDCG at any number of cut-offs from one pass.
+* ``fit_user_model`` -- the trained form of that user model: the scaling vector alpha and the decay beta learned from click
+  logs by a pairwise ranking loss, whose value and gradients ``user_pair_loss`` gets from one walk of the histories
+  (``dae_user_pair_loss``); ``sample_negatives`` and ``decay_factor_derivatives`` (host code) prepare its inputs."""
 from __future__ import annotations
 
 import numpy as np
@@ -469,6 +472,242 @@ def user_states(histories, embeddings, beta=0.9, *, timestamps=None, time_unit=N
     if return_tensor:
         return U
     return U.cpu().numpy()
+
+
+def decay_factor_derivatives(indptr, timestamps, beta, time_unit=None):
+    """The derivative of ``decay_factors`` with respect to ``beta``: ``(dt / time_unit) * beta ** (dt / time_unit - 1)`` per event,
+    computed in float64 and rounded once to float32; 0 where ``dt = 0`` (simultaneous events do not decay, whatever beta) and at
+    a user's first event (whose factor is ignored).  Same arguments and errors as ``decay_factors``, but ``0 < beta <= 1``.
+    Host code."""
+    beta = float(beta)
+    if not 0.0 < beta <= 1.0:
+        raise ValueError(f"beta must be in (0, 1] (got {beta})")
+    decay_factors(indptr, timestamps, beta, time_unit)                     # the argument checks
+    indptr = np.asarray(indptr, dtype=np.int64)
+    t = np.asarray(timestamps, dtype=np.float64).ravel()
+    unit = 1.0 if time_unit is None else float(time_unit)
+    dt = np.zeros(t.size, dtype=np.float64)
+    dt[1:] = t[1:] - t[:-1]
+    dt[indptr[:-1][np.diff(indptr) > 0]] = 0.0
+    p = dt / unit
+    return np.where(p > 0.0, p * np.power(beta, p - 1.0), 0.0).astype(np.float32)
+
+
+def sample_negatives(indptr, items, n_articles, n_neg, seed, *, window=None):
+    """Sampled negatives for ``user_pair_loss``: ``int32 [events x n_neg]``, drawn uniformly over ``[0, n_articles)`` or, with
+    ``window = (lo, hi)`` (one entry per EVENT), over the event's ``[lo, hi)``.  -1 ("no pair") is written where the draw equals
+    the event's own article, where the window is empty, and at every user's first event, which has no state to predict from.
+    Articles the user has read are NOT removed: a uniform negative is seen with small probability, and the standard form of
+    this loss (BPR) samples that way.  Seeded (``numpy.random.default_rng(seed)``) and reproducible.  Host code."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    items = np.asarray(items).ravel()
+    nnz, n_neg, Na = int(items.size), int(n_neg), int(n_articles)
+    if indptr.size < 1 or int(indptr[-1]) != nnz:
+        raise ValueError(f"indptr ends at {int(indptr[-1]) if indptr.size else None} for {nnz} events")
+    if n_neg < 1:
+        raise ValueError(f"n_neg must be positive (got {n_neg})")
+    if Na < 1:
+        raise ValueError(f"n_articles must be positive (got {Na})")
+    if window is None:
+        lo, hi = np.zeros(nnz, dtype=np.int64), np.full(nnz, Na, dtype=np.int64)
+    else:
+        lo, hi = (w.astype(np.int64) for w in normalize_window(window, nnz, Na))
+    u = np.random.default_rng(seed).random((nnz, n_neg))
+    width = (hi - lo)[:, None]
+    neg = lo[:, None] + np.minimum((u * width).astype(np.int64), np.maximum(width - 1, 0))
+    bad = (neg == items.astype(np.int64)[:, None]) | (width <= 0)
+    bad[indptr[:-1][np.diff(indptr) > 0]] = True
+    return np.ascontiguousarray(np.where(bad, -1, neg).astype(np.int32))
+
+
+def _fit_embeddings(torch, embeddings, dev):
+    """The embeddings as a float32 device matrix; a CUDA float32 view with unit column stride is read in place."""
+    if (isinstance(embeddings, torch.Tensor) and embeddings.is_cuda and embeddings.dtype == torch.float32 and embeddings.dim() == 2
+            and embeddings.stride(1) == 1):
+        return embeddings
+    return _device_matrix(torch, embeddings, dev)
+
+
+def _pair_loss_call(torch, E, ip_d, it_d, ng_d, M, nnz, n_neg, alpha, beta, dc_d=None, dd_d=None, margins=False):
+    """One ``dae_user_pair_loss`` on device operands: ``ip_d`` int64 [M + 1] starting at 0, ``it_d`` int32 / ``ng_d`` int32
+    [nnz x n_neg] / ``dc_d`` / ``dd_d`` float32 views of the batch's events.  Returns the result dict of ``user_pair_loss``."""
+    dev = E.device
+    Na, H = int(E.shape[0]), int(E.shape[1])
+    lib = L.load()
+    al_d = torch.from_numpy(np.ascontiguousarray(np.asarray(alpha, dtype=np.float32))).to(dev)
+    out = torch.zeros(H + 3, dtype=torch.float64, device=dev)               # dalpha [H], loss, dbeta, n_pairs (int64 bits)
+    mg = torch.empty((max(nnz, 1), n_neg), dtype=torch.float32, device=dev) if margins else None
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.dae_user_pair_loss_workspace(M, H))
+        ws_ptr, ws = _workspace(dev, ws_bytes)
+        base = out.data_ptr()
+        import ctypes
+        L.call("dae_user_pair_loss", L.ptr(E), E.stride(0), Na, H, L.ptr(ip_d), L.ptr(it_d), M, nnz, float(beta), L.ptr(dc_d),
+               L.ptr(dd_d), L.ptr(al_d), L.ptr(ng_d), n_neg, ctypes.c_void_p(base + 8 * H), ctypes.c_void_p(base),
+               ctypes.c_void_p(base + 8 * (H + 1)), ctypes.c_void_p(base + 8 * (H + 2)), L.ptr(mg), ws_ptr, ws_bytes,
+               L.current_stream())
+        host = out.cpu().numpy()                                           # synchronises: the workspace may go after this
+    res = {"loss": float(host[H]), "dalpha": host[:H].copy(), "dbeta": float(host[H + 1]), "n_pairs": int(host[H + 2:].view(np.int64)[0])}
+    if margins:
+        res["margins"] = mg[:nnz].cpu().numpy()
+    return res
+
+
+def _check_negatives(negatives, nnz, Na):
+    neg = np.asarray(negatives)
+    if neg.ndim != 2 or neg.shape[0] != nnz or not 1 <= neg.shape[1] <= 16:
+        raise ValueError(f"negatives must be [{nnz} events x n_neg] with 1 <= n_neg <= 16 (got {tuple(neg.shape)})")
+    if neg.size and neg.dtype.kind not in "iu":
+        raise ValueError("negatives must hold integer article indices")
+    if neg.size and int(neg.max()) >= Na:
+        raise ValueError(f"negatives must be below {Na}, or negative for no pair (got {int(neg.max())})")
+    return np.ascontiguousarray(np.maximum(neg, -1).astype(np.int32))
+
+
+def _event_times(timestamps):
+    return _csr_lists(timestamps, "timestamps")[1] if isinstance(timestamps, (tuple, list)) else timestamps
+
+
+def user_pair_loss(histories, embeddings, alpha, beta, negatives, *, timestamps=None, time_unit=None, return_margins=False,
+                   device=None):
+    """Pairwise ranking loss of the trained decay model of "Embedding-based News Recommendation for Millions of Users" (KDD'17) and
+    its gradients, in one walk of every history (``dae_user_pair_loss``): with the state ``u = s / z`` of ``user_states`` BEFORE a
+    click, relevance ``R(u, a) = (alpha * u) . a`` and margin ``x = R(u, clicked) - R(u, negative)``, the loss is the sum of
+    ``softplus(-x)`` over all valid (click, negative) pairs.  Neither the [events x H] matrix of states nor its derivative is
+    stored.
+
+    ``histories``, ``embeddings``, ``beta``, ``timestamps``, ``time_unit``: as ``user_states`` (with timestamps the per-event factor
+    is ``beta ** (dt / time_unit)`` and its derivative ``decay_factor_derivatives``; at ``beta = 0`` the factors are 0 or 1 -- session
+    resets -- and ``dbeta`` comes out 0).  ``alpha``: one
+    weight per embedding dimension.  ``negatives``: integer ``[events x n_neg]``, ``n_neg`` in 1..16, e.g. from ``sample_negatives``;
+    a negative entry, the click itself and every entry of a user's first click are no pair.  An entry >= the number of articles
+    raises ``ValueError``.
+
+    Returns ``{'loss': float, 'dalpha': float64 [H], 'dbeta': float, 'n_pairs': int}`` -- sums over the valid pairs, NOT divided by
+    ``n_pairs`` -- and with ``return_margins=True`` also ``'margins'``: float32 ``[events x n_neg]``, 0 where there is no pair.
+    Bit-identical run to run; ``n_pairs`` and the margins do not depend on the order of the users."""
+    import torch
+    indptr, items = _csr_lists(histories)
+    if items.size and items.dtype.kind not in "iu":
+        raise ValueError("histories must hold integer article indices")
+    beta = float(beta)
+    if not 0.0 <= beta <= 1.0:
+        raise ValueError(f"beta must be in [0, 1] (got {beta})")
+    decay = ddecay = None
+    if timestamps is not None:
+        t = _event_times(timestamps)
+        decay = decay_factors(indptr, t, beta, time_unit)
+        ddecay = decay_factor_derivatives(indptr, t, beta, time_unit) if beta > 0.0 else None      # beta = 0: factors in {0, 1}, dbeta = 0
+    L.load()
+    dev = torch.device("cuda" if device is None else device)
+    E = _fit_embeddings(torch, embeddings, dev)
+    Na, H = int(E.shape[0]), int(E.shape[1])
+    alpha = np.asarray(alpha, dtype=np.float64).ravel()
+    if alpha.size != H:
+        raise ValueError(f"alpha has {alpha.size} entries for {H} embedding dimensions")
+    if not 1 <= H <= 1024:
+        raise ValueError(f"the embedding dimension must be in 1..1024 (got {H})")
+    if items.size and (int(items.min()) < 0 or int(items.max()) >= Na):
+        raise ValueError(f"history items must be in 0..{Na - 1} (got {int(items.min())}..{int(items.max())})")
+    M, nnz = int(indptr.size - 1), int(items.size)
+    neg = _check_negatives(negatives, nnz, Na)
+    n_neg = int(neg.shape[1])
+    one = lambda a, dt: torch.from_numpy(a if a.size else np.zeros(1, dtype=dt)).to(dev)      # never a NULL pointer
+    return _pair_loss_call(torch, E, torch.from_numpy(indptr).to(dev), one(items.astype(np.int32), np.int32),
+                           torch.from_numpy(neg if nnz else np.zeros((1, n_neg), dtype=np.int32)).to(dev), M, nnz, n_neg, alpha, beta,
+                           None if decay is None else one(decay, np.float32), None if ddecay is None else one(ddecay, np.float32),
+                           margins=return_margins)
+
+
+class UserModel:
+    """A fitted decay user model (``fit_user_model``): ``alpha`` float64 [H], ``beta``, ``time_unit`` and ``history``, the loss per
+    pair of every optimisation step."""
+
+    def __init__(self, alpha, beta, time_unit, history):
+        self.alpha, self.beta, self.time_unit, self.history = alpha, float(beta), time_unit, history
+
+    def states(self, histories, embeddings, timestamps=None, return_tensor=False, device=None):
+        """``alpha * user_states(histories, embeddings, beta, ...)``: with these vectors the plain inner product of ``recommend`` /
+        ``recommend_ranks`` is the fitted relevance ``(alpha * u) . a``."""
+        import torch
+        U = user_states(histories, embeddings, self.beta, timestamps=timestamps, time_unit=self.time_unit, return_tensor=True,
+                        device=device)
+        U = U * torch.from_numpy(self.alpha.astype(np.float32)).to(U.device)
+        return U if return_tensor else U.cpu().numpy()
+
+
+def fit_user_model(histories, embeddings, *, beta0=0.9, fit_beta=True, n_neg=4, epochs=50, batch_users=None, lr=0.05, seed=0,
+                   timestamps=None, time_unit=None, window=None, device=None):
+    """Fits the decay user model of the KDD'17 paper to click histories: the scaling vector ``alpha`` (start: ones) and, with
+    ``fit_beta``, the decay ``beta = sigmoid(theta)`` (start: ``beta0``), by Adam in float64 NumPy on the mean pairwise ranking
+    loss of ``user_pair_loss``, whose sums ``dae_user_pair_loss`` delivers in one walk of the histories per step.  The article
+    embeddings stay fixed.
+
+    Every epoch draws ``n_neg`` negatives per click (``sample_negatives(..., seed + epoch, window=window)``; ``window``: per-EVENT
+    candidate ranges) and takes one step per mini-batch of ``batch_users`` consecutive users (None: all users, one step per
+    epoch).  The gradient is divided by the batch's number of pairs; ``d/dtheta = dbeta * beta * (1 - beta)``.  A batch without a
+    valid pair takes no step and records NaN.  Deterministic per seed.
+
+    Returns a ``UserModel``: ``alpha``, ``beta``, ``time_unit``, ``history`` (loss per pair of every step, before the step) and
+    ``.states(histories, embeddings, timestamps=None)``, the vectors to hand to ``recommend`` / ``recommend_ranks``."""
+    import torch
+    indptr, items = _csr_lists(histories)
+    if items.size and items.dtype.kind not in "iu":
+        raise ValueError("histories must hold integer article indices")
+    beta = float(beta0)
+    if not 0.0 <= beta <= 1.0:
+        raise ValueError(f"beta0 must be in [0, 1] (got {beta0})")
+    if int(epochs) < 0 or not float(lr) > 0.0:
+        raise ValueError("epochs must not be negative and lr must be positive")
+    t = None if timestamps is None else np.asarray(_event_times(timestamps), dtype=np.float64).ravel()
+    L.load()
+    dev = torch.device("cuda" if device is None else device)
+    E = _fit_embeddings(torch, embeddings, dev)
+    Na, H = int(E.shape[0]), int(E.shape[1])
+    if not 1 <= H <= 1024:
+        raise ValueError(f"the embedding dimension must be in 1..1024 (got {H})")
+    if items.size and (int(items.min()) < 0 or int(items.max()) >= Na):
+        raise ValueError(f"history items must be in 0..{Na - 1} (got {int(items.min())}..{int(items.max())})")
+    M, nnz = int(indptr.size - 1), int(items.size)
+    step_users = M if batch_users is None else int(batch_users)
+    if batch_users is not None and step_users < 1:
+        raise ValueError(f"batch_users must be positive (got {batch_users})")
+    if fit_beta:
+        beta = min(max(beta, 1e-6), 1.0 - 1e-6)                             # theta is finite
+    x = np.concatenate([np.ones(H), [np.log(beta / (1.0 - beta)) if fit_beta else 0.0]])      # (alpha, theta)
+    m1, m2, step = np.zeros(H + 1), np.zeros(H + 1), 0
+    history = []
+    it_d = torch.from_numpy(items.astype(np.int32) if nnz else np.zeros(1, dtype=np.int32)).to(dev)
+    for epoch in range(int(epochs)):
+        neg = sample_negatives(indptr, items, Na, n_neg, int(seed) + epoch, window=window)
+        ng_d = torch.from_numpy(neg if nnz else np.zeros((1, int(n_neg)), dtype=np.int32)).to(dev)
+        for u0 in range(0, M, max(step_users, 1)):
+            u1 = min(u0 + step_users, M)
+            a, b = int(indptr[u0]), int(indptr[u1])
+            if fit_beta:
+                beta = 1.0 / (1.0 + np.exp(-x[H]))
+            beta32 = float(np.float32(beta))
+            dc_d = dd_d = None
+            if t is not None:
+                ip = indptr[u0:u1 + 1] - a
+                dc_d = torch.from_numpy(decay_factors(ip, t[a:b], beta32, time_unit) if b > a else np.zeros(1, np.float32)).to(dev)
+                if fit_beta:
+                    dd_d = torch.from_numpy(decay_factor_derivatives(ip, t[a:b], beta32, time_unit) if b > a
+                                            else np.zeros(1, np.float32)).to(dev)
+            r = _pair_loss_call(torch, E, torch.from_numpy(indptr[u0:u1 + 1] - a).to(dev), it_d[a:max(b, a + 1)],
+                                ng_d[a:max(b, a + 1)], u1 - u0, b - a, int(n_neg), x[:H], beta32, dc_d, dd_d)
+            if r["n_pairs"] == 0:
+                history.append(float("nan"))
+                continue
+            history.append(r["loss"] / r["n_pairs"])
+            grad = np.concatenate([r["dalpha"], [r["dbeta"] * beta * (1.0 - beta) if fit_beta else 0.0]]) / r["n_pairs"]
+            step += 1
+            m1 = 0.9 * m1 + 0.1 * grad
+            m2 = 0.999 * m2 + 0.001 * grad * grad
+            x = x - float(lr) * (m1 / (1.0 - 0.9 ** step)) / (np.sqrt(m2 / (1.0 - 0.999 ** step)) + 1e-8)
+    if fit_beta:
+        beta = 1.0 / (1.0 + np.exp(-x[H]))
+    return UserModel(x[:H].copy(), float(np.float32(beta)), time_unit, np.asarray(history, dtype=np.float64))
 
 
 def recommend(user_vectors, embeddings, k=10, seen=None, norm="", metric="linear kernel", *, window=None, return_tensor=False,

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define DAE_PAD 128
-#define DAE_ABI_VERSION 9   /* still 9 with dae_user_states and dae_topk_similarity_ex / dae_topk_similarity_ex_workspace: they are new symbols only (no struct or signature of version 9 changed), which a caller detects by symbol lookup (dlsym); 9: dae_pair_hist / dae_pair_hist_workspace / dae_pair_hist_max_bins (label AUROC and pair statistics from fused per-class score histograms); 8: dae_threshold_pairs / dae_threshold_pairs_workspace (near-duplicate search: all pairs over a threshold); 7: dae_topk_similarity / dae_topk_similarity_workspace (fused similarity + top-k retrieval); 6:dae_comm_* / dae_allreduce_grads / dae_dp_exchange / dae_dp_bands (the data-parallel collective in the C ABI, RCCL on the step's stream); 5: dae_storage_format (the fp16 build libdae_hip_f16.so), options x3_terms / op_scale_log2, DAE_WAIT_DW_CREATED = 100; 4: DAE_BF16X3 (split-bf16 mode), dae_gemm_nt_n; 3: dae_buffers.grad_lo, option encode_w32 (and one since removed); 2: dae_step.c_row_idx, plan options, phases 4/5, sharded apply */
+#define DAE_ABI_VERSION 9   /* still 9 with dae_user_pair_loss / dae_user_pair_loss_workspace, dae_user_states and dae_topk_similarity_ex / dae_topk_similarity_ex_workspace: they are new symbols only (no struct or signature of version 9 changed), which a caller detects by symbol lookup (dlsym); 9: dae_pair_hist / dae_pair_hist_workspace / dae_pair_hist_max_bins (label AUROC and pair statistics from fused per-class score histograms); 8: dae_threshold_pairs / dae_threshold_pairs_workspace (near-duplicate search: all pairs over a threshold); 7: dae_topk_similarity / dae_topk_similarity_workspace (fused similarity + top-k retrieval); 6:dae_comm_* / dae_allreduce_grads / dae_dp_exchange / dae_dp_bands (the data-parallel collective in the C ABI, RCCL on the step's stream); 5: dae_storage_format (the fp16 build libdae_hip_f16.so), options x3_terms / op_scale_log2, DAE_WAIT_DW_CREATED = 100; 4: DAE_BF16X3 (split-bf16 mode), dae_gemm_nt_n; 3: dae_buffers.grad_lo, option encode_w32 (and one since removed); 2: dae_step.c_row_idx, plan options, phases 4/5, sharded apply */
 
 enum { DAE_BF16 = 0, DAE_F32 = 1,
        DAE_BF16X3 = 2 /* dae_config.dtype only: bf16 storage and MFMA, but every stored operand of the three gradient GEMMs is kept as
@@ -524,6 +524,46 @@ int dae_rank_similarity_win(const float* Q, int64_t ldq, int32_t Nq, const float
 int dae_user_states(const float* E, int64_t lde, int32_t Na, int32_t H, const int64_t* indptr, const int32_t* items,
                     int64_t M, int64_t nnz, float beta, const float* decay, int32_t all_states, float* U, int64_t ldu,
                     void* stream);
+
+/* -------------------------------------------------------------------------------------------------
+ * Training step of the decay user model: pairwise ranking loss of the relevance R(u, a) = (alpha * u) . a over click
+ * histories and its gradients with respect to alpha (one weight per embedding dimension) and the decay beta, in one
+ * walk of every history (helpers.user_pair_loss, helpers.fit_user_model).  E is fixed: there is no backward pass, and
+ * neither the [events x H] matrix of states nor its derivative is stored.
+ *   E, lde, Na, H, indptr, items, M, nnz: as dae_user_states (device memory).  alpha float[H].
+ *   Per-event factor f_e and its derivative f'_e = d f_e / d beta:
+ *       decay == NULL: f_e = beta, f'_e = 1.   Otherwise decay float[nnz] and ddecay float[nnz]; ddecay == NULL means
+ *       f' = 0, and dbeta comes out 0 (ddecay without decay is an argument error).  A user's first event ignores both.
+ *   negatives int32[nnz x n_neg], 1 <= n_neg <= 16: the sampled negatives of every event (those of a user's first event
+ *   are not read as pairs).
+ *   Per user, in event order; the first event starts the chain:
+ *       first event:   s = E[item], z = 1, g = 0, zg = 0                               (no pair is scored)
+ *       event e after: for each j < n_neg with n = negatives[e, j], n >= 0 and n != items[e]        (a valid pair)
+ *                          D_h   = E[items[e], h] - E[n, h]
+ *                          x     = (sum_h alpha_h s_h D_h) / z                          one division per pair
+ *                          xb    = (sum_h alpha_h g_h D_h) / z - x (zg / z)             = sum_h alpha_h d(s_h / z)/dbeta D_h
+ *                          loss += softplus(-x);   c = -sigmoid(-x)
+ *                          dalpha_h += c s_h D_h / z;   dbeta += c xb;   n_pairs += 1
+ *                          margin[e, j] = x
+ *                      then, with the OLD s and z on the right-hand sides:
+ *                          g = f_e g + f'_e s;   zg = f_e zg + f'_e z;   s = f_e s + E[item];   z = f_e z + 1
+ *   s / z is the all_states row of the previous event of dae_user_states, and the s and z updates are its fused
+ *   multiply-adds.  The sums are NOT divided by n_pairs.
+ *   Outputs (device memory): *loss, dalpha[H], *dbeta as double, *n_pairs as int64, and, unless NULL, margin
+ *   float[nnz x n_neg] (0 where the pair is not valid).
+ *   fp32 arithmetic per pair; sums over more than 64 events and all sums across users in fp64; no atomics.  The
+ *   result is bit-identical run to run on one device; n_pairs and margin do not depend on the grid, on the order of the
+ *   users or on the alignment of E, and a user's margins do not change when other users are added or permuted.
+ *   Preconditions, not reported: items in [0, Na); negatives < Na (a negative one marks "no pair").  An index outside is
+ *   read as the nearest valid row.
+ *   H <= 1024.  workspace: dae_user_pair_loss_workspace(M, H) bytes, 256-byte aligned (one partial per wave).
+ *   lde >= H; a 16-byte aligned E with lde and H multiples of 4 is read with 16-byte loads.
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_user_pair_loss_workspace(int64_t M, int32_t H);
+int dae_user_pair_loss(const float* E, int64_t lde, int32_t Na, int32_t H, const int64_t* indptr, const int32_t* items,
+                       int64_t M, int64_t nnz, float beta, const float* decay, const float* ddecay, const float* alpha,
+                       const int32_t* negatives, int32_t n_neg, double* loss, double* dalpha, double* dbeta,
+                       int64_t* n_pairs, float* margin, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------------------------------------------------
  * Near-duplicate search: every pair (i, j) whose score reaches a threshold, without an N x N matrix (the range query

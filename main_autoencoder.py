@@ -15,6 +15,7 @@ examples:
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rank_metrics --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rank_metrics --max_age 48 --similarity False
+  python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --fit_user_model --similarity False
 """
 import argparse
 import os
@@ -107,6 +108,10 @@ def build_parser():
                         "saved to article_encoded_ranks.npz, and AUC, full MRR, mean / median rank and hit@{1, 10, 100} per model")
     p.add_argument("--session_decay", type=float, default=0.9,
                    help="decay of --recommend's user states: per click, or per unit of time when the sessions carry timestamps")
+    p.add_argument("--fit_user_model", default=False, **b,
+                   help="with --sessions S --recommend K: learn the user model's scaling vector alpha and its decay beta (start: "
+                        "--session_decay) from the same histories by a pairwise ranking loss (helpers.fit_user_model), print the metrics "
+                        "once more for the fitted model, and save alpha, beta and the loss history to user_model.npz")
     p.add_argument("--max_age", type=float, default=0.,
                    help="HOURS > 0 (only with --sessions synthetic --recommend K): the sessions get a timeline (articles in publication "
                         "order, clicks after publication), and every user is recommended, ranked and compared with the baseline only among "
@@ -130,6 +135,7 @@ def validate(a):
     assert a.recommend == 0 or a.sessions != '', "--recommend needs --sessions"
     assert 0. <= a.session_decay <= 1.
     assert not a.rank_metrics or a.recommend > 0, "--rank_metrics needs --recommend K"
+    assert not a.fit_user_model or (a.sessions != '' and a.recommend > 0), "--fit_user_model needs --sessions S --recommend K"
     assert a.max_age >= 0., "--max_age is a number of hours"
     assert a.max_age == 0. or (a.sessions == 'synthetic' and a.recommend > 0), "--max_age needs --sessions synthetic --recommend K"
     return a
@@ -314,6 +320,8 @@ def evaluate_recommend(a, trY, emb, data_dir):
     print('calculate recommend %d done' % K)
     if a.rank_metrics:
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir)
+    if a.fit_user_model:
+        evaluate_fitted_user_model(a, emb, hist, targets, n, data_dir, timestamps=None if t is None else t[keep])
     return idx, score, targets
 
 
@@ -351,7 +359,36 @@ def evaluate_recommend_window(a, trY, emb, data_dir):
     print('calculate recommend %d done' % K)
     if a.rank_metrics:
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir, window=window, max_age=a.max_age)
+    if a.fit_user_model:
+        evaluate_fitted_user_model(a, emb, hist, targets, n, data_dir, timestamps=t[keep], window=window)
     return idx, score, targets
+
+
+def evaluate_fitted_user_model(a, emb, hist, targets, n, data_dir, timestamps=None, window=None):
+    """--fit_user_model: the scaling vector alpha and the decay beta of the user model are learned from the histories the unfitted
+    states were built from -- the held-out click is not among them -- by helpers.fit_user_model (negatives drawn uniformly over
+    the corpus), saved as ``alpha`` / ``beta`` / ``history`` in user_model.npz, and the metrics of --recommend (and of
+    --rank_metrics) are printed once more for ``alpha * state``; with ``window`` inside the same candidate windows."""
+    from dae_rnn_news_recommendation_amd import helpers
+    K = a.recommend
+    print('fit user model')
+    seed = a.seed if a.seed >= 0 else 1234
+    model = helpers.fit_user_model(hist, emb, beta0=a.session_decay, seed=seed, timestamps=timestamps)
+    np.savez(data_dir + 'user_model.npz', alpha=model.alpha, beta=model.beta, history=model.history)
+    print('  %d steps, loss per pair %.4f -> %.4f, beta %.4f -> %.4f, alpha %.3f .. %.3f -> user_model.npz'
+          % (model.history.size, model.history[0] if model.history.size else float('nan'),
+             model.history[-1] if model.history.size else float('nan'), a.session_decay, model.beta, model.alpha.min(), model.alpha.max()))
+    states = model.states(hist, emb, timestamps=timestamps, return_tensor=True)
+    idx, _ = helpers.recommend(states, emb, k=K, seen=hist, window=window)
+    m = helpers.next_click_metrics(idx, targets)
+    print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'fitted user model', m['hit'], m['mrr'], m['ndcg']))
+    if a.rank_metrics:
+        rank, _, n_cand = helpers.recommend_ranks(states, emb, targets, seen=hist, window=window)
+        m = helpers.rank_metrics(rank, n_cand, targets, ks=(1, 10, 100))
+        print('  ranks %-20s AUC %.4f  MRR %.4f  mean rank %.1f  median rank %.1f  hit@1 %.4f  hit@10 %.4f  hit@100 %.4f'
+              % ('fitted user model', m['auc'], m['mrr'], m['mean_rank'], m['median_rank'], m['hit@1'], m['hit@10'], m['hit@100']))
+    print('fit user model done')
+    return model
 
 
 def evaluate_rank_metrics(states, emb, hist, targets, n, data_dir, window=None, max_age=0.):
