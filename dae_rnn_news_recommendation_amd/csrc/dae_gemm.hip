@@ -20,12 +20,9 @@
 // types; only the MFMA differs:  bf16 -> 1 x v_mfma_f32_32x32x16_bf16 per 16-byte fragment,
 // fp32 -> 4 x v_mfma_f32_32x32x2_f32 (exact fp32, the parity mode).
 // LDS: 2 stages x (A 16 KiB + B 16 KiB) = 64 KiB -> 2 workgroups per CU.
-// LDS image: row-major [128 rows][8 slots of 16 B], slot XOR-swizzled with (row>>1)&7 so that the
-// 16 lanes of every ds_read_b128 lane group (rows distinct mod 16) hit 16 distinct 16-byte slots of
-// the 256-byte bank row (conflict-free), and 8 consecutive lanes of the staging write cover one row.
-// Staging: GLDS=true uses global_load_lds_dwordx4 (LDS image is lane-linear, so the swizzle is applied
-// to the per-lane SOURCE address); GLDS=false stages through registers (global_load_dwordx4 ->
-// ds_write_b128) with the loads issued before the MFMA block and the LDS write after it.
+// LDS image of an operand tile and the accumulator layout: dae_gemm_tile.h defines both, every kernel here goes through its
+// primitives.  Staging: NST >= 2 fills the image by LDS-DMA (global_load_lds_dwordx4); NST = 0 stages through registers
+// (global_load_dwordx4 -> ds_write_b128) with the loads issued before the MFMA block and the LDS write after it.
 #include "dae_sym.h"
 #include "dae_kernels.h"
 #include "dae_label.h"
@@ -84,6 +81,23 @@ namespace dae {
 // ROLE only names the instantiation (encode / dh / dW / gram / generic) so that per-kernel profiles
 // (rocprofv3 --kernel-trace) can tell the step's GEMMs apart; the code is identical.
 enum { ROLE_GENERIC = 0, ROLE_ENCODE = 1, ROLE_DH = 2, ROLE_DW = 3, ROLE_GRAM = 4 };
+// the 64 x 64 quadrant of MFMA wave `wave` (2 x 2 waves) of tile (tm, tn), straight from the accumulator layout: dword stores, two 128-byte
+// runs per instruction
+template <bool SCALED>
+__device__ __forceinline__ void store_quadrant(const f32x16 (&acc)[2][2], float* Cs, int64_t ldc, int tm, int tn, int wave, int lane, float scale = 1.f) {
+    const int wm = wave >> 1, wn = wave & 1, g = lane >> 5, c = lane & 31;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                int row = tm * BM + wm * 64 + acc_row(mt, r, g);
+                int col = tn * BN + wn * 64 + acc_col(nt, c);
+                if constexpr (SCALED) Cs[(int64_t)row * ldc + col] = acc[mt][nt][r] * scale;
+                else Cs[(int64_t)row * ldc + col] = acc[mt][nt][r];
+            }
+}
 template <typename T, int NST, int ROLE>
 __global__ __launch_bounds__(GEMM_THREADS, wg_per_cu_for(NST)) void gemm_nt_f32out(GemmParams p, float* __restrict__ C, int64_t ldc,
                                                                                    int64_t slab_stride) {
@@ -92,19 +106,7 @@ __global__ __launch_bounds__(GEMM_THREADS, wg_per_cu_for(NST)) void gemm_nt_f32o
     if (!block_to_tile(p, tm, tn, split, kt0, kt1)) return;
     f32x16 acc[2][2];
     gemm_mainloop<T, NST>(p, tm, tn, kt0, kt1, lds, acc);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave >> 1, wn = wave & 1, g = lane >> 5, c = lane & 31;
-    float* Cs = C + (int64_t)split * slab_stride;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int row = tm * BM + wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                int col = tn * BN + wn * 64 + nt * 32 + c;
-                Cs[(int64_t)row * ldc + col] = acc[mt][nt][r] * p.out_scale;
-            }
+    store_quadrant<true>(acc, C + (int64_t)split * slab_stride, ldc, tm, tn, threadIdx.x >> 6, threadIdx.x & 63, p.out_scale);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -166,7 +168,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_dw_opt(GemmParams p, Opt
                 for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        Gt[(mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g) * 128 + wn * 64 + nt * 32 + c] = acc[mt][nt][r];
+                        Gt[acc_row(mt, r, g) * 128 + wn * 64 + acc_col(nt, c)] = acc[mt][nt][r];
         }
         __syncthreads();
 #pragma unroll
@@ -238,6 +240,53 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_dw_opt(GemmParams p, Opt
 constexpr int PC_THREADS = 512;
 constexpr int PC_NST = 4;                            // 128 KiB of the CU's 160 KiB LDS
 
+// producer side of BARRIER_i: `ahead` = stages younger than i+1 already requested (PIECES LDS-DMA pieces per wave each) stay in flight
+template <int PIECES> __device__ __forceinline__ void wait_vm_ahead(int ahead) {
+    if (ahead >= 2) wait_vm<2 * PIECES>();
+    else if (ahead == 1) wait_vm<PIECES>();
+    else wait_vm<0>();
+}
+
+// Consumer side, MFMA wave (wm, wn) of 2 x 2 over nk > 0 K tiles of the NST-slot ring: the rolling fragment schedule of gemm_mainloop (R0 = k chunks
+// 0,1 and R1 = 2,3 of the next tile are read under the MFMAs of this one) without a DMA instruction; one s_barrier before the loop (stage 0 landed:
+// the producers waited for it) and one per K tile.
+template <typename T, int NST>
+__device__ __forceinline__ void pc_consume(char* lds, int wm, int wn, int lane, int nk, f32x16 (&acc)[2][2]) {
+    const uint32_t lbase = lds_addr(lds);
+    const uint32_t offa = frag_row(wm * 64, lane), offb = TILE_BYTES + frag_row(wn * 64, lane);
+    uint32_t so[4];
+    frag_slots(lane, so);
+    i32x4 fa[4][2], fb[4][2];
+    auto read_kk = [&](int kk, uint32_t slotbase) __attribute__((always_inline)) {
+        read_frags(fa[kk], slotbase + offa + so[kk]);
+        read_frags(fb[kk], slotbase + offb + so[kk]);
+    };
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    read_kk(0, lbase); read_kk(1, lbase); read_kk(2, lbase); read_kk(3, lbase);
+    __builtin_amdgcn_sched_barrier(0);
+    int cur = 0;
+    for (int i = 0; i < nk; ++i) {
+        const int nxt = cur + 1 == NST ? 0 : cur + 1;
+        wait_lgkm<8>();                                                   // R0 of tile i
+        __builtin_amdgcn_sched_barrier(0);
+        mma_block<T>(fa[0], fb[0], acc); mma_block<T>(fa[1], fb[1], acc);
+        __builtin_amdgcn_sched_barrier(0);
+        wait_lgkm<0>();                                                   // R1 landed; every LDS read of tile i is done
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const uint32_t nb = lbase + nxt * STAGE_BYTES;
+        read_kk(0, nb); read_kk(1, nb);                                   // stale (never consumed) after the last tile
+        __builtin_amdgcn_sched_barrier(0);
+        mma_block<T>(fa[2], fb[2], acc); mma_block<T>(fa[3], fb[3], acc);
+        __builtin_amdgcn_sched_barrier(0);
+        read_kk(2, nb); read_kk(3, nb);
+        __builtin_amdgcn_sched_barrier(0);
+        cur = nxt;
+    }
+    wait_lgkm<0>();
+}
+
 template <typename T, int NST, int ROLE>
 __global__ __launch_bounds__(PC_THREADS, 1) void gemm_nt_pc(GemmParams p, float* __restrict__ C, int64_t ldc, int64_t slab_stride,
                                                             LabelJob job, int label_block) {
@@ -263,14 +312,8 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_nt_pc(GemmParams p, float*
         auto seg_setup = [&](int kt) {
             int k;
             const int sg = seg_locate(p, kt, k, seg_end);
-            const uint32_t lda = (uint32_t)p.seg[sg].lda_b, ldb = (uint32_t)p.seg[sg].ldb_b;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = (i * 4 + wave) * 8 + (lane >> 3);
-                const uint32_t ss = (uint32_t)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
-                voA[i] = (uint32_t)(row0_m + row) * lda + ss;
-                voB[i] = (uint32_t)(row0_n + row) * ldb + ss;
-            }
+            dma_srcs<4>(voA, wave, lane, row0_m, (uint32_t)p.seg[sg].lda_b);
+            dma_srcs<4>(voB, wave, lane, row0_n, (uint32_t)p.seg[sg].ldb_b);
             gA = p.seg[sg].A + (int64_t)k * BKB;
             gB = p.seg[sg].Bt + (int64_t)k * BKB;
         };
@@ -278,11 +321,8 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_nt_pc(GemmParams p, float*
         auto dma_stage = [&](char* slot) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int piece = i * 4 + wave;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gA + voA[i]),
-                                                 (__attribute__((address_space(3))) void*)(slot + piece * 1024), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gB + voB[i]),
-                                                 (__attribute__((address_space(3))) void*)(slot + TILE_BYTES + piece * 1024), 16, 0, 0);
+                glds_piece<4>(i, wave, gA + voA[i], slot);
+                glds_piece<4>(i, wave, gB + voB[i], slot + TILE_BYTES);
             }
             ++kt_dma;
             if (kt_dma == seg_end && kt_dma < p.ktiles_total) seg_setup(kt_dma);
@@ -295,10 +335,7 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_nt_pc(GemmParams p, float*
         __builtin_amdgcn_s_barrier();
         int cur = 0;
         for (int i = 0; i < nk; ++i) {
-            const int ahead = min(NST - 2, nk - 2 - i);                   // stages younger than i+1 already requested
-            if (ahead >= 2) wait_vm<16>();
-            else if (ahead == 1) wait_vm<8>();
-            else wait_vm<0>();
+            wait_vm_ahead<8>(min(NST - 2, nk - 2 - i));
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             if (i + NST < nk) dma_stage(lds + cur * STAGE_BYTES);
@@ -307,76 +344,14 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_nt_pc(GemmParams p, float*
         }
     } else {
     // ================= consumer =================
-    const int wave = wave8;
-    const int wm = wave >> 1, wn = wave & 1;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    if (nk > 0) {
-        const int r = lane & 31, g = lane >> 5;
-        const int swz = (r >> 1) & 7;
-        const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-        const uint32_t offa = (wm * 64 + r) * BKB, offb = TILE_BYTES + (wn * 64 + r) * BKB;
-        uint32_t so[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) so[kk] = (uint32_t)(((kk * 2 + g) ^ swz) << 4);
-        i32x4 fa[4][2], fb[4][2];
-#define DAE_READ_KK(KK, SLOTBASE)                                          \
-    fa[KK][0] = lds_read_b128((SLOTBASE) + offa + so[KK]);                 \
-    fa[KK][1] = lds_read_b128_off4096((SLOTBASE) + offa + so[KK]);         \
-    fb[KK][0] = lds_read_b128((SLOTBASE) + offb + so[KK]);                 \
-    fb[KK][1] = lds_read_b128_off4096((SLOTBASE) + offb + so[KK]);
-#define DAE_MMA4(KK)                                                       \
-    Mma<T>::run(fa[KK][0], fb[KK][0], acc[0][0]);                          \
-    Mma<T>::run(fa[KK][0], fb[KK][1], acc[0][1]);                          \
-    Mma<T>::run(fa[KK][1], fb[KK][0], acc[1][0]);                          \
-    Mma<T>::run(fa[KK][1], fb[KK][1], acc[1][1]);
-        __builtin_amdgcn_s_barrier();                                     // stage 0 landed (producers waited for it)
-        asm volatile("" ::: "memory");
-        DAE_READ_KK(0, lbase) DAE_READ_KK(1, lbase) DAE_READ_KK(2, lbase) DAE_READ_KK(3, lbase)
-        __builtin_amdgcn_sched_barrier(0);
-        int cur = 0;
-        for (int i = 0; i < nk; ++i) {
-            const int nxt = cur + 1 == NST ? 0 : cur + 1;
-            asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");            // R0 (kk 0,1) of tile i
-            __builtin_amdgcn_sched_barrier(0);
-            DAE_MMA4(0) DAE_MMA4(1)
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // R1 landed; every LDS read of tile i is done
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            const uint32_t nb = lbase + nxt * STAGE_BYTES;
-            DAE_READ_KK(0, nb) DAE_READ_KK(1, nb)                         // stale (never consumed) after the last tile
-            __builtin_amdgcn_sched_barrier(0);
-            DAE_MMA4(2) DAE_MMA4(3)
-            __builtin_amdgcn_sched_barrier(0);
-            DAE_READ_KK(2, nb) DAE_READ_KK(3, nb)
-            __builtin_amdgcn_sched_barrier(0);
-            cur = nxt;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#undef DAE_READ_KK
-#undef DAE_MMA4
-    }
+    zero_acc(acc);
+    if (nk > 0) pc_consume<T, NST>(lds, wave8 >> 1, wave8 & 1, lane, nk, acc);
     }
     // ---- epilogue, all 8 waves: the accumulators are parked in LDS (fp32 [128][128], 64 KiB of the dead ring; conflict-free from the accumulator
     //      layout) and leave as 16-byte pieces of 512-byte row runs, 8 per thread.  (Before: 64 dword stores per lane from the four MFMA waves alone,
     //      two 128-byte runs per instruction, the producer waves gone -- the slab store tail was a third of the Gram launch.)
     if (!p.epi_vec) {                                                     // A/B (dae_set_glds(-9)): the former epilogue
-        if (wave8 < 4) {
-            const int wm = wave8 >> 1, wn = wave8 & 1, g = lane >> 5, c = lane & 31;
-            float* Cd = C + (int64_t)split * slab_stride;
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        Cd[(int64_t)(tm * BM + wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g) * ldc + tn * BN + wn * 64 + nt * 32 + c] = acc[mt][nt][r] * p.out_scale;
-        }
+        if (wave8 < 4) store_quadrant<true>(acc, C + (int64_t)split * slab_stride, ldc, tm, tn, wave8, lane, p.out_scale);
         return;
     }
     __builtin_amdgcn_s_barrier();                                         // every wave is out of the K loop: the ring is dead (all LDS-DMA landed)
@@ -390,9 +365,9 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_nt_pc(GemmParams p, float*
             for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    Ct[(wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g) * BN + wn * 64 + nt * 32 + c] = acc[mt][nt][r] * p.out_scale;
+                    Ct[(wm * 64 + acc_row(mt, r, g)) * BN + wn * 64 + acc_col(nt, c)] = acc[mt][nt][r] * p.out_scale;
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
     __builtin_amdgcn_s_barrier();                                         // the tile is complete
     asm volatile("" ::: "memory");
     float* Cs = C + (int64_t)split * slab_stride + (int64_t)(tm * BM) * ldc + tn * BN;
@@ -553,17 +528,12 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
                     const int cch = (i * 4 + wave) * 64 + lane, kr = cch / 20, mc = cch % 20;
                     voA[i] = (uint32_t)kr * lda + (uint32_t)min(row0_m + mc * 8, Mrows - 8) * 2u;
                 } else {
-                const int row = (i * 4 + wave) * 8 + (lane >> 3);
-                const int grow = min(row0_m + row, Mrows - 1);
-                voA[i] = (uint32_t)grow * lda + (uint32_t)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
+                voA[i] = dma_src<4>(i, wave, lane, row0_m, lda, Mrows - 1);
                 }
             }
             a_adv = TRA ? (int64_t)64 * lda : (int64_t)BKB;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = (i * 4 + wave) * 8 + (lane >> 3);
-                voB[i] = (uint32_t)(row0_n + row) * ldb + (uint32_t)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
-            }
+            for (int i = 0; i < 4; ++i) voB[i] = dma_src<4>(i, wave, lane, row0_n, ldb);
             gA = p.seg[sg].A + (int64_t)k * a_adv;
             gB = p.seg[sg].Bt + (int64_t)k * BKB;
         };
@@ -573,19 +543,13 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
             if (true) { ++kt_dma; return; }                // probe: no operand stream (the consumers multiply whatever the ring holds)
 #endif
 #pragma unroll
-            for (int i = 0; i < 5; ++i)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gA + voA[i]),
-                                                 (__attribute__((address_space(3))) void*)(slot + (i * 4 + wave) * 1024), 16, 0, 0);
+            for (int i = 0; i < 5; ++i) glds_piece<4>(i, wave, gA + voA[i], slot);
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gB + voB[i]),
-                                                 (__attribute__((address_space(3))) void*)(slot + DW_A_BYTES + (i * 4 + wave) * 1024), 16, 0, 0);
+            for (int i = 0; i < 4; ++i) glds_piece<4>(i, wave, gB + voB[i], slot + DW_A_BYTES);
             if constexpr (PAIR) {
                 if (gB2) {                                                  // the segment's second B tile (same rows, same leading dimension)
 #pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gB2 + voB[i]),
-                                                         (__attribute__((address_space(3))) void*)(slot + DW_A_BYTES + TILE_BYTES + (i * 4 + wave) * 1024), 16, 0, 0);
+                    for (int i = 0; i < 4; ++i) glds_piece<4>(i, wave, gB2 + voB[i], slot + DW_A_BYTES + TILE_BYTES);
                 }
             }
             ++kt_dma;
@@ -597,12 +561,12 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
         for (int st = 0; st < NSTG; ++st)
             if (st < nk) dma_stage(lds + st * STG);
         wait_vm_n(ops(1) + ops(2) + (PAIR ? 0 : ops(3)));                   // stage 0 landed (older plain loads return first)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
         __builtin_amdgcn_s_barrier();
         int cur = 0;
         for (int i = 0; i < nk; ++i) {
             wait_vm_n(ops(i + 2) + (PAIR ? 0 : ops(i + 3)));                // stage i+1 landed; younger stages stay in flight
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lgkm<0>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             if (i + NSTG < nk) dma_stage(lds + cur * STG);
@@ -615,9 +579,11 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
         for (int m = 0; m < DW_MB; ++m)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
+        // (frag_row / frag_slot / tile_swz of dae_gemm_tile.h written out: through the helpers the TRA and PAIR instantiations take one VGPR more.
+        //  This block is NOT covered by tile_image_ok: it must be kept equal to the helpers by hand)
         const int r = lane & 31;
         const int swz = (r >> 1) & 7;
-        const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
+        const uint32_t lbase = lds_addr(lds);
         const uint32_t offa = r * BKB, offb = DW_A_BYTES + (wave * 32 + r) * BKB;
         uint32_t so[4];
 #pragma unroll
@@ -644,10 +610,10 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
         DAE_DW_TR(S, KK, SLOTBASE, 3) DAE_DW_TR(S, KK, SLOTBASE, 4)                    \
     } else {                                                                           \
     fa[S][0] = lds_read_b128((SLOTBASE) + offa + so[KK]);                              \
-    fa[S][1] = lds_read_b128_off4096((SLOTBASE) + offa + so[KK]);                      \
-    fa[S][2] = lds_read_b128((SLOTBASE) + offa + 8192 + so[KK]);                       \
-    fa[S][3] = lds_read_b128_off4096((SLOTBASE) + offa + 8192 + so[KK]);               \
-    fa[S][4] = lds_read_b128((SLOTBASE) + offa + 16384 + so[KK]);                      \
+    fa[S][1] = lds_read_b128<FRAG_BLOCK>((SLOTBASE) + offa + so[KK]);                  \
+    fa[S][2] = lds_read_b128((SLOTBASE) + offa + 2 * FRAG_BLOCK + so[KK]);             \
+    fa[S][3] = lds_read_b128<FRAG_BLOCK>((SLOTBASE) + offa + 2 * FRAG_BLOCK + so[KK]); \
+    fa[S][4] = lds_read_b128((SLOTBASE) + offa + 4 * FRAG_BLOCK + so[KK]);             \
     }
 #define DAE_DW_MMA(S)                                                                  \
     Mma<bf16_t>::run(fa[S][0], fb[S], acc[0]);                                         \
@@ -665,9 +631,9 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
         }                                                                              \
     }
 #define DAE_DW_WAIT_SET()                                                              \
-    if constexpr (PAIR) asm volatile("s_waitcnt lgkmcnt(7)" ::: "memory");             \
-    else if constexpr (TRA) asm volatile("s_waitcnt lgkmcnt(11)" ::: "memory");        \
-    else asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
+    if constexpr (PAIR) wait_lgkm<7>();                                                \
+    else if constexpr (TRA) wait_lgkm<11>();                                           \
+    else wait_lgkm<6>();
 #if defined(DAE_DW_PROBE) && (DAE_DW_PROBE & 32)           // probe: the consumers only take part in the barriers
 #undef DAE_DW_READ
 #undef DAE_DW_MMA
@@ -707,7 +673,7 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
             __builtin_amdgcn_sched_barrier(0);
             DAE_DW_MMA(0)
             __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // every LDS read of tile i is done
+            wait_lgkm<0>();                                                  // every LDS read of tile i is done
             __builtin_amdgcn_s_barrier();                                   // slot free for the producers; stage i+1 landed
             asm volatile("" ::: "memory");
             DAE_DW_READ(0, 0, nb, ob2_nxt)                                   // stale (never consumed) after the last tile
@@ -717,7 +683,7 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
             cur = nxt;
             if constexpr (PAIR) { pair_cur = pair_nxt; ob2_cur = ob2_nxt; }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
 #undef DAE_DW_READ
 #undef DAE_DW_TR
 #undef DAE_DW_MMA
@@ -738,9 +704,9 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
 #pragma unroll
         for (int m = 0; m < DW_MB; ++m)
 #pragma unroll
-            for (int r2 = 0; r2 < 16; ++r2) Gt[(m * 32 + (r2 & 3) + 8 * (r2 >> 2) + 4 * g) * 128 + lcol] = acc[m][r2];
+            for (int r2 = 0; r2 < 16; ++r2) Gt[acc_row(m, r2, g) * 128 + lcol] = acc[m][r2];
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
     __builtin_amdgcn_s_barrier();                                           // B2: the gradient tile is complete
     asm volatile("" ::: "memory");
     float pvk[X3 ? DW_EB : 1][4][4];                                        // X3: the updated weights stay in registers for the lo round below
@@ -827,7 +793,7 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
         }
     }
     if constexpr (!UPDATE) return;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
     __builtin_amdgcn_s_barrier();                                           // B3: the transposed tile is complete
     asm volatile("" ::: "memory");
 #ifdef DAE_DW_PROBE
@@ -843,7 +809,7 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
         }
     }
     if constexpr (X3) {                                                     // second round through the same staging tile: Wt_lo2 = bf16(W - bf16(W))^T
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
         __builtin_amdgcn_s_barrier();                                       // every piece of the hi tile has been read
         asm volatile("" ::: "memory");
 #pragma unroll
@@ -858,7 +824,7 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_dw_pc(GemmParams p, OptEpi
                 *reinterpret_cast<uint2*>(R1 + (c4 * 4 + j) * DW_P1 + rg * 8) = v;
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         bf16_t* Wtlo2 = reinterpret_cast<bf16_t*>(e.Wt_lo2);
@@ -884,18 +850,7 @@ __global__ __launch_bounds__(GEMM_THREADS, wg_per_cu_for(NST)) void gemm_nt_trac
     gemm_mainloop<T, NST, true>(p, tm, tn, kt0, kt1, lds, acc);
     const unsigned long long t1 = __builtin_amdgcn_s_memtime();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave >> 1, wn = wave & 1, g = lane >> 5, c = lane & 31;
-    float* Cs = C + (int64_t)split * slab_stride;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int row = tm * BM + wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                int col = tn * BN + wn * 64 + nt * 32 + c;
-                Cs[(int64_t)row * ldc + col] = acc[mt][nt][r];
-            }
+    store_quadrant<false>(acc, C + (int64_t)split * slab_stride, ldc, tm, tn, wave, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned long long t2 = __builtin_amdgcn_s_memtime();
     if (lane == 0) {
@@ -972,6 +927,50 @@ template <int ACT> __device__ __forceinline__ float act_bwd(float a) {
 // raw barriers per K tile.  With three workgroups per CU the DMA latency and the barriers of one workgroup hide behind the
 // MFMAs / epilogue VALU of the other two, so the loop itself stays simple; K = Hp is only 8 tiles deep.
 // Waves 2 x 2: wave (wm, wn) owns rows [64 wm, +64) x columns [32 wn, +32) = 2 MFMA 32x32 accumulators.
+// What the three schedules share: the accumulators start at zero, the wave's DMA pieces of a stage (4 of the A tile, 2 of the B tile) and its
+// fragment addresses; a stage is issued whole (ab) or as its B tile alone (b) and read as 8 + 4 or 4 fragments.
+struct N64Wave {
+    uint32_t voA[4], voB[2];
+    uint32_t lbase, offa, offb, so[4];
+    int wave, lane, row0_m, row0_n;
+    __device__ __forceinline__ N64Wave(int tm, int tn, char* lds, f32x16 (&acc)[2][1]) {
+        lane = threadIdx.x & 63;
+        wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        row0_m = tm * BM; row0_n = tn * 64;
+        zero_acc(acc);
+        lbase = lds_addr(lds);
+        offa = frag_row((wave >> 1) * 64, lane); offb = TILE_BYTES + frag_row((wave & 1) * 32, lane);
+        frag_slots(lane, so);
+    }
+    __device__ __forceinline__ void offsets(uint32_t lda, uint32_t ldb) {      // the operand panels' leading dimensions in bytes
+#pragma unroll
+        for (int i = 0; i < 4; ++i) voA[i] = (uint32_t)(row0_m + piece_row(i * 4 + wave, lane)) * lda + (uint32_t)(piece_slot(i * 4 + wave, lane) << 4);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) voB[i] = (uint32_t)(row0_n + piece_row(i * 4 + wave, lane)) * ldb + (uint32_t)(piece_slot(i * 4 + wave, lane) << 4);
+    }
+    __device__ __forceinline__ void dma_ab(char* slot, const char* gA, const char* gB) const {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) glds_piece<4>(i, wave, gA + voA[i], slot);
+        dma_b(slot, gB);
+    }
+    __device__ __forceinline__ void dma_b(char* slot, const char* gB) const {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) glds_piece<4>(i, wave, gB + voB[i], slot + TILE_BYTES);
+    }
+    __device__ __forceinline__ void read_ab(uint32_t sb, i32x4 (&fa)[4][2], i32x4 (&fb)[4][1]) const {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            read_frags(fa[kk], sb + offa + so[kk]);
+            read_frags(fb[kk], sb + offb + so[kk]);
+        }
+    }
+    __device__ __forceinline__ void read_b(uint32_t sb, i32x4 (&fb)[4][1]) const {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) read_frags(fb[kk], sb + offb + so[kk]);
+    }
+};
+
+// (mainloop_n64 keeps its set-up and groups written out: on N64Wave the compiler's own vmcnt / lgkmcnt waits of the binary-input kernels move.)
 template <typename T>
 __device__ __forceinline__ void mainloop_n64(const GemmParams& p, int tm, int tn, char* lds, f32x16 (&acc)[2][1]) {
     constexpr int BN_T = 64, STAGE = DecGeo<64>::STAGE;
@@ -1009,19 +1008,17 @@ __device__ __forceinline__ void mainloop_n64(const GemmParams& p, int tm, int tn
     auto dma_stage = [&](char* slot) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gA + voA[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + (i * 4 + wave) * 1024), 16, 0, 0);
+            glds16(gA + voA[i], slot + (i * 4 + wave) * 1024);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gB + voB[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + TILE_BYTES + (i * 4 + wave) * 1024), 16, 0, 0);
+            glds16(gB + voB[i], slot + TILE_BYTES + (i * 4 + wave) * 1024);
         ++kt_dma;
         if (kt_dma == seg_end) { if (kt_dma < nk) seg_setup(kt_dma); }
         else { gA += BKB; gB += BKB; }
     };
     const int r = lane & 31, g = lane >> 5;
     const int swz = (r >> 1) & 7;
-    const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
+    const uint32_t lbase = lds_addr(lds);
     const uint32_t offa = (wm * 64 + r) * BKB, offb = TILE_BYTES + (wn * 32 + r) * BKB;
     uint32_t so[4];
 #pragma unroll
@@ -1037,11 +1034,11 @@ __device__ __forceinline__ void mainloop_n64(const GemmParams& p, int tm, int tn
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
             fa[kk][0] = lds_read_b128(sb + offa + so[kk]);
-            fa[kk][1] = lds_read_b128_off4096(sb + offa + so[kk]);
+            fa[kk][1] = lds_read_b128<FRAG_BLOCK>(sb + offa + so[kk]);
             fb[kk] = lds_read_b128(sb + offb + so[kk]);
         }
 #define DAE_N64_GROUP(KK, CNT)                                   \
-    asm volatile("s_waitcnt lgkmcnt(" #CNT ")" ::: "memory");    \
+    wait_lgkm<CNT>();                                            \
     __builtin_amdgcn_sched_barrier(0);                           \
     Mma<T>::run(fa[KK][0], fb[KK], acc[0][0]);                   \
     Mma<T>::run(fa[KK][1], fb[KK], acc[1][0]);
@@ -1068,58 +1065,45 @@ constexpr int G64_NST = 8;
 constexpr int G64_TILE = 64 * BKB;                 // 8 KiB per operand per stage
 constexpr int G64_STAGE = 2 * G64_TILE;
 constexpr int G64_LDS = G64_NST * G64_STAGE;       // 128 KiB: one workgroup per CU
-__device__ __forceinline__ void wait_vm_4n(int n) {   // vmcnt(4 n): n younger stages of 4 LDS-DMA pieces each may stay in flight
-    switch (n) {
-        case 0: wait_vm<0>(); break;
-        case 1: wait_vm<4>(); break;
-        case 2: wait_vm<8>(); break;
-        case 3: wait_vm<12>(); break;
-        case 4: wait_vm<16>(); break;
-        case 5: wait_vm<20>(); break;
-        case 6: wait_vm<24>(); break;
-        default: wait_vm<28>(); break;
-    }
+// Tile of block b of a Gram kernel (XCD-banded: XCD b % 8 takes a contiguous run of tiles); false for the padding blocks.
+__device__ __forceinline__ bool gram64_tile(int tiles, int& tm, int& tn) {
+    const int b = blockIdx.x, per = (tiles * tiles + 7) >> 3;
+    const int t = (b & 7) * per + (b >> 3);
+    tm = t / tiles; tn = t % tiles;
+    return (b >> 3) < per && t < tiles * tiles;
 }
+// the wave's 32 x 32 block of D from the accumulator layout
+__device__ __forceinline__ void gram64_store(const f32x16& v, float* D, int64_t ldd, int tm, int tn, int wave, int lane) {
+    float* Dt = D + (int64_t)(tm * 64 + (wave >> 1) * 32) * ldd + tn * 64 + (wave & 1) * 32 + acc_col(0, lane & 31);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) Dt[(int64_t)acc_row(0, q, lane >> 5) * ldd] = v[q];
+}
+
 __global__ __launch_bounds__(GEMM_THREADS, 1) void gram64_kernel(const char* __restrict__ A, int64_t lda_b, const char* __restrict__ Bt, int64_t ldb_b,
                                                                  int nk, int tiles, float* __restrict__ D, int64_t ldd) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    const int b = blockIdx.x, per = (tiles * tiles + 7) >> 3;
-    const int t = (b & 7) * per + (b >> 3);
-    if ((b >> 3) >= per || t >= tiles * tiles) return;
-    const int tm = t / tiles, tn = t % tiles;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    // LDS-DMA: this wave's pieces {wave, wave + 4} of each operand tile (8 rows of 128 B per 1-KiB piece), swizzled source slot per lane
+    int tm, tn;
+    if (!gram64_tile(tiles, tm, tn)) return;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint32_t voA[2], voB[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = (i * 4 + wave) * 8 + (lane >> 3);
-        const uint32_t ss = (uint32_t)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
-        voA[i] = (uint32_t)(tm * 64 + row) * (uint32_t)lda_b + ss;
-        voB[i] = (uint32_t)(tn * 64 + row) * (uint32_t)ldb_b + ss;
-    }
+    dma_srcs<4>(voA, wave, lane, tm * 64, (uint32_t)lda_b);
+    dma_srcs<4>(voB, wave, lane, tn * 64, (uint32_t)ldb_b);
     const char *gA = A, *gB = Bt;
+    f32x16 acc[1][1];
+    zero_acc(acc);
+    const uint32_t offa = frag_row((wave >> 1) * 32, lane), offb = G64_TILE + frag_row((wave & 1) * 32, lane);
+    uint32_t so[4];
+    frag_slots(lane, so);
     auto dma_stage = [&](char* slot) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gA + voA[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + (i * 4 + wave) * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gB + voB[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + G64_TILE + (i * 4 + wave) * 1024), 16, 0, 0);
+            glds_piece<4>(i, wave, gA + voA[i], slot);
+            glds_piece<4>(i, wave, gB + voB[i], slot + G64_TILE);
         }
         gA += BKB; gB += BKB;
     };
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    const int r = lane & 31, g = lane >> 5;
-    const int swz = (r >> 1) & 7;
-    const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-    const uint32_t offa = (wm * 32 + r) * BKB, offb = G64_TILE + (wn * 32 + r) * BKB;
-    uint32_t so[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) so[kk] = (uint32_t)(((kk * 2 + g) ^ swz) << 4);
+    const uint32_t lbase = lds_addr(lds);
 #pragma unroll
     for (int st = 0; st < G64_NST; ++st)
         if (st < nk) dma_stage(lds + st * G64_STAGE);
@@ -1129,35 +1113,28 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void gram64_kernel(const char* __r
     int cur = 0, prev = G64_NST - 1;
     for (int i = 0; i < nk; ++i) {
         const int issued = i == 0 ? min(nk, G64_NST) : min(nk, i - 1 + G64_NST);      // stages requested so far
-        wait_vm_4n(issued - (i + 1));                      // everything up to stage i has landed (this wave's pieces)
+        wait_vm_stages<4, G64_NST - 1>(issued - (i + 1));  // everything up to stage i has landed (this wave's pieces)
         __builtin_amdgcn_s_barrier();                      // ... and every other wave's; slot `prev` is free
         asm volatile("" ::: "memory");
         const uint32_t sb = lbase + cur * G64_STAGE;
-        i32x4 fa[4], fb[4];
+        i32x4 fa[4][1], fb[4][1];
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            fa[kk] = lds_read_b128(sb + offa + so[kk]);
-            fb[kk] = lds_read_b128(sb + offb + so[kk]);
+            read_frags(fa[kk], sb + offa + so[kk]);
+            read_frags(fb[kk], sb + offb + so[kk]);
         }
         __builtin_amdgcn_sched_barrier(0);
         if (i >= 1 && i - 1 + G64_NST < nk) dma_stage(lds + prev * G64_STAGE);
         __builtin_amdgcn_sched_barrier(0);
-#define DAE_G64_STEP(KK, CNT)                                    \
-    asm volatile("s_waitcnt lgkmcnt(" #CNT ")" ::: "memory");    \
-    __builtin_amdgcn_sched_barrier(0);                           \
-    Mma<bf16_t>::run(fa[KK], fb[KK], acc);
-        DAE_G64_STEP(0, 6)
-        DAE_G64_STEP(1, 4)
-        DAE_G64_STEP(2, 2)
-        DAE_G64_STEP(3, 0)
-#undef DAE_G64_STEP
+        mma_group<bf16_t, 6>(fa[0], fb[0], acc);
+        mma_group<bf16_t, 4>(fa[1], fb[1], acc);
+        mma_group<bf16_t, 2>(fa[2], fb[2], acc);
+        mma_group<bf16_t, 0>(fa[3], fb[3], acc);
         __builtin_amdgcn_sched_barrier(0);
         prev = cur;
         cur = cur + 1 == G64_NST ? 0 : cur + 1;
     }
-    float* Dt = D + (int64_t)(tm * 64 + wm * 32) * ldd + tn * 64 + wn * 32 + r;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) Dt[(int64_t)((q & 3) + 8 * (q >> 2) + 4 * g) * ldd] = acc[q];
+    gram64_store(acc[0][0], D, ldd, tm, tn, wave, lane);
 }
 
 // The same tile with the THREE products of a K tile in ONE stage (round 6): a stage holds the hi and the lo image of both row panels for 64 columns of h
@@ -1167,94 +1144,63 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void gram64_kernel(const char* __r
 constexpr int G64F_NST = 4;
 constexpr int G64F_STAGE = 4 * G64_TILE;
 constexpr int G64F_LDS = G64F_NST * G64F_STAGE;
-__device__ __forceinline__ void wait_vm_8n(int n) {   // vmcnt(8 n): n younger stages of 8 LDS-DMA pieces each may stay in flight
-    switch (n) {
-        case 0: wait_vm<0>(); break;
-        case 1: wait_vm<8>(); break;
-        case 2: wait_vm<16>(); break;
-        default: wait_vm<24>(); break;
-    }
-}
 __global__ __launch_bounds__(GEMM_THREADS, 1) void gram64f_kernel(const char* __restrict__ Hhi, const char* __restrict__ Hlo, int64_t ld_b, int nk, int tiles,
                                                                   float* __restrict__ D, int64_t ldd) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    const int b = blockIdx.x, per = (tiles * tiles + 7) >> 3;
-    const int t = (b & 7) * per + (b >> 3);
-    if ((b >> 3) >= per || t >= tiles * tiles) return;
-    const int tm = t / tiles, tn = t % tiles;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    // LDS-DMA: this wave's pieces {wave, wave + 4} of each of the four operand tiles (8 rows of 128 B per 1-KiB piece), swizzled source slot per lane
-    uint32_t voA[2], voB[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = (i * 4 + wave) * 8 + (lane >> 3);
-        const uint32_t ss = (uint32_t)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
-        voA[i] = (uint32_t)(tm * 64 + row) * (uint32_t)ld_b + ss;
-        voB[i] = (uint32_t)(tn * 64 + row) * (uint32_t)ld_b + ss;
-    }
+    int tm, tn;
+    if (!gram64_tile(tiles, tm, tn)) return;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t voA[2], voB[2];                           // A / B: the row panels tm / tn of h, each as a hi and a lo image
+    dma_srcs<4>(voA, wave, lane, tm * 64, (uint32_t)ld_b);
+    dma_srcs<4>(voB, wave, lane, tn * 64, (uint32_t)ld_b);
     const char *gH = Hhi, *gL = Hlo;
+    f32x16 acch[1][2], accl;                           // hi.hi and hi.lo; lo.hi
+    zero_acc(acch);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) accl[r] = 0.f;
+    const uint32_t offa = frag_row((wave >> 1) * 32, lane), offb = 2 * G64_TILE + frag_row((wave & 1) * 32, lane);
+    uint32_t so[4];
+    frag_slots(lane, so);
     auto dma_stage = [&](char* slot) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int piece = (i * 4 + wave) * 1024;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gH + voA[i]), (__attribute__((address_space(3))) void*)(slot + piece), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gL + voA[i]), (__attribute__((address_space(3))) void*)(slot + G64_TILE + piece), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gH + voB[i]), (__attribute__((address_space(3))) void*)(slot + 2 * G64_TILE + piece), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gL + voB[i]), (__attribute__((address_space(3))) void*)(slot + 3 * G64_TILE + piece), 16, 0, 0);
+            glds_piece<4>(i, wave, gH + voA[i], slot); glds_piece<4>(i, wave, gL + voA[i], slot + G64_TILE);
+            glds_piece<4>(i, wave, gH + voB[i], slot + 2 * G64_TILE); glds_piece<4>(i, wave, gL + voB[i], slot + 3 * G64_TILE);
         }
         gH += BKB; gL += BKB;
     };
-    f32x16 acc0, acc1, acc2;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; acc2[r] = 0.f; }
-    const int r = lane & 31, g = lane >> 5;
-    const int swz = (r >> 1) & 7;
-    const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-    const uint32_t offa = (wm * 32 + r) * BKB, offb = 2 * G64_TILE + (wn * 32 + r) * BKB;
-    uint32_t so[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) so[kk] = (uint32_t)(((kk * 2 + g) ^ swz) << 4);
+    const uint32_t lbase = lds_addr(lds);
 #pragma unroll
     for (int st = 0; st < G64F_NST; ++st)
         if (st < nk) dma_stage(lds + st * G64F_STAGE);
-    int cur = 0, prev = G64F_NST - 1;
+    int cur = 0, prev = G64F_NST - 1;                  // the ring protocol of gram64_kernel
     for (int i = 0; i < nk; ++i) {
-        const int issued = i == 0 ? min(nk, G64F_NST) : min(nk, i - 1 + G64F_NST);     // stages requested so far
-        wait_vm_8n(issued - (i + 1));                      // everything up to stage i has landed (this wave's pieces)
-        __builtin_amdgcn_s_barrier();                      // ... and every other wave's; slot `prev` is free
+        const int issued = i == 0 ? min(nk, G64F_NST) : min(nk, i - 1 + G64F_NST);
+        wait_vm_stages<8, G64F_NST - 1>(issued - (i + 1));
+        __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         const uint32_t sb = lbase + cur * G64F_STAGE;
-        i32x4 fah[4], fal[4], fbh[4], fbl[4];
+        i32x4 fah[4][1], fal[4][1], fb[4][2];          // fb[kk] = {hi, lo}
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            fah[kk] = lds_read_b128(sb + offa + so[kk]);
-            fbh[kk] = lds_read_b128(sb + offb + so[kk]);
-            fbl[kk] = lds_read_b128(sb + offb + G64_TILE + so[kk]);
-            fal[kk] = lds_read_b128(sb + offa + G64_TILE + so[kk]);
+            read_frags(fah[kk], sb + offa + so[kk]);
+            fb[kk][0] = lds_read_b128(sb + offb + so[kk]);
+            fb[kk][1] = lds_read_b128(sb + offb + G64_TILE + so[kk]);
+            read_frags(fal[kk], sb + offa + G64_TILE + so[kk]);
         }
         __builtin_amdgcn_sched_barrier(0);
         if (i >= 1 && i - 1 + G64F_NST < nk) dma_stage(lds + prev * G64F_STAGE);      // (its issue cost hides the LDS latency of the reads above)
         __builtin_amdgcn_sched_barrier(0);
-#define DAE_G64F_STEP(KK, CNT)                                   \
-    asm volatile("s_waitcnt lgkmcnt(" #CNT ")" ::: "memory");    \
-    __builtin_amdgcn_sched_barrier(0);                           \
-    Mma<bf16_t>::run(fah[KK], fbh[KK], acc0);                    \
-    Mma<bf16_t>::run(fah[KK], fbl[KK], acc1);                    \
-    Mma<bf16_t>::run(fal[KK], fbh[KK], acc2);
-        DAE_G64F_STEP(0, 12)
-        DAE_G64F_STEP(1, 8)
-        DAE_G64F_STEP(2, 4)
-        DAE_G64F_STEP(3, 0)
-#undef DAE_G64F_STEP
+        mma_group<bf16_t, 12>(fah[0], fb[0], acch); Mma<bf16_t>::run(fal[0][0], fb[0][0], accl);
+        mma_group<bf16_t, 8>(fah[1], fb[1], acch); Mma<bf16_t>::run(fal[1][0], fb[1][0], accl);
+        mma_group<bf16_t, 4>(fah[2], fb[2], acch); Mma<bf16_t>::run(fal[2][0], fb[2][0], accl);
+        mma_group<bf16_t, 0>(fah[3], fb[3], acch); Mma<bf16_t>::run(fal[3][0], fb[3][0], accl);
         __builtin_amdgcn_sched_barrier(0);
         prev = cur;
         cur = cur + 1 == G64F_NST ? 0 : cur + 1;
     }
-    float* Dt = D + (int64_t)(tm * 64 + wm * 32) * ldd + tn * 64 + wn * 32 + r;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) Dt[(int64_t)((q & 3) + 8 * (q >> 2) + 4 * g) * ldd] = (acc0[q] + acc1[q]) + acc2[q];
+    gram64_store((acch[0][0] + acch[0][1]) + accl, D, ldd, tm, tn, wave, lane);
 }
 
 static int g_gram_fused = 1;        // dae_set_glds(-19) off / (-20) on: the Gram's three products per K tile in one stage (gram64f_kernel) instead of the K-concatenated walk
@@ -1288,104 +1234,45 @@ int launch_gram64(const void* hcat_a, const void* hcat_b, int Bp, int Hp, float*
 template <typename T>
 __device__ __forceinline__ void mainloop_n64_x3(const GemmParams& p, int tm, int tn, char* lds, f32x16 (&acc)[2][1]) {
     constexpr int STAGE = DecGeo<64>::STAGE;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int row0_m = tm * BM, row0_n = tn * 64;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][0][r] = 0.f;
+    N64Wave w(tm, tn, lds, acc);
     const int nk = p.seg[0].ktiles;                    // the three segments: the same K extent and leading dimensions (checked by the launcher)
     if (nk <= 0) return;
-    uint32_t voA[4], voB[2];
-    const uint32_t lda = (uint32_t)p.seg[0].lda_b, ldb = (uint32_t)p.seg[0].ldb_b;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = (i * 4 + wave) * 8 + (lane >> 3);
-        voA[i] = (uint32_t)(row0_m + row) * lda + (uint32_t)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = (i * 4 + wave) * 8 + (lane >> 3);
-        voB[i] = (uint32_t)(row0_n + row) * ldb + (uint32_t)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
-    }
+    w.offsets((uint32_t)p.seg[0].lda_b, (uint32_t)p.seg[0].ldb_b);
     // segments as the launcher lists them: 0 = (h_hi, W_hi), 1 = (h_hi, W_lo), 2 = (h_lo, W_hi)
     const char *gAh = p.seg[0].A, *gBh = p.seg[0].Bt, *gAl = p.seg[2].A, *gBl = p.seg[1].Bt;
-    auto dma_stage = [&](char* slot, const char* gA, const char* gB) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gA + voA[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + (i * 4 + wave) * 1024), 16, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gB + voB[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + TILE_BYTES + (i * 4 + wave) * 1024), 16, 0, 0);
-    };
-    const int r = lane & 31, g = lane >> 5;
-    const int swz = (r >> 1) & 7;
-    const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-    const uint32_t offa = (wm * 64 + r) * BKB, offb = TILE_BYTES + (wn * 32 + r) * BKB;
-    uint32_t so[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) so[kk] = (uint32_t)(((kk * 2 + g) ^ swz) << 4);
-    dma_stage(lds, gAh, gBh);
+    w.dma_ab(lds, gAh, gBh);
     for (int i = 0; i < nk; ++i) {
         // ---- hi stage (slot 0): the lo stage of this K tile goes out first
-        dma_stage(lds + STAGE, gAl, gBl);
+        w.dma_ab(lds + STAGE, gAl, gBl);
         gAl += BKB; gBl += BKB;
         wait_vm<6>();
         __builtin_amdgcn_s_barrier();                  // the hi stage landed for every wave
         asm volatile("" ::: "memory");
-        i32x4 fah[4][2], fbh[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            fah[kk][0] = lds_read_b128(lbase + offa + so[kk]);
-            fah[kk][1] = lds_read_b128_off4096(lbase + offa + so[kk]);
-            fbh[kk] = lds_read_b128(lbase + offb + so[kk]);
-        }
-#define DAE_N64X_HI(KK, CNT)                                     \
-    asm volatile("s_waitcnt lgkmcnt(" #CNT ")" ::: "memory");    \
-    __builtin_amdgcn_sched_barrier(0);                           \
-    Mma<T>::run(fah[KK][0], fbh[KK], acc[0][0]);                 \
-    Mma<T>::run(fah[KK][1], fbh[KK], acc[1][0]);
-        DAE_N64X_HI(0, 9)
-        DAE_N64X_HI(1, 6)
-        DAE_N64X_HI(2, 3)
-        DAE_N64X_HI(3, 0)
-#undef DAE_N64X_HI
+        i32x4 fah[4][2], fbh[4][1];
+        w.read_ab(w.lbase, fah, fbh);
+        mma_group<T, 9>(fah[0], fbh[0], acc);
+        mma_group<T, 6>(fah[1], fbh[1], acc);
+        mma_group<T, 3>(fah[2], fbh[2], acc);
+        mma_group<T, 0>(fah[3], fbh[3], acc);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();                  // every wave has read slot 0: the next K tile's hi stage may refill it
         asm volatile("" ::: "memory");
         // ---- lo stage (slot 1)
         if (i + 1 < nk) {
             gAh += BKB; gBh += BKB;
-            dma_stage(lds, gAh, gBh);
+            w.dma_ab(lds, gAh, gBh);
             wait_vm<6>();
         } else {
             wait_vm<0>();
         }
         __builtin_amdgcn_s_barrier();                  // the lo stage landed for every wave
         asm volatile("" ::: "memory");
-        i32x4 fal[4][2], fbl[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            fal[kk][0] = lds_read_b128(lbase + STAGE + offa + so[kk]);
-            fal[kk][1] = lds_read_b128_off4096(lbase + STAGE + offa + so[kk]);
-            fbl[kk] = lds_read_b128(lbase + STAGE + offb + so[kk]);
-        }
-#define DAE_N64X_LO(KK, CNT)                                     \
-    asm volatile("s_waitcnt lgkmcnt(" #CNT ")" ::: "memory");    \
-    __builtin_amdgcn_sched_barrier(0);                           \
-    Mma<T>::run(fah[KK][0], fbl[KK], acc[0][0]);                 \
-    Mma<T>::run(fah[KK][1], fbl[KK], acc[1][0]);                 \
-    Mma<T>::run(fal[KK][0], fbh[KK], acc[0][0]);                 \
-    Mma<T>::run(fal[KK][1], fbh[KK], acc[1][0]);
-        DAE_N64X_LO(0, 9)
-        DAE_N64X_LO(1, 6)
-        DAE_N64X_LO(2, 3)
-        DAE_N64X_LO(3, 0)
-#undef DAE_N64X_LO
+        i32x4 fal[4][2], fbl[4][1];
+        w.read_ab(w.lbase + STAGE, fal, fbl);
+        mma_group<T, 9>(fah[0], fbl[0], acc); mma_block<T>(fal[0], fbh[0], acc);
+        mma_group<T, 6>(fah[1], fbl[1], acc); mma_block<T>(fal[1], fbh[1], acc);
+        mma_group<T, 3>(fah[2], fbl[2], acc); mma_block<T>(fal[2], fbh[2], acc);
+        mma_group<T, 0>(fah[3], fbl[3], acc); mma_block<T>(fal[3], fbh[3], acc);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();                  // every wave has read slot 1
         asm volatile("" ::: "memory");
@@ -1399,54 +1286,13 @@ __device__ __forceinline__ void mainloop_n64_x3(const GemmParams& p, int tm, int
 template <typename T>
 __device__ __forceinline__ void mainloop_n64_c2(const GemmParams& p, int tm, int tn, char* lds, f32x16 (&acc)[2][1]) {
     constexpr int STAGE = DecGeo<64>::STAGE;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int row0_m = tm * BM, row0_n = tn * 64;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][0][r] = 0.f;
+    N64Wave w(tm, tn, lds, acc);
     const int nk = p.seg[0].ktiles;                    // both segments: the same A operand, K extent and leading dimensions (checked by the launcher)
     if (nk <= 0) return;
-    uint32_t voA[4], voB[2];
-    const uint32_t lda = (uint32_t)p.seg[0].lda_b, ldb = (uint32_t)p.seg[0].ldb_b;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = (i * 4 + wave) * 8 + (lane >> 3);
-        voA[i] = (uint32_t)(row0_m + row) * lda + (uint32_t)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = (i * 4 + wave) * 8 + (lane >> 3);
-        voB[i] = (uint32_t)(row0_n + row) * ldb + (uint32_t)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
-    }
+    w.offsets((uint32_t)p.seg[0].lda_b, (uint32_t)p.seg[0].ldb_b);
     const char *gA = p.seg[0].A, *gBh = p.seg[0].Bt, *gBl = p.seg[1].Bt;
-    auto dma_hi = [&](char* slot) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gA + voA[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + (i * 4 + wave) * 1024), 16, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gBh + voB[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + TILE_BYTES + (i * 4 + wave) * 1024), 16, 0, 0);
-        gA += BKB; gBh += BKB;
-    };
-    auto dma_lo = [&](char* slot) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gBl + voB[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + TILE_BYTES + (i * 4 + wave) * 1024), 16, 0, 0);
-        gBl += BKB;
-    };
-    const int r = lane & 31, g = lane >> 5;
-    const int swz = (r >> 1) & 7;
-    const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-    const uint32_t offa = (wm * 64 + r) * BKB, offb = TILE_BYTES + (wn * 32 + r) * BKB;
-    uint32_t so[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) so[kk] = (uint32_t)(((kk * 2 + g) ^ swz) << 4);
+    auto dma_hi = [&](char* slot) { w.dma_ab(slot, gA, gBh); gA += BKB; gBh += BKB; };
+    auto dma_lo = [&](char* slot) { w.dma_b(slot, gBl); gBl += BKB; };
     dma_hi(lds);
     for (int i = 0; i < nk; ++i) {
         // ---- hi stage (slot 0); the W_lo tile of this K tile goes out first (slot 1, B region)
@@ -1454,23 +1300,12 @@ __device__ __forceinline__ void mainloop_n64_c2(const GemmParams& p, int tm, int
         wait_vm<2>();
         __builtin_amdgcn_s_barrier();                  // the hi stage landed for every wave
         asm volatile("" ::: "memory");
-        i32x4 fa[4][2], fbh[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            fa[kk][0] = lds_read_b128(lbase + offa + so[kk]);
-            fa[kk][1] = lds_read_b128_off4096(lbase + offa + so[kk]);
-            fbh[kk] = lds_read_b128(lbase + offb + so[kk]);
-        }
-#define DAE_N64C_HI(KK, CNT)                                     \
-    asm volatile("s_waitcnt lgkmcnt(" #CNT ")" ::: "memory");    \
-    __builtin_amdgcn_sched_barrier(0);                           \
-    Mma<T>::run(fa[KK][0], fbh[KK], acc[0][0]);                  \
-    Mma<T>::run(fa[KK][1], fbh[KK], acc[1][0]);
-        DAE_N64C_HI(0, 9)
-        DAE_N64C_HI(1, 6)
-        DAE_N64C_HI(2, 3)
-        DAE_N64C_HI(3, 0)
-#undef DAE_N64C_HI
+        i32x4 fa[4][2], fbh[4][1];
+        w.read_ab(w.lbase, fa, fbh);
+        mma_group<T, 9>(fa[0], fbh[0], acc);
+        mma_group<T, 6>(fa[1], fbh[1], acc);
+        mma_group<T, 3>(fa[2], fbh[2], acc);
+        mma_group<T, 0>(fa[3], fbh[3], acc);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();                  // every wave has read slot 0: the next K tile's hi stage may refill it
         asm volatile("" ::: "memory");
@@ -1479,19 +1314,12 @@ __device__ __forceinline__ void mainloop_n64_c2(const GemmParams& p, int tm, int
         else wait_vm<0>();
         __builtin_amdgcn_s_barrier();                  // the W_lo tile landed for every wave
         asm volatile("" ::: "memory");
-        i32x4 fbl[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) fbl[kk] = lds_read_b128(lbase + STAGE + offb + so[kk]);
-#define DAE_N64C_LO(KK, CNT)                                     \
-    asm volatile("s_waitcnt lgkmcnt(" #CNT ")" ::: "memory");    \
-    __builtin_amdgcn_sched_barrier(0);                           \
-    Mma<T>::run(fa[KK][0], fbl[KK], acc[0][0]);                  \
-    Mma<T>::run(fa[KK][1], fbl[KK], acc[1][0]);
-        DAE_N64C_LO(0, 3)
-        DAE_N64C_LO(1, 2)
-        DAE_N64C_LO(2, 1)
-        DAE_N64C_LO(3, 0)
-#undef DAE_N64C_LO
+        i32x4 fbl[4][1];
+        w.read_b(w.lbase + STAGE, fbl);
+        mma_group<T, 3>(fa[0], fbl[0], acc);
+        mma_group<T, 2>(fa[1], fbl[1], acc);
+        mma_group<T, 1>(fa[2], fbl[2], acc);
+        mma_group<T, 0>(fa[3], fbl[3], acc);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();                  // every wave has read the W_lo tile
         asm volatile("" ::: "memory");
@@ -1626,8 +1454,8 @@ __global__ __launch_bounds__(GEMM_THREADS, DecGeo<BN_T>::WG_PER_CU) void gemm_de
     }
     __syncthreads();
 
-    const int lcol0 = wn * WCOLS + c;                  // local column of nt = 0
-    const int lrow0 = wm * 64 + 4 * g;                 // local row of (mt = 0, r = 0)
+    const int lcol0 = wn * WCOLS + c;                  // local column of nt = 0: acc_col(0, c)
+    const int lrow0 = wm * 64 + 4 * g;                 // local row of (mt = 0, r = 0): acc_row(0, 0, g) (through the helper the two-term kernels take 2 VGPRs more)
     const float eps = 1e-16f;
     float colsum[NTB];
     float cm[NTB], bvv[NTB];                           // column mask as a multiplier: padded features contribute nothing
@@ -1659,7 +1487,7 @@ __global__ __launch_bounds__(GEMM_THREADS, DecGeo<BN_T>::WG_PER_CU) void gemm_de
     auto epi_block = [&](auto MT, auto R4, auto FASTV) {
         constexpr int mt = decltype(MT)::value, r4 = decltype(R4)::value;
         constexpr bool FAST = decltype(FASTV)::value;
-        constexpr int rloc = mt * 32 + 8 * r4;         // local row offset of q = 0 relative to lrow0
+        constexpr int rloc = acc_row(mt, 4 * r4, 0);   // local row offset of q = 0 (register 4 r4 + q) relative to lrow0
         float d2v[NTB][4];
         float xin[4][NTB];
         float xlo[RES ? 4 : 1][RES ? NTB : 1];
@@ -1786,7 +1614,7 @@ __global__ __launch_bounds__(GEMM_THREADS, DecGeo<BN_T>::WG_PER_CU) void gemm_de
         if constexpr (STAGED) {
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) {
-                const int rloc = mt * 32 + 8 * r4;
+                const int rloc = acc_row(mt, 4 * r4, 0);
 #pragma unroll
                 for (int nt = 0; nt < NTB; ++nt) {
 #pragma unroll
@@ -1801,7 +1629,7 @@ __global__ __launch_bounds__(GEMM_THREADS, DecGeo<BN_T>::WG_PER_CU) void gemm_de
             for (int r4 = 0; r4 < 4; ++r4)
 #pragma unroll
                 for (int nt = 0; nt < NTB; ++nt) {
-                    const int rloc = mt * 32 + 8 * r4;
+                    const int rloc = acc_row(mt, 4 * r4, 0);
                     if (!pass1) {
 #pragma unroll
                         for (int q = 0; q < 4; ++q) if (d2_lane) d2_lane[(int64_t)(rloc + q) * e.ldd + nt * 32] = Elem<T>::from(0.f);
@@ -1868,7 +1696,7 @@ __global__ __launch_bounds__(GEMM_THREADS, DecGeo<BN_T>::WG_PER_CU) void gemm_de
                 __syncthreads();                        // every piece of the hi tiles has been read
 #pragma unroll
                 for (int blk = 0; blk < 8; ++blk) {
-                    const int rloc = (blk >> 2) * 32 + 8 * (blk & 3);
+                    const int rloc = acc_row(blk >> 2, 4 * (blk & 3), 0);
 #pragma unroll
                     for (int nt = 0; nt < NTB; ++nt) {
                         const uint32_t a = resv[blk][nt][0], b = resv[blk][nt][1];
@@ -2435,7 +2263,7 @@ int launch_decode_loss_n(int dtype, int Bp, int Fp, const GemmSegDesc* segs, int
 //   z1 slab[split] = bits(x~)[Bp x Fp] . Wt_lo[Hp x Fp]^T
 // The corrupted batch reaches the kernel as the gather's BIT image (1 bit per feature: 1.1 MB instead of 18 MB of bf16);
 // the dense x~ operand is never written to or read from HBM.  Producer/consumer structure of gemm_nt_pc:
-//   consumer waves 0-3: fragment reads + MFMAs, byte-for-byte the loop of gemm_nt_pc (the LDS image is identical);
+//   consumer waves 0-3: fragment reads + MFMAs, the loop of gemm_nt_pc (pc_consume: the LDS image is the same);
 //   producer waves 4-7: W^T tile by LDS-DMA (4 x 1 KiB pieces per wave per K tile -- HALF the DMA instructions of the dense
 //     kernel, whose ~70-cycle issue cost per piece is what paces its K loop), and the x~ tile BUILT in LDS from the bits:
 //     zero-fill of the wave's 32 rows (4 ds_write_b128) + one ds_write_b16 of bf16 1.0 per set bit (x~ is ~1.4 % dense:
@@ -2482,21 +2310,16 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_encode_bits_pc(EncBitsPara
         const int wave = wave8 - 4;
         uint32_t voB[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = (i * 4 + wave) * 8 + (lane >> 3);
-            voB[i] = (uint32_t)(row0_n + row) * (uint32_t)p.ldb_b + (uint32_t)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
-        }
+        for (int i = 0; i < 4; ++i) voB[i] = dma_src<4>(i, wave, lane, row0_n, (uint32_t)p.ldb_b);
         const char* gB = p.Bt + (int64_t)kt0 * BKB;
         auto dma_stage = [&](char* slot) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gB + voB[i]),
-                                                 (__attribute__((address_space(3))) void*)(slot + TILE_BYTES + (i * 4 + wave) * 1024), 16, 0, 0);
+            for (int i = 0; i < 4; ++i) glds_piece<4>(i, wave, gB + voB[i], slot + TILE_BYTES);
             gB += BKB;
         };
         // A tile of K tile t (relative to kt0) into `slot`: this wave's rows [32 wave, +32); lane = (row, 32-feature half)
         const int arow = wave * 32 + (lane >> 1), half = lane & 1;
-        const uint32_t aswz = (uint32_t)((arow >> 1) & 7);
+        const uint32_t aswz = (uint32_t)tile_swz(arow);
         const uint32_t* const myword = slice + arow * sstride + half;
         auto build_a = [&](int t, char* slot) {
             uint32_t word = myword[2 * t];
@@ -2515,7 +2338,7 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_encode_bits_pc(EncBitsPara
             } else {
                 const i32x4 z = {0, 0, 0, 0};
 #pragma unroll
-                for (int i = 0; i < 4; ++i) *reinterpret_cast<i32x4*>(slot + (wave * 4 + i) * 1024 + lane * 16) = z;
+                for (int i = 0; i < 4; ++i) *reinterpret_cast<i32x4*>(slot + (wave * 4 + i) * PIECE_BYTES + lane * 16) = z;
                 while (word) {                             // one 2-byte store per set bit (in-order LDS: lands after the zero fill)
                     const int b = __builtin_ctz(word);
                     word &= word - 1;
@@ -2531,15 +2354,12 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_encode_bits_pc(EncBitsPara
         for (int st = 0; st < NST; ++st)
             if (st < nk) { dma_stage(lds + st * STAGE_BYTES); build_a(st, lds + st * STAGE_BYTES); }
         if (nk >= NST) wait_vm<(NST - 1) * 4>(); else wait_vm<0>();      // stage 0's W^T tile landed
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // ... and every A tile written so far
+        wait_lgkm<0>();                                                   // ... and every A tile written so far
         __builtin_amdgcn_s_barrier();
         int cur = 0;
         for (int i = 0; i < nk; ++i) {
-            const int ahead = min(NST - 2, nk - 2 - i);                   // stages younger than i+1 already requested (4 DMAs each)
-            if (ahead >= 2) wait_vm<8>();
-            else if (ahead == 1) wait_vm<4>();
-            else wait_vm<0>();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_vm_ahead<4>(min(NST - 2, nk - 2 - i));
+            wait_lgkm<0>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             if (i + NST < nk) { dma_stage(lds + cur * STAGE_BYTES); build_a(i + NST, lds + cur * STAGE_BYTES); }
@@ -2548,77 +2368,14 @@ __global__ __launch_bounds__(PC_THREADS, 1) void gemm_encode_bits_pc(EncBitsPara
         return;
     }
 
-    // ================= consumer (same loop as gemm_nt_pc) =================
-    const int wave = wave8;
-    const int wm = wave >> 1, wn = wave & 1;
+    // ================= consumer =================
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");          // my part of the bit slice is in LDS
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (nk > 0) {
-        const int r = lane & 31, g = lane >> 5;
-        const int swz = (r >> 1) & 7;
-        const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-        const uint32_t offa = (wm * 64 + r) * BKB, offb = TILE_BYTES + (wn * 64 + r) * BKB;
-        uint32_t so[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) so[kk] = (uint32_t)(((kk * 2 + g) ^ swz) << 4);
-        i32x4 fa[4][2], fb[4][2];
-#define DAE_READ_KK(KK, SLOTBASE)                                          \
-    fa[KK][0] = lds_read_b128((SLOTBASE) + offa + so[KK]);                 \
-    fa[KK][1] = lds_read_b128_off4096((SLOTBASE) + offa + so[KK]);         \
-    fb[KK][0] = lds_read_b128((SLOTBASE) + offb + so[KK]);                 \
-    fb[KK][1] = lds_read_b128_off4096((SLOTBASE) + offb + so[KK]);
-#define DAE_MMA4(KK)                                                       \
-    Mma<bf16_t>::run(fa[KK][0], fb[KK][0], acc[0][0]);                     \
-    Mma<bf16_t>::run(fa[KK][0], fb[KK][1], acc[0][1]);                     \
-    Mma<bf16_t>::run(fa[KK][1], fb[KK][0], acc[1][0]);                     \
-    Mma<bf16_t>::run(fa[KK][1], fb[KK][1], acc[1][1]);
-        __builtin_amdgcn_s_barrier();                                     // stage 0 complete (producers waited for it)
-        asm volatile("" ::: "memory");
-        DAE_READ_KK(0, lbase) DAE_READ_KK(1, lbase) DAE_READ_KK(2, lbase) DAE_READ_KK(3, lbase)
-        __builtin_amdgcn_sched_barrier(0);
-        int cur = 0;
-        for (int i = 0; i < nk; ++i) {
-            const int nxt = cur + 1 == NST ? 0 : cur + 1;
-            asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");            // R0 (kk 0,1) of tile i
-            __builtin_amdgcn_sched_barrier(0);
-            DAE_MMA4(0) DAE_MMA4(1)
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // R1 landed; every LDS read of tile i is done
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            const uint32_t nb = lbase + nxt * STAGE_BYTES;
-            DAE_READ_KK(0, nb) DAE_READ_KK(1, nb)                         // stale (never consumed) after the last tile
-            __builtin_amdgcn_sched_barrier(0);
-            DAE_MMA4(2) DAE_MMA4(3)
-            __builtin_amdgcn_sched_barrier(0);
-            DAE_READ_KK(2, nb) DAE_READ_KK(3, nb)
-            __builtin_amdgcn_sched_barrier(0);
-            cur = nxt;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#undef DAE_READ_KK
-#undef DAE_MMA4
-    }
-    const int g = lane >> 5, c = lane & 31;
-    float* Cs = C + (int64_t)split * slab_stride;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int row = tm * BM + wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                int col = tn * BN + wn * 64 + nt * 32 + c;
-                Cs[(int64_t)row * ldc + col] = acc[mt][nt][r];
-            }
+    if (nk > 0) pc_consume<bf16_t, NST>(lds, wave8 >> 1, wave8 & 1, lane, nk, acc);
+    store_quadrant<false>(acc, C + (int64_t)split * slab_stride, ldc, tm, tn, wave8, lane);
 }
 
 int launch_encode_bits(int Bp, int Hp, int Fp, const uint32_t* bits, int64_t ldw, const void* Wt_lo, int64_t ldb, float* C,

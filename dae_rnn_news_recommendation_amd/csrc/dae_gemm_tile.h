@@ -1,5 +1,7 @@
-// dae_gemm_tile.h -- the 128 x 128 MFMA tile and its K loop (gemm_mainloop), shared by the GEMM kernels of dae_gemm.hip and the
-// fused similarity + top-k kernel of dae_topk.hip.  Tiling, LDS image and staging: see the head of dae_gemm.hip.
+// dae_gemm_tile.h -- the LDS image of an operand tile, the accumulator layout of the 32 x 32 MFMA and the 128 x 128 K loop
+// (gemm_mainloop), shared by the GEMM kernels of dae_gemm.hip / dae_gemm_w8.h and the score sweeps of dae_score_sweep.h.
+// The two formats are DEFINED here, once ("the tile image", "the accumulator layout" below); why the tiles have these shapes:
+// the head of dae_gemm.hip.
 #pragma once
 #include "dae_kernels.h"
 
@@ -51,6 +53,90 @@ template <> struct Mma<float> {
     }
 };
 
+// ---- the tile image ----
+// An operand tile in LDS is [rows][128 bytes] = eight 16-byte slots per row, and logical slot s of row `row` lives in physical slot
+// s ^ tile_swz(row): the 16 lanes of a ds_read_b128 lane group (rows distinct mod 16) then hit 16 distinct slots of the 256-byte bank row
+// (conflict-free).  LDS-DMA writes the image lane-linear in 1-KiB pieces of 8 rows (lane l lands at byte 16 l of its piece), so the
+// swizzle sits on the per-lane SOURCE address (dma_src); the MFMA fragments come back with ds_read_b128 at frag_row + frag_slot, 32-row
+// blocks FRAG_BLOCK bytes apart.  tile_image_ok() below proves at compile time that the two sides agree.
+constexpr int PIECE_BYTES = 1024, PIECE_ROWS = PIECE_BYTES / BKB;
+constexpr int FRAG_BLOCK = 32 * BKB;     // bytes between the 32-row MFMA blocks of a tile: the immediate offsets of the fragment reads
+__host__ __device__ constexpr int tile_swz(int row) { return (row >> 1) & 7; }
+
+// DMA side.  Piece i of wave `wave` (of WAVES that fill the tile) is piece i * WAVES + wave of the tile; lane `lane` of it fills one
+// cell of row piece_row.  dma_src: the byte offset of the 16 bytes this lane must fetch, relative to the K tile's first byte of panel
+// row 0 -- panel row row0 + piece_row (clamped to row_last: tiles that overhang the panel re-read its last row), leading dimension ld bytes.
+__host__ __device__ constexpr int piece_row(int piece, int lane) { return piece * PIECE_ROWS + (lane >> 3); }
+__host__ __device__ constexpr int piece_slot(int piece, int lane) { return (lane & 7) ^ tile_swz(piece_row(piece, lane)); }
+template <int WAVES>
+__host__ __device__ constexpr uint32_t dma_src(int i, int wave, int lane, int row0, uint32_t ld, int row_last = INT32_MAX) {
+    const int row = row0 + piece_row(i * WAVES + wave, lane);
+    return (uint32_t)(row < row_last ? row : row_last) * ld + (uint32_t)(piece_slot(i * WAVES + wave, lane) << 4);
+}
+__device__ __forceinline__ uint32_t lds_addr(const char* l) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)l; }
+// 16 bytes per lane, global -> LDS (global_load_lds_dwordx4): the wave's 1 KiB lands lane-linear at l
+__device__ __forceinline__ void glds16(const char* g, char* l) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
+}
+template <int WAVES> __device__ __forceinline__ void glds_piece(int i, int wave, const char* src, char* tile) {
+    glds16(src, tile + (i * WAVES + wave) * PIECE_BYTES);
+}
+// the offsets of all N pieces of a wave
+template <int WAVES, int N>
+__device__ __forceinline__ void dma_srcs(uint32_t (&vo)[N], int wave, int lane, int row0, uint32_t ld, int row_last = INT32_MAX) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) vo[i] = dma_src<WAVES>(i, wave, lane, row0, ld, row_last);
+}
+
+// Fragment side.  Lane (g = lane >> 5, r = lane & 31) reads row r of a 32-row block (first row row0, a multiple of 32) and, for the
+// 16-byte k chunk kk of 4, the logical slot kk * 2 + g.
+__host__ __device__ constexpr uint32_t frag_row(int row0, int lane) { return (uint32_t)((row0 + (lane & 31)) * BKB); }
+__host__ __device__ constexpr uint32_t frag_slot(int kk, int lane) { return (uint32_t)(((kk * 2 + (lane >> 5)) ^ tile_swz(lane & 31)) << 4); }
+__device__ __forceinline__ void frag_slots(int lane, uint32_t (&so)[4]) {
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) so[kk] = frag_slot(kk, lane);
+}
+
+// the DMA mapping is a bijection of (piece, lane) onto the (row, logical slot) cells of a ROWS-row tile, every cell inside its 128-byte
+// row, and the fragment side addresses exactly the cell where the DMA put logical slot kk * 2 + g of its row.  (The proof covers dma_src,
+// frag_row and frag_slot and takes the hardware's destination -- piece * PIECE_BYTES + 16 * lane, what glds_piece passes -- as given; the
+// writers that build the image with ds_write, stage_write and gemm_encode_bits_pc's build_a, and the offset code a kernel keeps written
+// out are outside it.)
+template <int ROWS, int WAVES> constexpr bool tile_image_ok() {
+    int at[ROWS * 8] = {};                   // 1 + the 16-byte LDS cell that holds logical slot s of row r, at r * 8 + s
+    for (int piece = 0; piece < ROWS / PIECE_ROWS; ++piece)
+        for (int lane = 0; lane < 64; ++lane) {
+            const int row = piece_row(piece, lane), cell = (piece * PIECE_BYTES >> 4) + lane;
+            const int slot = (int)(dma_src<WAVES>(piece / WAVES, piece % WAVES, lane, 0, 0u) >> 4);
+            if (row >= ROWS || slot > 7 || (cell >> 3) != row || at[row * 8 + slot]) return false;
+            at[row * 8 + slot] = 1 + cell;
+        }
+    for (int row = 0; row < ROWS; ++row)
+        for (int kk = 0; kk < 4; ++kk)
+            for (int g = 0; g < 2; ++g) {
+                const int lane = g * 32 + (row & 31);
+                if (frag_row(row & ~31, lane) + frag_slot(kk, lane) != (uint32_t)(at[row * 8 + kk * 2 + g] - 1) << 4) return false;
+            }
+    return true;
+}
+static_assert(tile_image_ok<64, 4>() && tile_image_ok<128, 4>() && tile_image_ok<160, 4>() && tile_image_ok<256, 8>(),
+              "the LDS-DMA side and the fragment side of the tile image disagree");
+
+// ---- the accumulator layout of v_mfma_f32_32x32x* ----
+// A 32 x 32 block lives in 16 registers per lane: lane (g = lane >> 5, c = lane & 31) holds in register r the value of row
+// (r & 3) + 8 * (r >> 2) + 4 * g, column c.  For a wave tile of mt x nt blocks, acc[mt][nt][r] sits at (acc_row(mt, r, g), acc_col(nt, c))
+// of the wave tile: a lane's values are its first one's place, (4 * g, c), plus the compile-time offsets acc_row(mt, r, 0), acc_col(nt, 0).
+__host__ __device__ constexpr int acc_row(int mt, int r, int g) { return mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g; }
+__host__ __device__ constexpr int acc_col(int nt, int c) { return nt * 32 + c; }
+template <int M, int N> __device__ __forceinline__ void zero_acc(f32x16 (&acc)[M][N]) {
+#pragma unroll
+    for (int i = 0; i < M; ++i)
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
 // segment of K tile kt: its index, the tile's position inside it and the first K tile AFTER it (where the stream switches operands)
 template <typename P>
 __device__ __forceinline__ int seg_locate(const P& p, int kt, int& k_in_seg, int& seg_end) {
@@ -87,83 +173,79 @@ __device__ __forceinline__ void stage_write(char* stage, int tid, const StageReg
     for (int i = 0; i < 4; ++i) {
         int c = tid + GEMM_THREADS * i;
         int row = c >> 3, slot = c & 7;
-        int off = row * BKB + ((slot ^ ((row >> 1) & 7)) << 4);
+        int off = row * BKB + ((slot ^ tile_swz(row)) << 4);
         *reinterpret_cast<i32x4*>(stage + off) = r.a[i];
         *reinterpret_cast<i32x4*>(stage + TILE_BYTES + off) = r.b[i];
     }
 }
 
-// ---- staging: direct global -> LDS (global_load_lds_dwordx4) ----
-// wave w, piece i covers LDS bytes [(i*4+w)*1024, +1024) of each operand tile = 8 rows; lane l lands at
-// +l*16, i.e. (row = (i*4+w)*8 + (l>>3), physical slot = l&7) and must fetch logical slot
-// (l&7) ^ ((row>>1)&7) of that row.
-__device__ __forceinline__ void stage_glds(const GemmParams& p, int kt, int row0_m, int row0_n, int wave, int lane,
-                                           char* stage) {
-    const char *A, *Bt; int64_t lda, ldb, kb;
-    seg_of(p, kt, A, Bt, lda, ldb, kb);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        int piece = i * 4 + wave;
-        int row = piece * 8 + (lane >> 3);
-        int sslot = (lane & 7) ^ ((row >> 1) & 7);
-        const char* ga = A + (int64_t)(row0_m + row) * lda + kb + sslot * 16;
-        const char* gb = Bt + (int64_t)(row0_n + row) * ldb + kb + sslot * 16;
-        char* la = stage + piece * 1024;
-        char* lb = stage + TILE_BYTES + piece * 1024;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)ga,
-                                         (__attribute__((address_space(3))) void*)la, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gb,
-                                         (__attribute__((address_space(3))) void*)lb, 16, 0, 0);
-    }
-}
-
+// ---- counted waits ----
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// One K tile of MFMA work for a wave.  All 16 fragment reads (ds_read_b128, 64 VGPRs) are issued back to back and
-// the four MFMA groups wait with COUNTED lgkmcnt (12/8/4/0): the first MFMAs start as soon as their fragments land
-// and the LDS latency of the rest hides behind them.  rocprofv3 showed ~50 % of wave time parked in lgkmcnt(0) with
-// the compiler's own read->wait(0)->MFMA x4 schedule, and hipcc turns any source-level hoisting back into a full
-// wait, so the reads are inline asm (invisible to its scoreboard) with hand-placed waits; each wait is followed by
-// sched_barrier(0) because register-only MFMAs may otherwise be hoisted above an asm s_waitcnt (guide 5.4 rule 18).
-__device__ __forceinline__ i32x4 lds_read_b128(uint32_t addr) {
-    i32x4 v;
-    asm volatile("ds_read_b128 %0, %1" : "=&v"(v) : "v"(addr));
-    return v;
-}
-__device__ __forceinline__ i32x4 lds_read_b128_off4096(uint32_t addr) {
-    i32x4 v;
-    asm volatile("ds_read_b128 %0, %1 offset:4096" : "=&v"(v) : "v"(addr));
-    return v;
+template <int N> __device__ __forceinline__ void wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
+// vmcnt(PIECES * n): n younger stages of PIECES LDS-DMA pieces per wave each may stay in flight; n is at most NMAX (a ring of NMAX + 1 stages).
+// A compare chain over template constants, so that exactly the waits of the NMAX + 1 reachable counts are emitted.
+template <int PIECES, int NMAX> __device__ __forceinline__ void wait_vm_stages(int n) {
+    static_assert(PIECES * NMAX < 64, "vmcnt is a 6-bit counter");
+    if constexpr (NMAX == 0) wait_vm<0>();
+    else if (n >= NMAX) wait_vm<PIECES * NMAX>();
+    else wait_vm_stages<PIECES, NMAX - 1>(n);
 }
 
+// ---- fragment reads and MFMA groups ----
+// All fragment reads of a K tile (ds_read_b128) are issued back to back and the MFMA groups wait with COUNTED lgkmcnt: the first MFMAs
+// start as soon as their fragments land and the LDS latency of the rest hides behind them.  rocprofv3 showed ~50 % of wave time parked
+// in lgkmcnt(0) with the compiler's own read->wait(0)->MFMA x4 schedule, and hipcc turns any source-level hoisting back into a full
+// wait, so the reads are inline asm (invisible to its scoreboard) with hand-placed waits.  Every wait is followed by sched_barrier(0),
+// and so is every MFMA block that an asm read or wait follows: register-only MFMAs may otherwise be moved across an asm statement
+// (guide 5.4 rule 18) -- which is why each sched_barrier(0) of the K loops stays exactly where it is (tools/check_gemm_asm.py replays
+// the result).
+template <int OFF = 0> __device__ __forceinline__ i32x4 lds_read_b128(uint32_t addr) {   // OFF: 0..3 blocks of FRAG_BLOCK bytes, as an immediate
+    static_assert(OFF % FRAG_BLOCK == 0 && OFF >= 0 && OFF <= 3 * FRAG_BLOCK && FRAG_BLOCK == 4096, "the offsets are spelled out below");
+    i32x4 v;
+    if constexpr (OFF == 0) asm volatile("ds_read_b128 %0, %1" : "=&v"(v) : "v"(addr));
+    else if constexpr (OFF == 4096) asm volatile("ds_read_b128 %0, %1 offset:4096" : "=&v"(v) : "v"(addr));
+    else if constexpr (OFF == 8192) asm volatile("ds_read_b128 %0, %1 offset:8192" : "=&v"(v) : "v"(addr));
+    else asm volatile("ds_read_b128 %0, %1 offset:12288" : "=&v"(v) : "v"(addr));
+    return v;
+}
+// the fragments of one k chunk for NB consecutive 32-row blocks of a tile; addr = slot base + frag_row + frag_slot
+template <int NB> __device__ __forceinline__ void read_frags(i32x4 (&f)[NB], uint32_t addr) {
+    static_assert(NB >= 1 && NB <= 4, "immediate offsets up to 3 blocks");
+    f[0] = lds_read_b128(addr);
+    if constexpr (NB > 1) f[1] = lds_read_b128<FRAG_BLOCK>(addr);
+    if constexpr (NB > 2) f[2] = lds_read_b128<2 * FRAG_BLOCK>(addr);
+    if constexpr (NB > 3) f[3] = lds_read_b128<3 * FRAG_BLOCK>(addr);
+}
+// acc[nt] += a . b[nt]; acc[mt][nt] += a[mt] . b[nt] (row blocks outer)
+template <typename T, int NT> __device__ __forceinline__ void mma_row(const i32x4& a, const i32x4 (&b)[NT], f32x16 (&acc)[NT]) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) Mma<T>::run(a, b[nt], acc[nt]);
+}
+template <typename T, int MT, int NT> __device__ __forceinline__ void mma_block(const i32x4 (&a)[MT], const i32x4 (&b)[NT], f32x16 (&acc)[MT][NT]) {
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) mma_row<T>(a[mt], b, acc[mt]);
+}
+// ... once all but the youngest CNT fragment reads have landed
+template <typename T, int CNT, int MT, int NT> __device__ __forceinline__ void mma_group(const i32x4 (&a)[MT], const i32x4 (&b)[NT], f32x16 (&acc)[MT][NT]) {
+    wait_lgkm<CNT>();
+    __builtin_amdgcn_sched_barrier(0);
+    mma_block<T>(a, b, acc);
+}
+
+// One K tile of MFMA work for a wave of the register-staged path: 16 fragment reads (64 VGPRs), four groups at lgkmcnt 12/8/4/0.
 template <typename T>
 __device__ __forceinline__ void compute_stage(const char* stage, int wm, int wn, int lane, f32x16 (&acc)[2][2]) {
-    const int r = lane & 31, g = lane >> 5;
-    const int swz = (r >> 1) & 7;
-    const uint32_t base = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)stage;
-    const uint32_t pa = base + (wm * 64 + r) * BKB;
-    const uint32_t pb = base + TILE_BYTES + (wn * 64 + r) * BKB;
+    const uint32_t pa = lds_addr(stage) + frag_row(wm * 64, lane), pb = lds_addr(stage) + TILE_BYTES + frag_row(wn * 64, lane);
     i32x4 a[4][2], b[4][2];
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-        const uint32_t so = ((kk * 2 + g) ^ swz) << 4;
-        a[kk][0] = lds_read_b128(pa + so);
-        a[kk][1] = lds_read_b128_off4096(pa + so);          // + 32 rows * 128 B
-        b[kk][0] = lds_read_b128(pb + so);
-        b[kk][1] = lds_read_b128_off4096(pb + so);
+        read_frags(a[kk], pa + frag_slot(kk, lane));
+        read_frags(b[kk], pb + frag_slot(kk, lane));
     }
-#define DAE_MMA_GROUP(KK, CNT)                                   \
-    asm volatile("s_waitcnt lgkmcnt(" #CNT ")" ::: "memory");    \
-    __builtin_amdgcn_sched_barrier(0);                           \
-    Mma<T>::run(a[KK][0], b[KK][0], acc[0][0]);                  \
-    Mma<T>::run(a[KK][0], b[KK][1], acc[0][1]);                  \
-    Mma<T>::run(a[KK][1], b[KK][0], acc[1][0]);                  \
-    Mma<T>::run(a[KK][1], b[KK][1], acc[1][1]);
-    DAE_MMA_GROUP(0, 12)
-    DAE_MMA_GROUP(1, 8)
-    DAE_MMA_GROUP(2, 4)
-    DAE_MMA_GROUP(3, 0)
-#undef DAE_MMA_GROUP
+    mma_group<T, 12>(a[0], b[0], acc);
+    mma_group<T, 8>(a[1], b[1], acc);
+    mma_group<T, 4>(a[2], b[2], acc);
+    mma_group<T, 0>(a[3], b[3], acc);
     __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -190,18 +272,16 @@ __device__ __forceinline__ void gemm_mainloop(const GemmParams& p, int tm, int t
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int row0_m = tm * BM, row0_n = tn * BN;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
     const int nk = kt1 - kt0;
     if (nk <= 0) return;
 
     if constexpr (NST >= 2) {
         // ---- LDS-DMA addressing: this lane's 16-byte chunk of each of its 4 pieces per operand, as a 32-bit byte offset
         //      from a uniform (SGPR) panel pointer that advances by one K tile per stage ----
+        // (This loop keeps dma_src, frag_row / frag_slot and its read / MFMA macros written out: through the helpers the offsets regroup
+        //  -- up to 18 VGPRs fewer, so another reported occupancy in 16 kernels -- and the compiler's own waits move in the score sweeps:
+        //  profiles/gemm_tile_refactor.md.  Not covered by tile_image_ok: keep equal to the helpers by hand.)
         uint32_t voA[4], voB[4];
         const char *gA = nullptr, *gB = nullptr;
         int kt_dma = kt0, seg_end = 0;
@@ -221,11 +301,8 @@ __device__ __forceinline__ void gemm_mainloop(const GemmParams& p, int tm, int t
         };
         seg_setup(kt0);
         auto dma_piece = [&](int i, char* slot) {        // piece i of both operands of the stage at (gA, gB)
-            const int piece = i * 4 + wave;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gA + voA[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + piece * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gB + voB[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + TILE_BYTES + piece * 1024), 16, 0, 0);
+            glds_piece<4>(i, wave, gA + voA[i], slot);
+            glds_piece<4>(i, wave, gB + voB[i], slot + TILE_BYTES);
         };
         auto dma_advance = [&]() {
             ++kt_dma;
@@ -243,7 +320,7 @@ __device__ __forceinline__ void gemm_mainloop(const GemmParams& p, int tm, int t
         constexpr bool SPLIT = NST >= 3;
         const int r = lane & 31, g = lane >> 5;
         const int swz = (r >> 1) & 7;
-        const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
+        const uint32_t lbase = lds_addr(lds);
         const uint32_t offa = (wm * 64 + r) * BKB, offb = TILE_BYTES + (wn * 64 + r) * BKB;
         uint32_t so[4];
 #pragma unroll
@@ -251,9 +328,9 @@ __device__ __forceinline__ void gemm_mainloop(const GemmParams& p, int tm, int t
         i32x4 fa[4][2], fb[4][2];
 #define DAE_READ_KK(KK, SLOTBASE)                                          \
     fa[KK][0] = lds_read_b128((SLOTBASE) + offa + so[KK]);                 \
-    fa[KK][1] = lds_read_b128_off4096((SLOTBASE) + offa + so[KK]);         \
+    fa[KK][1] = lds_read_b128<FRAG_BLOCK>((SLOTBASE) + offa + so[KK]);     \
     fb[KK][0] = lds_read_b128((SLOTBASE) + offb + so[KK]);                 \
-    fb[KK][1] = lds_read_b128_off4096((SLOTBASE) + offb + so[KK]);
+    fb[KK][1] = lds_read_b128<FRAG_BLOCK>((SLOTBASE) + offb + so[KK]);
 #define DAE_MMA2(KK, MT)                                                   \
     Mma<T>::run(fa[KK][MT], fb[KK][0], acc[MT][0]);                        \
     Mma<T>::run(fa[KK][MT], fb[KK][1], acc[MT][1]);                        \
@@ -279,7 +356,7 @@ __device__ __forceinline__ void gemm_mainloop(const GemmParams& p, int tm, int t
         for (int i = 0; i < nk; ++i) {
             const int nxt = cur + 1 == NST ? 0 : cur + 1;
             // (a)
-            asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
+            wait_lgkm<8>();
             __builtin_amdgcn_sched_barrier(0);
             DAE_MMA2(0, 0)
             if constexpr (SPLIT) { if (i + NST - 1 < nk) dma_piece(2, lds + (cur == 0 ? NST - 1 : cur - 1) * STAGE_BYTES); __builtin_amdgcn_sched_barrier(0); }
@@ -295,7 +372,7 @@ __device__ __forceinline__ void gemm_mainloop(const GemmParams& p, int tm, int t
                 else if (ahead == 1) wait_vm<8>();
                 else wait_vm<0>();
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lgkm<0>();
             DAE_STAMP(1)
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
@@ -325,7 +402,7 @@ __device__ __forceinline__ void gemm_mainloop(const GemmParams& p, int tm, int t
             DAE_STAMP(3)
             cur = nxt;
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // drain the stale tail reads before the LDS is reused
+        wait_lgkm<0>();                                       // drain the stale tail reads before the LDS is reused
 #undef DAE_READ_KK
 #undef DAE_MMA2
         if constexpr (TRACE) {

@@ -11,8 +11,7 @@
 //   * fragments double buffered per 16-deep k chunk: chunk kk+1 is read while the 8 MFMAs of chunk kk run (counted lgkmcnt),
 //   * ONE s_barrier per K tile (64 deep): [all my reads of tile i done] + [my DMA pieces of tile i+1 landed] -> barrier ->
 //     DMA(tile i+2 -> slot of tile i), first chunk of tile i+1, MFMAs of the last chunk of tile i.
-// LDS image of a stage: the one of dae_gemm.hip -- rows of 128 B, eight 16-byte slots XOR-swizzled with (row >> 1) & 7, written
-// lane-linear by the DMA (the swizzle sits on the per-lane SOURCE address), conflict-free ds_read_b128.
+// LDS image of a stage: two 256-row tile images of dae_gemm_tile.h, each filled by all 8 waves.
 // Rows of the last row tile beyond M re-read row M-1 and are never stored (B = 800 -> Bp = 896 = 3.5 tiles).
 #pragma once
 
@@ -50,14 +49,9 @@ __device__ __forceinline__ void w8_mainloop(const W8Params& p, int row0_m, int r
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;                 // 2 x 4 waves: rows [128 wm, +128), columns [64 wn, +64)
     const int nk = kt1 - kt0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
     if (nk <= 0) return;
-    // ---- LDS-DMA addressing: 4 pieces (8 rows x 128 B) per operand per wave and stage ----
+    // ---- LDS-DMA addressing: 4 pieces per operand per wave and stage ----
     uint32_t voA[4], voB[4];
     const char *gA = nullptr, *gB = nullptr;
     int kt_dma = kt0, seg_end = 0;
@@ -67,8 +61,8 @@ __device__ __forceinline__ void w8_mainloop(const W8Params& p, int row0_m, int r
         const uint32_t lda = (uint32_t)p.seg[sg].lda_b, ldb = (uint32_t)p.seg[sg].ldb_b;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int row = (i * 8 + wave) * 8 + (lane >> 3);
-            const uint32_t ss = (uint32_t)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
+            const int row = piece_row(i * 8 + wave, lane);
+            const uint32_t ss = (uint32_t)(piece_slot(i * 8 + wave, lane) << 4);
             voA[i] = (uint32_t)min(row0_m + row, p.M - 1) * lda + ss;
             voB[i] = (uint32_t)min(row0_n + row, p.N - 1) * ldb + ss;
         }
@@ -79,40 +73,28 @@ __device__ __forceinline__ void w8_mainloop(const W8Params& p, int row0_m, int r
     auto dma_stage = [&](char* slot) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int piece = i * 8 + wave;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gA + voA[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + piece * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gB + voB[i]),
-                                             (__attribute__((address_space(3))) void*)(slot + W8_TILE_BYTES + piece * 1024), 16, 0, 0);
+            glds_piece<8>(i, wave, gA + voA[i], slot);
+            glds_piece<8>(i, wave, gB + voB[i], slot + W8_TILE_BYTES);
         }
         ++kt_dma;
         if (kt_dma == seg_end) { if (kt_dma < p.ktiles_total) seg_setup(kt_dma); }
         else { gA += BKB; gB += BKB; }
     };
 
-    // ---- fragment addressing ----
-    const int r = lane & 31, g = lane >> 5;
-    const int swz = (r >> 1) & 7;
-    const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-    const uint32_t offa = (wm * 128 + r) * BKB, offb = W8_TILE_BYTES + (wn * 64 + r) * BKB;
+    const uint32_t lbase = lds_addr(lds);
+    const uint32_t offa = frag_row(wm * 128, lane), offb = W8_TILE_BYTES + frag_row(wn * 64, lane);
     uint32_t so[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) so[kk] = (uint32_t)(((kk * 2 + g) ^ swz) << 4);
+    frag_slots(lane, so);
     i32x4 fa[2][4], fb[2][2];
-    // one 16-deep chunk: A fragments of the 4 row blocks (32 rows = 4096 B apart), B fragments of the 2 column blocks
-#define W8_READ(SET, KK, SLOTBASE)                                                         \
-    asm volatile("ds_read_b128 %0, %1" : "=&v"(fa[SET][0]) : "v"((SLOTBASE) + offa + so[KK]));               \
-    asm volatile("ds_read_b128 %0, %1 offset:4096" : "=&v"(fa[SET][1]) : "v"((SLOTBASE) + offa + so[KK]));   \
-    asm volatile("ds_read_b128 %0, %1 offset:8192" : "=&v"(fa[SET][2]) : "v"((SLOTBASE) + offa + so[KK]));   \
-    asm volatile("ds_read_b128 %0, %1 offset:12288" : "=&v"(fa[SET][3]) : "v"((SLOTBASE) + offa + so[KK]));  \
-    asm volatile("ds_read_b128 %0, %1" : "=&v"(fb[SET][0]) : "v"((SLOTBASE) + offb + so[KK]));               \
-    asm volatile("ds_read_b128 %0, %1 offset:4096" : "=&v"(fb[SET][1]) : "v"((SLOTBASE) + offb + so[KK]));
-#define W8_MMA(SET)                                                                        \
-    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) {                                     \
-        Mma<bf16_t>::run(fa[SET][mt], fb[SET][0], acc[mt][0]);                             \
-        Mma<bf16_t>::run(fa[SET][mt], fb[SET][1], acc[mt][1]);                             \
-    }                                                                                      \
-    __builtin_amdgcn_sched_barrier(0);
+    // one 16-deep chunk kk into fragment set `set`: A fragments of the 4 row blocks, B fragments of the 2 column blocks
+    auto w8_read = [&](int set, int kk, uint32_t slotbase) __attribute__((always_inline)) {
+        read_frags(fa[set], slotbase + offa + so[kk]);
+        read_frags(fb[set], slotbase + offb + so[kk]);
+    };
+    auto w8_mma = [&](int set) __attribute__((always_inline)) {
+        mma_block<bf16_t>(fa[set], fb[set], acc);
+        __builtin_amdgcn_sched_barrier(0);
+    };
 
     // ---- prologue: tiles 0 and 1 requested, tile 0 landed, its first chunk read ----
     dma_stage(lds);
@@ -120,40 +102,38 @@ __device__ __forceinline__ void w8_mainloop(const W8Params& p, int row0_m, int r
     if (nk > 1) wait_vm<8>(); else wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    W8_READ(0, 0, lbase)
+    w8_read(0, 0, lbase);
     __builtin_amdgcn_sched_barrier(0);
     int cur = 0;
     for (int i = 0; i < nk; ++i) {
         const uint32_t cb = lbase + cur * W8_STAGE, nb = lbase + (cur ^ 1) * W8_STAGE;
         // chunk 0 (set 0) | prefetch chunk 1 -> set 1
-        W8_READ(1, 1, cb)
-        asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
+        w8_read(1, 1, cb);
+        wait_lgkm<6>();
         __builtin_amdgcn_sched_barrier(0);
-        W8_MMA(0)
+        w8_mma(0);
         // chunk 1 (set 1) | prefetch chunk 2 -> set 0
-        W8_READ(0, 2, cb)
-        asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
+        w8_read(0, 2, cb);
+        wait_lgkm<6>();
         __builtin_amdgcn_sched_barrier(0);
-        W8_MMA(1)
+        w8_mma(1);
         // chunk 2 (set 0) | prefetch chunk 3 -> set 1
-        W8_READ(1, 3, cb)
-        asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
+        w8_read(1, 3, cb);
+        wait_lgkm<6>();
         __builtin_amdgcn_sched_barrier(0);
-        W8_MMA(0)
+        w8_mma(0);
         // every read of tile i has been issued; retire them and my DMA pieces of tile i+1, then the tile barrier
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
         wait_vm<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (i + 2 < nk) dma_stage(lds + cur * W8_STAGE);      // tile i+2 into the slot tile i just left
-        W8_READ(0, 0, nb)                                      // first chunk of tile i+1 (stale and unused after the last tile)
+        w8_read(0, 0, nb);                                      // first chunk of tile i+1 (stale and unused after the last tile)
         __builtin_amdgcn_sched_barrier(0);
-        W8_MMA(1)                                              // chunk 3
+        w8_mma(1);                                              // chunk 3
         cur ^= 1;
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#undef W8_READ
-#undef W8_MMA
+    wait_lgkm<0>();
 }
 
 template <int ROLE>
@@ -176,8 +156,8 @@ __global__ __launch_bounds__(W8_THREADS, 1) void gemm_nt_w8(W8Params p, float* _
         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = row0_m + wm * 128 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                const int col = row0_n + wn * 64 + nt * 32 + c;
+                const int row = row0_m + wm * 128 + acc_row(mt, r, g);
+                const int col = row0_n + wn * 64 + acc_col(nt, c);
                 if (row < p.M && col < p.N) Cs[(int64_t)row * ldc + col] = acc[mt][nt][r];
             }
 }

@@ -1,6 +1,6 @@
 // dae_score_sweep.h -- what the "without the N x N matrix" kernels share: dae_topk.hip, dae_rank.hip, dae_pairs.hip and
 // dae_pair_hist.hip sweep the 128 x 128 score tiles of gemm_mainloop<float, 2> over two normalised operand images and differ
-// only in the epilogue.  Here: the order-preserving keys, the accumulator layout, the tile enumerations, the candidate-window
+// only in the epilogue.  Here: the order-preserving keys, the score tile in LDS, the tile enumerations, the candidate-window
 // prologue, and the host prologue (argument checks, workspace carve, normalisation, GemmParams) and launch of every entry.
 #pragma once
 #include "dae_gemm_tile.h"
@@ -25,14 +25,9 @@ __device__ __forceinline__ uint64_t pair_key(float s, int j) {
 __device__ __forceinline__ float pair_key_score(uint64_t x) { return key_score((uint32_t)(x >> 32)); }
 __device__ __forceinline__ int32_t pair_key_index(uint64_t x) { return (int32_t)~(uint32_t)x; }
 
-// ---- the accumulator layout of v_mfma_f32_32x32x2_f32 ----
-// Wave (wm, wn) of gemm_mainloop<float, 2> holds the 64 x 64 quadrant (wm * 64, wn * 64) of the tile as acc[mt][nt][r]: 2 x 2
-// blocks of 32 x 32, and inside a block lane (g = lane >> 5, c = lane & 31) holds in register r the value of row
-// (r & 3) + 8 * (r >> 2) + 4 * g, column c.  Row and column below are relative to the quadrant.  A lane's 64 values are thus its
-// first one's place, (4 * g, c), plus the compile-time offsets acc_row(mt, r, 0) and acc_col(nt, 0).
-__device__ __forceinline__ int acc_row(int mt, int r, int g) { return mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * g; }
-__device__ __forceinline__ int acc_col(int nt, int c) { return nt * 32 + c; }
-
+// ---- the score tile ----
+// Wave (wm, wn) of gemm_mainloop<float, 2> holds the 64 x 64 quadrant (wm * 64, wn * 64) of the tile as acc[mt][nt][r], in the accumulator
+// layout of dae_gemm_tile.h (acc_row / acc_col, relative to the quadrant).
 // the accumulators as a [128][128] fp32 tile in LDS (over the dead staging ring: the caller's barriers frame it)
 __device__ __forceinline__ void acc_to_tile(const f32x16 (&acc)[2][2], float* tile, int wm, int wn, int g, int c) {
     float* first = tile + (wm * 64 + 4 * g) * BN + wn * 64 + c;  // the lane's first value

@@ -7,7 +7,8 @@ file to gfx950 assembly and, for every basic block that contains MFMAs fed by ds
 in-order LDS return rule: after `s_waitcnt lgkmcnt(N)` all but the youngest N reads have landed.  Every MFMA
 source register must come from a read that has landed.  Exit code 1 on any violation.
 
-usage: python tools/check_gemm_asm.py [path/to/dae_gemm.hip]"""
+usage: python tools/check_gemm_asm.py [path/to/dae_gemm.hip] [-DNAME=VALUE ...]
+Arguments that start with "-" go to hipcc as they are: -DDAE_F16=1 checks the fp16 build."""
 import os
 import re
 import subprocess
@@ -15,7 +16,9 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "dae_rnn_news_recommendation_amd", "csrc", "dae_gemm.hip")
+flags = [a for a in sys.argv[1:] if a.startswith("-")]
+paths = [a for a in sys.argv[1:] if not a.startswith("-")]
+src = paths[0] if paths else os.path.join(ROOT, "dae_rnn_news_recommendation_amd", "csrc", "dae_gemm.hip")
 
 
 def regs(tok):
@@ -29,7 +32,7 @@ def regs(tok):
 def main():
     with tempfile.TemporaryDirectory() as d:
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-S",
-                               "--cuda-device-only", src, "-o", os.path.join(d, "k.s")], stderr=subprocess.DEVNULL)
+                               "--cuda-device-only"] + flags + [src, "-o", os.path.join(d, "k.s")], stderr=subprocess.DEVNULL)
         text = open(os.path.join(d, "k.s")).read()
     bad = 0
     checked = 0
