@@ -1,10 +1,9 @@
-// dae_api.hip -- extern "C" surface of libdae_hip.so (declared in include/dae_hip.h) and the whole-step
-// driver that enqueues one DAE training step (DenoisingAutoencoder._run_train_step's per-batch body,
-// autoencoder.py:223-245) as a fixed sequence of HIP kernels on one stream, with no host sync.
+// dae_api.hip -- extern "C" surface of libdae_hip.so (declared in include/dae_hip.h): the thin wrappers of the launchers, the plan's lifecycle,
+// options and profile, and the data-parallel entry points.  The step driver (dae_train_step, dae_encode_rows) is dae_step.hip.
 #include <stdarg.h>
 #include <new>
 
-#include "dae_kernels.h"
+#include "dae_plan.h"
 
 namespace dae {
 
@@ -88,101 +87,10 @@ extern "C" int dae_decode_loss(int32_t dtype, int32_t B, int32_t F, int32_t H, c
 // ------------------------------------------------------------------------------------------------
 // plan: sizes, workspace carving, step driver
 // ------------------------------------------------------------------------------------------------
-// per-kernel HIP-event timing slots of the step driver (bench.py's roofline leg)
-enum { PS_MEMSET = 0, PS_GATHER, PS_ENC_GEMM, PS_ENC_FIN, PS_LABEL, PS_GRAM, PS_MINER, PS_TRI_FIN, PS_SYM, PS_DECODE,
-       PS_COS_REDUCE, PS_STATS, PS_DH_GEMM, PS_DH_FIN, PS_DW_GEMM, PS_BIAS, PS_OPT, PS_COUNT };
+// names of the per-kernel HIP-event timing slots of the step driver (PS_*, dae_plan.h; bench.py's roofline leg)
 static const char* const kProfNames[PS_COUNT] = {"memset_xct", "gather", "encode_gemm", "encode_finish", "label_stats", "gram",
                                                  "miner", "triplet_finalize", "sym_scale", "decode_loss", "cos_reduce",
                                                  "step_stats", "dh_gemm", "dh_finish", "dw_gemm", "bias_grads", "opt_step"};
-
-struct dae_plan {
-    bool prof;
-    hipEvent_t ev0, ev1;
-    // profile mode 2 (queued): one event pair per launch taken from this pool, the host never waits between launches; the pairs are read
-    // when the pool cannot hold another step and by dae_plan_profile_read -- kernels and steps run back to back as they do un-profiled
-    enum { PROF_POOL = 256, PROF_STEP_MAX = 48 };
-    bool prof_queued;
-    bool prof_stamps;                 // profile mode 3: the pairs carry the dispatches' own begin / end timestamps (DAE_LAUNCH, dae_common.h)
-    int pev_used;
-    hipEvent_t pev[PROF_POOL];
-    int pev_slot[PROF_POOL / 2];
-    bool ev_dw_live;                  // ev_dw was recorded by the last dae_train_step (an event that never was recorded does not hold a waiter back)
-    hipEvent_t ev_dw;                 // recorded right behind the kernel that completes the W gradient (dae_plan_dw_event): a data-parallel
-                                      // caller starts its reduce-scatter from here, beside the step's tail kernel
-    bool sym_ride_ok;                 // Gs = a/Nv (G + G^T) computed by rider workgroups of the decode launch instead of its own launch
-    bool miner_order_ok;              // dispatch the batch_all workgroups by descending sweep cost (LabelJob::order)
-    int32_t* miner_order;
-    int32_t* cls_range;               // [1 + 2 Bpm]: sortedness flag + class range of every row (LabelJob::cls), the miner's range fast path
-    bool miner_ranges_ok;             // option "miner_ranges" = 0: always compact positives / negatives by ballots
-    double prof_ms[PS_COUNT];
-    int prof_n[PS_COUNT];
-    dae_config cfg;
-    dae_buffers b;
-    bool bound;
-    int F, H, Fp, Hp, Bmax, Bpm;     // Bpm = padded max batch (leading dimension of every [.. x batch] image)
-    int es;
-    int s_enc, s_dh, s_gram;
-    uint64_t ws_bytes;
-    // carved pointers
-    char *x, *xc, *xct, *h_lo, *h_t, *Gs, *delta2, *delta2_t, *delta1_t, *delta1_lo, *hcat_a, *hcat_b;
-    // split-bf16 mode (dae_config.dtype = DAE_BF16X3): every stored operand x of the gradient GEMMs is hi + lo, both bf16; the *_2 images are the lo parts
-    bool x3;
-    char *W_lo2, *Wt_lo2, *h_t2, *delta2_2, *delta2_t2, *delta1_t2;
-    char *x_2, *xct_2, *xc_2;         // ... and of the clean rows x / of x~^T / of x~ (dense input), used when the input values (or the corruption scale) are not exact in bf16
-    int s_enc3, s_dh3;               // split-K slice counts of the dense-input encode / dh GEMMs in split-bf16 mode (3 resp. 4-5 K segments)
-    // split-bf16 mode, the two lo product terms a CPU replay of the 20-step curve called droppable (tools/precision_study.py --per-term: cost 2.5e-5,
-    // triplet 4.4e-5).  Measured on the GPU against the frozen reference curve, dropping them leaves the gate: cost 7.0e-5, triplet 1.56e-4
-    // (profiles/r04_precision_terms.txt) -- so both stay ON; the options exist for that measurement (decode 57.9 -> 48.3 us without its term)
-    // -> generalised to one bit per lo product term (X3T_* in dae_kernels.h, option "x3_terms"; the legacy options "x3_dec_wlo" / "x3_dh_hlo" flip their bit).
-    // bf16 storage: all terms on.  fp16 storage (libdae_hip_f16.so): the two W terms alone (decode (h, W_lo), dh (delta2, W^T_lo)) -- no lo image of
-    // delta2 / delta2^T / h / delta1 is written or read (CPU replay of the 20-step curve: cost 1.4e-5, triplet 6.5e-5; profiles/r04_precision_fp16_study.txt)
-    uint32_t terms;
-    // 16-bit images of the back-propagated operands (delta2, delta2^T, Gs, delta1^T) hold op_scale * value, a power of two the consuming epilogues
-    // divide out (dh_finish: 1 / op_scale; the dW epilogue: OptEpi::gin): fp16's normal range ends at 6.1e-5 and delta2 ~ (y - x) / B, Gs ~ 1e-6 sit
-    // below it.  1 for bf16 storage and fp32.  Option "op_scale_log2".
-    float op_scale;
-    int dec_bn;                      // tile width of the decode kernel: decode_tile_n(dtype), or 128 in the 16-bit modes when the 64-column tiles would be more than
-                                     // DEC_WIDE_ROUNDS rounds of the chip's 768 slots (option "decode_bn" = 64 | 128 | 0 auto; before dae_plan_bind)
-    bool dw_pair_ok;                 // option "dw_pair": split-bf16 dW kernel streams x~^T resp. delta2^T_hi ONCE for the hi and lo image of delta1^T resp. h^T
-    bool xct2_clean;
-    bool enc_w32_ok;                 // option "encode_w32": bf16 mode encodes from the fp32 MASTER weights (h fp32-accurate); 0 = from W_lo
-    int w32_cols;                    // option "encode_w32_cols": 128 (default) or 64 H columns per workgroup of that kernel
-    bool gram_split;                 // Gram matrix as a 3-term split-bf16 MFMA GEMM (bf16 mode) instead of exact-fp32 MFMA
-    int dw_tr_mode;                  // option "dw_tr": the dW kernel reads x~ and delta2 ROW-MAJOR through transposing LDS reads (gemm_dw_pc<TRA>) -- the decode stores
-                                     // delta2 once (no delta2^T), the gathers write x~ instead of x~^T.  1 on, 0 off, -1 (default) = on for DENSE train sets only:
-                                     // measured (profiles/r05_ab_measurements.txt) -38 us per step at F = 50000 (the gather and the decode each write 90 MB less),
-                                     // but +3..5 us at the CSR shape of c2 (11 fragment-read instructions per k step instead of 6; its decode does not get faster)
-    bool gram64_ok;                  // option "gram64" (default 1): the split Gram on 64 x 64 tiles over the whole K, ONE slab (gram64_kernel); 0: 128 x 128 tiles, split-K
-    float *slabs, *h_f32, *D_slabs, *G, *rowloss_part, *dbv_part, *colsum_part, *cos_part, *cos_stats, *cw, *loss_part,
-        *dw_f32, *tri_scalars, *dh_extra, *rowsq_scratch, *tile_part, *zbuf;
-    bool cos_zstore_ok;               // option "cos_zstore" (default 1): the cosine decode's second pass reads the first pass's accumulators back instead of recomputing the GEMM
-    uint32_t *cnt_part, *role_cnt, *xc_bits, *x_bits;
-    bool xbits_ok;                   // binary CSR + bf16: the decode epilogue reads x as a bit image (option "x_bits" = 0 disables)
-    bool xct_clean;                  // x~^T holds only zeros (every step un-scatters what it wrote; see step_tail_kernel)
-    bool tail_ok;                    // option "tail" = 0: separate bias_grads / step_stats launches and a full memset per step (A/B)
-    bool fuse_opt_ok;                // option "fused_opt" = 0 keeps the separate optimizer kernel (A/B, equivalence tests)
-    bool label_enc_ok;               // option "label_with_encode" = 0: label statistics ride on the gather launch / their own
-    bool ce_literal;                 // option "ce_literal" = 1: cross_entropy always by the reference-literal formula
-    bool sparse_ok;                  // CSR input: fused corrupt + gather + encode on the stored entries (option "encode_sparse" = 0: dense MFMA GEMM)
-    bool bits_ok;                    // binary CSR + bf16: x~ handed to the encode GEMM as a bit image (dae_plan_set_option("encode_bits", 0) disables)
-    int32_t *dw_i32, *n_same;
-    int64_t *nvalid, *dw_i64;
-    uint64_t* acc;
-};
-
-// lo image of the row-major shadow: exists (and is kept current by every kernel that updates W) only while the decode's (h, W_lo) term is on
-static void* plan_w_lo2(const dae_plan* p) { return (p->x3 && (p->terms & X3T_DEC_WLO)) ? (void*)p->W_lo2 : nullptr; }
-
-// tile width the decode launch of this plan uses (see dae_plan::dec_bn); lo images of delta2 / valued x keep the 64-column kernel
-static int plan_dec_bn(const dae_plan* p) {
-    const int def = decode_tile_n(p->cfg.dtype);
-    if (p->es != 2) return def;
-    const bool res = p->x3 && (p->terms & (X3T_DH_D2LO | X3T_DW_D2LO | X3T_XV));
-    if (res) return def;
-    if (p->dec_bn == 64 || p->dec_bn == 128) return p->dec_bn;
-    const int64_t tiles64 = (int64_t)(p->Bpm / 128) * (p->Fp / 64);
-    return tiles64 > 4 * 768 ? 128 : def;             // F = 50000: 5474 tiles of 128 x 64 = 7.1 rounds of 768 slots -> 2737 wide tiles
-}
 
 static int auto_splits(int tiles, int ktiles) {
     int s = 384 / (tiles > 0 ? tiles : 1);
@@ -192,6 +100,13 @@ static int auto_splits(int tiles, int ktiles) {
     if (s > cap) s = cap;
     if (s < 1) s = 1;
     return s;
+}
+// slab count of the Gram matrix: ONE for the 64 x 64-tile kernel over the whole K (gram64_ok), else split-K slices of the 128 x 128 kernel
+static int plan_gram_splits(const dae_plan* p) {
+    if (p->gram64_ok) return 1;
+    const int kt = p->Hp * 4 / 128;
+    const int s = p->cfg.gram_splits > 0 ? p->cfg.gram_splits : auto_splits((p->Bpm / 128) * (p->Bpm / 128), kt);
+    return s > kt ? kt : s;
 }
 
 // split-bf16 mode on dense-ndarray input: slice counts of the 3-segment encode and the 4-5-segment dh contraction (see dae_plan_create)
@@ -295,8 +210,6 @@ extern "C" int dae_plan_create(const dae_config* cfg, dae_plan** out) {
     const int kt_f = p->Fp * p->es / 128;
     p->s_enc = cfg->encode_splits > 0 ? cfg->encode_splits : auto_splits(tiles_bh, kt_f);
     p->s_dh = cfg->dh_splits > 0 ? cfg->dh_splits : auto_splits(tiles_bh, kt_f);
-    const int tiles_bb = (p->Bpm / 128) * (p->Bpm / 128);
-    p->s_gram = cfg->gram_splits > 0 ? cfg->gram_splits : auto_splits(tiles_bb, p->Hp * 4 / 128);
     // large dense-input shapes: the 256 x 256 kernel picks its own slice count (one workgroup per CU)
     if (cfg->encode_splits <= 0) if (const int w = gemm_w8_splits(cfg->dtype, p->Bpm, p->Hp, kt_f)) p->s_enc = w;
     if (cfg->dh_splits <= 0) if (const int w = gemm_w8_splits(cfg->dtype, p->Bpm, p->Hp, kt_f + p->Bpm * p->es / 128)) p->s_dh = w;
@@ -311,11 +224,10 @@ extern "C" int dae_plan_create(const dae_config* cfg, dae_plan** out) {
     if (kF16 && p->es == 2) { float sc = 1.f; while (sc * 2.f <= 16.f * (float)p->Bmax && sc < 16384.f) sc *= 2.f; p->op_scale = sc; }
     p->dw_pair_ok = true;
     plan_x3_splits(p);
-    if (p->s_gram > p->Hp * 4 / 128) p->s_gram = p->Hp * 4 / 128;
     p->gram_split = (cfg->dtype == DAE_BF16) && (p->x3 || cfg->triplet == DAE_TRIPLET_BATCH_ALL || cfg->triplet == DAE_TRIPLET_BATCH_HARD);   // x3: hcat_a also holds the row-major h_lo
     p->dw_tr_mode = -1;
     p->gram64_ok = p->gram_split && cfg->gram_splits <= 0;        // (an explicit split count keeps the 128 x 128 split-K form)
-    if (p->gram64_ok) p->s_gram = 1;
+    p->s_gram = plan_gram_splits(p);
     p->ws_bytes = carve(p, nullptr);
     // code-path choices below are plan state (dae_plan_set_option), never read from the environment
     p->fuse_opt_ok = true;
@@ -342,6 +254,14 @@ extern "C" void dae_plan_destroy(dae_plan* p) {
     for (int i = 0; i < dae_plan::PROF_POOL; ++i) if (p->pev[i]) (void)hipEventDestroy(p->pev[i]);
     if (p->ev_dw) (void)hipEventDestroy(p->ev_dw);
     delete p;
+}
+
+// the options that change the workspace layout (and what of it, for the error message); NULL for every other name
+static const char* relayout_reason(const char* name) {
+    if (!strcmp(name, "x3_dec_wlo") || !strcmp(name, "x3_dh_hlo") || !strcmp(name, "x3_terms")) return "split-K plan (workspace layout)";
+    if (!strcmp(name, "gram64")) return "workspace layout (slab count)";
+    if (!strcmp(name, "decode_bn") || !strcmp(name, "gram_fp32")) return "workspace layout";
+    return nullptr;
 }
 
 // Code-path choices of a plan (A/B measurements and equivalence tests).  Every option selects between implementations of
@@ -371,42 +291,31 @@ extern "C" int dae_plan_set_option(dae_plan* p, const char* name, int32_t value)
     else if (!strcmp(name, "miner_pack")) set_miner_pack(on);        // process-wide (the launcher's choice), like dae_set_glds
     else if (!strcmp(name, "miner_tile")) set_miner_tile(on);        // process-wide: 0 = the former wave-per-positive batch_all kernel
     else if (!strcmp(name, "sym_in_decode")) p->sym_ride_ok = on;
-    else if (!strcmp(name, "x3_dec_wlo") || !strcmp(name, "x3_dh_hlo") || !strcmp(name, "x3_terms")) {
-        DAE_CHECK_ARG(!p->bound, "plan_set_option: %s changes the split-K plan (workspace layout), set it before dae_plan_bind", name);
-        if (name[3] == 't') { DAE_CHECK_ARG(value >= 0 && (uint32_t)value <= X3T_ALL, "plan_set_option: x3_terms is a mask of the X3T_* bits (0..%u)", (unsigned)X3T_ALL); p->terms = (uint32_t)value; }
-        else { const uint32_t bit = name[4] == 'e' ? X3T_DEC_WLO : X3T_DH_HLO; p->terms = on ? (p->terms | bit) : (p->terms & ~bit); }
-        plan_x3_splits(p);
-        p->ws_bytes = carve(p, nullptr);
-    }
-    else if (!strcmp(name, "decode_bn")) {
-        DAE_CHECK_ARG(!p->bound, "plan_set_option: decode_bn changes the workspace layout, set it before dae_plan_bind");
-        DAE_CHECK_ARG(value == 0 || value == 64 || value == 128, "plan_set_option: decode_bn is 0 (auto), 64 or 128");
-        p->dec_bn = value;
-        p->ws_bytes = carve(p, nullptr);
-    }
     else if (!strcmp(name, "op_scale_log2")) {
         DAE_CHECK_ARG(value >= 0 && value <= 20, "plan_set_option: op_scale_log2 in 0..20");
         DAE_CHECK_ARG(p->es == 2, "plan_set_option: op_scale_log2 applies to the 16-bit modes");
         p->op_scale = (float)(1u << value);
     }
-    else if (!strcmp(name, "gram64")) {
-        DAE_CHECK_ARG(!p->bound, "plan_set_option: gram64 changes the workspace layout (slab count), set it before dae_plan_bind");
-        p->gram64_ok = on && p->gram_split;
-        const int tiles_bb = (p->Bpm / 128) * (p->Bpm / 128);
-        p->s_gram = p->gram64_ok ? 1 : (p->cfg.gram_splits > 0 ? p->cfg.gram_splits : auto_splits(tiles_bb, p->Hp * 4 / 128));
-        if (p->s_gram > p->Hp * 4 / 128) p->s_gram = p->Hp * 4 / 128;
-        p->ws_bytes = carve(p, nullptr);
-    }
-    else if (!strcmp(name, "gram_fp32")) {
-        DAE_CHECK_ARG(!p->bound, "plan_set_option: gram_fp32 changes the workspace layout, set it before dae_plan_bind");
-        DAE_CHECK_ARG(!p->x3, "plan_set_option: gram_fp32 is not available in split-bf16 mode (its Gram operands double as the row-major h images)");
-        p->gram_split = !on && p->cfg.dtype == DAE_BF16 && (p->cfg.triplet == DAE_TRIPLET_BATCH_ALL || p->cfg.triplet == DAE_TRIPLET_BATCH_HARD);
-        if (!p->gram_split && p->gram64_ok) {          // the exact-fp32 Gram runs on the 128 x 128 split-K kernel: its slab count again
-            p->gram64_ok = false;
-            const int tiles_bb = (p->Bpm / 128) * (p->Bpm / 128);
-            p->s_gram = p->cfg.gram_splits > 0 ? p->cfg.gram_splits : auto_splits(tiles_bb, p->Hp * 4 / 128);
-            if (p->s_gram > p->Hp * 4 / 128) p->s_gram = p->Hp * 4 / 128;
+    else if (const char* why = relayout_reason(name)) {      // the options that change the workspace layout: before dae_plan_bind only, then re-plan and re-carve
+        DAE_CHECK_ARG(!p->bound, "plan_set_option: %s changes the %s, set it before dae_plan_bind", name, why);
+        if (!strcmp(name, "x3_terms")) {
+            DAE_CHECK_ARG(value >= 0 && (uint32_t)value <= X3T_ALL, "plan_set_option: x3_terms is a mask of the X3T_* bits (0..%u)", (unsigned)X3T_ALL);
+            p->terms = (uint32_t)value;
+        } else if (name[0] == 'x') {                         // the legacy options flip their bit of the mask
+            const uint32_t bit = !strcmp(name, "x3_dec_wlo") ? X3T_DEC_WLO : X3T_DH_HLO;
+            p->terms = on ? (p->terms | bit) : (p->terms & ~bit);
+        } else if (!strcmp(name, "decode_bn")) {
+            DAE_CHECK_ARG(value == 0 || value == 64 || value == 128, "plan_set_option: decode_bn is 0 (auto), 64 or 128");
+            p->dec_bn = value;
+        } else if (!strcmp(name, "gram64")) {
+            p->gram64_ok = on && p->gram_split;
+        } else {                                             // gram_fp32; the exact-fp32 Gram runs on the 128 x 128 split-K kernel
+            DAE_CHECK_ARG(!p->x3, "plan_set_option: gram_fp32 is not available in split-bf16 mode (its Gram operands double as the row-major h images)");
+            p->gram_split = !on && p->cfg.dtype == DAE_BF16 && (p->cfg.triplet == DAE_TRIPLET_BATCH_ALL || p->cfg.triplet == DAE_TRIPLET_BATCH_HARD);
+            if (!p->gram_split) p->gram64_ok = false;
         }
+        plan_x3_splits(p);
+        p->s_gram = plan_gram_splits(p);
         p->ws_bytes = carve(p, nullptr);
     } else {
         set_error("plan_set_option: unknown option '%s'", name);
@@ -415,14 +324,13 @@ extern "C" int dae_plan_set_option(dae_plan* p, const char* name, int32_t value)
     return 0;
 }
 
-static int prof_flush(dae_plan* p);
 extern "C" int dae_plan_profile(dae_plan* p, int32_t enable) {
     DAE_CHECK_ARG(p, "plan_profile: null plan");
     if (enable && !p->ev0) {
         DAE_CHECK_HIP(hipEventCreate(&p->ev0));
         DAE_CHECK_HIP(hipEventCreate(&p->ev1));
     }
-    const int rf = p->pev_used ? prof_flush(p) : 0;     // pairs still queued belong to the mode being left; a failed read is reported, the switch still happens
+    const int rf = p->pev_used ? plan_prof_flush(p) : 0;     // pairs still queued belong to the mode being left; a failed read is reported, the switch still happens
     if ((enable == 2 || enable == 3) && !p->pev[0])
         for (int i = 0; i < dae_plan::PROF_POOL; ++i) DAE_CHECK_HIP(hipEventCreate(&p->pev[i]));
     if (enable) { memset(p->prof_ms, 0, sizeof(p->prof_ms)); memset(p->prof_n, 0, sizeof(p->prof_n)); }
@@ -435,7 +343,7 @@ extern "C" int dae_plan_profile(dae_plan* p, int32_t enable) {
 
 extern "C" int dae_plan_profile_read(const dae_plan* p, int32_t max_slots, double* ms_total, int32_t* counts) {
     DAE_CHECK_ARG(p && ms_total && counts, "plan_profile_read: null argument");
-    if (int rf = prof_flush(const_cast<dae_plan*>(p))) return rf;
+    if (int rf = plan_prof_flush(const_cast<dae_plan*>(p))) return rf;
     for (int i = 0; i < PS_COUNT && i < max_slots; ++i) { ms_total[i] = p->prof_ms[i]; counts[i] = p->prof_n[i]; }
     return PS_COUNT <= max_slots ? 0 : 1;
 }
@@ -464,8 +372,7 @@ extern "C" int dae_plan_bind(dae_plan* p, const dae_buffers* bufs) {
 
 extern "C" int dae_plan_sync_shadows(dae_plan* p, void* stream) {
     DAE_CHECK_ARG(p && p->bound, "plan_sync_shadows: plan not bound");
-    return launch_opt_step(p->cfg.opt, 0.f, 0.f, 1.f, p->b.W, p->b.bh, p->b.bv, p->b.grad, p->b.opt_s1, p->b.opt_s2, p->Fp, p->Hp,
-                           p->cfg.dtype, p->b.W_lo, p->b.Wt_lo, plan_w_lo2(p), p->x3 ? p->Wt_lo2 : nullptr, /*apply=*/0, stream);
+    return plan_opt_step(p, 0.f, 1.f, /*apply=*/0, stream);
 }
 
 extern "C" void* dae_plan_buffer(dae_plan* p, const char* name) {
@@ -487,73 +394,8 @@ extern "C" int dae_plan_info(const dae_plan* p, int32_t* out8) {
     return 0;
 }
 
-static int gather_batch(dae_plan* p, const int64_t* indptr, const int32_t* indices, const float* values, const float* dense,
-                        int64_t ld_dense, const int32_t* row_idx, int B, void* x, void* xc, void* xct, float* rowsq,
-                        int corr_mode, const uint32_t* keep_bits, uint64_t seed, uint32_t rng_stream, float corr_frac,
-                        float scale, void* stream, uint32_t* xc_bits = nullptr, const LabelJob* label_job = nullptr,
-                        uint32_t* x_bits = nullptr, void* x2 = nullptr) {
-    if (indptr)
-        return launch_gather_csr(indptr, indices, values, row_idx, B, p->F, p->cfg.dtype, x, xc, p->Fp, xct, p->Bpm, rowsq, corr_mode,
-                                 keep_bits, seed, rng_stream, corr_frac, scale, xc_bits, p->Fp / 32, label_job, (hipStream_t)stream, x_bits, x2);
-    DAE_CHECK_ARG(dense, "step: no train set bound");
-    return dae_gather_dense(dense, ld_dense, row_idx, B, p->F, p->cfg.dtype, x, xc, p->Fp, xct, p->Bpm, rowsq, p->rowsq_scratch,
-                            corr_mode, keep_bits, seed, rng_stream, corr_frac, scale, stream);
-}
-// split-bf16 mode, dense input: the lo images of x / x~ / x~^T (a second pass over the fp32 rows with the same keep decisions)
-static int gather_dense_lo(dae_plan* p, const float* dense, int64_t ld_dense, const int32_t* row_idx, int B, void* x2, void* xc2, void* xct2,
-                           int corr_mode, const uint32_t* keep_bits, uint64_t seed, uint32_t rng_stream, float corr_frac, float scale, void* stream) {
-    return launch_gather_dense(dense, ld_dense, row_idx, B, p->F, p->cfg.dtype, x2, xc2, p->Fp, xct2, p->Bpm, nullptr, nullptr, corr_mode, keep_bits,
-                               seed, rng_stream, corr_frac, scale, stream, 1);
-}
-
-#define RC(expr) do { if (int rc__ = (expr)) return rc__; } while (0)
-// K5: D = h h^T (triplet_loss_utils.py:93,219).  fp32 mode: exact-fp32 MFMA.  bf16 mode: split-bf16 (h = hi + lo,
-// three bf16 MFMA products concatenated along K = 3*Hp), ~2^-17 relative error, 16x the MFMA rate.
-// learning rate handed to the optimizer kernels (Adam: lr_t = lr * sqrt(1-b2^t)/(1-b1^t), TF AdamOptimizer)
-static float plan_lr(const dae_plan* p, int adam_t) {
-    float lr = p->cfg.learning_rate;
-    if (p->cfg.opt == DAE_OPT_ADAM) {
-        const double t = adam_t < 1 ? 1 : adam_t;
-        lr = (float)((double)lr * sqrt(1.0 - pow(0.999, t)) / (1.0 - pow(0.9, t)));
-    }
-    return lr;
-}
-static int launch_gram(dae_plan* p, int Bp, int Hp, int64_t dslab, hipStream_t st) {
-    if (p->gram_split && p->gram64_ok && p->s_gram == 1) return launch_gram64(p->hcat_a, p->hcat_b, Bp, Hp, p->D_slabs, st);
-    if (p->gram_split)
-        return launch_gemm_f32out(DAE_BF16, Bp, Bp, p->hcat_a, 3 * Hp, p->hcat_b, 3 * Hp, 3 * Hp, nullptr, 0, nullptr, 0, 0, p->D_slabs, Bp,
-                                  p->s_gram, dslab, st, GEMM_ROLE_GRAM);
-    return launch_gemm_f32out(DAE_F32, Bp, Bp, p->h_f32, Hp, p->h_f32, Hp, Hp, nullptr, 0, nullptr, 0, 0, p->D_slabs, Bp, p->s_gram, dslab, st,
-                              GEMM_ROLE_GRAM);
-}
-// PROF(slot, call): in profile mode time the call with HIP events ON THE STEP'S STREAM and accumulate the elapsed GPU time of that slot
-// (dae_plan_profile, include/dae_hip.h).  Mode 1: an event pair around the call and a host wait behind it.  Mode 2 (q__): a pair of the
-// plan's pool around the call, read later by prof_flush.  Mode 3 (k__): the pool is handed to DAE_LAUNCH (dae_common.h) for the duration
-// of the call, every kernel launch inside takes a pair and has it stamped by its own dispatch; memsets keep the mode-2 form.
-#define PROF(slot, expr)                                                            \
-    do {                                                                            \
-        const bool q__ = p->prof && p->prof_queued && p->pev_used + 2 <= dae_plan::PROF_POOL; \
-        const bool k__ = q__ && p->prof_stamps && (slot) != PS_MEMSET;              \
-        if (k__) g_lt = LaunchTimer{p->pev, &p->pev_used, p->pev_slot, dae_plan::PROF_POOL, (slot), true}; \
-        else if (q__) DAE_CHECK_HIP(hipEventRecord(p->pev[p->pev_used], st));       \
-        else if (p->prof) DAE_CHECK_HIP(hipEventRecord(p->ev0, st));                \
-        const int rc_prof__ = (expr);                                               \
-        if (k__) g_lt.pool = nullptr;                                               \
-        if (rc_prof__) return rc_prof__;                                            \
-        if (k__) break;                     /* the launches took their pairs */     \
-        if (q__) {                                                                  \
-            DAE_CHECK_HIP(hipEventRecord(p->pev[p->pev_used + 1], st));             \
-            p->pev_slot[p->pev_used / 2] = (slot) | 0x100; p->pev_used += 2;        \
-        } else if (p->prof) {                                                       \
-            DAE_CHECK_HIP(hipEventRecord(p->ev1, st));                              \
-            DAE_CHECK_HIP(hipEventSynchronize(p->ev1));                             \
-            float ms__ = 0.f;                                                       \
-            DAE_CHECK_HIP(hipEventElapsedTime(&ms__, p->ev0, p->ev1));              \
-            p->prof_ms[slot] += ms__; p->prof_n[slot] += 1;                         \
-        }                                                                           \
-    } while (0)
 // queued profile mode: wait for the step's last pair, then add every pair to its slot
-static int prof_flush(dae_plan* p) {
+int plan_prof_flush(dae_plan* p) {
     if (!p->prof_queued || p->pev_used == 0) return 0;
     const int used = p->pev_used;
     p->pev_used = 0;                                    // (also on the error paths below: a failed read must not poison the next profile call)
@@ -566,336 +408,10 @@ static int prof_flush(dae_plan* p) {
     }
     return 0;
 }
-static int memset_async(void* ptr, size_t bytes, hipStream_t st) {
-    DAE_CHECK_HIP(hipMemsetAsync(ptr, 0, bytes, st));
-    return 0;
-}
-
-static int train_step_body(dae_plan* p, const dae_step* s, void* stream);
-extern "C" int dae_train_step(dae_plan* p, const dae_step* s, void* stream) {
-    const int rc = train_step_body(p, s, stream);
-    if (p && p->prof_queued && p->pev_used + dae_plan::PROF_STEP_MAX > dae_plan::PROF_POOL) { const int rf = prof_flush(p); return rc ? rc : rf; }
-    return rc;
-}
-static int train_step_body(dae_plan* p, const dae_step* s, void* stream) {
-    DAE_CHECK_ARG(p && p->bound && s, "train_step: plan not bound / null step");
-    DAE_CHECK_ARG(s->row_idx && s->B > 0 && s->B <= p->Bmax, "train_step: batch %d outside (0, %d]", s ? s->B : -1, p->Bmax);
-    const dae_config& c = p->cfg;
-    const bool explicit3 = (c.triplet == 3);
-    DAE_CHECK_ARG(c.triplet == DAE_TRIPLET_NONE || explicit3 || s->labels, "train_step: labels required for triplet mining");
-    DAE_CHECK_ARG(!explicit3 || s->B % 3 == 0, "train_step: explicit-triplet batch must stack org/pos/neg (B %% 3 == 0)");
-    DAE_CHECK_ARG(s->stats, "train_step: stats pointer required");
-    hipStream_t st = (hipStream_t)stream;
-    const int B = s->B, Bp = (int)pad128(B), F = p->F, H = p->H, Fp = p->Fp, Hp = p->Hp, ldB = p->Bpm, dt = c.dtype;
-    const bool is_cos = c.loss_func == DAE_LOSS_COSINE;
-    const bool backward = s->phase != 2;
-    // phases 4 / 5 split the step around an EXTERNAL miner (data parallel with global-batch mining, dp.GlobalMiner): phase 4
-    // stops after the encode (h_f32 / h_lo / h_t and the side images stay in the workspace); the caller mines over the
-    // all-gathered batch and writes the row weights (cw), the triplet scalars and d(triplet)/dh (dh_extra) into the plan's
-    // buffers; phase 5 resumes at the decode and ends like phase 1 (gradients in the flat buffer).
-    const bool h_only = s->phase == 4, resume = s->phase == 5, ext_mine = h_only || resume;
-
-    // 1-2. corrupt + gather  (K0/K1 front half)
-    // x~^T: the CSR gather only scatters kept entries, so the image must be zero beforehand.  The step tail un-scatters
-    // exactly what was written, so the 18 MB memset runs once (or after a failed / foreign step); the dense gather
-    // overwrites whole tiles and never needs it.
-    const bool csr_in = s->c_indptr || p->b.indptr;
-    // label statistics (cw, N_valid, data weights) depend on the labels alone: they ride on the CSR gather launch
-    LabelJob lj{s->labels, B, Bp, c.triplet, p->nvalid, p->dw_i64, p->cw, c.alpha, p->tri_scalars, p->miner_order_ok ? p->miner_order : nullptr,
-                p->miner_ranges_ok ? p->cls_range : nullptr};
-    // ... on the encode GEMM's launch when that grid leaves a CU free (else on the CSR gather's, else their own)
-    const bool label_with_encode = p->tail_ok && !explicit3 && !ext_mine && Bp <= 1024 && p->label_enc_ok;
-    const bool label_in_gather = p->tail_ok && !label_with_encode && !explicit3 && !ext_mine && !s->c_indptr && p->b.indptr && Bp <= 1024;
-    const bool tail = p->tail_ok;
-    float* rowsq = is_cos ? p->cos_stats : nullptr;
-    bool use_bits = false;
-    // binary CSR train set in bf16 mode: the clean rows reach the decode epilogue as a bit image (1.1 MB, not 18 MB)
-    const bool use_xbits = p->xbits_ok && p->b.indptr && !p->b.values;
-    const bool use_sparse = p->sparse_ok && csr_in;
-    const bool dense_in = !csr_in && p->b.dense;
-    // phase 0 / 3 in bf16 mode: the optimizer runs in the dW GEMM's epilogue (phase 3 does not materialise the W gradient);
-    // phase 1 / 5 (data parallel) in bf16 mode: the same kernel in its gradient-only form when the shape fits it
-    const bool apply_now = (s->phase == 0 || s->phase == 3);
-    const bool fuse_opt0 = backward && apply_now && dt == DAE_BF16 && p->fuse_opt_ok;
-    const bool src_binary = s->c_indptr ? !s->c_values : (p->b.indptr && !p->b.values);
-    const bool x3 = p->x3;
-    const uint32_t T = x3 ? p->terms : 0u;                   // lo product terms that are multiplied (X3T_*)
-    const float osc = p->es == 2 ? p->op_scale : 1.f, oinv = 1.f / osc;   // operand scale of the 16-bit delta images (a power of two)
-    // split-bf16 mode: the fused dW + optimizer kernel exists for shapes of at most one 160 x 128 tile per CU; larger shapes (and the
-    // data-parallel gradient-only phases) take the N-segment dW GEMM to memory + the optimizer kernel that writes all four shadows
-    const bool fuse_opt = fuse_opt0 && (!x3 || dw_x3_fits(Fp, Hp, Bp));
-    // (split-bf16 mode: the gradient-only form of the same N-segment kernel, fp32 gradient to the flat buffer)
-    const bool dw_pc_grad = backward && !apply_now && dt == DAE_BF16 && p->fuse_opt_ok && (x3 ? dw_x3_fits(Fp, Hp, Bp) : dw_grad_fits(Fp, Hp, Bp));
-    // contractions over the BATCH (dW's K, the Gs.h segment of dh) stop at the last 64-deep K tile that holds a real row: the images are zero beyond B, and
-    // B = 800 pads to 896 = 14 K tiles of which 13 hold data
-    const int Bk = (B + 63) / 64 * 64;
-    // Transposed-A dW (gemm_dw_pc<TRA>): x~ and delta2 are consumed ROW-MAJOR [batch x feature], so delta2^T is never stored and the gathers write x~ (the
-    // CSR scatter lands in one 20 KB row per batch row instead of one line per entry).  Needs the 160 x 128 kernel and the two plain K segments
-    // (16-bit modes without lo images of x~ / delta2 / delta1 / h in dW: f16x2, bf16, f16); decided from plan state and shapes only, so that the
-    // phase-4 / phase-5 halves of an externally mined step agree
-    const bool dw_plain2 = !x3 || !(T & (X3T_DW_D1LO | X3T_DW_HLO | X3T_DW_D2LO | X3T_XV));
-    const bool dw_tr = (p->dw_tr_mode == 1 || (p->dw_tr_mode < 0 && dense_in)) && dt == DAE_BF16 && backward && (fuse_opt || dw_pc_grad) && dw_plain2 && (use_sparse || dense_in) &&
-                       (x3 || dw_pc_taken(Fp, Hp, Bk, Bk, !fuse_opt));
-    if (x3) {
-        // split-bf16 mode: CSR input encoded from the fp32 master weights (h is fp32-accurate and its hi / lo images come from the same
-        // launch); x~ must be exact in bf16 (binary data, or values with <= 8 significant bits).  Every phase: the data-parallel
-        // exchange of this mode moves fp32 gradients and fp32 master rows (dp.ShardedExchange), so the master is current on every rank
-        // (h from the 16-bit hi image of W alone was measured in round 6, profiles/r06_ab_measurements.txt: the same 26.8 us -- the kernel is not bound by its
-        //  W-row bytes -- and the triplet leg of c2 leaves the gate at step 5 (1.5e-3): refused, not offered)
-        DAE_CHECK_ARG((use_sparse && p->enc_w32_ok) || dense_in, "train_step: split-bf16 mode needs the fp32-master sparse encode (CSR input) or a dense train set");
-        DAE_CHECK_ARG(!p->b.grad_lo, "train_step: split-bf16 mode exchanges fp32 gradients (no bf16 gradient image)");
-    }
-    // split-bf16 mode with VALUED input (tf-idf, salt-and-pepper copies, decay noise's scale factor): x~ = scale * v is not exact in bf16, so
-    // x~^T and the clean rows x get lo images too (xct_2, x_2) and the dW contraction walks 6 segments; binary data with a bf16-exact scale
-    // (masking noise: 1.0) needs neither
-    bool x3_vals = false;
-    if (x3) {
-        uint32_t u; memcpy(&u, &s->scale, 4);
-        x3_vals = (T & X3T_XV) && (!src_binary || (u & 0xffffu) != 0u || (p->b.indptr && p->b.values) || dense_in);
-    }
-    const bool x2_clean = x3 && (T & X3T_XV) && !use_xbits && (p->b.values || p->b.dense);    // the clean rows get a lo image (valued CSR / dense train set)
-    if (!resume && backward && csr_in) {
-        if (!(tail && p->xct_clean)) PROF(PS_MEMSET, memset_async(p->xct, (size_t)Fp * ldB * p->es, st));
-        if (x3_vals && !(tail && p->xct2_clean)) PROF(PS_MEMSET, memset_async(p->xct_2, (size_t)Fp * ldB * 2, st));
-    }
-    if (backward) { p->xct_clean = false; if (x3_vals) p->xct2_clean = false; }
-    const int64_t slab = (int64_t)Bp * Hp;
-    int enc_label_done = 0;
-    bool labels_done = ext_mine;               // label statistics already produced by a workgroup of an earlier launch (or by the caller)
-    if (resume) {
-        // h and the side images are those of the preceding phase-4 call
-    } else if (use_sparse) {
-        // CSR input: corrupt + gather + encode in one launch on the stored entries (tf.sparse.matmul, autoencoder.py:377,389);
-        // the dense x~ image is never formed.  The clean rows reach the decode epilogue as a bit image written by the same
-        // launch (binary data) or as a dense tile from the gather kernel (valued data / explicitly corrupted copy).
-        const bool w32 = p->enc_w32_ok && dt == DAE_BF16;   // (a sharded-optimizer exchange turns the option off: only W_lo is current on every rank)
-        // the encode launch also emits the clean-row images, unless their LDS rows do not fit (e.g. 50000 features)
-        const bool own_clean = !s->c_indptr && use_xbits && encode_csr_lds_bytes(dt, w32, p->w32_cols, Fp / 32) <= 64 * 1024;
-        if (!own_clean)
-            PROF(PS_GATHER, gather_batch(p, p->b.indptr, p->b.indices, p->b.values, p->b.dense, p->b.ld_dense, s->row_idx, B,
-                            use_xbits ? nullptr : p->x, nullptr, nullptr, rowsq, DAE_CORR_NONE, nullptr, 0, 0, 0.f, 1.f, stream, nullptr, nullptr,
-                            use_xbits ? p->x_bits : nullptr, (x2_clean && p->b.values) ? p->x_2 : nullptr));
-        // a DENSE train set with an explicitly corrupted CSR copy (salt-and-pepper): the clean rows' lo image comes from the dense rows
-        if (!own_clean && x2_clean && p->b.dense && !p->b.indptr)
-            PROF(PS_GATHER, gather_dense_lo(p, p->b.dense, p->b.ld_dense, s->row_idx, B, p->x_2, nullptr, nullptr, DAE_CORR_NONE, nullptr, 0, 0, 0.f, 1.f, stream));
-        EncCsrLaunch q;
-        memset(&q, 0, sizeof(q));
-        q.indptr = s->c_indptr ? s->c_indptr : p->b.indptr; q.indices = s->c_indptr ? s->c_indices : p->b.indices;
-        q.values = s->c_indptr ? s->c_values : p->b.values; q.row_idx = (s->c_indptr && s->c_row_idx) ? s->c_row_idx : s->row_idx; q.B = B; q.F = F; q.H = H; q.dtype = dt;
-        q.W = w32 ? (const void*)p->b.W : (const void*)p->b.W_lo; q.w_f32 = w32 ? 1 : 0; q.w32_cols = p->w32_cols; q.ldw = Hp; q.bh = p->b.bh; q.enc_act = c.enc_act;
-        q.corr_mode = s->c_indptr ? DAE_CORR_NONE : s->corr_mode; q.keep_bits = s->keep_bits; q.seed = s->seed; q.rng_stream = s->rng_stream;
-        q.corr_frac = s->corr_frac; q.scale = s->scale;
-        q.h_f32 = p->h_f32; q.h_lo = p->h_lo; q.ldh = Hp; q.h_t = p->h_t; q.ldht = ldB;
-        q.hcat_a = p->gram_split ? p->hcat_a : nullptr; q.hcat_b = p->gram_split ? p->hcat_b : nullptr;
-        q.x_bits = own_clean ? p->x_bits : nullptr; q.ldxb = Fp / 32; q.xct = backward ? p->xct : nullptr; q.ldt = dw_tr ? Fp : ldB;
-        q.xct_rm = dw_tr ? 1 : 0;
-        q.rowsq = own_clean ? rowsq : nullptr;
-        q.h_t2 = (T & (X3T_DH_HLO | X3T_DW_HLO)) ? p->h_t2 : nullptr;
-        q.xct2 = (x3_vals && backward) ? p->xct_2 : nullptr;
-        q.label_job = label_with_encode ? &lj : nullptr;
-        PROF(PS_ENC_GEMM, launch_encode_csr(q, st));
-        labels_done = label_with_encode;
-    } else {
-        if (s->c_indptr) {   // an explicitly corrupted copy of the train set (salt&pepper, host-side noise)
-            PROF(PS_GATHER, gather_batch(p, p->b.indptr, p->b.indices, p->b.values, p->b.dense, p->b.ld_dense, s->row_idx, B, use_xbits ? nullptr : p->x,
-                            nullptr, nullptr, rowsq, DAE_CORR_NONE, nullptr, 0, 0, 0.f, 1.f, stream, nullptr, nullptr, use_xbits ? p->x_bits : nullptr));
-            PROF(PS_GATHER, gather_batch(p, s->c_indptr, s->c_indices, s->c_values, nullptr, 0, s->c_row_idx ? s->c_row_idx : s->row_idx, B, nullptr, p->xc,
-                            backward ? p->xct : nullptr, nullptr, DAE_CORR_NONE, nullptr, 0, 0, 0.f, s->scale, stream));
-        } else {
-            // binary CSR, unit scale, bf16: the corrupted batch goes to the encode GEMM as a BIT image (1.1 MB, not 18 MB of bf16)
-            use_bits = p->bits_ok && p->b.indptr && !p->b.values && s->scale == 1.0f;
-            PROF(PS_GATHER, gather_batch(p, p->b.indptr, p->b.indices, p->b.values, p->b.dense, p->b.ld_dense, s->row_idx, B,
-                            use_xbits ? nullptr : p->x, use_bits ? nullptr : p->xc, (backward && !dw_tr) ? p->xct : nullptr, rowsq, s->corr_mode, s->keep_bits,
-                            s->seed, s->rng_stream, s->corr_frac, s->scale, stream, use_bits ? p->xc_bits : nullptr, label_in_gather ? &lj : nullptr,
-                            use_xbits ? p->x_bits : nullptr));
-        }
-        if (x3 && dense_in && (T & (X3T_XV | X3T_ENC_XLO)))
-            PROF(PS_GATHER, gather_dense_lo(p, p->b.dense, p->b.ld_dense, s->row_idx, B, (T & X3T_XV) ? p->x_2 : nullptr, (T & X3T_ENC_XLO) ? p->xc_2 : nullptr,
-                                            (backward && (T & X3T_XV)) ? p->xct_2 : nullptr, s->corr_mode,
-                                            s->keep_bits, s->seed, s->rng_stream, s->corr_frac, s->scale, stream));
-        // 3-4. encode (K1/K2)
-        if (x3 && dense_in) {     // z1 = x~ W as (x~_hi, W^T_hi) (x~_hi, W^T_lo) (x~_lo, W^T_hi)
-            const GemmSegDesc es3[3] = {{p->xc, Fp, p->b.Wt_lo, Fp, Fp}, {p->xc, Fp, p->Wt_lo2, Fp, (T & X3T_ENC_WLO) ? Fp : 0},
-                                        {p->xc_2, Fp, p->b.Wt_lo, Fp, (T & X3T_ENC_XLO) ? Fp : 0}};
-            PROF(PS_ENC_GEMM, launch_gemm_f32out_n(dt, Bp, Hp, es3, 3, p->slabs, Hp, p->s_enc3, slab, st, GEMM_ROLE_ENCODE,
-                                                   label_with_encode ? &lj : nullptr, label_with_encode ? &enc_label_done : nullptr));
-        } else if (use_bits)
-            PROF(PS_ENC_GEMM, launch_encode_bits(Bp, Hp, Fp, p->xc_bits, Fp / 32, p->b.Wt_lo, Fp, p->slabs, Hp, p->s_enc, slab, st,
-                                                 label_with_encode ? &lj : nullptr, label_with_encode ? &enc_label_done : nullptr));
-        else
-            PROF(PS_ENC_GEMM, launch_gemm_f32out(dt, Bp, Hp, p->xc, Fp, p->b.Wt_lo, Fp, Fp, nullptr, 0, nullptr, 0, 0, p->slabs, Hp, p->s_enc, slab, st,
-                                                 GEMM_ROLE_ENCODE, label_with_encode ? &lj : nullptr, label_with_encode ? &enc_label_done : nullptr));
-        PROF(PS_ENC_FIN, launch_encode_finish(p->slabs, (x3 && dense_in) ? p->s_enc3 : p->s_enc, slab, Hp, p->b.bh, B, H, c.enc_act, dt, p->h_f32, p->h_lo, Hp,
-                                              p->h_t, ldB, p->gram_split ? p->hcat_a : nullptr, p->gram_split ? p->hcat_b : nullptr,
-                                              (T & (X3T_DH_HLO | X3T_DW_HLO)) ? p->h_t2 : nullptr, stream));
-        labels_done = (label_in_gather && !s->c_indptr) || enc_label_done;
-    }
-    if (h_only) return 0;
-    // 5-6. miners (K5-K7)
-    const int Bt = explicit3 ? B / 3 : B;
-    if (ext_mine) {
-        // mined by the caller
-    } else if (explicit3) {
-        PROF(PS_LABEL, dae_label_stats(nullptr, Bt, Bp, DAE_TRIPLET_NONE, nullptr, nullptr, nullptr, nullptr, p->cw, 0.f, nullptr, stream));
-        // every one of the 3*Bt stacked rows carries weight 1/(Bt + 1e-16): three unweighted row means (:303-305)
-        DAE_CHECK_HIP(hipMemcpyAsync(p->cw + Bt, p->cw, (size_t)Bt * 4, hipMemcpyDeviceToDevice, st));
-        DAE_CHECK_HIP(hipMemcpyAsync(p->cw + 2 * Bt, p->cw, (size_t)Bt * 4, hipMemcpyDeviceToDevice, st));
-        PROF(PS_MINER, dae_explicit_triplet(p->h_f32, Hp, Bt, H, c.alpha, p->dh_extra, p->loss_part, p->tri_scalars, stream));
-    } else if (!labels_done) {
-        PROF(PS_LABEL, dae_label_stats(s->labels, B, Bp, c.triplet, p->n_same, p->acc, p->nvalid, p->dw_i64, p->cw, c.alpha, p->tri_scalars, stream));
-    }
-    bool sym_ride = false;
-    const bool fold_finalize = (c.triplet == DAE_TRIPLET_BATCH_ALL && !c.pos_triplets_only) && !ext_mine;
-    if (!ext_mine && (c.triplet == DAE_TRIPLET_BATCH_ALL || c.triplet == DAE_TRIPLET_BATCH_HARD)) {
-        const int64_t dslab = (int64_t)Bp * Bp;
-        // the label block of this step's encode launch also ranked the anchors by sweep cost (only then is the buffer current)
-        const int32_t* order = (labels_done && !ext_mine && p->miner_order_ok && c.triplet == DAE_TRIPLET_BATCH_ALL) ? p->miner_order : nullptr;
-        const int32_t* cls = (labels_done && !ext_mine && p->miner_ranges_ok && c.triplet == DAE_TRIPLET_BATCH_ALL) ? p->cls_range : nullptr;
-        PROF(PS_GRAM, launch_gram(p, Bp, Hp, dslab, st));
-        if (c.triplet == DAE_TRIPLET_BATCH_ALL)
-            PROF(PS_MINER, launch_batch_all(p->D_slabs, p->s_gram, dslab, Bp, s->labels, B, Bp, 0, B,
-                                     (c.pos_triplets_only ? DAE_MINER_POS_ONLY : 0) | (dt == DAE_BF16 ? DAE_MINER_FAST : 0), p->loss_part,
-                                     p->cnt_part, p->G, p->role_cnt, order, st, cls));
-        else
-            PROF(PS_MINER, dae_triplet_batch_hard(p->D_slabs, p->s_gram, dslab, Bp, s->labels, B, Bp, p->loss_part, p->cnt_part, p->dw_i32, p->G,
-                                      stream));
-        if (!fold_finalize)   // batch_all over all valid triplets: scale comes from label_stats, sums from step_stats
-            PROF(PS_TRI_FIN, dae_triplet_finalize(c.triplet, c.pos_triplets_only, B, Bp, c.alpha, p->loss_part, p->cnt_part, p->nvalid,
-                                    p->dw_i32, p->role_cnt, p->dw_f32, p->cw, p->tri_scalars, stream));
-        sym_ride = backward && p->sym_ride_ok;                   // the decode launch below carries it
-        if (backward && !sym_ride) PROF(PS_SYM, launch_sym_scale(p->G, B, Bp, p->tri_scalars, dt, p->Gs, osc, st));
-    }
-    // 7. decode + reconstruction loss + d cost/d z2   (K3/K4); `sym_ride`: the launch also scales G + G^T (sym_scale)
-    const int dbn = plan_dec_bn(p);
-    const int ncw = 2 * Fp / dbn;
-    {
-        DecodeEpi e;
-        memset(&e, 0, sizeof(e));
-        e.bv = p->b.bv; e.x = p->x; e.ldx = Fp; e.x_bits = use_xbits ? p->x_bits : nullptr; e.ldxb = Fp / 32; e.cw = p->cw; e.cos_stats = is_cos ? p->cos_stats : nullptr;
-        e.rowloss_part = is_cos ? p->rowloss_part : nullptr; e.tile_part = is_cos ? nullptr : p->tile_part;
-        e.dbv_part = backward ? p->dbv_part : nullptr; e.cos_part = p->cos_part;
-        e.delta2 = backward ? p->delta2 : nullptr; e.ldd = Fp; e.delta2_t = (backward && !dw_tr) ? p->delta2_t : nullptr; e.lddt = ldB;
-        e.B = B; e.F = F; e.Bp = Bp; e.Fp = Fp; e.dec_act = c.dec_act; e.loss_func = c.loss_func; e.ce_literal = p->ce_literal ? 1 : 0;
-        e.op_scale = osc; e.bn = dbn;
-        if (sym_ride) { e.sym_G = p->G; e.sym_scalars = p->tri_scalars; e.sym_Gs = p->Gs; e.sym_B = B; e.sym_Bp = Bp; }
-        // z2 = h W^T: one K segment, or -- split-bf16 -- (h_hi, W_hi) (h_hi, W_lo) (h_lo, W_hi); the row-major h_hi / h_lo are the first and
-        // third block of the Gram operand hcat_a = [hi | hi | lo] (leading dimension 3 Hp)
-        GemmSegDesc dsegs[3] = {{p->h_lo, Hp, p->b.W_lo, Hp, Hp}, {nullptr, 0, nullptr, 0, 0}, {nullptr, 0, nullptr, 0, 0}};
-        int ndseg = 1;
-        if (x3) {
-            dsegs[0] = {p->hcat_a, 3 * (int64_t)Hp, p->b.W_lo, Hp, Hp};
-            dsegs[1] = {p->hcat_a, 3 * (int64_t)Hp, p->W_lo2, Hp, (T & X3T_DEC_WLO) ? Hp : 0};      // K = 0: the term is dropped
-            dsegs[2] = {p->hcat_a + (size_t)2 * Hp * 2, 3 * (int64_t)Hp, p->b.W_lo, Hp, (T & X3T_DEC_HLO) ? Hp : 0};
-            ndseg = 3;
-            if (backward) { e.delta2_2 = (T & X3T_DH_D2LO) ? p->delta2_2 : nullptr; e.delta2_t2 = (T & X3T_DW_D2LO) ? p->delta2_t2 : nullptr; }
-            if (x2_clean) e.x2 = p->x_2;    // valued clean rows: x = hi + lo (RES instantiations)
-        }
-        if (is_cos) {
-            e.cos_pass = 1;
-            const bool zs = backward && p->cos_zstore_ok && p->zbuf;
-            if (zs) { e.z_io = p->zbuf; e.ldz = Fp; e.z_mode = 1; }
-            PROF(PS_DECODE, launch_decode_loss_n(dt, Bp, Fp, dsegs, ndseg, e, st));
-            if (zs) e.z_mode = 2;
-            PROF(PS_COS_REDUCE, dae_cos_reduce(p->cos_part, ncw, B, Bp, p->cos_stats, p->rowloss_part, stream));
-            e.sym_G = nullptr;                                 // the first pass carried the rider
-            if (backward) { e.cos_pass = 2; PROF(PS_DECODE, launch_decode_loss_n(dt, Bp, Fp, dsegs, ndseg, e, st)); }
-        } else {
-            e.cos_pass = 0;
-            PROF(PS_DECODE, launch_decode_loss_n(dt, Bp, Fp, dsegs, ndseg, e, st));
-        }
-    }
-    // 8. statistics of this step (autoencoder.py:233 fetch list)
-    StatsArgs sa{is_cos ? p->rowloss_part : nullptr, 1, is_cos ? nullptr : p->tile_part, (Bp / 128) * (Fp / dbn), p->cw, B, Bp,
-                 c.triplet == 3 ? DAE_TRIPLET_BATCH_HARD : c.triplet, c.alpha, p->tri_scalars,
-                 (c.triplet == DAE_TRIPLET_BATCH_ALL && !ext_mine) ? p->nvalid : nullptr, s->stats, fold_finalize ? p->loss_part : nullptr,
-                 fold_finalize ? p->cnt_part : nullptr};
-    const bool stats_in_tail = backward && tail;     // rides on the step-tail launch after the dW GEMM
-    if (!stats_in_tail)
-        PROF(PS_STATS, dae_step_stats(sa.rowloss_part, sa.n_col_waves, sa.tile_part, sa.n_tiles, sa.cw, B, Bp, sa.triplet, sa.alpha, sa.tri_scalars,
-                                      sa.nvalid, sa.loss_part, sa.cnt_part, s->stats, stream));
-    if (!backward) return 0;
-    // 9-10. dL/dh = delta2 W + alpha (G+G^T) h ; delta1                     (K8)
-    const bool mined = !ext_mine && (c.triplet == DAE_TRIPLET_BATCH_ALL || c.triplet == DAE_TRIPLET_BATCH_HARD);
-    const int s_dh = (x3 && dense_in) ? p->s_dh3 : p->s_dh;
-    if (x3) {       // (d2_hi, Wt_hi) (d2_hi, Wt_lo) (d2_lo, Wt_hi) + Gs.h_hi (+ Gs.h_lo with option x3_dh_hlo): Gs itself stays bf16 (tools/precision_study.py)
-        const GemmSegDesc hs[5] = {{p->delta2, Fp, p->b.Wt_lo, Fp, Fp}, {p->delta2, Fp, p->Wt_lo2, Fp, (T & X3T_DH_WLO) ? Fp : 0},
-                                   {p->delta2_2, Fp, p->b.Wt_lo, Fp, (T & X3T_DH_D2LO) ? Fp : 0},
-                                   {p->Gs, Bp, p->h_t, ldB, mined ? Bk : 0}, {p->Gs, Bp, p->h_t2, ldB, (mined && (T & X3T_DH_HLO)) ? Bk : 0}};
-        PROF(PS_DH_GEMM, launch_gemm_f32out_n(dt, Bp, Hp, hs, 5, p->slabs, Hp, s_dh, slab, st, GEMM_ROLE_DH, nullptr, nullptr, 1.f, B));
-    } else {
-        PROF(PS_DH_GEMM, launch_gemm_f32out(dt, Bp, Hp, p->delta2, Fp, p->b.Wt_lo, Fp, Fp, mined ? p->Gs : nullptr, Bp, mined ? p->h_t : nullptr, ldB,
-                              mined ? Bk : 0, p->slabs, Hp, p->s_dh, slab, st, GEMM_ROLE_DH, nullptr, nullptr, B));
-    }
-    PROF(PS_DH_FIN, launch_dh_finish(p->slabs, s_dh, slab, Hp, (explicit3 || ext_mine) ? p->dh_extra : nullptr, p->h_f32, Hp, p->b.bh, B, H, c.enc_act, dt,
-                     p->delta1_t, ldB, p->colsum_part, nullptr, nullptr, st, (T & X3T_DW_D1LO) ? p->delta1_t2 : nullptr, oinv, osc));
-    // 11. dW = x~^T delta1 + delta2^T h                                      (K8, tied weights)
-    // split-bf16 segment list (K = 0 segments are skipped): the third one exists only when x~^T has a lo image
-    // (dw_tr: the A operands are the row-major images -- x~ from the CSR scatter (p->xct used as [Bp x Fp]) or the dense gather (p->xc), and delta2)
-    const void* a_x = dw_tr ? (const void*)(dense_in ? p->xc : p->xct) : (const void*)p->xct;
-    const void* a_d2 = dw_tr ? (const void*)p->delta2 : (const void*)p->delta2_t;
-    const int64_t lda_w = dw_tr ? Fp : ldB;
-    const GemmSegDesc ws3[6] = {{a_x, lda_w, p->delta1_t, ldB, Bk}, {p->xct, ldB, p->delta1_t2, ldB, (T & X3T_DW_D1LO) ? Bk : 0},
-                                {p->xct_2, ldB, p->delta1_t, ldB, x3_vals ? Bk : 0},
-                                {a_d2, lda_w, p->h_t, ldB, Bk}, {p->delta2_t, ldB, p->h_t2, ldB, (T & X3T_DW_HLO) ? Bk : 0},
-                                {p->delta2_t2, ldB, p->h_t, ldB, (T & X3T_DW_D2LO) ? Bk : 0}};
-    if (fuse_opt || dw_pc_grad) {
-        OptEpi oe;
-        memset(&oe, 0, sizeof(oe));
-        oe.ldw = Hp; oe.ldwt = Fp; oe.gin = oinv;
-        if (fuse_opt) {
-            oe.W = p->b.W; oe.grad = s->phase == 3 ? nullptr : p->b.grad; oe.s1 = p->b.opt_s1; oe.s2 = p->b.opt_s2;
-            oe.W_lo = p->b.W_lo; oe.Wt_lo = p->b.Wt_lo; oe.opt = c.opt; oe.lr = plan_lr(p, s->adam_t);
-            oe.mom = c.momentum; oe.gscale = s->grad_scale;
-        } else {                                     // data parallel: gradient to memory (fp32 flat buffer, or the bf16 exchange image)
-            oe.opt = DW_OPT_GRAD_ONLY; oe.grad = p->b.grad_lo ? nullptr : p->b.grad; oe.grad_lo = p->b.grad_lo;
-            oe.ldw = Hp;
-        }
-        if (x3) {   // x~^T.(d1_hi + d1_lo) + (d2^T_hi, h^T_hi) (d2^T_hi, h^T_lo) (d2^T_lo, h^T_hi); the epilogue writes both parts of both shadows
-            oe.W_lo2 = (T & X3T_DEC_WLO) ? p->W_lo2 : nullptr; oe.Wt_lo2 = p->Wt_lo2;     // W_lo2 feeds the decode's (h_hi, W_lo) term only
-            PROF(PS_DW_GEMM, launch_dw_opt_n(Fp, Hp, ws3, 6, oe, st, p->dw_pair_ok, dw_tr));
-        } else {
-            PROF(PS_DW_GEMM, launch_dw_opt(Fp, Hp, a_x, lda_w, p->delta1_t, ldB, Bk, a_d2, lda_w, p->h_t, ldB, Bk, oe, st, dw_tr));
-        }
-    } else if (x3) {
-        PROF(PS_DW_GEMM, launch_gemm_f32out_n(dt, Fp, Hp, ws3, 6, p->b.grad, Hp, 1, 0, st, GEMM_ROLE_DW, nullptr, nullptr, oinv));
-    } else {
-        const GemmSegDesc ws2[2] = {{p->xct, ldB, p->delta1_t, ldB, Bk}, {p->delta2_t, ldB, p->h_t, ldB, Bk}};
-        PROF(PS_DW_GEMM, launch_gemm_f32out_n(dt, Fp, Hp, ws2, 2, p->b.grad, Hp, 1, 0, st, GEMM_ROLE_DW, nullptr, nullptr, oinv));
-        // data parallel with a bf16 exchange image: the shape did not fit the kernel that writes it directly
-        if (!apply_now && dt == DAE_BF16 && p->b.grad_lo) RC(launch_cast_bf16(p->b.grad, p->b.grad_lo, (int64_t)Fp * Hp, st));
-    }
-    p->ev_dw_live = false;
-    if (p->ev_dw) { DAE_CHECK_HIP(hipEventRecord(p->ev_dw, st)); p->ev_dw_live = true; }      // the W gradient (grad / grad_lo) is complete from here on
-    // 12. bias gradients
-    float* g_bh = p->b.grad + (int64_t)Fp * Hp;
-    const int64_t boff = (int64_t)Fp * Hp;
-    const bool fuse_bias = apply_now;               // single-GPU step: the bias update rides on the bias-gradient kernel
-    if (tail) {
-        BiasArgs ba{p->dbv_part, 2 * Bp / 128, p->colsum_part, Bp / 32, p->b.bh, H, Hp, F, Fp, c.enc_act, g_bh, g_bh + Hp,
-                    fuse_bias ? 1 : 0, c.opt, plan_lr(p, s->adam_t), c.momentum, s->grad_scale, p->b.bv,
-                    p->b.opt_s1 ? p->b.opt_s1 + boff : nullptr, p->b.opt_s2 ? p->b.opt_s2 + boff : nullptr};
-        ClearArgs ca{s->c_indptr ? s->c_indptr : p->b.indptr, s->c_indptr ? s->c_indices : p->b.indices,
-                     (s->c_indptr && s->c_row_idx) ? s->c_row_idx : s->row_idx, B, F, p->xct, dw_tr ? (int64_t)Fp : (int64_t)ldB, p->es,
-                     x3_vals ? p->xct_2 : nullptr, dw_tr ? 1 : 0};
-        PROF(PS_BIAS, launch_step_tail(ba, &sa, csr_in ? &ca : nullptr, st));
-        if (csr_in) { p->xct_clean = true; if (x3_vals) p->xct2_clean = true; }
-    } else {
-        PROF(PS_BIAS, dae_bias_grads(p->dbv_part, 2 * Bp / 128, p->colsum_part, Bp / 32, p->b.bh, H, Hp, F, Fp, c.enc_act, g_bh, g_bh + Hp,
-                                     fuse_bias ? 1 : 0, c.opt, plan_lr(p, s->adam_t), c.momentum, s->grad_scale, p->b.bv,
-                                     p->b.opt_s1 ? p->b.opt_s1 + boff : nullptr, p->b.opt_s2 ? p->b.opt_s2 + boff : nullptr, stream));
-    }
-    if (s->phase == 1 || s->phase == 5 || fuse_opt) return 0;
-    // 13. optimizer (K9): W (+ shadows); biases were updated above
-    PROF(PS_OPT, launch_opt_step(c.opt, plan_lr(p, s->adam_t), c.momentum, s->grad_scale, p->b.W, p->b.bh, p->b.bv, p->b.grad, p->b.opt_s1,
-                                 p->b.opt_s2, Fp, Hp, dt, p->b.W_lo, p->b.Wt_lo, plan_w_lo2(p), x3 ? p->Wt_lo2 : nullptr, /*apply=*/2, stream));
-    return 0;
-}
 
 extern "C" int dae_plan_apply(dae_plan* p, int32_t adam_t, float grad_scale, void* stream) {
     DAE_CHECK_ARG(p && p->bound, "plan_apply: plan not bound");
-    const float lr = plan_lr(p, adam_t);
-    return launch_opt_step(p->cfg.opt, lr, p->cfg.momentum, grad_scale, p->b.W, p->b.bh, p->b.bv, p->b.grad, p->b.opt_s1, p->b.opt_s2,
-                           p->Fp, p->Hp, p->cfg.dtype, p->b.W_lo, p->b.Wt_lo, plan_w_lo2(p), p->x3 ? p->Wt_lo2 : nullptr, /*apply=*/1, stream);
+    return plan_opt_step(p, plan_lr(p, adam_t), grad_scale, /*apply=*/1, stream);
 }
 
 // The same on the row band [f0, f1) of W (multiples of 64) -- dp.AllReduceExchange with buckets: the flat gradient is all-reduced band by band and every
@@ -903,9 +419,7 @@ extern "C" int dae_plan_apply(dae_plan* p, int32_t adam_t, float grad_scale, voi
 // gradients sit behind the W part of the flat buffer, i.e. in the last bucket).  Bands applied in any order give the weights of one dae_plan_apply.
 extern "C" int dae_plan_apply_band(dae_plan* p, int32_t adam_t, float grad_scale, int32_t f0, int32_t f1, void* stream) {
     DAE_CHECK_ARG(p && p->bound, "plan_apply_band: plan not bound");
-    const float lr = plan_lr(p, adam_t);
-    return launch_opt_step(p->cfg.opt, lr, p->cfg.momentum, grad_scale, p->b.W, p->b.bh, p->b.bv, p->b.grad, p->b.opt_s1, p->b.opt_s2,
-                           p->Fp, p->Hp, p->cfg.dtype, p->b.W_lo, p->b.Wt_lo, plan_w_lo2(p), p->x3 ? p->Wt_lo2 : nullptr, /*apply=*/1, stream, f0, f1);
+    return plan_opt_step(p, plan_lr(p, adam_t), grad_scale, /*apply=*/1, stream, f0, f1);
 }
 
 // ---- the exchange itself, on the step's stream (dae_comm.hip holds the communicator; reference step: autoencoder.py:206-246) ----
@@ -983,8 +497,8 @@ extern "C" int dae_plan_apply_rows(dae_plan* p, int32_t adam_t, float grad_scale
     if (update_bias) {
         const int64_t off = (int64_t)p->Fp * p->Hp;
         dim3 grid((p->Hp + p->Fp + 255) / 256), block(256);
-        RC(dae_opt_bias(p->cfg.opt, lr, p->cfg.momentum, grad_scale, p->b.bh, p->b.bv, p->b.grad + off, p->b.opt_s1 ? p->b.opt_s1 + off : nullptr,
-                        p->b.opt_s2 ? p->b.opt_s2 + off : nullptr, p->Hp, p->Fp, stream));
+        RC(dae_opt_bias(p->cfg.opt, lr, p->cfg.momentum, grad_scale, p->b.bh, p->b.bv, p->b.grad + off, plan_bias_slot(p, p->b.opt_s1),
+                        plan_bias_slot(p, p->b.opt_s2), p->Hp, p->Fp, stream));
     }
     return 0;
 }
@@ -1026,58 +540,12 @@ extern "C" int dae_plan_dp_unpack(dae_plan* p, const void* recv, int32_t world, 
     DAE_CHECK_ARG(p && p->bound && recv, "plan_dp_unpack: plan not bound / null buffer");
     const int64_t off = (int64_t)p->Fp * p->Hp;
     return dae_dp_unpack(recv, world, chunk_rows, chunk_stride_bytes, bias_off_bytes, p->Fp, p->Hp, p->cfg.dtype, p->b.W_lo, p->b.Wt_lo, p->cfg.opt,
-                         plan_lr(p, adam_t), p->cfg.momentum, grad_scale, p->b.bh, p->b.bv, p->b.opt_s1 ? p->b.opt_s1 + off : nullptr,
-                         p->b.opt_s2 ? p->b.opt_s2 + off : nullptr, p->b.grad + off, stream);
+                         plan_lr(p, adam_t), p->cfg.momentum, grad_scale, p->b.bh, p->b.bv, plan_bias_slot(p, p->b.opt_s1),
+                         plan_bias_slot(p, p->b.opt_s2), p->b.grad + off, stream);
 }
 
 extern "C" int dae_plan_refresh_wt(dae_plan* p, void* stream) {
     DAE_CHECK_ARG(!p || !p->x3, "plan_refresh_wt: split-bf16 mode has no data-parallel path yet");
     DAE_CHECK_ARG(p && p->bound, "plan_refresh_wt: plan not bound");
     return dae_transpose_shadow(p->b.W_lo, p->Fp, p->Hp, p->cfg.dtype, p->b.Wt_lo, stream);
-}
-
-extern "C" int dae_encode_rows(dae_plan* p, const int32_t* row_idx, int32_t B, float scale, const int64_t* indptr,
-                               const int32_t* indices, const float* values, const float* dense, int64_t ld_dense, float* out,
-                               int64_t ld_out, void* stream) {
-    DAE_CHECK_ARG(p && p->bound && row_idx && out, "encode_rows: bad arguments");
-    DAE_CHECK_ARG(B > 0 && B <= p->Bmax, "encode_rows: batch %d outside (0, %d]", B, p->Bmax);
-    DAE_CHECK_ARG((indptr != nullptr) != (dense != nullptr), "encode_rows: give either a CSR or a dense matrix");
-    hipStream_t st = (hipStream_t)stream;
-    const int Bp = (int)pad128(B), Fp = p->Fp, Hp = p->Hp, dt = p->cfg.dtype;
-    if (indptr && p->sparse_ok) {        // CSR: one launch on the stored entries, straight into the caller's [B x H] matrix when it is padded like h
-        EncCsrLaunch q;
-        memset(&q, 0, sizeof(q));
-        q.indptr = indptr; q.indices = indices; q.values = values; q.row_idx = row_idx; q.B = B; q.F = p->F; q.H = p->H; q.dtype = dt;
-        const bool w32 = p->enc_w32_ok && dt == DAE_BF16;
-        q.W = w32 ? (const void*)p->b.W : (const void*)p->b.W_lo; q.w_f32 = w32 ? 1 : 0; q.w32_cols = p->w32_cols;
-        q.ldw = Hp; q.bh = p->b.bh; q.enc_act = p->cfg.enc_act; q.corr_mode = DAE_CORR_NONE; q.scale = scale;
-        q.h_f32 = p->h_f32; q.ldh = Hp;
-        RC(launch_encode_csr(q, st));
-        DAE_CHECK_HIP(hipMemcpy2DAsync(out, (size_t)ld_out * 4, p->h_f32, (size_t)Hp * 4, (size_t)p->H * 4, B, hipMemcpyDeviceToDevice, st));
-        return 0;
-    }
-    const bool use_bits = p->bits_ok && indptr && !values && scale == 1.0f;
-    RC(gather_batch(p, indptr, indices, values, dense, ld_dense, row_idx, B, nullptr, use_bits ? nullptr : p->xc, nullptr, nullptr,
-                    DAE_CORR_NONE, nullptr, 0, 0, 0.f, scale, stream, use_bits ? p->xc_bits : nullptr));
-    const int64_t slab = (int64_t)Bp * Hp;
-    if (p->x3 && dense) {        // split mode: x = hi + lo against W^T = hi + lo (the lo terms the plan keeps), as the training step encodes
-        const uint32_t T = p->terms;
-        if (T & X3T_ENC_XLO) RC(gather_dense_lo(p, dense, ld_dense, row_idx, B, nullptr, p->xc_2, nullptr, DAE_CORR_NONE, nullptr, 0, 0, 0.f, scale, stream));
-        const GemmSegDesc es3[3] = {{p->xc, Fp, p->b.Wt_lo, Fp, Fp}, {p->xc, Fp, p->Wt_lo2, Fp, (T & X3T_ENC_WLO) ? Fp : 0},
-                                    {p->xc_2, Fp, p->b.Wt_lo, Fp, (T & X3T_ENC_XLO) ? Fp : 0}};
-        RC(launch_gemm_f32out_n(dt, Bp, Hp, es3, 3, p->slabs, Hp, p->s_enc3, slab, st, GEMM_ROLE_ENCODE));
-        RC(dae_encode_finish(p->slabs, p->s_enc3, slab, Hp, p->b.bh, B, p->H, p->cfg.enc_act, dt, p->h_f32, nullptr, Hp, nullptr, 0, nullptr, nullptr,
-                             stream));
-        DAE_CHECK_HIP(hipMemcpy2DAsync(out, (size_t)ld_out * 4, p->h_f32, (size_t)Hp * 4, (size_t)p->H * 4, B, hipMemcpyDeviceToDevice, st));
-        return 0;
-    }
-    if (use_bits)
-        RC(launch_encode_bits(Bp, Hp, Fp, p->xc_bits, Fp / 32, p->b.Wt_lo, Fp, p->slabs, Hp, p->s_enc, slab, st));
-    else
-        RC(launch_gemm_f32out(dt, Bp, Hp, p->xc, Fp, p->b.Wt_lo, Fp, Fp, nullptr, 0, nullptr, 0, 0, p->slabs, Hp, p->s_enc, slab, st,
-                              GEMM_ROLE_ENCODE));
-    RC(dae_encode_finish(p->slabs, p->s_enc, slab, Hp, p->b.bh, B, p->H, p->cfg.enc_act, dt, p->h_f32, nullptr, Hp, nullptr, 0, nullptr, nullptr,
-                         stream));
-    DAE_CHECK_HIP(hipMemcpy2DAsync(out, (size_t)ld_out * 4, p->h_f32, (size_t)Hp * 4, (size_t)p->H * 4, B, hipMemcpyDeviceToDevice, st));
-    return 0;
 }
