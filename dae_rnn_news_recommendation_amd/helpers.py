@@ -25,7 +25,10 @@ library / a GPU this raises.
   untruncated MRR / nDCG and hit / MRR / nDCG at any number of cut-offs from one pass.
 * ``fit_user_model`` -- the trained form of that user model: the scaling vector alpha and the decay beta learned from click
   logs by a pairwise ranking loss, whose value and gradients ``user_pair_loss`` gets from one walk of the histories
-  (``dae_user_pair_loss``); ``sample_negatives`` and ``decay_factor_derivatives`` (host code) prepare its inputs."""
+  (``dae_user_pair_loss``); ``sample_negatives`` and ``decay_factor_derivatives`` (host code) prepare its inputs.
+* ``gru_user_states`` -- the recurrent user model of the same paper, inference: the GRU state of every user after every click
+  from weights in the layout of ``torch.nn.GRU`` (``GRUUserModel``; ``dae_gru_user_states``, time-major, one exact-fp32 MFMA GEMM
+  per step over the users still active); ``gru_schedule`` and ``trim_histories`` (host code) prepare its inputs."""
 from __future__ import annotations
 
 import numpy as np
@@ -469,6 +472,186 @@ def user_states(histories, embeddings, beta=0.9, *, timestamps=None, time_unit=N
     with torch.cuda.device(dev):
         L.call("dae_user_states", L.ptr(E), E.stride(0), Na, H, L.ptr(ip_d), L.ptr(it_d), M, nnz, beta, L.ptr(dc_d),
                1 if all_states else 0, L.ptr(U), U.stride(0), L.current_stream())
+    if return_tensor:
+        return U
+    return U.cpu().numpy()
+
+
+class GRUUserModel:
+    """The weights of the GRU user model, float32 in the layout of ``torch.nn.GRU`` (one layer, gate row blocks r, z, n):
+    ``weight_ih`` [3H x D], ``weight_hh`` [3H x H], ``bias_ih`` and ``bias_hh`` [3H].  ``save`` / ``load`` keep them in an ``.npz``
+    under those four names -- the hand-over format of any trainer (``tools/gru_fit_torch.py`` writes it).  Host code; the states
+    come from ``gru_user_states`` (or ``.states``)."""
+    NAMES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
+
+    def __init__(self, weight_ih, weight_hh, bias_ih, bias_hh):
+        w = [np.ascontiguousarray(np.asarray(a, dtype=np.float32)) for a in (weight_ih, weight_hh, bias_ih, bias_hh)]
+        self.weight_ih, self.weight_hh, self.bias_ih, self.bias_hh = w
+        if self.weight_hh.ndim != 2 or self.weight_hh.shape[0] != 3 * self.weight_hh.shape[1] or self.weight_hh.shape[1] < 1:
+            raise ValueError(f"weight_hh must be [3H x H] (got {self.weight_hh.shape})")
+        H = int(self.weight_hh.shape[1])
+        if self.weight_ih.ndim != 2 or self.weight_ih.shape[0] != 3 * H or self.weight_ih.shape[1] < 1:
+            raise ValueError(f"weight_ih must be [3H x D] with H = {H} (got {self.weight_ih.shape})")
+        if self.bias_ih.shape != (3 * H,) or self.bias_hh.shape != (3 * H,):
+            raise ValueError(f"bias_ih and bias_hh must be [3H] with H = {H} (got {self.bias_ih.shape}, {self.bias_hh.shape})")
+        if not all(np.isfinite(a).all() for a in w):
+            raise ValueError("GRU weights must be finite")
+
+    @property
+    def hidden_size(self):
+        return int(self.weight_hh.shape[1])
+
+    @property
+    def input_size(self):
+        return int(self.weight_ih.shape[1])
+
+    def save(self, path):
+        with open(path, "wb") as f:
+            np.savez(f, **{n: getattr(self, n) for n in self.NAMES})
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            missing = [n for n in cls.NAMES if n not in z.files]
+            if missing:
+                raise ValueError(f"{path}: no array named {missing[0]} (a GRU weight file holds {', '.join(cls.NAMES)})")
+            return cls(*(z[n] for n in cls.NAMES))
+
+    @classmethod
+    def from_torch(cls, x):
+        """From a ``torch.nn.GRU`` (one layer, unidirectional, with bias) or its state dict."""
+        if hasattr(x, "state_dict"):
+            if getattr(x, "num_layers", 1) != 1 or getattr(x, "bidirectional", False) or not getattr(x, "bias", True):
+                raise ValueError("from_torch takes a one-layer, unidirectional GRU with bias")
+            if type(x).__name__ != "GRU":
+                raise ValueError(f"from_torch takes a torch.nn.GRU (got {type(x).__name__})")
+            x = x.state_dict()
+        keys = [n + "_l0" for n in cls.NAMES]
+        extra = [k for k in x if k not in keys]
+        if extra or any(k not in x for k in keys):
+            raise ValueError(f"a one-layer, unidirectional GRU with bias has the entries {keys} (got {sorted(x)})")
+        return cls(*(x[k].detach().cpu().numpy() if hasattr(x[k], "detach") else x[k] for k in keys))
+
+    def states(self, histories, embeddings, **kw):
+        return gru_user_states(histories, embeddings, self, **kw)
+
+
+def gru_schedule(indptr):
+    """The time-major schedule ``dae_gru_user_states`` runs: ``(order int32 [users], active int64 [T])``.  ``order`` lists the
+    users by history length, longest first -- a stable sort, so equal lengths keep the input order; ``active[t]`` is the number
+    of users with more than t events (non-increasing; T = the longest history, 0 without events).  Host code."""
+    indptr = np.asarray(indptr, dtype=np.int64).ravel()
+    if indptr.size < 1 or (np.diff(indptr) < 0).any():
+        raise ValueError("indptr must be non-decreasing and hold at least one entry")
+    n = np.diff(indptr)
+    order = np.argsort(-n, kind="stable").astype(np.int32)
+    T = int(n.max()) if n.size else 0
+    active = n.size - np.cumsum(np.bincount(n, minlength=T + 1))[:T]
+    return order, np.ascontiguousarray(active.astype(np.int64))
+
+
+def trim_histories(histories, max_events):
+    """Every user's ``max_events`` most recent events as an ``(indptr, items)`` tuple (the order within a user is kept).  Host code."""
+    indptr, items = _csr_lists(histories)
+    k = int(max_events)
+    if k < 0:
+        raise ValueError(f"max_events must not be negative (got {max_events})")
+    n = np.minimum(np.diff(indptr), k)
+    out = np.zeros(indptr.size, dtype=np.int64)
+    out[1:] = np.cumsum(n)
+    start = indptr[1:] - n                                              # first kept event of every user
+    pos = np.repeat(start - out[:-1], n) + np.arange(int(out[-1]), dtype=np.int64)
+    return out, items[pos]
+
+
+def gru_user_states(histories, embeddings, model, *, initial=None, max_events=None, all_states=False, batch_users=262144,
+                    return_tensor=False, device=None):
+    """User states from browsing histories by the recurrent (GRU) user model of "Embedding-based News Recommendation for Millions
+    of Users" (KDD'17): per user, over the events oldest first, with ``x = E[item]`` and the weights of ``model`` (a
+    ``GRUUserModel``; gate order and "reset-after" form of ``torch.nn.GRU``)
+
+        r = sigmoid(W_ir x + b_ir + W_hr h + b_hr)   z = sigmoid(W_iz x + b_iz + W_hz h + b_hz)
+        n = tanh(W_in x + b_in + r * (W_hn h + b_hn))   h' = (1 - z) * n + z * h
+
+    (``dae_gru_user_states``: time-major, one exact-fp32 MFMA GEMM launch per step over the users still active; fixed order, no
+    atomics: bit-identical run to run and independent of the other users of the call and of their order).
+
+    ``histories`` and ``embeddings`` [articles x D] as for ``user_states``; ``model.input_size`` must be D.  The states have
+    ``H = model.hidden_size`` columns (``recommend`` needs H = D).  ``h`` starts at zero, or at the rows of ``initial``
+    [users x H]: the states of an earlier call, continued with the new clicks without replaying the history.  ``max_events``
+    keeps every user's most recent events (trimmed on the host; with ``all_states`` a ``ValueError``: the rows would no longer
+    be the caller's events).  The users are processed in chunks of at most ``batch_users``, which bounds the workspace; the
+    chunking does not change a bit of the result.  An item outside ``[0, articles)`` raises ``ValueError``.
+
+    Returns float32 ``[users x H]``: the state after each user's last event (zeros, or the ``initial`` row, for an empty
+    history); with ``all_states=True`` ``[events x H]``: row e is the state after event e, the one that predicts event e + 1,
+    and the row of a user's last event equals that user's row of the default form bit for bit."""
+    import torch
+    if not isinstance(model, GRUUserModel):
+        raise TypeError("model must be a GRUUserModel (GRUUserModel.load / from_torch)")
+    if max_events is not None and all_states:
+        raise ValueError("max_events and all_states do not go together: the rows of all_states are the caller's events")
+    if int(batch_users) < 1:
+        raise ValueError(f"batch_users must be positive (got {batch_users})")
+    indptr, items = _csr_lists(histories)
+    if items.size and items.dtype.kind not in "iu":
+        raise ValueError("histories must hold integer article indices")
+    if max_events is not None:
+        indptr, items = trim_histories((indptr, items), max_events)
+    H, D = model.hidden_size, model.input_size
+    M, nnz = int(indptr.size - 1), int(items.size)
+    if not isinstance(embeddings, torch.Tensor):
+        shape = getattr(embeddings, "shape", None)
+        if shape is None:
+            shape = np.asarray(embeddings).shape
+        if len(shape) != 2:
+            raise ValueError("Expected 2D array")
+        if int(shape[1]) != D:
+            raise ValueError(f"embeddings have {int(shape[1])} columns, the model's weight_ih has {D}")
+        if items.size and (int(items.min()) < 0 or int(items.max()) >= int(shape[0])):
+            raise ValueError(f"history items must be in 0..{int(shape[0]) - 1} (got {int(items.min())}..{int(items.max())})")
+    if initial is not None and not isinstance(initial, torch.Tensor):
+        initial = np.asarray(initial, dtype=np.float32)
+    if initial is not None and tuple(initial.shape) != (M, H):
+        raise ValueError(f"initial must be [users x H] = [{M} x {H}] (got {tuple(initial.shape)})")
+    lib = L.load()
+    dev = torch.device("cuda" if device is None else device)
+    E = _fit_embeddings(torch, embeddings, dev)
+    Na = int(E.shape[0])
+    if int(E.shape[1]) != D:
+        raise ValueError(f"embeddings have {int(E.shape[1])} columns, the model's weight_ih has {D}")
+    if items.size and (int(items.min()) < 0 or int(items.max()) >= Na):
+        raise ValueError(f"history items must be in 0..{Na - 1} (got {int(items.min())}..{int(items.max())})")
+    rows = nnz if all_states else M
+    U = torch.empty((rows, H), dtype=torch.float32, device=dev)
+    if rows == 0:
+        return U if return_tensor else U.cpu().numpy()
+    if Na == 0:
+        raise ValueError("embeddings hold no articles")
+    h0 = None
+    if initial is not None:
+        h0 = (initial.to(device=dev, dtype=torch.float32) if isinstance(initial, torch.Tensor)
+              else torch.as_tensor(np.asarray(initial, dtype=np.float32)).to(dev)).contiguous()
+    w = [torch.from_numpy(getattr(model, n)).to(dev) for n in GRUUserModel.NAMES]
+    it_d = torch.from_numpy(items.astype(np.int32) if nnz else np.zeros(1, dtype=np.int32)).to(dev)
+    chunk = min(int(batch_users), M)
+    ws_bytes = int(lib.dae_gru_user_states_workspace(Na, D, H, chunk))
+    ws_ptr, ws = _workspace(dev, ws_bytes)
+    import ctypes
+    with torch.cuda.device(dev):
+        for c0 in range(0, M, chunk):
+            c1 = min(c0 + chunk, M)
+            e0, e1 = int(indptr[c0]), int(indptr[c1])
+            ip = np.ascontiguousarray(indptr[c0:c1 + 1] - e0)
+            order, active = gru_schedule(ip)
+            ip_d, or_d = torch.from_numpy(ip).to(dev), torch.from_numpy(order).to(dev)
+            Uc = U[e0:e1] if all_states else U[c0:c1]
+            h0c = None if h0 is None else h0[c0:c1]
+            L.call("dae_gru_user_states", L.ptr(E), E.stride(0), Na, D, H, L.ptr(w[0]), D, L.ptr(w[1]), H, L.ptr(w[2]), L.ptr(w[3]),
+                   L.ptr(ip_d), ctypes.c_void_p(it_d.data_ptr() + 4 * e0), L.ptr(or_d), c1 - c0, e1 - e0, int(active.size),
+                   active.ctypes.data_as(ctypes.c_void_p), L.ptr(h0c), H, 1 if all_states else 0,
+                   ctypes.c_void_p(Uc.data_ptr()), U.stride(0), ws_ptr, ws_bytes, L.current_stream())
+    del ws
     if return_tensor:
         return U
     return U.cpu().numpy()

@@ -566,6 +566,38 @@ int dae_user_pair_loss(const float* E, int64_t lde, int32_t Na, int32_t H, const
                        int64_t* n_pairs, float* margin, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------------------------------------------------
+ * GRU user states: the recurrent user model of the same paper, inference only (helpers.gru_user_states).  The state of
+ * every user after every click, from weights in the layout of torch.nn.GRU (one layer, gate row blocks r, z, n).
+ *   E [Na x lde] fp32 article embeddings, D columns (device).  W_ih [3H x ldwi] (D columns), W_hh [3H x ldwh] (H columns),
+ *   b_ih, b_hh float[3H] (device).  History CSR as dae_user_states.  Per user, events oldest first, x = E[items[e]]:
+ *       gi = W_ih x + b_ih        gh = W_hh h + b_hh
+ *       r = sigmoid(gi_r + gh_r)  z = sigmoid(gi_z + gh_z)  n = tanh(gi_n + r * gh_n)  h' = (1 - z) * n + z * h
+ *   h starts at zero (h0 == NULL) or at row u of h0 [M x ldh0] (device, one row per user in the caller's order: the
+ *   states of an earlier call, continued without replaying the history).  D != H is allowed.
+ *   Schedule (helpers.gru_schedule): the work is time-major, one launch per step over the users still active.
+ *       order int32[M] (device): a permutation of the users with history lengths non-increasing.
+ *       active_host int64[T] (HOST memory): active_host[t] = number of users with more than t events; non-increasing,
+ *       active_host[0] <= M, and their sum at most nnz.  T = the longest history (fewer steps truncate every history).
+ *   all_states == 0: U [M x ldu], row u = the state after u's last event; zeros, or its h0 row, for an empty history.
+ *   all_states != 0: U [nnz x ldu], row e = the state after event e (the state that predicts event e + 1).
+ *   fp32 throughout: the products are exact-fp32 MFMA chains in a fixed k order, the gates use expf / tanhf and IEEE
+ *   division; no atomics.  Bit-identical run to run; a user's states do not depend on the other users of the call, on
+ *   their order or on all_states, and continuing from a stored state gives the bits of the unsplit history.
+ *   Preconditions, not reported: items in [0, Na) (an index outside is read as the nearest valid row); order and
+ *   active_host agree with indptr.
+ *   workspace: dae_gru_user_states_workspace(Na, D, H, M) bytes, 256-byte aligned: padded images of E, W_ih, W_hh, the
+ *   input projection of every article [pad(Na) x 3 pad(H)] and two state buffers [pad(M) x pad(H)] -- no events x H term.
+ *   Every image must stay below 4 GiB (split the users into several calls).  M == 0 returns 0 without a launch.
+ *   lde, ldwi >= D; ldwh, ldu, ldh0 >= H.
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_gru_user_states_workspace(int32_t Na, int32_t D, int32_t H, int64_t M);
+int dae_gru_user_states(const float* E, int64_t lde, int32_t Na, int32_t D, int32_t H, const float* W_ih, int64_t ldwi,
+                        const float* W_hh, int64_t ldwh, const float* b_ih, const float* b_hh, const int64_t* indptr,
+                        const int32_t* items, const int32_t* order, int64_t M, int64_t nnz, int32_t T,
+                        const int64_t* active_host, const float* h0, int64_t ldh0, int32_t all_states, float* U,
+                        int64_t ldu, void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
  * Near-duplicate search: every pair (i, j) whose score reaches a threshold, without an N x N matrix (the range query
  * of article de-duplication; helpers.similar_pairs).
  *   Q, ldq, Nq, C, ldc, Nc, D, norm, metric: exactly as dae_topk_similarity, and the same scores.
