@@ -28,7 +28,9 @@ library / a GPU this raises.
   (``dae_user_pair_loss``); ``sample_negatives`` and ``decay_factor_derivatives`` (host code) prepare its inputs.
 * ``gru_user_states`` -- the recurrent user model of the same paper, inference: the GRU state of every user after every click
   from weights in the layout of ``torch.nn.GRU`` (``GRUUserModel``; ``dae_gru_user_states``, time-major, one exact-fp32 MFMA GEMM
-  per step over the users still active); ``gru_schedule`` and ``trim_histories`` (host code) prepare its inputs."""
+  per step over the users still active); ``gru_schedule`` and ``trim_histories`` (host code) prepare its inputs.
+* ``gru_pair_loss`` / ``fit_gru_user_model`` -- the training half of that model: the pairwise ranking loss and, by back-propagation
+  through time on the device, the gradients of the four weight arrays (``dae_gru_pair_loss``); mini-batch Adam on top of it."""
 from __future__ import annotations
 
 import numpy as np
@@ -480,11 +482,13 @@ def user_states(histories, embeddings, beta=0.9, *, timestamps=None, time_unit=N
 class GRUUserModel:
     """The weights of the GRU user model, float32 in the layout of ``torch.nn.GRU`` (one layer, gate row blocks r, z, n):
     ``weight_ih`` [3H x D], ``weight_hh`` [3H x H], ``bias_ih`` and ``bias_hh`` [3H].  ``save`` / ``load`` keep them in an ``.npz``
-    under those four names -- the hand-over format of any trainer (``tools/gru_fit_torch.py`` writes it).  Host code; the states
-    come from ``gru_user_states`` (or ``.states``)."""
+    under those four names -- the hand-over format of any trainer (``fit_gru_user_model`` returns one, with the loss per pair of
+    every epoch in ``.history``, which is not saved; ``tools/gru_fit_torch.py`` writes the file too).  Host code; the states come
+    from ``gru_user_states`` (or ``.states``)."""
     NAMES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
 
-    def __init__(self, weight_ih, weight_hh, bias_ih, bias_hh):
+    def __init__(self, weight_ih, weight_hh, bias_ih, bias_hh, history=None):
+        self.history = history                                              # a trainer's loss per pair of every epoch; not saved
         w = [np.ascontiguousarray(np.asarray(a, dtype=np.float32)) for a in (weight_ih, weight_hh, bias_ih, bias_hh)]
         self.weight_ih, self.weight_hh, self.bias_ih, self.bias_hh = w
         if self.weight_hh.ndim != 2 or self.weight_hh.shape[0] != 3 * self.weight_hh.shape[1] or self.weight_hh.shape[1] < 1:
@@ -891,6 +895,172 @@ def fit_user_model(histories, embeddings, *, beta0=0.9, fit_beta=True, n_neg=4, 
     if fit_beta:
         beta = 1.0 / (1.0 + np.exp(-x[H]))
     return UserModel(x[:H].copy(), float(np.float32(beta)), time_unit, np.asarray(history, dtype=np.float64))
+
+
+def _embedding_shape(embeddings):
+    shape = getattr(embeddings, "shape", None)
+    if shape is None:
+        shape = np.asarray(embeddings).shape
+    if len(shape) != 2:
+        raise ValueError("Expected 2D array")
+    return int(shape[0]), int(shape[1])
+
+
+def _gru_fit_checks(embeddings, H, D, items):
+    """The host-side refusals of ``gru_pair_loss`` / ``fit_gru_user_model``, before any device work: ``(articles, H)``."""
+    Na, De = _embedding_shape(embeddings)
+    if items.size and items.dtype.kind not in "iu":
+        raise ValueError("histories must hold integer article indices")
+    if De != D:
+        raise ValueError(f"embeddings have {De} columns, the model's weight_ih has {D}")
+    if D != H:
+        raise ValueError(f"training scores the state against the embeddings: the hidden size ({H}) must equal the embedding size D = {D}")
+    if items.size and (int(items.min()) < 0 or int(items.max()) >= Na):
+        raise ValueError(f"history items must be in 0..{Na - 1} (got {int(items.min())}..{int(items.max())})")
+    if Na == 0:
+        raise ValueError("embeddings hold no articles")
+    return Na, H
+
+
+def _gru_pair_loss_call(torch, E, w, indptr, it_d, ng_d, n_neg, grads, scal, margins=None):
+    """One ``dae_gru_pair_loss`` on device operands, nothing read back.  ``indptr``: host int64 [M + 1] starting at 0; ``it_d``
+    int32 [nnz], ``ng_d`` int32 [nnz x n_neg]; ``w`` / ``grads``: the four float32 weight tensors and their gradients (contiguous);
+    ``scal``: float64 [2] that receives the loss and the bits of the int64 pair count; ``margins``: float32 [nnz x n_neg] or None."""
+    import ctypes
+    dev = E.device
+    lib = L.load()
+    Na, H = int(E.shape[0]), int(E.shape[1])
+    M, nnz = int(indptr.size - 1), int(indptr[-1])
+    order, active = gru_schedule(indptr)
+    T = int(active.size)
+    ip_d = torch.from_numpy(np.array(indptr, dtype=np.int64)).to(dev)
+    or_d = torch.from_numpy(order if M else np.zeros(1, dtype=np.int32)).to(dev)
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.dae_gru_pair_loss_workspace(Na, H, M, nnz, T, n_neg))
+        ws_ptr, ws = _workspace(dev, ws_bytes)
+        L.call("dae_gru_pair_loss", L.ptr(E), E.stride(0), Na, H, L.ptr(w[0]), H, L.ptr(w[1]), H, L.ptr(w[2]), L.ptr(w[3]), L.ptr(ip_d),
+               L.ptr(it_d), L.ptr(or_d), M, nnz, T, active.ctypes.data_as(ctypes.c_void_p), L.ptr(ng_d), n_neg,
+               ctypes.c_void_p(scal.data_ptr()), ctypes.c_void_p(scal.data_ptr() + 8), L.ptr(grads[0]), H, L.ptr(grads[1]), H,
+               L.ptr(grads[2]), L.ptr(grads[3]), L.ptr(margins), ws_ptr, ws_bytes, L.current_stream())
+    del ws
+
+
+def gru_pair_loss(histories, embeddings, model, negatives, *, return_margins=False, device=None):
+    """The training step of the GRU user model (``dae_gru_pair_loss``): the pairwise ranking loss of ``user_pair_loss`` on the states
+    of ``gru_user_states`` -- with ``h`` the state BEFORE a click, margin ``x = h . (E[clicked] - E[negative])``, loss = the sum of
+    ``softplus(-x)`` over the valid pairs -- and, by back-propagation through time on the device, its gradients with respect to the
+    four weight arrays of ``model`` (a ``GRUUserModel`` whose hidden size equals the embedding size; ``h`` starts at zero).  The
+    embeddings are fixed and get no gradient.
+
+    ``histories``, ``embeddings``: as ``gru_user_states``; ``negatives``: as ``user_pair_loss`` (integer ``[events x n_neg]``, 1..16
+    columns; a negative entry, the click itself and every entry of a user's first click are no pair).  The same ``ValueError``s:
+    items outside the articles, negatives of the wrong shape or >= the number of articles, and ``D != H``.
+
+    Returns ``{'loss': float, 'n_pairs': int, 'weight_ih', 'weight_hh', 'bias_ih', 'bias_hh': float32 gradients in the model's
+    shapes}`` -- sums over the valid pairs, NOT divided by ``n_pairs`` -- and with ``return_margins=True`` also ``'margins'``:
+    float32 ``[events x n_neg]``, 0 where there is no pair.  Bit-identical run to run; ``n_pairs`` and the margins do not depend
+    on the order of the users, the gradients agree under a permutation of the users to rounding."""
+    import torch
+    if not isinstance(model, GRUUserModel):
+        raise TypeError("model must be a GRUUserModel (GRUUserModel.load / from_torch)")
+    indptr, items = _csr_lists(histories)
+    Na, H = _gru_fit_checks(embeddings, model.hidden_size, model.input_size, items)
+    nnz = int(items.size)
+    neg = _check_negatives(negatives, nnz, Na)
+    n_neg = int(neg.shape[1])
+    L.load()
+    dev = torch.device("cuda" if device is None else device)
+    E = _fit_embeddings(torch, embeddings, dev)
+    w = [torch.from_numpy(getattr(model, n)).to(dev) for n in GRUUserModel.NAMES]
+    grads = [torch.empty_like(a) for a in w]
+    scal = torch.zeros(2, dtype=torch.float64, device=dev)
+    mg = torch.empty((max(nnz, 1), n_neg), dtype=torch.float32, device=dev) if return_margins else None
+    it_d = torch.from_numpy(items.astype(np.int32) if nnz else np.zeros(1, dtype=np.int32)).to(dev)
+    ng_d = torch.from_numpy(neg if nnz else np.zeros((1, n_neg), dtype=np.int32)).to(dev)
+    _gru_pair_loss_call(torch, E, w, indptr, it_d, ng_d, n_neg, grads, scal, mg)
+    host = scal.cpu().numpy()
+    res = {"loss": float(host[0]), "n_pairs": int(host[1:].view(np.int64)[0])}
+    for name, g in zip(GRUUserModel.NAMES, grads):
+        res[name] = g.cpu().numpy()
+    if return_margins:
+        res["margins"] = mg[:nnz].cpu().numpy()
+    return res
+
+
+def fit_gru_user_model(histories, embeddings, *, epochs=5, batch_users=256, n_neg=4, lr=1e-2, seed=0, max_events=50, init=None,
+                       window=None, device=None):
+    """Trains the GRU user model of the KDD'17 paper on click histories, on the device: mini-batch Adam on the mean pairwise
+    ranking loss of ``gru_pair_loss``, whose sums and gradients ``dae_gru_pair_loss`` delivers in one call per mini-batch.  The
+    article embeddings [articles x H] stay fixed; the hidden size is H.
+
+    Every user's ``max_events`` most recent events are kept (``trim_histories``).  Every epoch draws ``n_neg`` negatives per click
+    (``sample_negatives(..., seed * 1000003 + epoch, window=window)``; ``window``: per-EVENT candidate ranges of the trimmed
+    histories) and one permutation of the users with at least two events (``numpy.random.default_rng(seed)``), taken in
+    mini-batches of ``batch_users``.  The gradient is divided by the batch's number of pairs; a batch without a pair takes no step.
+    Adam (beta1 = 0.9, beta2 = 0.999, eps = 1e-8) runs on the device as tensor operations on the four float32 weight tensors: only
+    the two scalars of a batch, its loss and its pair count, come back to the host.  The weights start from ``torch.nn.GRU``'s
+    rule, uniform in +-1 / sqrt(H), drawn from the same generator before the permutations -- or from ``init``, a ``GRUUserModel``,
+    to continue a fit.  Two fits with equal arguments return bit-equal weights.
+
+    Returns a ``GRUUserModel`` whose ``.history`` is the loss per pair of every epoch (float64 [epochs])."""
+    import torch
+    if int(epochs) < 0 or not float(lr) > 0.0:
+        raise ValueError("epochs must not be negative and lr must be positive")
+    if int(batch_users) < 1:
+        raise ValueError(f"batch_users must be positive (got {batch_users})")
+    if not 1 <= int(n_neg) <= 16:
+        raise ValueError(f"n_neg must be in 1..16 (got {n_neg})")
+    if init is not None and not isinstance(init, GRUUserModel):
+        raise TypeError("init must be a GRUUserModel")
+    indptr, items = _csr_lists(histories)
+    D = _embedding_shape(embeddings)[1]
+    H = D if init is None else init.hidden_size
+    Na, H = _gru_fit_checks(embeddings, H, D if init is None else init.input_size, items)
+    indptr, items = trim_histories((indptr, items), max_events)
+    n_neg, batch_users = int(n_neg), int(batch_users)
+    rng = np.random.default_rng(seed)
+    if init is None:
+        k = 1.0 / np.sqrt(H)
+        start = [rng.uniform(-k, k, s).astype(np.float32) for s in ((3 * H, H), (3 * H, H), (3 * H,), (3 * H,))]
+    else:
+        start = [getattr(init, n) for n in GRUUserModel.NAMES]
+    L.load()
+    dev = torch.device("cuda" if device is None else device)
+    E = _fit_embeddings(torch, embeddings, dev)
+    w = [torch.from_numpy(np.array(a, dtype=np.float32)).to(dev) for a in start]
+    grads = [torch.empty_like(a) for a in w]
+    m1, m2 = [torch.zeros_like(a) for a in w], [torch.zeros_like(a) for a in w]
+    scal = torch.zeros(2, dtype=torch.float64, device=dev)
+    users = np.flatnonzero(np.diff(indptr) >= 2)
+    history, step = [], 0
+    for epoch in range(int(epochs)):
+        neg = sample_negatives(indptr, items, Na, n_neg, int(seed) * 1000003 + epoch, window=window)
+        perm = rng.permutation(users)
+        total, pairs = 0.0, 0
+        for b0 in range(0, perm.size, batch_users):
+            ub = perm[b0:b0 + batch_users]
+            n = np.diff(indptr)[ub]
+            ip = np.zeros(ub.size + 1, dtype=np.int64)
+            ip[1:] = np.cumsum(n)
+            take = np.repeat(indptr[:-1][ub] - ip[:-1], n) + np.arange(int(ip[-1]), dtype=np.int64)
+            it_d = torch.from_numpy(items[take].astype(np.int32)).to(dev)
+            ng_d = torch.from_numpy(np.ascontiguousarray(neg[take])).to(dev)
+            _gru_pair_loss_call(torch, E, w, ip, it_d, ng_d, n_neg, grads, scal)
+            host = scal.cpu().numpy()                                  # two scalars; the gradients stay on the device
+            n_pairs = int(host[1:].view(np.int64)[0])
+            if n_pairs == 0:
+                continue
+            total += float(host[0])
+            pairs += n_pairs
+            step += 1
+            c1, c2 = 1.0 - 0.9 ** step, 1.0 - 0.999 ** step
+            for a, g, a1, a2 in zip(w, grads, m1, m2):
+                g.div_(float(n_pairs))
+                a1.mul_(0.9).add_(g, alpha=0.1)
+                a2.mul_(0.999).addcmul_(g, g, value=0.001)
+                a.sub_(float(lr) * (a1 / c1) / ((a2 / c2).sqrt_() + 1e-8))
+        history.append(total / max(pairs, 1))
+    return GRUUserModel(*(a.cpu().numpy() for a in w), history=np.asarray(history, dtype=np.float64))
 
 
 def recommend(user_vectors, embeddings, k=10, seen=None, norm="", metric="linear kernel", *, window=None, return_tensor=False,

@@ -598,6 +598,50 @@ int dae_gru_user_states(const float* E, int64_t lde, int32_t Na, int32_t D, int3
                         int64_t ldu, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------------------------------------------------
+ * Training step of the GRU user model: the pairwise ranking loss of dae_user_pair_loss on the states of
+ * dae_gru_user_states, forward and backward through time over one mini-batch of histories, with the gradients of the
+ * four weight arrays (helpers.gru_pair_loss, helpers.fit_gru_user_model).  E is fixed and gets no gradient.
+ *   E, lde, Na, W_ih, ldwi, W_hh, ldwh, b_ih, b_hh, indptr, items, order, M, nnz, T, active_host: as
+ *   dae_gru_user_states, with D = H (the state is scored against the embeddings: W_ih is [3H x H]); h starts at zero.
+ *   negatives int32[nnz x n_neg], 1 <= n_neg <= 16 (device): the sampled negatives of every event; those of a user's
+ *   first event are not read.
+ *   Per user with events e0 .. e1 - 1, h_e the state after event e (the all_states row e of dae_gru_user_states):
+ *       for e = e0 + 1 .. e1 - 1, j < n_neg, n = negatives[e, j], n >= 0 and n != items[e]              (a valid pair)
+ *           x = h_(e-1) . (E[items[e]] - E[n]);   loss += softplus(-x);   n_pairs += 1;   margin[e, j] = x
+ *   and the gradients of `loss` with respect to W_ih, W_hh, b_ih, b_hh by back-propagation through time, per event with
+ *   the stored r, z, n, q = W_hn h + b_hn and h_prev (dh = the loss term plus the carry from the next event):
+ *       dn = dh (1 - z)      dz = dh (h_prev - n)      da_n = dn (1 - n^2)      da_z = dz z (1 - z)
+ *       dq = da_n r          da_r = da_n q r (1 - r)   dgi = [da_r, da_z, da_n]   dgh = [da_r, da_z, dq]
+ *       carry to h_prev = dh z + dgh . W_hh
+ *       dW_ih += dgi^T x     dW_hh += dgh^T h_prev     db_ih += dgi     db_hh += dgh
+ *   The state after a user's last event predicts nothing; the histories are run without it.  The sums are NOT divided
+ *   by n_pairs.
+ *   Outputs (device memory): *loss as double, *n_pairs as int64, dW_ih [3H x ld_dwi], dW_hh [3H x ld_dwh], db_ih and
+ *   db_hh float[3H], and, unless NULL, margin float[nnz x n_neg] (0 where there is no pair).  A call without a pair to
+ *   score (M == 0, T <= 1, only histories of one event) writes zero loss, zero pairs and zero gradients.
+ *   fp32 arithmetic (exact-fp32 MFMA chains in a fixed k order, expf / tanhf / log1pf, IEEE division); the loss of a
+ *   pair is widened to fp64 before any sum across pairs or rows, the pair count is int64.  No atomics of any kind.
+ *   Every output is bit-identical run to run on one device.  n_pairs and margin do not depend on the order of the
+ *   users or on the alignment or leading dimension of E.  The gradients sum over the users in schedule order: under a
+ *   permutation of the users they agree to rounding, not bit for bit.
+ *   Preconditions, not reported: items in [0, Na), negatives < Na (an index outside is read as the nearest valid row);
+ *   order and active_host agree with indptr.
+ *   workspace: dae_gru_pair_loss_workspace(Na, H, M, nnz, T, n_neg) bytes, 256-byte aligned.  Unlike inference it HAS an
+ *   events x H term -- the time-major stash of every step's h_prev, h, r, z, n, q, their gradients and the K-contiguous
+ *   copies the weight-gradient GEMMs read: at most 13 float arrays of pad128(nnz + 128 T) x pad128(H), beside the images of
+ *   dae_gru_user_states, one of W_hh^T, one [pad128(M) x pad128(H)] buffer and 16 split-K slabs [3 pad128(H) x
+ *   pad128(H)].  Every image must stay below 4 GiB: 16 pad128(H) (nnz + 128 T) < 2^32 (train in mini-batches of users).
+ *   lde, ldwi, ldwh, ld_dwi, ld_dwh >= H.
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_gru_pair_loss_workspace(int32_t Na, int32_t H, int64_t M, int64_t nnz, int32_t T, int32_t n_neg);
+int dae_gru_pair_loss(const float* E, int64_t lde, int32_t Na, int32_t H, const float* W_ih, int64_t ldwi, const float* W_hh,
+                      int64_t ldwh, const float* b_ih, const float* b_hh, const int64_t* indptr, const int32_t* items,
+                      const int32_t* order, int64_t M, int64_t nnz, int32_t T, const int64_t* active_host,
+                      const int32_t* negatives, int32_t n_neg, double* loss, int64_t* n_pairs, float* dW_ih, int64_t ld_dwi,
+                      float* dW_hh, int64_t ld_dwh, float* db_ih, float* db_hh, float* margin, void* workspace,
+                      uint64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
  * Near-duplicate search: every pair (i, j) whose score reaches a threshold, without an N x N matrix (the range query
  * of article de-duplication; helpers.similar_pairs).
  *   Q, ldq, Nq, C, ldc, Nc, D, norm, metric: exactly as dae_topk_similarity, and the same scores.

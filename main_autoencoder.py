@@ -125,6 +125,11 @@ def build_parser():
     p.add_argument("--gru_weights", default="",
                    help="an .npz with weight_ih, weight_hh, bias_ih, bias_hh in the layout of torch.nn.GRU (helpers.GRUUserModel; "
                         "tools/gru_fit_torch.py writes one); the hidden size must equal the embedding size")
+    p.add_argument("--fit_gru", action="store_true",
+                   help="with --user_model gru: train the GRU weights on the device (helpers.fit_gru_user_model) on the histories the "
+                        "states are built from -- the held-out click is not among them -- print the loss per pair of every epoch and "
+                        "save them as gru_user_model.npz; with --gru_weights the fit continues from those weights")
+    p.add_argument("--gru_epochs", type=int, default=5, help="epochs of --fit_gru")
     return p
 
 
@@ -144,8 +149,10 @@ def validate(a):
     assert 0. <= a.session_decay <= 1.
     assert not a.rank_metrics or a.recommend > 0, "--rank_metrics needs --recommend K"
     assert not a.fit_user_model or (a.sessions != '' and a.recommend > 0), "--fit_user_model needs --sessions S --recommend K"
-    assert a.user_model == 'decay' or (a.sessions != '' and a.recommend > 0 and a.gru_weights != ''), \
-        "--user_model gru needs --sessions S --recommend K --gru_weights PATH"
+    assert a.user_model == 'decay' or (a.sessions != '' and a.recommend > 0 and (a.gru_weights != '' or a.fit_gru)), \
+        "--user_model gru needs --sessions S --recommend K and --gru_weights PATH or --fit_gru"
+    assert not a.fit_gru or a.user_model == 'gru', "--fit_gru needs --user_model gru"
+    assert a.gru_epochs >= 0
     assert a.max_age >= 0., "--max_age is a number of hours"
     assert a.max_age == 0. or (a.sessions == 'synthetic' and a.recommend > 0), "--max_age needs --sessions synthetic --recommend K"
     return a
@@ -407,14 +414,22 @@ def evaluate_fitted_user_model(a, emb, hist, targets, n, data_dir, timestamps=No
 
 def evaluate_gru_user_model(a, emb, hist, targets, n, data_dir, window=None):
     """--user_model gru: the recurrent user model on the histories the decayed states were built from.  The states come from
-    helpers.gru_user_states with the weights of --gru_weights (helpers.GRUUserModel) and go through the same helpers.recommend
+    helpers.gru_user_states with the weights of --gru_weights (helpers.GRUUserModel) -- or, with --fit_gru, with weights trained
+    here by helpers.fit_gru_user_model on these histories and saved as gru_user_model.npz -- and go through the same helpers.recommend
     and, with --rank_metrics, helpers.recommend_ranks -- with ``window`` (--max_age) inside the same candidate windows.  The
     files are those of the decay model with `_gru` appended to the name: article_encoded_recommend{K}[_window]_gru.npz
     (``indices`` / ``scores`` / ``targets``) and article_encoded_ranks[_window]_gru.npz."""
     from dae_rnn_news_recommendation_amd import helpers
     K = a.recommend
     print('gru user model')
-    model = helpers.GRUUserModel.load(a.gru_weights)
+    model = helpers.GRUUserModel.load(a.gru_weights) if a.gru_weights else None
+    if a.fit_gru:
+        seed = a.seed if a.seed >= 0 else 1234
+        model = helpers.fit_gru_user_model(hist, emb, epochs=a.gru_epochs, seed=seed, init=model)
+        for ep, v in enumerate(model.history):
+            print('  fit epoch %d: loss per pair %.4f' % (ep + 1, v))
+        model.save(data_dir + 'gru_user_model.npz')
+        print('  -> gru_user_model.npz')
     assert model.input_size == emb.shape[1] and model.hidden_size == emb.shape[1], \
         "--gru_weights: input and hidden size (%d, %d) must equal the embedding size %d" % (model.input_size, model.hidden_size, emb.shape[1])
     w = '' if window is None else '_window'

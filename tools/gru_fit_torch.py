@@ -1,9 +1,10 @@
 #!/usr/bin/env python
 """Train the weights of the GRU user model with torch autograd and write them as helpers.GRUUserModel's .npz.
 
-This is a TOOL, not product code: it stands in for the device trainer (BPTT kernels in the library) that does not exist yet
-(DESIGN 11), so that the demo (main_autoencoder.py --user_model gru) and tools/gru_bench.py have real weights.  The library's
-part of the GRU model is the inference half, helpers.gru_user_states.
+This is a TOOL, not product code: the comparison route of the device trainer, helpers.fit_gru_user_model (dae_gru_pair_loss: BPTT
+kernels in the library).  It is no longer the only way to weights -- main_autoencoder.py --user_model gru --fit_gru trains
+on the device -- but it is what tests/test_hip_gru_fit.py holds the device fit against and what tools/gru_fit_bench.py times it
+against, and it trains on the CPU where there is no device.
 
 Model and loss: a torch.nn.GRU (one layer, hidden size = embedding size) reads every user's clicks oldest first, x = E[item]
 with E fixed; the state u_t after event t predicts event t + 1 by the pairwise ranking loss of helpers.user_pair_loss,
