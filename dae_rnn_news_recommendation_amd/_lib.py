@@ -125,6 +125,12 @@ SIGNATURES = {
     "dae_topk_similarity_win": (i32, [vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, u64, vp]),
     "dae_rank_similarity_win_workspace": (u64, [i32, i32, i32]),
     "dae_rank_similarity_win": (i32, [vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]),
+    "dae_topk_similarity_seq_workspace": (u64, [i32, i32, i32, i32]),
+    "dae_topk_similarity_seq": (i32, [vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i64, vp,
+                                      u64, vp]),
+    "dae_rank_similarity_seq_workspace": (u64, [i32, i32, i32]),
+    "dae_rank_similarity_seq": (i32, [vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, u64,
+                                      vp]),
     "dae_user_states": (i32, [vp, i64, i32, i32, vp, vp, i64, i64, f32, vp, i32, vp, i64, vp]),
     "dae_user_pair_loss_workspace": (u64, [i64, i32]),
     "dae_user_pair_loss": (i32, [vp, i64, i32, i32, vp, vp, i64, i64, f32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, u64, vp]),

@@ -34,6 +34,12 @@
 // count loop (bounds read from LDS per row, not kept across the K loop), a list item outside the row's window is not taken out
 // again (the sweep never counted it), and a workgroup with an empty slice adds nothing.  rank_tiles_kernel<*, false> is the
 // kernel as it was; rank_gather_kernel and rank_target_kernel do not know about windows.
+//
+// Shared stamped lists (dae_rank_similarity_seq, rank_tiles_kernel<true, *, true>): the owner lane's cursor walks the list of its row's
+// USER (row_list[i]; outside [0, n_lists): no list, tested here) instead of a list of its own, and an item is taken out again only if its
+// stamp is at most row_limit[i] -- the test sits in front of the "was it counted, does it beat the target" step; an item stamped later
+// stays counted.  Per owner lane that is one more pointer (the stamps beside the items) and the limit; nothing new lives in the count loop.
+// rank_tiles_kernel<*, *, false> is the kernel as it was.
 #include "dae_score_sweep.h"
 
 namespace dae {
@@ -101,10 +107,17 @@ struct RankParams {
     const int32_t* excl_items;    // excl_items[excl_indptr[i] .. excl_indptr[i + 1]), ascending and unique
     const int32_t* win_lo;        // [Nq] candidate windows (rank_tiles_kernel<*, true> only): row i's competitors are the
     const int32_t* win_hi;        // columns win_lo[i] <= j < win_hi[i]
+    // shared stamped lists (rank_tiles_kernel<true, *, true> only): excl_indptr [n_lists + 1] / excl_items are then the CSR of
+    // n_lists lists, one stamp per item; row i reads list row_list[i] (outside [0, n_lists): none) and only its items with
+    const int32_t* list_stamps;   // list_stamps[p] <= row_limit[i] are taken out again
+    const int32_t* row_list;      // [Nq]
+    const int32_t* row_limit;     // [Nq]
+    int n_lists;
 };
 
-template <bool EXCL, bool WIN>
+template <bool EXCL, bool WIN, bool SEQ = false>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams p) {
+    static_assert(EXCL || !SEQ, "the shared lists are a form of the exclusion lists");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     float* tile = reinterpret_cast<float*>(lds);
     uint64_t* tk = reinterpret_cast<uint64_t*>(lds + RANK_TILE_BYTES);     // the query tile's target keys
@@ -126,7 +139,23 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams 
     const int32_t* X = nullptr;
     int xpos = 0, xend = 0, xnext = INT32_MAX, xsub = 0;
     uint64_t xkey = ~0ull;
-    if constexpr (EXCL) {
+    const int32_t* XS = nullptr;                                // SEQ: the stamps beside X, and the row's limit
+    int xlim = 0;
+    if constexpr (SEQ) {
+        if (lane < 32 && xgi < p.Nq) {
+            xkey = p.tkey[xgi];
+            const int u = p.row_list[xgi];
+            if (u >= 0 && u < p.n_lists && xkey != ~0ull) {     // anything else: no list, and never a stray read
+                const int64_t x0 = p.excl_indptr[u];
+                X = p.excl_items + x0;
+                XS = p.list_stamps + x0;
+                xend = (int)(p.excl_indptr[u + 1] - x0);
+                xlim = p.row_limit[xgi];
+                xpos = lower_bound_i32(X, xend, ct0 * BN);      // first item of the slice
+                if (xpos < xend) xnext = X[xpos];
+            }
+        }
+    } else if constexpr (EXCL) {
         if (lane < 32 && xgi < p.Nq) {
             xkey = p.tkey[xgi];
             const int64_t x0 = p.excl_indptr[xgi];
@@ -181,6 +210,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams 
                     const int x = xnext;
                     bool inw = true;                            // outside the row's window the sweep did not count it
                     if constexpr (WIN) inw = x >= wlo[xrow] && x < whi[xrow];
+                    if constexpr (SEQ) inw = inw && XS[xpos] <= xlim;      // stamped later than this row: not barred, stays counted
                     if (x >= ct * BN && x != last && x < p.Nc && !(p.exclude_self && x == xgi) && inw)
                         xsub += (int)(pair_key(tile[xrow * BN + (x - ct * BN)], x) > xkey);
                     last = x;
@@ -216,10 +246,17 @@ extern "C" uint64_t dae_rank_similarity_win_workspace(int32_t Nq, int32_t Nc, in
     return dae_rank_similarity_workspace(Nq, Nc, D);            // the windows are read in place
 }
 
-extern "C" int dae_rank_similarity_win(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
-                                       int32_t norm, int32_t metric, int32_t exclude_self, const int64_t* excl_indptr,
-                                       const int32_t* excl_items, const int32_t* win_lo, const int32_t* win_hi, const int32_t* targets,
-                                       int32_t* rank, float* target_score, void* workspace, uint64_t workspace_bytes, void* stream) {
+extern "C" uint64_t dae_rank_similarity_seq_workspace(int32_t Nq, int32_t Nc, int32_t D) {
+    return dae_rank_similarity_workspace(Nq, Nc, D);            // the shared lists are read in place
+}
+
+// dae_rank_similarity_win and dae_rank_similarity_seq.  list_stamps != NULL: (excl_indptr, excl_items) is the CSR of the n_lists
+// shared lists and row_list / row_limit say what a row reads of it; else they are the per-row lists (or NULL).
+static int rank_run(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D, int32_t norm,
+                    int32_t metric, int32_t exclude_self, const int64_t* excl_indptr, const int32_t* excl_items,
+                    const int32_t* list_stamps, int32_t n_lists, const int32_t* row_list, const int32_t* row_limit,
+                    const int32_t* win_lo, const int32_t* win_hi, const int32_t* targets, int32_t* rank, float* target_score,
+                    void* workspace, uint64_t workspace_bytes, void* stream) {
     DAE_CHECK_ARG((excl_indptr == nullptr) == (excl_items == nullptr),
                   "rank_similarity: excl_indptr and excl_items go together (exactly one of them is NULL)");
     DAE_CHECK_ARG((win_lo == nullptr) == (win_hi == nullptr),
@@ -248,11 +285,36 @@ extern "C" int dae_rank_similarity_win(const float* Q, int64_t ldq, int32_t Nq, 
     p.g = o.g;
     p.Nq = Nq; p.Nc = Nc; p.exclude_self = exclude_self ? 1 : 0; p.splits = splits; p.ctiles = (int)(o.Ncp / BN);
     p.tkey = tkey; p.rank = rank; p.excl_indptr = excl_indptr; p.excl_items = excl_items; p.win_lo = win_lo; p.win_hi = win_hi;
+    p.list_stamps = list_stamps; p.row_list = row_list; p.row_limit = row_limit; p.n_lists = n_lists;
     const int64_t grid = o.Nqp / BM * splits;
+    if (list_stamps) return win_lo ? sweep_launch<rank_tiles_kernel<true, true, true>>(grid, RANK_WIN_LDS, RANK_WIN_LDS, st, p)
+                                   : sweep_launch<rank_tiles_kernel<true, false, true>>(grid, RANK_LDS, RANK_LDS, st, p);
     if (win_lo) return excl_indptr ? sweep_launch<rank_tiles_kernel<true, true>>(grid, RANK_WIN_LDS, RANK_WIN_LDS, st, p)
                                    : sweep_launch<rank_tiles_kernel<false, true>>(grid, RANK_WIN_LDS, RANK_WIN_LDS, st, p);
     return excl_indptr ? sweep_launch<rank_tiles_kernel<true, false>>(grid, RANK_LDS, RANK_LDS, st, p)
                        : sweep_launch<rank_tiles_kernel<false, false>>(grid, RANK_LDS, RANK_LDS, st, p);
+}
+
+extern "C" int dae_rank_similarity_win(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                                       int32_t norm, int32_t metric, int32_t exclude_self, const int64_t* excl_indptr,
+                                       const int32_t* excl_items, const int32_t* win_lo, const int32_t* win_hi, const int32_t* targets,
+                                       int32_t* rank, float* target_score, void* workspace, uint64_t workspace_bytes, void* stream) {
+    return rank_run(Q, ldq, Nq, C, ldc, Nc, D, norm, metric, exclude_self, excl_indptr, excl_items, nullptr, 0, nullptr, nullptr, win_lo,
+                    win_hi, targets, rank, target_score, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dae_rank_similarity_seq(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                                       int32_t norm, int32_t metric, int32_t exclude_self, const int64_t* list_indptr,
+                                       const int32_t* list_items, const int32_t* list_stamps, int32_t n_lists, const int32_t* row_list,
+                                       const int32_t* row_limit, const int32_t* win_lo, const int32_t* win_hi, const int32_t* targets,
+                                       int32_t* rank, float* target_score, void* workspace, uint64_t workspace_bytes, void* stream) {
+    const int given = (list_indptr != nullptr) + (list_items != nullptr) + (list_stamps != nullptr) + (row_list != nullptr) +
+                      (row_limit != nullptr);
+    DAE_CHECK_ARG(given == 0 || given == 5,
+                  "rank_similarity: list_indptr, list_items, list_stamps, row_list and row_limit go together (%d of the 5 are NULL)", 5 - given);
+    DAE_CHECK_ARG(given == 0 || n_lists >= 0, "rank_similarity: n_lists must not be negative (got %d)", n_lists);
+    return rank_run(Q, ldq, Nq, C, ldc, Nc, D, norm, metric, exclude_self, list_indptr, list_items, list_stamps, given ? n_lists : 0,
+                    row_list, row_limit, win_lo, win_hi, targets, rank, target_score, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dae_rank_similarity(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,

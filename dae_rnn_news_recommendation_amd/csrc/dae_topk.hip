@@ -31,6 +31,13 @@
 // a row whose window misses the current tile is passed over, and the two compares join ok0 / ok1, so a column outside the
 // window never reaches the ballot, the exclusion search or the merge.  A workgroup with an empty slice writes part_n = 0.
 // topk_tiles_kernel<*, false> is the kernel as it was.
+//
+// Shared stamped lists (dae_topk_similarity_seq, topk_tiles_kernel<true, *, true>): query rows that are the successive states of one
+// user read ONE list per user, each item stamped with the position of its first click; row i is barred from the items of list
+// row_list[i] whose stamp is at most row_limit[i].  The lookup above becomes lower_bound in the shared list plus the stamp compare
+// (seq_has), still only for the candidates that beat the row's threshold; a row_list outside [0, n_lists) is "no list" (tested here, never
+// a stray read).  Neighbouring rows read the same list addresses; nothing is staged in LDS, the budget is unchanged.
+// topk_tiles_kernel<*, *, false> is the kernel as it was.
 #include "dae_score_sweep.h"
 
 namespace dae {
@@ -61,6 +68,12 @@ struct TopkParams {
     const int32_t* excl_items;    // excl_items[excl_indptr[i] .. excl_indptr[i + 1]), ascending and unique
     const int32_t* win_lo;        // [Nq] candidate windows (topk_tiles_kernel<*, true> only): row i admits the columns
     const int32_t* win_hi;        // win_lo[i] <= j < win_hi[i]
+    // shared stamped lists (topk_tiles_kernel<true, *, true> only): excl_indptr [n_lists + 1] / excl_items are then the CSR of
+    // n_lists lists, one stamp per item; row i reads list row_list[i] (outside [0, n_lists): none) and is barred from its items
+    const int32_t* list_stamps;   // with list_stamps[p] <= row_limit[i]
+    const int32_t* row_list;      // [Nq]
+    const int32_t* row_limit;     // [Nq]
+    int n_lists;
 };
 
 // is j in the ascending list X[0, n)?
@@ -69,8 +82,15 @@ __device__ __forceinline__ bool excl_has(const int32_t* X, int n, int j) {
     return lo < n && X[lo] == j;
 }
 
-template <bool EXCL, bool WIN>
+// is j an item of the ascending list X[0, n) whose stamp S[.] is at most lim?
+__device__ __forceinline__ bool seq_has(const int32_t* X, const int32_t* S, int n, int j, int lim) {
+    const int lo = lower_bound_i32(X, n, j);
+    return lo < n && X[lo] == j && S[lo] <= lim;
+}
+
+template <bool EXCL, bool WIN, bool SEQ = false>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams p) {
+    static_assert(EXCL || !SEQ, "the shared lists are a form of the exclusion lists");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     float* tile = reinterpret_cast<float*>(lds);
     uint64_t* th = reinterpret_cast<uint64_t*>(lds + TOPK_TILE_BYTES);
@@ -109,7 +129,22 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams 
             bool in0 = c0 > t, in1 = c1 > t;
             uint64_t b0 = __ballot(in0), b1 = __ballot(in1);
             if ((b0 | b1) == 0) continue;
-            if constexpr (EXCL) {                               // drop the candidates in the row's exclusion list, then ballot again
+            if constexpr (SEQ) {                                // the same, in the list the row shares: an item counts up to its stamp
+                const int u = p.row_list[gi];
+                if (u >= 0 && u < p.n_lists) {                  // anything else: no list, and never a stray read
+                    const int64_t x0 = p.excl_indptr[u];
+                    const int xn = (int)(p.excl_indptr[u + 1] - x0);
+                    if (xn > 0) {
+                        const int32_t* X = p.excl_items + x0;
+                        const int32_t* S = p.list_stamps + x0;
+                        const int lim = p.row_limit[gi];
+                        if (in0 && seq_has(X, S, xn, j0, lim)) in0 = false;
+                        if (in1 && seq_has(X, S, xn, j1, lim)) in1 = false;
+                        b0 = __ballot(in0); b1 = __ballot(in1);
+                        if ((b0 | b1) == 0) continue;
+                    }
+                }
+            } else if constexpr (EXCL) {                        // drop the candidates in the row's exclusion list, then ballot again
                 const int64_t x0 = p.excl_indptr[gi];
                 const int xn = (int)(p.excl_indptr[gi + 1] - x0);
                 if (xn > 0) {
@@ -212,10 +247,17 @@ extern "C" uint64_t dae_topk_similarity_win_workspace(int32_t Nq, int32_t Nc, in
     return dae_topk_similarity_workspace(Nq, Nc, D, k);         // the windows are read in place
 }
 
-extern "C" int dae_topk_similarity_win(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
-                                       int32_t norm, int32_t metric, int32_t k, int32_t exclude_self, const int64_t* excl_indptr,
-                                       const int32_t* excl_items, const int32_t* win_lo, const int32_t* win_hi, int32_t* idx,
-                                       float* score, int64_t ldk, void* workspace, uint64_t workspace_bytes, void* stream) {
+extern "C" uint64_t dae_topk_similarity_seq_workspace(int32_t Nq, int32_t Nc, int32_t D, int32_t k) {
+    return dae_topk_similarity_workspace(Nq, Nc, D, k);         // the shared lists are read in place
+}
+
+// dae_topk_similarity_win and dae_topk_similarity_seq.  list_stamps != NULL: (excl_indptr, excl_items) is the CSR of the n_lists
+// shared lists and row_list / row_limit say what a row reads of it; else they are the per-row lists (or NULL).
+static int topk_run(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D, int32_t norm,
+                    int32_t metric, int32_t k, int32_t exclude_self, const int64_t* excl_indptr, const int32_t* excl_items,
+                    const int32_t* list_stamps, int32_t n_lists, const int32_t* row_list, const int32_t* row_limit,
+                    const int32_t* win_lo, const int32_t* win_hi, int32_t* idx, float* score, int64_t ldk, void* workspace,
+                    uint64_t workspace_bytes, void* stream) {
     DAE_CHECK_ARG((excl_indptr == nullptr) == (excl_items == nullptr),
                   "topk_similarity: excl_indptr and excl_items go together (exactly one of them is NULL)");
     DAE_CHECK_ARG((win_lo == nullptr) == (win_hi == nullptr),
@@ -237,9 +279,12 @@ extern "C" int dae_topk_similarity_win(const float* Q, int64_t ldq, int32_t Nq, 
     p.ctiles = (int)(o.Ncp / BN);
     p.part = (uint64_t*)o.rest; p.part_n = (int*)(o.rest + al256((uint64_t)splits * o.Nqp * k * 8));
     p.excl_indptr = excl_indptr; p.excl_items = excl_items; p.win_lo = win_lo; p.win_hi = win_hi;
+    p.list_stamps = list_stamps; p.row_list = row_list; p.row_limit = row_limit; p.n_lists = n_lists;
     const int64_t grid = o.Nqp / BM * splits;
     int rc;
-    if (win_lo) rc = excl_indptr ? sweep_launch<topk_tiles_kernel<true, true>>(grid, TOPK_WIN_LDS, TOPK_WIN_LDS, st, p)
+    if (list_stamps) rc = win_lo ? sweep_launch<topk_tiles_kernel<true, true, true>>(grid, TOPK_WIN_LDS, TOPK_WIN_LDS, st, p)
+                                 : sweep_launch<topk_tiles_kernel<true, false, true>>(grid, TOPK_LDS, TOPK_LDS, st, p);
+    else if (win_lo) rc = excl_indptr ? sweep_launch<topk_tiles_kernel<true, true>>(grid, TOPK_WIN_LDS, TOPK_WIN_LDS, st, p)
                                  : sweep_launch<topk_tiles_kernel<false, true>>(grid, TOPK_WIN_LDS, TOPK_WIN_LDS, st, p);
     else rc = excl_indptr ? sweep_launch<topk_tiles_kernel<true, false>>(grid, TOPK_LDS, TOPK_LDS, st, p)
                           : sweep_launch<topk_tiles_kernel<false, false>>(grid, TOPK_LDS, TOPK_LDS, st, p);
@@ -247,6 +292,28 @@ extern "C" int dae_topk_similarity_win(const float* Q, int64_t ldq, int32_t Nq, 
     DAE_LAUNCH(topk_merge_kernel, dim3(Nq), dim3(256), 0, st, p.part, p.part_n, p.Nqp, splits, k, idx, score, ldk);
     DAE_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int dae_topk_similarity_win(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                                       int32_t norm, int32_t metric, int32_t k, int32_t exclude_self, const int64_t* excl_indptr,
+                                       const int32_t* excl_items, const int32_t* win_lo, const int32_t* win_hi, int32_t* idx,
+                                       float* score, int64_t ldk, void* workspace, uint64_t workspace_bytes, void* stream) {
+    return topk_run(Q, ldq, Nq, C, ldc, Nc, D, norm, metric, k, exclude_self, excl_indptr, excl_items, nullptr, 0, nullptr, nullptr,
+                    win_lo, win_hi, idx, score, ldk, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dae_topk_similarity_seq(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                                       int32_t norm, int32_t metric, int32_t k, int32_t exclude_self, const int64_t* list_indptr,
+                                       const int32_t* list_items, const int32_t* list_stamps, int32_t n_lists, const int32_t* row_list,
+                                       const int32_t* row_limit, const int32_t* win_lo, const int32_t* win_hi, int32_t* idx,
+                                       float* score, int64_t ldk, void* workspace, uint64_t workspace_bytes, void* stream) {
+    const int given = (list_indptr != nullptr) + (list_items != nullptr) + (list_stamps != nullptr) + (row_list != nullptr) +
+                      (row_limit != nullptr);
+    DAE_CHECK_ARG(given == 0 || given == 5,
+                  "topk_similarity: list_indptr, list_items, list_stamps, row_list and row_limit go together (%d of the 5 are NULL)", 5 - given);
+    DAE_CHECK_ARG(given == 0 || n_lists >= 0, "topk_similarity: n_lists must not be negative (got %d)", n_lists);
+    return topk_run(Q, ldq, Nq, C, ldc, Nc, D, norm, metric, k, exclude_self, list_indptr, list_items, list_stamps, given ? n_lists : 0,
+                    row_list, row_limit, win_lo, win_hi, idx, score, ldk, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dae_topk_similarity_ex(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,

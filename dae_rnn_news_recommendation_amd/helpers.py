@@ -30,7 +30,12 @@ library / a GPU this raises.
   from weights in the layout of ``torch.nn.GRU`` (``GRUUserModel``; ``dae_gru_user_states``, time-major, one exact-fp32 MFMA GEMM
   per step over the users still active); ``gru_schedule`` and ``trim_histories`` (host code) prepare its inputs.
 * ``gru_pair_loss`` / ``fit_gru_user_model`` -- the training half of that model: the pairwise ranking loss and, by back-propagation
-  through time on the device, the gradients of the four weight arrays (``dae_gru_pair_loss``); mini-batch Adam on top of it."""
+  through time on the device, the gradients of the four weight arrays (``dae_gru_pair_loss``); mini-batch Adam on top of it.
+* ``evaluate_every_click`` -- next-click evaluation at every click of every history, not only the last: ``recommend_every_click`` /
+  ``recommend_ranks_every_click`` sweep the ``all_states`` rows against one stamped exclusion list per user, shared by that user's
+  rows (``click_prefix_lists``, ``every_click_rows``; ``dae_topk_similarity_seq`` / ``dae_rank_similarity_seq``);
+  ``rank_metrics_by_position`` and ``popularity_ranks_every_click`` (host code) give the accuracy-by-history-length table and the
+  baseline."""
 from __future__ import annotations
 
 import numpy as np
@@ -267,6 +272,53 @@ def normalize_exclusions(exclude, n_rows, n_candidates):
     return out_ptr, np.zeros(0, dtype=np.int32)
 
 
+def normalize_shared_exclusions(exclude_shared, n_rows, n_candidates):
+    """The shared stamped lists of ``most_similar`` / ``target_ranks`` (``exclude_shared=``) in the form ``dae_topk_similarity_seq``
+    reads: ``(indptr int64 [n_lists + 1], items int32, stamps int32, row_list int32 [n_rows], row_limit int32 [n_rows])``.
+    ``exclude_shared``: ``(lists, stamps, row_list, row_limit)`` -- ``lists`` a list of index sequences or an ``(indptr, items)``
+    tuple, every list ascending and unique with items in ``[0, n_candidates)``; ``stamps`` one integer per item (flat, or in the
+    layout of ``lists``); ``row_list`` / ``row_limit`` one integer per query row (a ``row_list`` outside ``[0, n_lists)``: no
+    list).  ``ValueError`` for anything else -- the kernel's lookup is a binary search, so the order is checked here.  Host code."""
+    if not (isinstance(exclude_shared, (tuple, list)) and len(exclude_shared) == 4):
+        raise ValueError("exclude_shared must be (lists, stamps, row_list, row_limit)")
+    lists, stamps, row_list, row_limit = exclude_shared
+    indptr, items = _csr_lists(lists, "exclude_shared")
+    if items.size and items.dtype.kind not in "iu":
+        raise ValueError("exclude_shared must hold integer indices")
+    items = items.astype(np.int64)
+    st = _csr_lists(stamps, "exclude_shared stamps")[1] if isinstance(stamps, (tuple, list)) else np.asarray(stamps).ravel()
+    if st.shape[0] != items.shape[0]:
+        raise ValueError(f"{st.shape[0]} stamps for {items.shape[0]} list items")
+    if st.size and st.dtype.kind not in "iu":
+        raise ValueError("exclude_shared stamps must be integers")
+    if items.size and (int(items.min()) < 0 or int(items.max()) >= int(n_candidates)):
+        raise ValueError(f"exclude_shared items must be in 0..{int(n_candidates) - 1} (got {int(items.min())}..{int(items.max())})")
+    if items.size > 1:
+        inner = np.ones(items.size - 1, dtype=bool)
+        starts = indptr[1:-1]
+        inner[starts[(starts > 0) & (starts < items.size)] - 1] = False     # the step from one list to the next
+        if (np.diff(items)[inner] <= 0).any():
+            raise ValueError("every list of exclude_shared must be ascending and unique")
+    out = []
+    for name, r in (("row_list", row_list), ("row_limit", row_limit)):
+        if hasattr(r, "detach"):
+            r = r.detach().cpu().numpy()
+        r = np.asarray(r).ravel()
+        if r.shape[0] != int(n_rows):
+            raise ValueError(f"exclude_shared {name} has {r.shape[0]} entries for {int(n_rows)} queries")
+        if r.size and r.dtype.kind not in "iu":
+            raise ValueError(f"exclude_shared {name} must hold integers")
+        out.append(np.ascontiguousarray(np.clip(r.astype(np.int64), -2 ** 31, 2 ** 31 - 1).astype(np.int32)))
+    st = np.clip(st.astype(np.int64), -2 ** 31, 2 ** 31 - 1).astype(np.int32)
+    return indptr, np.ascontiguousarray(items.astype(np.int32)), np.ascontiguousarray(st), out[0], out[1]
+
+
+def _upload_shared(shared, dev):
+    """The five arrays of ``normalize_shared_exclusions`` on the device; empty item arrays go up as one element: never a NULL pointer."""
+    import torch
+    return tuple(torch.from_numpy(a if a.size else np.zeros(1, dtype=a.dtype)).to(dev) for a in shared)
+
+
 def _n_rows(data):
     """The number of rows of a container ``_device_matrix`` takes, without touching it."""
     shape = getattr(data, "shape", None)
@@ -341,8 +393,8 @@ def candidate_windows(query_times, publish_times, max_age=None):
     return lo.astype(np.int32), hi.astype(np.int32)
 
 
-def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candidates=None, *, exclude=None, window=None,
-                 return_tensor=False, device=None):
+def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candidates=None, *, exclude=None, exclude_shared=None,
+                 window=None, return_tensor=False, device=None):
     """The ``k`` most similar rows of ``candidates`` (default: ``in_df`` itself) for every row of ``in_df``, by the scores
     ``pairwise_similarity`` would give (same ``norm`` / ``metric``, same exact-fp32 products), without the N x N matrix:
     ``dae_topk_similarity`` keeps a running top-k per row inside the GEMM's epilogue.
@@ -362,14 +414,25 @@ def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candi
     admits only the candidates ``lo[i] <= j < hi[i]`` (``normalize_window``; e.g. from ``candidate_windows``), on top of
     ``exclude`` and ``exclude_self`` (``dae_topk_similarity_win``).  An empty window gives a row of -1 / -inf.  The kernel walks
     the union of the windows of 128 neighbouring rows, so with ``candidates`` the rows are handed over in the stable order of
-    ``(lo, hi)`` and the result is put back in the caller's order; the order is total, so the result does not depend on it."""
+    ``(lo, hi)`` and the result is put back in the caller's order; the order is total, so the result does not depend on it.
+
+    ``exclude_shared = (lists, stamps, row_list, row_limit)`` (instead of ``exclude``) is the form for query rows that are the
+    successive states of one user: one list per USER with a stamp per item (``click_prefix_lists``), and per query row the list
+    it reads and its stamp limit (``every_click_rows``); row i skips the items of list ``row_list[i]`` whose stamp is at most
+    ``row_limit[i]`` (``normalize_shared_exclusions``, ``dae_topk_similarity_seq``).  The result equals, bit for bit, that of
+    ``exclude`` with those items listed row by row."""
     import torch
     if exclude_self is None:
         exclude_self = candidates is None
     elif exclude_self and candidates is not None:
         raise ValueError("exclude_self=True needs candidates=None (the self pair exists only when the corpus is in_df itself)")
+    if exclude is not None and exclude_shared is not None:
+        raise ValueError("exclude and exclude_shared do not go together")
     if window is not None:
         window = normalize_window(window, _n_rows(in_df), _n_rows(in_df if candidates is None else candidates))
+    shared = None
+    if exclude_shared is not None:
+        shared = normalize_shared_exclusions(exclude_shared, _n_rows(in_df), _n_rows(in_df if candidates is None else candidates))
     lib, dev, Q, Cm, Nq, Nc, D = _sweep_inputs(in_df, candidates, norm, metric, device)
     k = int(k)
     idx = torch.empty((Nq, max(k, 1)), dtype=torch.int32, device=dev)
@@ -387,9 +450,19 @@ def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candi
             Q, wlo, whi = Q[perm_d].contiguous(), wlo[perm], whi[perm]
             if xp is not None:
                 xp, xi = _permute_csr(xp, xi, perm)
+            if shared is not None:
+                shared = shared[:3] + (np.ascontiguousarray(shared[3][perm]), np.ascontiguousarray(shared[4][perm]))
         lo_d, hi_d = torch.from_numpy(np.ascontiguousarray(wlo)).to(dev), torch.from_numpy(np.ascontiguousarray(whi)).to(dev)
     xp_d, xi_d = _upload_exclusions(xp, xi, dev)
-    if Nq > 0 or window is None:                                      # without rows only the windowed call is skipped
+    if shared is not None:
+        if Nq > 0:
+            sh_d = _upload_shared(shared, dev)
+            with torch.cuda.device(dev):
+                L.call("dae_topk_similarity_seq", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
+                       _NORMS[norm], _METRICS[metric], k, 1 if exclude_self else 0, L.ptr(sh_d[0]), L.ptr(sh_d[1]), L.ptr(sh_d[2]),
+                       int(shared[0].size - 1), L.ptr(sh_d[3]), L.ptr(sh_d[4]), L.ptr(lo_d), L.ptr(hi_d), L.ptr(idx), L.ptr(score),
+                       idx.stride(0), ws_p, ws_bytes, L.current_stream())
+    elif Nq > 0 or window is None:                                    # without rows only the windowed call is skipped
         with torch.cuda.device(dev):
             L.call("dae_topk_similarity_win", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
                    _NORMS[norm], _METRICS[metric], k, 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(lo_d), L.ptr(hi_d),
@@ -487,8 +560,9 @@ class GRUUserModel:
     from ``gru_user_states`` (or ``.states``)."""
     NAMES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
 
-    def __init__(self, weight_ih, weight_hh, bias_ih, bias_hh, history=None):
+    def __init__(self, weight_ih, weight_hh, bias_ih, bias_hh, history=None, validation=None):
         self.history = history                                              # a trainer's loss per pair of every epoch; not saved
+        self.validation = validation                                        # and its validation metrics (fit_gru_user_model); not saved
         w = [np.ascontiguousarray(np.asarray(a, dtype=np.float32)) for a in (weight_ih, weight_hh, bias_ih, bias_hh)]
         self.weight_ih, self.weight_hh, self.bias_ih, self.bias_hh = w
         if self.weight_hh.ndim != 2 or self.weight_hh.shape[0] != 3 * self.weight_hh.shape[1] or self.weight_hh.shape[1] < 1:
@@ -988,7 +1062,7 @@ def gru_pair_loss(histories, embeddings, model, negatives, *, return_margins=Fal
 
 
 def fit_gru_user_model(histories, embeddings, *, epochs=5, batch_users=256, n_neg=4, lr=1e-2, seed=0, max_events=50, init=None,
-                       window=None, device=None):
+                       window=None, validation=None, validation_every=1, keep_best=False, device=None):
     """Trains the GRU user model of the KDD'17 paper on click histories, on the device: mini-batch Adam on the mean pairwise
     ranking loss of ``gru_pair_loss``, whose sums and gradients ``dae_gru_pair_loss`` delivers in one call per mini-batch.  The
     article embeddings [articles x H] stay fixed; the hidden size is H.
@@ -1002,10 +1076,21 @@ def fit_gru_user_model(histories, embeddings, *, epochs=5, batch_users=256, n_ne
     rule, uniform in +-1 / sqrt(H), drawn from the same generator before the permutations -- or from ``init``, a ``GRUUserModel``,
     to continue a fit.  Two fits with equal arguments return bit-equal weights.
 
+    ``validation`` (histories of held-out users, default None): after every ``validation_every`` epochs the weights of that
+    epoch are scored on them by ``evaluate_every_click`` -- every click ranked given the clicks before it -- and the metric dicts
+    (``rank_metrics`` plus ``'epoch'``, counted from 1) are collected in ``.validation`` (not saved, like ``.history``).  The
+    validation pass reads the weights and nothing else: it does not touch the generator or Adam's state, so without ``keep_best``
+    the returned weights are bit-equal to those of a fit without ``validation``.  With ``keep_best`` the weights of the scored
+    epoch with the highest validation ``mrr`` (the first of equals) are returned instead of the last epoch's.
+
     Returns a ``GRUUserModel`` whose ``.history`` is the loss per pair of every epoch (float64 [epochs])."""
     import torch
     if int(epochs) < 0 or not float(lr) > 0.0:
         raise ValueError("epochs must not be negative and lr must be positive")
+    if int(validation_every) < 1:
+        raise ValueError(f"validation_every must be positive (got {validation_every})")
+    if keep_best and validation is None:
+        raise ValueError("keep_best needs validation histories")
     if int(batch_users) < 1:
         raise ValueError(f"batch_users must be positive (got {batch_users})")
     if not 1 <= int(n_neg) <= 16:
@@ -1033,6 +1118,7 @@ def fit_gru_user_model(histories, embeddings, *, epochs=5, batch_users=256, n_ne
     scal = torch.zeros(2, dtype=torch.float64, device=dev)
     users = np.flatnonzero(np.diff(indptr) >= 2)
     history, step = [], 0
+    scored, best, best_w = [], None, None
     for epoch in range(int(epochs)):
         neg = sample_negatives(indptr, items, Na, n_neg, int(seed) * 1000003 + epoch, window=window)
         perm = rng.permutation(users)
@@ -1060,7 +1146,15 @@ def fit_gru_user_model(histories, embeddings, *, epochs=5, batch_users=256, n_ne
                 a2.mul_(0.999).addcmul_(g, g, value=0.001)
                 a.sub_(float(lr) * (a1 / c1) / ((a2 / c2).sqrt_() + 1e-8))
         history.append(total / max(pairs, 1))
-    return GRUUserModel(*(a.cpu().numpy() for a in w), history=np.asarray(history, dtype=np.float64))
+        if validation is not None and (epoch + 1) % int(validation_every) == 0:
+            host = [a.cpu().numpy() for a in w]                       # a copy: the fit goes on with the device tensors
+            m = evaluate_every_click(validation, E, GRUUserModel(*host), device=device)["metrics"]
+            m["epoch"] = epoch + 1
+            scored.append(m)
+            if keep_best and m["mrr"] == m["mrr"] and (best is None or m["mrr"] > best):      # NaN (no click to score): never the best
+                best, best_w = m["mrr"], host
+    final = best_w if keep_best and best_w is not None else [a.cpu().numpy() for a in w]
+    return GRUUserModel(*final, history=np.asarray(history, dtype=np.float64), validation=scored if validation is not None else None)
 
 
 def recommend(user_vectors, embeddings, k=10, seen=None, norm="", metric="linear kernel", *, window=None, return_tensor=False,
@@ -1099,7 +1193,30 @@ def next_click_metrics(indices, targets):
             "ndcg": float(np.where(hit, 1.0 / np.log2(1.0 + rank), 0.0).mean()), "n": n}
 
 
-def _competitors(tgt, Nq, Nc, exclude_self, xp, xi, window):
+def _shared_row_chunks(n, max_pairs=1 << 22):
+    """Row ranges ``[a, b)`` whose list lengths ``n`` sum to about ``max_pairs``: the O(sum of L^2) host work goes chunk by chunk."""
+    total = np.concatenate([[0], np.cumsum(n)])
+    a = 0
+    while a < n.size:
+        b = max(int(np.searchsorted(total, total[a] + max_pairs, side="right")) - 1, a + 1)
+        yield a, min(b, n.size)
+        a = min(b, n.size)
+
+
+def _shared_pairs(lp, row_list, a, b):
+    """For the query rows ``[a, b)``: every (row, item of the row's shared list) pair as ``(rows int64, places int64)``, ``places``
+    pointing into the lists' item / stamp arrays."""
+    u = row_list[a:b].astype(np.int64)
+    ok = (u >= 0) & (u < lp.size - 1)
+    us = np.where(ok, u, 0)
+    n = np.where(ok, lp[us + 1] - lp[us], 0)
+    start = np.concatenate([[0], np.cumsum(n)])
+    rows = np.repeat(np.arange(a, b, dtype=np.int64), n)
+    places = np.repeat(lp[us] - start[:-1], n) + np.arange(int(start[-1]), dtype=np.int64)
+    return rows, places
+
+
+def _competitors(tgt, Nq, Nc, exclude_self, xp, xi, window, shared=None):
     """The host bookkeeping of ``target_ranks``: ``(n_cand int64 [Nq], barred bool [Nq])`` -- how many candidates compete in each
     row, the target included, and which targets can never be returned.  ``tgt``: int64 targets (negative: none); ``xp, xi``: the
     lists of ``normalize_exclusions`` or None; ``window``: the pair of ``normalize_window``, None meaning ``(0, Nc)`` for every row."""
@@ -1120,6 +1237,34 @@ def _competitors(tgt, Nq, Nc, exclude_self, xp, xi, window):
         inside = (it >= wlo[rows]) & (it < whi[rows])
         n_cand -= np.bincount(rows[inside & ~is_t], minlength=Nq)
         self_in &= np.bincount(rows[(it == rows) & ~is_t], minlength=Nq) == 0      # unless the list took the self column already
+    if shared is not None:                                            # the same bookkeeping for the shared stamped lists
+        lp, li, ls, row_list, row_limit = shared
+        u = row_list.astype(np.int64)
+        has = (u >= 0) & (u < lp.size - 1)
+        us = np.where(has, u, 0)
+        lim = row_limit.astype(np.int64)
+        key = np.repeat(np.arange(lp.size - 1, dtype=np.int64), np.diff(lp)) * max(Nc, 1) + li.astype(np.int64)      # ascending
+
+        def listed(col):                                              # is column col[i] barred by row i's list?
+            q = us * max(Nc, 1) + np.clip(col, 0, max(Nc - 1, 0))
+            at = np.minimum(np.searchsorted(key, q), max(key.size - 1, 0))
+            return has & (col >= 0) & (key[at] == q) & (ls[at] <= lim) if key.size else np.zeros(Nq, dtype=bool)
+        t_listed = listed(tgt)
+        barred |= t_listed
+        if window is None:                                            # items up to the limit: one search in the lists' sorted stamps
+            smin = int(ls.min()) if ls.size else 0
+            span = (int(ls.max()) - smin + 2) if ls.size else 1
+            skey = np.sort(np.repeat(np.arange(lp.size - 1, dtype=np.int64), np.diff(lp)) * span + (ls.astype(np.int64) - smin))
+            n_list = np.where(has, np.searchsorted(skey, us * span + np.clip(lim - smin, -1, span - 2), side="right") - lp[us], 0)
+            n_cand -= n_list - t_listed.astype(np.int64)
+        else:
+            n_in = np.diff(lp)[us] * has
+            for a, b in _shared_row_chunks(n_in):
+                rows, places = _shared_pairs(lp, row_list, a, b)
+                it = li[places].astype(np.int64)
+                take = (ls[places] <= lim[rows]) & (it >= wlo[rows]) & (it < whi[rows]) & (it != tgt[rows])
+                n_cand[a:b] -= np.bincount(rows[take] - a, minlength=b - a)
+        self_in &= ~(listed(me) & (me != tgt))                        # unless the list took the self column already
     if exclude_self:
         self_t = tgt == me
         barred |= self_t
@@ -1127,8 +1272,8 @@ def _competitors(tgt, Nq, Nc, exclude_self, xp, xi, window):
     return n_cand, barred
 
 
-def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, candidates=None, *, exclude=None, window=None,
-                 return_tensor=False, device=None):
+def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, candidates=None, *, exclude=None, exclude_shared=None,
+                 window=None, return_tensor=False, device=None):
     """The position of one target row of ``candidates`` (default: ``in_df`` itself) per row of ``in_df`` among ALL candidates, by
     the scores and the order of ``most_similar`` (score descending, ties by index ascending), without the N x N matrix:
     ``dae_rank_similarity`` counts the candidates ahead of the target inside the GEMM's epilogue.
@@ -1149,14 +1294,24 @@ def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, ca
     candidates inside the row's window, and the sentence about k above holds for ``most_similar(..., window=window)``: a target
     outside its row's window can never be returned and gets ``rank`` 0 (its ``score`` is still the pair's score), and
     ``n_candidates`` is the window's size minus the row's exclusion items inside the window other than the target, minus the
-    row itself when it is excluded and lies inside."""
+    row itself when it is excluded and lies inside.
+
+    ``exclude_shared = (lists, stamps, row_list, row_limit)`` (instead of ``exclude``; ``dae_rank_similarity_seq``) is the shared
+    stamped form of ``most_similar``: every sentence above holds with "row i's exclusion items" read as the items of list
+    ``row_list[i]`` whose stamp is at most ``row_limit[i]``, and the result equals that of ``exclude`` with those items bit for
+    bit."""
     import torch
     if exclude_self is None:
         exclude_self = candidates is None
     elif exclude_self and candidates is not None:
         raise ValueError("exclude_self=True needs candidates=None (the self pair exists only when the corpus is in_df itself)")
+    if exclude is not None and exclude_shared is not None:
+        raise ValueError("exclude and exclude_shared do not go together")
     if window is not None:
         window = normalize_window(window, _n_rows(in_df), _n_rows(in_df if candidates is None else candidates))
+    shared = None
+    if exclude_shared is not None:
+        shared = normalize_shared_exclusions(exclude_shared, _n_rows(in_df), _n_rows(in_df if candidates is None else candidates))
     lib, dev, Q, Cm, Nq, Nc, D = _sweep_inputs(in_df, candidates, norm, metric, device)
     tgt = targets.detach().cpu().numpy() if isinstance(targets, torch.Tensor) else np.asarray(targets)
     tgt = tgt.ravel()
@@ -1170,7 +1325,7 @@ def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, ca
     xp = xi = None
     if exclude is not None:
         xp, xi = normalize_exclusions(exclude, Nq, Nc)
-    n_cand, barred = _competitors(tgt, Nq, Nc, exclude_self, xp, xi, window)
+    n_cand, barred = _competitors(tgt, Nq, Nc, exclude_self, xp, xi, window, shared)
     rank = torch.empty(Nq, dtype=torch.int32, device=dev)
     score = torch.empty(Nq, dtype=torch.float32, device=dev)
     if Nq == 0:
@@ -1188,12 +1343,21 @@ def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, ca
             Q, wlo, whi, t_d = Q[perm_d].contiguous(), wlo[perm], whi[perm], t_d[perm_d].contiguous()
             if xp is not None:
                 xp, xi = _permute_csr(xp, xi, perm)
+            if shared is not None:
+                shared = shared[:3] + (np.ascontiguousarray(shared[3][perm]), np.ascontiguousarray(shared[4][perm]))
         lo_d, hi_d = torch.from_numpy(np.ascontiguousarray(wlo)).to(dev), torch.from_numpy(np.ascontiguousarray(whi)).to(dev)
     xp_d, xi_d = _upload_exclusions(xp, xi, dev)
     with torch.cuda.device(dev):
-        L.call("dae_rank_similarity_win", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
-               _NORMS[norm], _METRICS[metric], 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(lo_d), L.ptr(hi_d),
-               L.ptr(t_d), L.ptr(rank), L.ptr(score), ws_p, ws_bytes, L.current_stream())
+        if shared is not None:
+            sh_d = _upload_shared(shared, dev)
+            L.call("dae_rank_similarity_seq", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
+                   _NORMS[norm], _METRICS[metric], 1 if exclude_self else 0, L.ptr(sh_d[0]), L.ptr(sh_d[1]), L.ptr(sh_d[2]),
+                   int(shared[0].size - 1), L.ptr(sh_d[3]), L.ptr(sh_d[4]), L.ptr(lo_d), L.ptr(hi_d), L.ptr(t_d), L.ptr(rank),
+                   L.ptr(score), ws_p, ws_bytes, L.current_stream())
+        else:
+            L.call("dae_rank_similarity_win", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
+                   _NORMS[norm], _METRICS[metric], 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(lo_d), L.ptr(hi_d),
+                   L.ptr(t_d), L.ptr(rank), L.ptr(score), ws_p, ws_bytes, L.current_stream())
     if perm_d is not None:
         rank, score = torch.empty_like(rank).index_copy_(0, perm_d, rank), torch.empty_like(score).index_copy_(0, perm_d, score)
     rank = rank.long()
@@ -1315,6 +1479,247 @@ def popularity_recommend(histories, n_articles, k, seen=None, *, window=None):
         keep = head[~np.isin(head, mine)][:int(k)]
         out[u, :keep.size] = keep
     return out
+
+
+def click_prefix_lists(histories):
+    """One exclusion list per user for the every-click protocol, shared by all of that user's rows: ``(indptr int64 [users + 1],
+    items int32, stamps int32)`` -- per user the distinct articles of the history, ascending, each with the 0-based position of
+    its FIRST click.  The state after click e must skip exactly the items with ``stamp <= e`` (``exclude_shared=``,
+    ``dae_topk_similarity_seq``): the lists are no larger than the click log, where one materialised prefix per event would be
+    sum of L (L + 1) / 2 items.  ``ValueError`` for a negative article index.  Host code, no per-user loop."""
+    indptr, items = _csr_lists(histories)
+    if items.size and items.dtype.kind not in "iu":
+        raise ValueError("histories must hold integer article indices")
+    items = items.astype(np.int64)
+    if items.size and int(items.min()) < 0:
+        raise ValueError(f"history items must not be negative (got {int(items.min())})")
+    M = indptr.size - 1
+    users = np.repeat(np.arange(M, dtype=np.int64), np.diff(indptr))
+    span = int(items.max()) + 1 if items.size else 1
+    key, first = np.unique(users * span + items, return_index=True)      # by user, then article; the index of the first occurrence
+    out = np.zeros(M + 1, dtype=np.int64)
+    out[1:] = np.cumsum(np.bincount(key // span, minlength=M))
+    return out, (key % span).astype(np.int32), (first - indptr[:-1][key // span]).astype(np.int32)
+
+
+def every_click_rows(histories, timestamps=None):
+    """The query rows of the every-click protocol, one per event e in the order of ``user_states(all_states=True)``, as a dict:
+    ``targets`` int64 (the user's next article, -1 at the user's last event), ``row_list`` int32 (the user: the list of
+    ``click_prefix_lists`` the row reads), ``row_limit`` int32 (the event's 0-based position within the user: the row skips the
+    items stamped at most that), ``positions`` int64 (the number of clicks seen, ``row_limit + 1``) and, with ``timestamps`` (one per
+    event), ``query_times`` float64: the time of the NEXT click, which is what ``candidate_windows`` wants (at a user's last
+    event, which has no target, the event's own time).  Host code."""
+    indptr, items = _csr_lists(histories)
+    if items.size and items.dtype.kind not in "iu":
+        raise ValueError("histories must hold integer article indices")
+    nnz, n = int(items.size), np.diff(indptr)
+    users = np.repeat(np.arange(indptr.size - 1, dtype=np.int64), n)
+    pos = np.arange(nnz, dtype=np.int64) - indptr[:-1][users]
+    last = np.zeros(nnz, dtype=bool)
+    last[indptr[1:][n > 0] - 1] = True
+    nxt = np.minimum(np.arange(nnz, dtype=np.int64) + 1, max(nnz - 1, 0))
+    out = {"targets": np.where(last, -1, items.astype(np.int64)[nxt] if nnz else np.zeros(0, np.int64)).astype(np.int64),
+           "row_list": users.astype(np.int32), "row_limit": pos.astype(np.int32), "positions": pos + 1}
+    if timestamps is not None:
+        t = np.asarray(_event_times(timestamps), dtype=np.float64).ravel()
+        if t.size != nnz:
+            raise ValueError(f"{t.size} timestamps for {nnz} events")
+        out["query_times"] = np.where(last, t, t[nxt] if nnz else t)
+    return out
+
+
+def _every_click_chunks(states, embeddings, histories, window, batch_rows, device):
+    """What the two every-click sweeps share: the checked inputs, and per chunk of ``batch_rows`` rows the arguments of the sweep.
+    Returns ``(rows dict, E, chunks)``; a chunk is ``(a, b, states[a:b], exclude_shared, window or None)``."""
+    import torch
+    if int(batch_rows) < 1:
+        raise ValueError(f"batch_rows must be positive (got {batch_rows})")
+    indptr, items = _csr_lists(histories)
+    rows = every_click_rows((indptr, items))
+    nnz = int(items.size)
+    if _n_rows(states) != nnz:
+        raise ValueError(f"{_n_rows(states)} state rows for {nnz} events (states is the all_states=True output for these histories)")
+    Na = _n_rows(embeddings)
+    if items.size and int(items.max()) >= Na:
+        raise ValueError(f"history items must be in 0..{Na - 1} (got {int(items.min())}..{int(items.max())})")
+    lists = click_prefix_lists((indptr, items))
+    if window is not None:
+        window = normalize_window(window, nnz, Na)
+    L.load()
+    dev = torch.device("cuda" if device is None else device)
+    E = _fit_embeddings(torch, embeddings, dev)
+
+    def chunks():
+        for a in range(0, nnz, int(batch_rows)):
+            b = min(a + int(batch_rows), nnz)
+            yield (a, b, states[a:b], ((lists[0], lists[1]), lists[2], rows["row_list"][a:b], rows["row_limit"][a:b]),
+                   None if window is None else (window[0][a:b], window[1][a:b]))
+    return rows, E, chunks()
+
+
+def recommend_every_click(states, embeddings, histories, k=10, *, window=None, batch_rows=1 << 20, norm="", metric="linear kernel",
+                          return_tensor=False, device=None):
+    """``recommend`` at every click: for the state after each event e of every history -- ``states`` [events x H], the
+    ``all_states=True`` output of ``user_states`` / ``gru_user_states`` for the same ``histories`` -- the ``k`` articles with the
+    largest relevance among those the user had not clicked by then (positions <= e).  The seen articles are one stamped list
+    per user, shared by that user's rows (``click_prefix_lists``, ``most_similar(exclude_shared=...)``, ``dae_topk_similarity_seq``).
+
+    ``window``: a pair ``(lo, hi)`` per EVENT, e.g. ``candidate_windows(every_click_rows(histories, t)['query_times'], publish,
+    max_age)``.  The rows go through the sweep in chunks of ``batch_rows`` (an operand image must stay below 4 GiB); the chunking
+    does not change a bit.  Returns ``(indices int64 [events x k], scores float32 [events x k], targets int64 [events])``:
+    ``targets[e]`` is the user's next click, -1 at a user's last event."""
+    import torch
+    rows, E, chunks = _every_click_chunks(states, embeddings, histories, window, batch_rows, device)
+    idx, score = [], []
+    for a, b, S, shared, win in chunks:
+        i, s = most_similar(S, k=k, norm=norm, metric=metric, candidates=E, exclude_shared=shared, window=win, return_tensor=True,
+                            device=device)
+        idx.append(i)
+        score.append(s)
+    if not idx:
+        idx = [torch.empty((0, max(int(k), 1)), dtype=torch.int64, device=E.device)]
+        score = [torch.empty((0, max(int(k), 1)), dtype=torch.float32, device=E.device)]
+    idx, score = torch.cat(idx), torch.cat(score)
+    if return_tensor:
+        return idx, score, torch.from_numpy(rows["targets"]).to(idx.device)
+    return idx.cpu().numpy(), score.cpu().numpy(), rows["targets"]
+
+
+def recommend_ranks_every_click(states, embeddings, histories, *, window=None, batch_rows=1 << 20, norm="", metric="linear kernel",
+                                return_tensor=False, device=None):
+    """``recommend_ranks`` at every click, the full-rank twin of ``recommend_every_click`` (same arguments and chunking;
+    ``target_ranks(exclude_shared=...)``, ``dae_rank_similarity_seq``): the rank of every next click among all the articles the
+    user had not clicked by then.  Returns ``(rank, score, n_candidates, targets)`` with the conventions of ``target_ranks``:
+    ``rank`` is 0 at a user's last event (no target), for a re-click of an article already seen, and for a target outside its
+    event's window."""
+    import torch
+    rows, E, chunks = _every_click_chunks(states, embeddings, histories, window, batch_rows, device)
+    out = [[], [], []]
+    for a, b, S, shared, win in chunks:
+        r = target_ranks(S, rows["targets"][a:b], norm=norm, metric=metric, candidates=E, exclude_shared=shared, window=win,
+                         return_tensor=True, device=device)
+        for o, x in zip(out, r):
+            o.append(x)
+    if not out[0]:
+        out = [[torch.empty(0, dtype=dt, device=E.device)] for dt in (torch.int64, torch.float32, torch.int64)]
+    rank, score, n_cand = (torch.cat(o) for o in out)
+    if return_tensor:
+        return rank, score, n_cand, torch.from_numpy(rows["targets"]).to(rank.device)
+    return rank.cpu().numpy(), score.cpu().numpy(), n_cand.cpu().numpy(), rows["targets"]
+
+
+def evaluate_every_click(histories, embeddings, model, *, timestamps=None, time_unit=None, window=None, batch_users=4096,
+                         ks=(1, 5, 10, 50, 100), device=None):
+    """Next-click evaluation at EVERY click of every history (the per-position protocol of session-based recommendation), where
+    the last-click protocol scores one click per user: the state after each event is ranked against the event that follows,
+    among all the articles the user had not clicked by then (``recommend_ranks_every_click``).
+
+    ``model``: a ``GRUUserModel`` (states of ``gru_user_states``), a fitted ``UserModel`` (``alpha *`` the states of ``user_states``
+    with its ``beta`` and ``time_unit``, as ``UserModel.states`` applies them) or a float ``beta`` (``user_states``; ``time_unit``
+    as there).  ``timestamps`` (one per event) drive the decay of the two decay forms; ``window`` is a pair ``(lo, hi)`` per EVENT.
+    The states are produced for ``batch_users`` users at a time and ranked at once, so [events x H] never exists whole.
+
+    Returns a dict: the per-event arrays ``rank``, ``score``, ``n_candidates``, ``targets``, ``positions`` (clicks seen, for
+    ``rank_metrics_by_position``) and ``metrics`` = ``rank_metrics`` over all events with a target."""
+    import torch
+    if int(batch_users) < 1:
+        raise ValueError(f"batch_users must be positive (got {batch_users})")
+    indptr, items = _csr_lists(histories)
+    if items.size and items.dtype.kind not in "iu":
+        raise ValueError("histories must hold integer article indices")
+    M, nnz = int(indptr.size - 1), int(items.size)
+    t = None if timestamps is None else np.asarray(_event_times(timestamps), dtype=np.float64).ravel()
+    if t is not None and t.size != nnz:
+        raise ValueError(f"{t.size} timestamps for {nnz} events")
+    if window is not None:
+        window = normalize_window(window, nnz, _n_rows(embeddings))
+    if not isinstance(model, (GRUUserModel, UserModel)):
+        model = float(model)
+    L.load()
+    dev = torch.device("cuda" if device is None else device)
+    E = _fit_embeddings(torch, embeddings, dev)
+    alpha = torch.from_numpy(model.alpha.astype(np.float32)).to(dev) if isinstance(model, UserModel) else None
+    out = [[], [], []]
+    for u0 in range(0, M, int(batch_users)):
+        u1 = min(u0 + int(batch_users), M)
+        a, b = int(indptr[u0]), int(indptr[u1])
+        if b == a:
+            continue
+        hist = (indptr[u0:u1 + 1] - a, items[a:b])
+        tb = None if t is None else t[a:b]
+        if isinstance(model, GRUUserModel):
+            S = gru_user_states(hist, E, model, all_states=True, return_tensor=True, device=device)
+        elif isinstance(model, UserModel):
+            S = user_states(hist, E, model.beta, timestamps=tb, time_unit=model.time_unit, all_states=True, return_tensor=True,
+                            device=device) * alpha
+        else:
+            S = user_states(hist, E, model, timestamps=tb, time_unit=time_unit, all_states=True, return_tensor=True, device=device)
+        r = recommend_ranks_every_click(S, E, hist, window=None if window is None else (window[0][a:b], window[1][a:b]), device=device)
+        for o, x in zip(out, r[:3]):
+            o.append(x)
+        del S
+    rows = every_click_rows((indptr, items))
+    rank, score, n_cand = (np.concatenate(o) if o else np.zeros(0, dtype=dt) for o, dt in zip(out, (np.int64, np.float32, np.int64)))
+    return {"rank": rank, "score": score, "n_candidates": n_cand, "targets": rows["targets"], "positions": rows["positions"],
+            "metrics": rank_metrics(rank, n_cand, rows["targets"], ks=ks)}
+
+
+def rank_metrics_by_position(rank, n_candidates, targets, positions, edges=(1, 2, 3, 5, 10, 20, 50), ks=(1, 5, 10, 50, 100)):
+    """``rank_metrics`` per bucket of clicks seen: the accuracy-against-history-length table of the every-click protocol.  Host code.
+
+    ``positions``: per row the number of clicks the state has seen (``every_click_rows``).  The buckets are ``[edges[i], edges[i + 1])``
+    and ``[edges[-1], inf)``, plus a leading bucket for the rows below ``edges[0]`` when there are any: every row is in exactly one,
+    and pooling them gives ``rank_metrics`` of all rows.  Returns a list of dicts, one per bucket in order: ``lo``, ``hi`` (None: open
+    end) and the entries of ``rank_metrics`` over the bucket's rows."""
+    r, nc, tgt, pos = (np.asarray(x).ravel() for x in (rank, n_candidates, targets, positions))
+    if not (r.shape[0] == nc.shape[0] == tgt.shape[0] == pos.shape[0]):
+        raise ValueError(f"{r.shape[0]} ranks, {nc.shape[0]} candidate counts, {tgt.shape[0]} targets and {pos.shape[0]} positions")
+    edges = [int(e) for e in edges]
+    if not edges or any(b <= a for a, b in zip(edges, edges[1:])):
+        raise ValueError("edges must be a non-empty increasing sequence")
+    which = np.searchsorted(np.asarray(edges, dtype=np.int64), pos.astype(np.int64), side="right")      # 0: below edges[0]
+    out = []
+    for b in range(0 if (which == 0).any() else 1, len(edges) + 1):
+        m = which == b
+        out.append(dict(lo=None if b == 0 else edges[b - 1], hi=None if b == len(edges) else edges[b], **rank_metrics(r[m], nc[m], tgt[m], ks=ks)))
+    return out
+
+
+def popularity_ranks_every_click(histories, n_articles, *, window=None):
+    """Full ranks of the popularity baseline under the every-click protocol: ``popularity_ranks``' order (click count over all
+    ``histories`` descending, index ascending), per event e the articles the user clicked at positions <= e skipped, the target
+    the user's next click.  ``window``: a pair ``(lo, hi)`` per EVENT.  Host code (chunked, O(sum of L^2)).  Returns ``(rank int64
+    [events], n_candidates int64 [events], targets int64 [events])`` with the conventions of ``target_ranks``: rank 0 without a
+    target, for a seen one and for one outside the window."""
+    indptr, items = _csr_lists(histories)
+    Na, nnz = int(n_articles), int(items.size)
+    if items.size and int(items.max()) >= Na:
+        raise ValueError(f"history items must be in 0..{Na - 1} (got {int(items.min())}..{int(items.max())})")
+    rows = every_click_rows((indptr, items))
+    lp, li, ls = click_prefix_lists((indptr, items))
+    tgt = rows["targets"]
+    if window is not None:
+        window = normalize_window(window, nnz, Na)
+    n_cand, barred = _competitors(tgt, nnz, Na, False, None, None, window, (lp, li, ls, rows["row_list"], rows["row_limit"]))
+    order = np.argsort(-np.bincount(items.astype(np.int64), minlength=Na), kind="stable")
+    pos = np.empty(Na, dtype=np.int64)
+    pos[order] = np.arange(Na)
+    ok = (tgt >= 0) & ~barred
+    pt = pos[np.where(ok, tgt, 0)]
+    if window is None:
+        ahead = pt.copy()                                                   # every article before the target in the order
+    else:
+        ahead = np.array([int((pos[window[0][e]:window[1][e]] < pt[e]).sum()) if ok[e] else 0 for e in range(nnz)], dtype=np.int64)
+    lim = rows["row_limit"].astype(np.int64)
+    n_in = np.diff(lp)[rows["row_list"]] if nnz else np.zeros(0, dtype=np.int64)
+    for a, b in _shared_row_chunks(n_in):                                   # minus the seen ones among them
+        r, places = _shared_pairs(lp, rows["row_list"], a, b)
+        it = li[places].astype(np.int64)
+        take = (ls[places] <= lim[r]) & (pos[it] < pt[r])
+        if window is not None:
+            take &= (it >= window[0][r]) & (it < window[1][r])
+        ahead[a:b] -= np.bincount(r[take] - a, minlength=b - a)
+    return np.where(ok, 1 + ahead, 0).astype(np.int64), n_cand, tgt
 
 
 def _label_keys(labels):

@@ -505,6 +505,43 @@ int dae_rank_similarity_win(const float* Q, int64_t ldq, int32_t Nq, const float
                             uint64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------------------------------------------------
+ * Shared stamped exclusion lists: the windowed calls for query rows that are the successive states of one user (row e = the
+ * state after click e, which must skip the articles clicked at positions <= e; helpers.most_similar / target_ranks
+ * (exclude_shared=...), recommend_every_click, recommend_ranks_every_click).  Instead of one list per query row there is one
+ * list per user, read by all of that user's rows, with a stamp per item: the lists stay the size of the click log.
+ *   Every argument of the _win calls but excl_indptr / excl_items, and the same scores, 64-bit key order, tails, exclude_self,
+ *   windows, determinism, grid-independence and workspace size, plus (all on the device)
+ *     list_indptr int64[n_lists + 1], list_items int32[list_indptr[n_lists]], list_stamps int32[same]: a CSR of n_lists lists;
+ *       each list's items are corpus indices, sorted ascending and unique (a precondition, as in dae_topk_similarity_ex), and
+ *       every item carries one stamp (for a click log: the position of the item's first click);
+ *     row_list int32[Nq]: the list that query row i reads; a value outside [0, n_lists) means "no list" (tested in the kernel:
+ *       a wrong value never becomes a stray read);
+ *     row_limit int32[Nq]: the row's stamp limit.
+ *   Candidate j is barred for query row i iff j == list_items[p] for some p in row i's list with list_stamps[p] <= row_limit[i].
+ *   Everything else is exactly the _win call given, per row, the materialised list { list_items[p] : list_stamps[p] <=
+ *   row_limit[i] } -- bit for bit: in dae_rank_similarity_seq the list removes competitors only, and a list item outside the
+ *   row's window is neither counted nor taken out again.  The top-k lookup (a binary search in the shared list, then the
+ *   stamp compare) runs only on the candidates that beat the row's current k-th score; the rank call walks the shared list
+ *   once per row, one step per item.
+ *   All five list pointers NULL: exactly the _win call without lists, bit for bit; some but not all NULL is an argument
+ *   error, and so is a negative n_lists.  All other argument checks are those of the _win calls, with their messages.
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_topk_similarity_seq_workspace(int32_t Nq, int32_t Nc, int32_t D, int32_t k);
+int dae_topk_similarity_seq(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc,
+                            int32_t D, int32_t norm, int32_t metric, int32_t k, int32_t exclude_self,
+                            const int64_t* list_indptr, const int32_t* list_items, const int32_t* list_stamps,
+                            int32_t n_lists, const int32_t* row_list, const int32_t* row_limit, const int32_t* win_lo,
+                            const int32_t* win_hi, int32_t* idx, float* score, int64_t ldk, void* workspace,
+                            uint64_t workspace_bytes, void* stream);
+uint64_t dae_rank_similarity_seq_workspace(int32_t Nq, int32_t Nc, int32_t D);
+int dae_rank_similarity_seq(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
+                            int32_t norm, int32_t metric, int32_t exclude_self, const int64_t* list_indptr,
+                            const int32_t* list_items, const int32_t* list_stamps, int32_t n_lists,
+                            const int32_t* row_list, const int32_t* row_limit, const int32_t* win_lo,
+                            const int32_t* win_hi, const int32_t* targets, int32_t* rank, float* target_score,
+                            void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
  * User states from browsing histories: the decaying model of "Embedding-based News Recommendation for Millions of
  * Users" (KDD'17), a decay-weighted mean of the embeddings of the articles a user has read (helpers.user_states).
  *   E [Na x lde] fp32 article embeddings (device).  History CSR (device): indptr int64[M + 1], items int32[nnz], each

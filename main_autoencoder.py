@@ -16,6 +16,8 @@ examples:
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rank_metrics --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rank_metrics --max_age 48 --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --fit_user_model --similarity False
+  python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --every_click --similarity False
+  python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --every_click --user_model gru --fit_gru --gru_validation 0.2 --similarity False
 """
 import argparse
 import os
@@ -130,6 +132,15 @@ def build_parser():
                         "states are built from -- the held-out click is not among them -- print the loss per pair of every epoch and "
                         "save them as gru_user_model.npz; with --gru_weights the fit continues from those weights")
     p.add_argument("--gru_epochs", type=int, default=5, help="epochs of --fit_gru")
+    p.add_argument("--every_click", default=False, **b,
+                   help="with --recommend K: beside the last-click evaluation (whose output and files stay what they are), rank EVERY click "
+                        "of every session given the clicks before it (helpers.evaluate_every_click: one stamped seen-list per user, shared "
+                        "by the user's rows) -- the decay model, the most-clicked-unseen baseline and, when selected, the fitted and GRU "
+                        "models -- print the metrics and the table by clicks seen, and save rank / score / n_candidates / targets / "
+                        "positions to article_encoded_every_click[_gru|_fitted][_window].npz; honours --max_age")
+    p.add_argument("--gru_validation", type=float, default=0.,
+                   help="FRACTION in (0, 1) with --fit_gru: hold out that share of the users (drawn by the fit's seed), train on the rest and "
+                        "print the every-click MRR of the held-out users after every epoch (helpers.fit_gru_user_model(validation=...))")
     return p
 
 
@@ -153,6 +164,9 @@ def validate(a):
         "--user_model gru needs --sessions S --recommend K and --gru_weights PATH or --fit_gru"
     assert not a.fit_gru or a.user_model == 'gru', "--fit_gru needs --user_model gru"
     assert a.gru_epochs >= 0
+    assert not a.every_click or a.recommend > 0, "--every_click needs --recommend K"
+    assert 0. <= a.gru_validation < 1., "--gru_validation is a fraction in [0, 1)"
+    assert a.gru_validation == 0. or a.fit_gru, "--gru_validation needs --fit_gru"
     assert a.max_age >= 0., "--max_age is a number of hours"
     assert a.max_age == 0. or (a.sessions == 'synthetic' and a.recommend > 0), "--max_age needs --sessions synthetic --recommend K"
     return a
@@ -335,12 +349,15 @@ def evaluate_recommend(a, trY, emb, data_dir):
     print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'decayed user state', m['hit'], m['mrr'], m['ndcg']))
     print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'most clicked unseen', b['hit'], b['mrr'], b['ndcg']))
     print('calculate recommend %d done' % K)
+    models = {}
     if a.rank_metrics:
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir)
     if a.fit_user_model:
-        evaluate_fitted_user_model(a, emb, hist, targets, n, data_dir, timestamps=None if t is None else t[keep])
+        models['fitted'] = evaluate_fitted_user_model(a, emb, hist, targets, n, data_dir, timestamps=None if t is None else t[keep])
     if a.user_model == 'gru':
-        evaluate_gru_user_model(a, emb, hist, targets, n, data_dir)
+        evaluate_gru_user_model(a, emb, hist, targets, n, data_dir, models=models)
+    if a.every_click:
+        evaluate_every_click(a, emb, (indptr, items), t, None, models, data_dir)
     return idx, score, targets
 
 
@@ -376,12 +393,15 @@ def evaluate_recommend_window(a, trY, emb, data_dir):
     print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'decayed user state', m['hit'], m['mrr'], m['ndcg']))
     print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'most clicked unseen', b['hit'], b['mrr'], b['ndcg']))
     print('calculate recommend %d done' % K)
+    models = {}
     if a.rank_metrics:
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir, window=window, max_age=a.max_age)
     if a.fit_user_model:
-        evaluate_fitted_user_model(a, emb, hist, targets, n, data_dir, timestamps=t[keep], window=window)
+        models['fitted'] = evaluate_fitted_user_model(a, emb, hist, targets, n, data_dir, timestamps=t[keep], window=window)
     if a.user_model == 'gru':
-        evaluate_gru_user_model(a, emb, hist, targets, n, data_dir, window=window)
+        evaluate_gru_user_model(a, emb, hist, targets, n, data_dir, window=window, models=models)
+    if a.every_click:
+        evaluate_every_click(a, emb, (indptr, items), t, publish, models, data_dir)
     return idx, score, targets
 
 
@@ -412,24 +432,37 @@ def evaluate_fitted_user_model(a, emb, hist, targets, n, data_dir, timestamps=No
     return model
 
 
-def evaluate_gru_user_model(a, emb, hist, targets, n, data_dir, window=None):
+def evaluate_gru_user_model(a, emb, hist, targets, n, data_dir, window=None, models=None):
     """--user_model gru: the recurrent user model on the histories the decayed states were built from.  The states come from
     helpers.gru_user_states with the weights of --gru_weights (helpers.GRUUserModel) -- or, with --fit_gru, with weights trained
     here by helpers.fit_gru_user_model on these histories and saved as gru_user_model.npz -- and go through the same helpers.recommend
     and, with --rank_metrics, helpers.recommend_ranks -- with ``window`` (--max_age) inside the same candidate windows.  The
     files are those of the decay model with `_gru` appended to the name: article_encoded_recommend{K}[_window]_gru.npz
-    (``indices`` / ``scores`` / ``targets``) and article_encoded_ranks[_window]_gru.npz."""
+    (``indices`` / ``scores`` / ``targets``) and article_encoded_ranks[_window]_gru.npz.  With --gru_validation FRACTION that share of
+    the users (drawn by the fit's seed) is kept out of the fit and scored after every epoch by the every-click protocol
+    (helpers.fit_gru_user_model(validation=...)).  ``models``: a dict that receives the model under 'gru' (for --every_click)."""
     from dae_rnn_news_recommendation_amd import helpers
     K = a.recommend
     print('gru user model')
     model = helpers.GRUUserModel.load(a.gru_weights) if a.gru_weights else None
     if a.fit_gru:
         seed = a.seed if a.seed >= 0 else 1234
-        model = helpers.fit_gru_user_model(hist, emb, epochs=a.gru_epochs, seed=seed, init=model)
+        if a.gru_validation > 0:
+            held = np.random.default_rng(seed).random(hist[0].size - 1) < a.gru_validation
+            val = helpers._permute_csr(hist[0], hist[1], np.flatnonzero(held))
+            model = helpers.fit_gru_user_model(helpers._permute_csr(hist[0], hist[1], np.flatnonzero(~held)), emb, epochs=a.gru_epochs,
+                                               seed=seed, init=model, validation=val)
+        else:
+            model = helpers.fit_gru_user_model(hist, emb, epochs=a.gru_epochs, seed=seed, init=model)
         for ep, v in enumerate(model.history):
             print('  fit epoch %d: loss per pair %.4f' % (ep + 1, v))
+        for m in model.validation or ():
+            print('  fit epoch %d: validation MRR %.4f  hit@10 %.4f  (%d clicks of %d held-out users)'
+                  % (m['epoch'], m['mrr'], m['hit@10'], m['n'], int(held.sum())))
         model.save(data_dir + 'gru_user_model.npz')
         print('  -> gru_user_model.npz')
+    if models is not None:
+        models['gru'] = model
     assert model.input_size == emb.shape[1] and model.hidden_size == emb.shape[1], \
         "--gru_weights: input and hidden size (%d, %d) must equal the embedding size %d" % (model.input_size, model.hidden_size, emb.shape[1])
     w = '' if window is None else '_window'
@@ -447,6 +480,51 @@ def evaluate_gru_user_model(a, emb, hist, targets, n, data_dir, window=None):
               % ('gru user state', m['auc'], m['mrr'], m['mean_rank'], m['median_rank'], m['hit@1'], m['hit@10'], m['hit@100']))
     print('gru user model done')
     return idx, score
+
+
+def evaluate_every_click(a, emb, sessions, t, publish, models, data_dir):
+    """--every_click: next-click evaluation at every click of every session (helpers.evaluate_every_click), beside the last-click
+    evaluation.  The state after each click is ranked against the click that follows among the articles the user had not
+    clicked by then -- for the decay model (--session_decay), for the fitted and the GRU model when they were selected (``models``:
+    fitted here on the sessions without their last click), and for the most-clicked-unseen baseline
+    (helpers.popularity_ranks_every_click).  One line of rank metrics per model, then the MRR by clicks seen
+    (helpers.rank_metrics_by_position).  Files: article_encoded_every_click[_fitted|_gru][_window].npz with ``rank`` / ``score`` /
+    ``n_candidates`` / ``targets`` / ``positions``.  With ``publish`` (--max_age) every click competes only with the articles
+    published by the time of the next click and at most --max_age hours before it."""
+    from dae_rnn_news_recommendation_amd import helpers
+    print('calculate every click')
+    n = emb.shape[0]
+    window, w = None, ''
+    if publish is not None:
+        times = helpers.every_click_rows(sessions, t)['query_times']
+        window, w = helpers.candidate_windows(times, publish, None if np.isinf(a.max_age) else a.max_age), '_window'
+    runs = [('decayed user state', '', a.session_decay)]
+    if 'fitted' in models:
+        runs.append(('fitted user model', '_fitted', models['fitted']))
+    if 'gru' in models:
+        runs.append(('gru user state', '_gru', models['gru']))
+    rows = []
+    for name, tag, model in runs:
+        r = helpers.evaluate_every_click(sessions, emb, model, timestamps=t, window=window, ks=(1, 10, 100))
+        np.savez(data_dir + 'article_encoded_every_click%s%s.npz' % (tag, w), rank=r['rank'], score=r['score'],
+                 n_candidates=r['n_candidates'], targets=r['targets'], positions=r['positions'])
+        rows.append((name, r['metrics'], helpers.rank_metrics_by_position(r['rank'], r['n_candidates'], r['targets'], r['positions'], ks=())))
+    b_rank, b_cand, targets = helpers.popularity_ranks_every_click(sessions, n, window=window)
+    positions = helpers.every_click_rows(sessions)['positions']
+    rows.append(('most clicked unseen', helpers.rank_metrics(b_rank, b_cand, targets, ks=(1, 10, 100)),
+                 helpers.rank_metrics_by_position(b_rank, b_cand, targets, positions, ks=())))
+    print('  %d users, %d clicks, %d with a next click -> article_encoded_every_click%s.npz'
+          % (sessions[0].shape[0] - 1, sessions[1].shape[0], rows[0][1]['n'], w))
+    for name, m, _ in rows:
+        print('  every click %-20s AUC %.4f  MRR %.4f  mean rank %.1f  median rank %.1f  hit@1 %.4f  hit@10 %.4f  hit@100 %.4f'
+              % (name, m['auc'], m['mrr'], m['mean_rank'], m['median_rank'], m['hit@1'], m['hit@10'], m['hit@100']))
+    print('  MRR by clicks seen %s' % ''.join('  %20s' % name for name, _, _ in rows))
+    for i, bucket in enumerate(rows[0][2]):
+        span = '%d+' % bucket['lo'] if bucket['hi'] is None else ('%d' % bucket['lo'] if bucket['hi'] == bucket['lo'] + 1
+                                                                  else '%d-%d' % (bucket['lo'], bucket['hi'] - 1))
+        print('  seen %-6s n %6d %s' % (span, bucket['n'], ''.join('  %20.4f' % by[i]['mrr'] for _, _, by in rows)))
+    print('calculate every click done')
+    return rows
 
 
 def evaluate_rank_metrics(states, emb, hist, targets, n, data_dir, window=None, max_age=0.):
