@@ -19,8 +19,8 @@
 //    the tile; the compare's lane mask is counted per half wave on the scalar unit and lane l of a wave keeps the running
 //    count of the wave's row l for the whole slice.  Columns >= Nc (zero padding: score 0, which would
 //    beat every negative target) and the self pair are masked; the target itself has an equal key and is never counted.
-//    Exclusion lists (sorted CSR rows, as in dae_topk_similarity_ex) only remove competitors: the sweep counts every column,
-//    then the listed ones are taken out again.  Lane l < 32 of wave w owns query row 32 w + l and a cursor into its list; the
+//    Exclusion lists (RowFilter, dae_score_sweep.h) only remove competitors: the sweep counts every column, then the listed
+//    ones are taken out again.  Lane l < 32 of wave w owns query row 32 w + l and a cursor into the list it reads (row_list_of); the
 //    items of a list that fall into the current tile are the run behind the cursor.  Only when some row of the query tile has
 //    an item in the tile is the tile written to LDS (over the dead staging ring); the owner lanes read the listed columns'
 //    scores there, compare and count.  The work is one step per list item -- it does not grow with rank.
@@ -35,11 +35,10 @@
 // again (the sweep never counted it), and a workgroup with an empty slice adds nothing.  rank_tiles_kernel<*, false> is the
 // kernel as it was; rank_gather_kernel and rank_target_kernel do not know about windows.
 //
-// Shared stamped lists (dae_rank_similarity_seq, rank_tiles_kernel<true, *, true>): the owner lane's cursor walks the list of its row's
-// USER (row_list[i]; outside [0, n_lists): no list, tested here) instead of a list of its own, and an item is taken out again only if its
-// stamp is at most row_limit[i] -- the test sits in front of the "was it counted, does it beat the target" step; an item stamped later
-// stays counted.  Per owner lane that is one more pointer (the stamps beside the items) and the limit; nothing new lives in the count loop.
-// rank_tiles_kernel<*, *, false> is the kernel as it was.
+// Shared stamped lists (dae_rank_similarity_seq, rank_tiles_kernel<true, *, true>): the cursor walks the list of its row's USER and an
+// item is taken out again only if its stamp is at most the row's limit -- the test sits in front of the "was it counted, does it beat
+// the target" step; an item stamped later stays counted.  Per owner lane that is one more pointer (the stamps beside the items) and
+// the limit; nothing new lives in the count loop.  rank_tiles_kernel<*, *, false> is the kernel as it was.
 #include "dae_score_sweep.h"
 
 namespace dae {
@@ -100,19 +99,10 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_target_kernel(RankTarget
 
 struct RankParams {
     GemmParams g;                 // one K segment: A = query image, Bt = corpus image
-    int Nq, Nc, exclude_self, splits, ctiles;
+    int Nq, Nc, splits, ctiles;
     const uint64_t* tkey;         // [Nqp] target keys (rank_target_kernel)
     int32_t* rank;                // [Nq], holds 1 (0 without a target) on entry
-    const int64_t* excl_indptr;   // [Nq + 1] exclusion CSR (rank_tiles_kernel<true> only): row i's list is
-    const int32_t* excl_items;    // excl_items[excl_indptr[i] .. excl_indptr[i + 1]), ascending and unique
-    const int32_t* win_lo;        // [Nq] candidate windows (rank_tiles_kernel<*, true> only): row i's competitors are the
-    const int32_t* win_hi;        // columns win_lo[i] <= j < win_hi[i]
-    // shared stamped lists (rank_tiles_kernel<true, *, true> only): excl_indptr [n_lists + 1] / excl_items are then the CSR of
-    // n_lists lists, one stamp per item; row i reads list row_list[i] (outside [0, n_lists): none) and only its items with
-    const int32_t* list_stamps;   // list_stamps[p] <= row_limit[i] are taken out again
-    const int32_t* row_list;      // [Nq]
-    const int32_t* row_limit;     // [Nq]
-    int n_lists;
+    RowFilter f;                  // which columns compete in a row (dae_score_sweep.h); a listed column is counted, then taken out again
 };
 
 template <bool EXCL, bool WIN, bool SEQ = false>
@@ -133,37 +123,19 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams 
     }
     int* wlo = reinterpret_cast<int*>(lds + RANK_LDS);          // the query tile's windows (WIN only; behind the counts)
     int* whi = wlo + 128;
-    if constexpr (WIN) window_prologue(p.win_lo, p.win_hi, p.Nq, p.Nc, qt, split, p.splits, wlo, whi, whi + 128, ct0, ct1);
+    if constexpr (WIN) window_prologue(p.f.win_lo, p.f.win_hi, p.Nq, p.Nc, qt, split, p.splits, wlo, whi, whi + 128, ct0, ct1);
     // ---- the exclusion cursor of this lane's row (lanes 0..31 of every wave) ----
     const int xrow = wave * 32 + lane, xgi = qt * BM + xrow;
-    const int32_t* X = nullptr;
-    int xpos = 0, xend = 0, xnext = INT32_MAX, xsub = 0;
+    RowList xl = {nullptr, nullptr, 0, 0};
+    int xpos = 0, xnext = INT32_MAX, xsub = 0;
     uint64_t xkey = ~0ull;
-    const int32_t* XS = nullptr;                                // SEQ: the stamps beside X, and the row's limit
-    int xlim = 0;
-    if constexpr (SEQ) {
+    if constexpr (EXCL) {
         if (lane < 32 && xgi < p.Nq) {
             xkey = p.tkey[xgi];
-            const int u = p.row_list[xgi];
-            if (u >= 0 && u < p.n_lists && xkey != ~0ull) {     // anything else: no list, and never a stray read
-                const int64_t x0 = p.excl_indptr[u];
-                X = p.excl_items + x0;
-                XS = p.list_stamps + x0;
-                xend = (int)(p.excl_indptr[u + 1] - x0);
-                xlim = p.row_limit[xgi];
-                xpos = lower_bound_i32(X, xend, ct0 * BN);      // first item of the slice
-                if (xpos < xend) xnext = X[xpos];
-            }
-        }
-    } else if constexpr (EXCL) {
-        if (lane < 32 && xgi < p.Nq) {
-            xkey = p.tkey[xgi];
-            const int64_t x0 = p.excl_indptr[xgi];
-            X = p.excl_items + x0;
-            xend = (int)(p.excl_indptr[xgi + 1] - x0);
-            if (xkey == ~0ull) xend = 0;                        // no target: nothing to count
-            xpos = lower_bound_i32(X, xend, ct0 * BN);          // first item of the slice
-            if (xpos < xend) xnext = X[xpos];
+            xl = row_list_of<SEQ>(p.f, xgi);
+            if (xkey == ~0ull) xl.n = 0;                        // no target: nothing to count
+            xpos = lower_bound_i32(xl.X, xl.n, ct0 * BN);       // first item of the slice
+            if (xpos < xl.n) xnext = xl.X[xpos];
         }
     }
     int n = 0;                                                  // lane l: keys above the target of row wm * 64 + l in this wave's 64 columns
@@ -184,7 +156,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams 
                 const int lrow = acc_row(mt, r, 0);                         // the row of lanes 0..31 (g = 0); lanes 32..63 hold lrow + 4
                 const int row = wm * 64 + lrow + 4 * (ln >> 5);
                 const uint64_t t = tk[row];
-                const int self = p.exclude_self ? qt * BM + row : -1;
+                const int self = p.f.exclude_self ? qt * BM + row : -1;
                 uint64_t b0, b1;
                 if constexpr (WIN) {                            // the row's bounds come from LDS here: nothing lives across the K loop
                     const int wl = wlo[row], wh = whi[row];
@@ -210,12 +182,12 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rank_tiles_kernel(RankParams 
                     const int x = xnext;
                     bool inw = true;                            // outside the row's window the sweep did not count it
                     if constexpr (WIN) inw = x >= wlo[xrow] && x < whi[xrow];
-                    if constexpr (SEQ) inw = inw && XS[xpos] <= xlim;      // stamped later than this row: not barred, stays counted
-                    if (x >= ct * BN && x != last && x < p.Nc && !(p.exclude_self && x == xgi) && inw)
+                    if constexpr (SEQ) inw = inw && xl.S[xpos] <= xl.lim;      // stamped later than this row: not barred, stays counted
+                    if (x >= ct * BN && x != last && x < p.Nc && !(p.f.exclude_self && x == xgi) && inw)
                         xsub += (int)(pair_key(tile[xrow * BN + (x - ct * BN)], x) > xkey);
                     last = x;
                     ++xpos;
-                    xnext = xpos < xend ? X[xpos] : INT32_MAX;
+                    xnext = xpos < xl.n ? xl.X[xpos] : INT32_MAX;
                 }
                 __syncthreads();                                // the tile is the next K loop's staging ring
             }
@@ -250,20 +222,14 @@ extern "C" uint64_t dae_rank_similarity_seq_workspace(int32_t Nq, int32_t Nc, in
     return dae_rank_similarity_workspace(Nq, Nc, D);            // the shared lists are read in place
 }
 
-// dae_rank_similarity_win and dae_rank_similarity_seq.  list_stamps != NULL: (excl_indptr, excl_items) is the CSR of the n_lists
-// shared lists and row_list / row_limit say what a row reads of it; else they are the per-row lists (or NULL).
+// dae_rank_similarity_win and dae_rank_similarity_seq (seq: the entry takes the shared stamped lists)
 static int rank_run(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D, int32_t norm,
-                    int32_t metric, int32_t exclude_self, const int64_t* excl_indptr, const int32_t* excl_items,
-                    const int32_t* list_stamps, int32_t n_lists, const int32_t* row_list, const int32_t* row_limit,
-                    const int32_t* win_lo, const int32_t* win_hi, const int32_t* targets, int32_t* rank, float* target_score,
-                    void* workspace, uint64_t workspace_bytes, void* stream) {
-    DAE_CHECK_ARG((excl_indptr == nullptr) == (excl_items == nullptr),
-                  "rank_similarity: excl_indptr and excl_items go together (exactly one of them is NULL)");
-    DAE_CHECK_ARG((win_lo == nullptr) == (win_hi == nullptr),
-                  "rank_similarity: win_lo and win_hi go together (exactly one of them is NULL)");
+                    int32_t metric, RowFilter f, bool seq, const int32_t* targets, int32_t* rank, float* target_score, void* workspace,
+                    uint64_t workspace_bytes, void* stream) {
+    if (int rc = sweep_filter_check("rank_similarity", f, seq)) return rc;
     DAE_CHECK_ARG(Q && workspace && Nq > 0 && D > 0 && ldq >= D, "rank_similarity: bad input");
     DAE_CHECK_ARG(targets && rank && target_score, "rank_similarity: targets / rank / target_score are NULL");
-    DAE_CHECK_ARG(!exclude_self || !C, "rank_similarity: exclude_self needs C == NULL (the corpus is Q itself)");
+    DAE_CHECK_ARG(!f.exclude_self || !C, "rank_similarity: exclude_self needs C == NULL (the corpus is Q itself)");
     hipStream_t st = (hipStream_t)stream;
     SweepOperands o;
     if (int rc = sweep_prepare("rank_similarity", Q, ldq, Nq, C, ldc, Nc, D, norm, metric, workspace, workspace_bytes,
@@ -283,24 +249,17 @@ static int rank_run(const float* Q, int64_t ldq, int32_t Nq, const float* C, int
     RankParams p;
     memset(&p, 0, sizeof(p));
     p.g = o.g;
-    p.Nq = Nq; p.Nc = Nc; p.exclude_self = exclude_self ? 1 : 0; p.splits = splits; p.ctiles = (int)(o.Ncp / BN);
-    p.tkey = tkey; p.rank = rank; p.excl_indptr = excl_indptr; p.excl_items = excl_items; p.win_lo = win_lo; p.win_hi = win_hi;
-    p.list_stamps = list_stamps; p.row_list = row_list; p.row_limit = row_limit; p.n_lists = n_lists;
-    const int64_t grid = o.Nqp / BM * splits;
-    if (list_stamps) return win_lo ? sweep_launch<rank_tiles_kernel<true, true, true>>(grid, RANK_WIN_LDS, RANK_WIN_LDS, st, p)
-                                   : sweep_launch<rank_tiles_kernel<true, false, true>>(grid, RANK_LDS, RANK_LDS, st, p);
-    if (win_lo) return excl_indptr ? sweep_launch<rank_tiles_kernel<true, true>>(grid, RANK_WIN_LDS, RANK_WIN_LDS, st, p)
-                                   : sweep_launch<rank_tiles_kernel<false, true>>(grid, RANK_WIN_LDS, RANK_WIN_LDS, st, p);
-    return excl_indptr ? sweep_launch<rank_tiles_kernel<true, false>>(grid, RANK_LDS, RANK_LDS, st, p)
-                       : sweep_launch<rank_tiles_kernel<false, false>>(grid, RANK_LDS, RANK_LDS, st, p);
+    p.Nq = Nq; p.Nc = Nc; p.splits = splits; p.ctiles = (int)(o.Ncp / BN);
+    p.tkey = tkey; p.rank = rank; p.f = f;
+    return DAE_SWEEP_LAUNCH_FILTERED(rank_tiles_kernel, f, RANK_LDS, RANK_WIN_LDS, o.Nqp / BM * splits, st, p);
 }
 
 extern "C" int dae_rank_similarity_win(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
                                        int32_t norm, int32_t metric, int32_t exclude_self, const int64_t* excl_indptr,
                                        const int32_t* excl_items, const int32_t* win_lo, const int32_t* win_hi, const int32_t* targets,
                                        int32_t* rank, float* target_score, void* workspace, uint64_t workspace_bytes, void* stream) {
-    return rank_run(Q, ldq, Nq, C, ldc, Nc, D, norm, metric, exclude_self, excl_indptr, excl_items, nullptr, 0, nullptr, nullptr, win_lo,
-                    win_hi, targets, rank, target_score, workspace, workspace_bytes, stream);
+    const RowFilter f = {exclude_self, excl_indptr, excl_items, win_lo, win_hi, nullptr, nullptr, nullptr, 0};
+    return rank_run(Q, ldq, Nq, C, ldc, Nc, D, norm, metric, f, false, targets, rank, target_score, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dae_rank_similarity_seq(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
@@ -308,13 +267,8 @@ extern "C" int dae_rank_similarity_seq(const float* Q, int64_t ldq, int32_t Nq, 
                                        const int32_t* list_items, const int32_t* list_stamps, int32_t n_lists, const int32_t* row_list,
                                        const int32_t* row_limit, const int32_t* win_lo, const int32_t* win_hi, const int32_t* targets,
                                        int32_t* rank, float* target_score, void* workspace, uint64_t workspace_bytes, void* stream) {
-    const int given = (list_indptr != nullptr) + (list_items != nullptr) + (list_stamps != nullptr) + (row_list != nullptr) +
-                      (row_limit != nullptr);
-    DAE_CHECK_ARG(given == 0 || given == 5,
-                  "rank_similarity: list_indptr, list_items, list_stamps, row_list and row_limit go together (%d of the 5 are NULL)", 5 - given);
-    DAE_CHECK_ARG(given == 0 || n_lists >= 0, "rank_similarity: n_lists must not be negative (got %d)", n_lists);
-    return rank_run(Q, ldq, Nq, C, ldc, Nc, D, norm, metric, exclude_self, list_indptr, list_items, list_stamps, given ? n_lists : 0,
-                    row_list, row_limit, win_lo, win_hi, targets, rank, target_score, workspace, workspace_bytes, stream);
+    const RowFilter f = {exclude_self, list_indptr, list_items, win_lo, win_hi, list_stamps, row_list, row_limit, n_lists};
+    return rank_run(Q, ldq, Nq, C, ldc, Nc, D, norm, metric, f, true, targets, rank, target_score, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dae_rank_similarity(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,

@@ -1,7 +1,8 @@
 // dae_score_sweep.h -- what the "without the N x N matrix" kernels share: dae_topk.hip, dae_rank.hip, dae_pairs.hip and
 // dae_pair_hist.hip sweep the 128 x 128 score tiles of gemm_mainloop<float, 2> over two normalised operand images and differ
-// only in the epilogue.  Here: the order-preserving keys, the score tile in LDS, the tile enumerations, the candidate-window
-// prologue, and the host prologue (argument checks, workspace carve, normalisation, GemmParams) and launch of every entry.
+// only in the epilogue.  Here: the order-preserving keys, the score tile in LDS, the tile enumerations, the row filter of top-k and
+// rank (exclusion lists, stamped lists, candidate windows: its fields, the list a row reads, the window prologue, its checks and
+// its launch), and the host prologue (argument checks, workspace carve, normalisation, GemmParams) and launch of every entry.
 #pragma once
 #include "dae_gemm_tile.h"
 
@@ -56,6 +57,51 @@ __device__ __forceinline__ int lower_bound_i32(const int32_t* X, int n, int v) {
         if (X[m] < v) lo = m + 1; else hi = m;
     }
     return lo;
+}
+
+// ---- the row filter ----
+// May corpus column j compete in query row i?  dae_topk.hip and dae_rank.hip ask it per (row, column) and differ only in where
+// their epilogue applies the answer; the terms, every one optional:
+struct RowFilter {
+    int exclude_self;             // the corpus is the query set itself: row i does not admit column i
+    const int64_t* excl_indptr;   // [Nq + 1] exclusion CSR (*_tiles_kernel<true> only): row i's list is
+    const int32_t* excl_items;    // excl_items[excl_indptr[i] .. excl_indptr[i + 1]), ascending and unique
+    const int32_t* win_lo;        // [Nq] candidate windows (*_tiles_kernel<*, true> only): row i admits the columns
+    const int32_t* win_hi;        // win_lo[i] <= j < win_hi[i]
+    // shared stamped lists (*_tiles_kernel<true, *, true> only): excl_indptr [n_lists + 1] / excl_items are then the CSR of
+    // n_lists lists, one stamp per item; row i reads list row_list[i] (outside [0, n_lists): none) and is barred from its items
+    const int32_t* list_stamps;   // with list_stamps[p] <= row_limit[i]
+    const int32_t* row_list;      // [Nq]
+    const int32_t* row_limit;     // [Nq]
+    int n_lists;
+};
+
+// the list one query row reads: items X[0, n) ascending and unique; SEQ: their stamps S[0, n) and the row's limit
+struct RowList { const int32_t* X; const int32_t* S; int n, lim; };
+
+// the list of row gi: its own CSR row, or (SEQ) the shared list row_list[gi] -- outside [0, n_lists): n == 0, never a stray read
+template <bool SEQ>
+__device__ __forceinline__ RowList row_list_of(const RowFilter& f, int gi) {
+    RowList l = {nullptr, nullptr, 0, 0};
+    int u = gi;
+    if constexpr (SEQ) {
+        u = f.row_list[gi];
+        if (u < 0 || u >= f.n_lists) return l;
+        l.lim = f.row_limit[gi];
+    }
+    const int64_t x0 = f.excl_indptr[u];
+    l.X = f.excl_items + x0;
+    if constexpr (SEQ) l.S = f.list_stamps + x0;
+    l.n = (int)(f.excl_indptr[u + 1] - x0);
+    return l;
+}
+
+// does the list bar column j: is j one of its items, and (SEQ) stamped at most lim?
+template <bool SEQ>
+__device__ __forceinline__ bool list_has(const RowList& l, int j) {
+    const int lo = lower_bound_i32(l.X, l.n, j);
+    if constexpr (SEQ) return lo < l.n && l.X[lo] == j && l.S[lo] <= l.lim;
+    else return lo < l.n && l.X[lo] == j;
 }
 
 // Candidate windows: row i admits only the columns win_lo[i] <= j < win_hi[i].  The 128 (lo, hi) pairs of query tile qt, clamped
@@ -133,6 +179,23 @@ static inline int sweep_prepare(const char* who, const float* Q, int64_t ldq, in
     return 0;
 }
 
+// The pointer checks of a RowFilter, in front of everything else an entry checks (messages prefixed with `who`).  seq: the entry
+// takes the shared stamped form, whose five arrays come together or not at all; without them n_lists does not count.
+static inline int sweep_filter_check(const char* who, RowFilter& f, bool seq) {
+    if (seq) {
+        const int given = (f.excl_indptr != nullptr) + (f.excl_items != nullptr) + (f.list_stamps != nullptr) + (f.row_list != nullptr) +
+                          (f.row_limit != nullptr);
+        DAE_CHECK_ARG(given == 0 || given == 5,
+                      "%s: list_indptr, list_items, list_stamps, row_list and row_limit go together (%d of the 5 are NULL)", who, 5 - given);
+        DAE_CHECK_ARG(given == 0 || f.n_lists >= 0, "%s: n_lists must not be negative (got %d)", who, f.n_lists);
+        if (!given) f.n_lists = 0;
+    }
+    DAE_CHECK_ARG((f.excl_indptr == nullptr) == (f.excl_items == nullptr),
+                  "%s: excl_indptr and excl_items go together (exactly one of them is NULL)", who);
+    DAE_CHECK_ARG((f.win_lo == nullptr) == (f.win_hi == nullptr), "%s: win_lo and win_hi go together (exactly one of them is NULL)", who);
+    return 0;
+}
+
 // launches kernel K (GEMM_THREADS threads, `lds` bytes of dynamic LDS, one parameter block) through DAE_LAUNCH; the first launch
 // of every instantiation raises the kernel's dynamic-LDS limit to `lds_max`
 template <auto K, typename P>
@@ -143,5 +206,14 @@ static inline int sweep_launch(int64_t grid, int lds_max, int lds, hipStream_t s
     DAE_CHECK_LAUNCH();
     return 0;
 }
+
+// sweep_launch of KERNEL<EXCL, WIN, SEQ> for the terms the RowFilter f holds, with LDS bytes of dynamic LDS (WIN_LDS with windows)
+#define DAE_SWEEP_LAUNCH_FILTERED(KERNEL, f, LDS, WIN_LDS, grid, st, p)                                                                 \
+    ((f).list_stamps ? ((f).win_lo ? sweep_launch<KERNEL<true, true, true>>(grid, WIN_LDS, WIN_LDS, st, p)                             \
+                                   : sweep_launch<KERNEL<true, false, true>>(grid, LDS, LDS, st, p))                                   \
+     : (f).win_lo    ? ((f).excl_indptr ? sweep_launch<KERNEL<true, true>>(grid, WIN_LDS, WIN_LDS, st, p)                              \
+                                        : sweep_launch<KERNEL<false, true>>(grid, WIN_LDS, WIN_LDS, st, p))                            \
+                     : ((f).excl_indptr ? sweep_launch<KERNEL<true, false>>(grid, LDS, LDS, st, p)                                     \
+                                        : sweep_launch<KERNEL<false, false>>(grid, LDS, LDS, st, p)))
 
 }  // namespace dae

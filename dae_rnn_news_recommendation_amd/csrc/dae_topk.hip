@@ -17,10 +17,10 @@
 //      the row's sorted list (k keys in the global partial buffer, L2-resident) merged with them: every old entry moves
 //      down by the number of candidates above it, every candidate lands at (old entries above it: binary search) +
 //      (candidates above it), positions >= k drop out.
-//      With an exclusion list (dae_topk_similarity_ex: a sorted CSR row of corpus indices per query row, the articles a user
-//      has already read) the lanes whose key beat the threshold look their column up in the row's list (binary search) and
-//      the ballot is taken again: the test runs only on the few candidates that would enter a merge, and an excluded
-//      candidate never takes one of the k slots.  topk_tiles_kernel<false> is the kernel without the list, unchanged.
+//      With exclusion lists (dae_topk_similarity_ex / _seq; RowFilter, dae_score_sweep.h) the lanes whose key beat the threshold
+//      look their column up in the list their row reads (row_list_of, list_has: a binary search) and the ballot is taken again:
+//      the test runs only on the few candidates that would enter a merge, and an excluded candidate never takes one of the k
+//      slots.  topk_tiles_kernel<false> is the kernel without lists, unchanged.
 // LDS: 64 KiB tile / staging + 1 KiB thresholds + 0.5 KiB list lengths + 4 x 2 KiB merge scratch = 73.5 KiB, two
 // workgroups per CU.  Phase B, topk_merge_kernel: one workgroup per query row merges the `splits` sorted lists the same
 // way (each entry's rank = its position + the entries above it in the other lists) and writes idx / score.
@@ -32,12 +32,9 @@
 // window never reaches the ballot, the exclusion search or the merge.  A workgroup with an empty slice writes part_n = 0.
 // topk_tiles_kernel<*, false> is the kernel as it was.
 //
-// Shared stamped lists (dae_topk_similarity_seq, topk_tiles_kernel<true, *, true>): query rows that are the successive states of one
-// user read ONE list per user, each item stamped with the position of its first click; row i is barred from the items of list
-// row_list[i] whose stamp is at most row_limit[i].  The lookup above becomes lower_bound in the shared list plus the stamp compare
-// (seq_has), still only for the candidates that beat the row's threshold; a row_list outside [0, n_lists) is "no list" (tested here, never
-// a stray read).  Neighbouring rows read the same list addresses; nothing is staged in LDS, the budget is unchanged.
-// topk_tiles_kernel<*, *, false> is the kernel as it was.
+// Shared stamped lists (dae_topk_similarity_seq, topk_tiles_kernel<true, *, true>): the same lookup in the list the row shares with
+// the other states of its user, an item counting up to its stamp.  Neighbouring rows read the same list addresses; nothing is
+// staged in LDS, the budget is unchanged.  topk_tiles_kernel<*, *, false> is the kernel as it was.
 #include "dae_score_sweep.h"
 
 namespace dae {
@@ -61,32 +58,11 @@ __device__ __forceinline__ int keys_above(const uint64_t* L, int n, uint64_t x) 
 
 struct TopkParams {
     GemmParams g;                 // one K segment: A = query image, Bt = corpus image
-    int Nq, Nc, Nqp, k, exclude_self, splits, ctiles;
+    int Nq, Nc, Nqp, k, splits, ctiles;
     uint64_t* part;               // [splits][Nqp][k] sorted keys
     int* part_n;                  // [splits][Nqp] valid keys per list
-    const int64_t* excl_indptr;   // [Nq + 1] exclusion CSR (topk_tiles_kernel<true> only): row i's list is
-    const int32_t* excl_items;    // excl_items[excl_indptr[i] .. excl_indptr[i + 1]), ascending and unique
-    const int32_t* win_lo;        // [Nq] candidate windows (topk_tiles_kernel<*, true> only): row i admits the columns
-    const int32_t* win_hi;        // win_lo[i] <= j < win_hi[i]
-    // shared stamped lists (topk_tiles_kernel<true, *, true> only): excl_indptr [n_lists + 1] / excl_items are then the CSR of
-    // n_lists lists, one stamp per item; row i reads list row_list[i] (outside [0, n_lists): none) and is barred from its items
-    const int32_t* list_stamps;   // with list_stamps[p] <= row_limit[i]
-    const int32_t* row_list;      // [Nq]
-    const int32_t* row_limit;     // [Nq]
-    int n_lists;
+    RowFilter f;                  // which columns may compete in a row (dae_score_sweep.h)
 };
-
-// is j in the ascending list X[0, n)?
-__device__ __forceinline__ bool excl_has(const int32_t* X, int n, int j) {
-    const int lo = lower_bound_i32(X, n, j);
-    return lo < n && X[lo] == j;
-}
-
-// is j an item of the ascending list X[0, n) whose stamp S[.] is at most lim?
-__device__ __forceinline__ bool seq_has(const int32_t* X, const int32_t* S, int n, int j, int lim) {
-    const int lo = lower_bound_i32(X, n, j);
-    return lo < n && X[lo] == j && S[lo] <= lim;
-}
 
 template <bool EXCL, bool WIN, bool SEQ = false>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams p) {
@@ -104,7 +80,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams 
     if (tid < 128) { th[tid] = 0; len[tid] = 0; }
     int* wlo = reinterpret_cast<int*>(lds + TOPK_LDS);          // the query tile's windows (WIN only; behind the merge scratch)
     int* whi = wlo + 128;
-    if constexpr (WIN) window_prologue(p.win_lo, p.win_hi, p.Nq, p.Nc, qt, split, p.splits, wlo, whi, whi + 128, ct0, ct1);
+    if constexpr (WIN) window_prologue(p.f.win_lo, p.f.win_hi, p.Nq, p.Nc, qt, split, p.splits, wlo, whi, whi + 128, ct0, ct1);
     const int wm = wave >> 1, wn = wave & 1, g = lane >> 5, c = lane & 31;
     const uint64_t below = (1ull << lane) - 1ull;
     for (int ct = ct0; ct < ct1; ++ct) {
@@ -123,34 +99,17 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams 
                 if (wh <= ct * BN || wl >= (ct + 1) * BN) continue;      // the row's window misses this tile (wave-uniform)
             }
             const uint64_t t = th[row];
-            const bool ok0 = j0 < p.Nc && !(p.exclude_self && j0 == gi) && (!WIN || (j0 >= wl && j0 < wh)),
-                       ok1 = j1 < p.Nc && !(p.exclude_self && j1 == gi) && (!WIN || (j1 >= wl && j1 < wh));
+            const bool ok0 = j0 < p.Nc && !(p.f.exclude_self && j0 == gi) && (!WIN || (j0 >= wl && j0 < wh)),
+                       ok1 = j1 < p.Nc && !(p.f.exclude_self && j1 == gi) && (!WIN || (j1 >= wl && j1 < wh));
             const uint64_t c0 = ok0 ? pair_key(tile[row * BN + lane], j0) : 0, c1 = ok1 ? pair_key(tile[row * BN + 64 + lane], j1) : 0;
             bool in0 = c0 > t, in1 = c1 > t;
             uint64_t b0 = __ballot(in0), b1 = __ballot(in1);
             if ((b0 | b1) == 0) continue;
-            if constexpr (SEQ) {                                // the same, in the list the row shares: an item counts up to its stamp
-                const int u = p.row_list[gi];
-                if (u >= 0 && u < p.n_lists) {                  // anything else: no list, and never a stray read
-                    const int64_t x0 = p.excl_indptr[u];
-                    const int xn = (int)(p.excl_indptr[u + 1] - x0);
-                    if (xn > 0) {
-                        const int32_t* X = p.excl_items + x0;
-                        const int32_t* S = p.list_stamps + x0;
-                        const int lim = p.row_limit[gi];
-                        if (in0 && seq_has(X, S, xn, j0, lim)) in0 = false;
-                        if (in1 && seq_has(X, S, xn, j1, lim)) in1 = false;
-                        b0 = __ballot(in0); b1 = __ballot(in1);
-                        if ((b0 | b1) == 0) continue;
-                    }
-                }
-            } else if constexpr (EXCL) {                        // drop the candidates in the row's exclusion list, then ballot again
-                const int64_t x0 = p.excl_indptr[gi];
-                const int xn = (int)(p.excl_indptr[gi + 1] - x0);
-                if (xn > 0) {
-                    const int32_t* X = p.excl_items + x0;
-                    if (in0 && excl_has(X, xn, j0)) in0 = false;
-                    if (in1 && excl_has(X, xn, j1)) in1 = false;
+            if constexpr (EXCL) {                               // drop the candidates the row's list bars, then ballot again
+                const RowList l = row_list_of<SEQ>(p.f, gi);
+                if (l.n > 0) {
+                    if (in0 && list_has<SEQ>(l, j0)) in0 = false;
+                    if (in1 && list_has<SEQ>(l, j1)) in1 = false;
                     b0 = __ballot(in0); b1 = __ballot(in1);
                     if ((b0 | b1) == 0) continue;
                 }
@@ -251,20 +210,14 @@ extern "C" uint64_t dae_topk_similarity_seq_workspace(int32_t Nq, int32_t Nc, in
     return dae_topk_similarity_workspace(Nq, Nc, D, k);         // the shared lists are read in place
 }
 
-// dae_topk_similarity_win and dae_topk_similarity_seq.  list_stamps != NULL: (excl_indptr, excl_items) is the CSR of the n_lists
-// shared lists and row_list / row_limit say what a row reads of it; else they are the per-row lists (or NULL).
+// dae_topk_similarity_win and dae_topk_similarity_seq (seq: the entry takes the shared stamped lists)
 static int topk_run(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D, int32_t norm,
-                    int32_t metric, int32_t k, int32_t exclude_self, const int64_t* excl_indptr, const int32_t* excl_items,
-                    const int32_t* list_stamps, int32_t n_lists, const int32_t* row_list, const int32_t* row_limit,
-                    const int32_t* win_lo, const int32_t* win_hi, int32_t* idx, float* score, int64_t ldk, void* workspace,
+                    int32_t metric, int32_t k, RowFilter f, bool seq, int32_t* idx, float* score, int64_t ldk, void* workspace,
                     uint64_t workspace_bytes, void* stream) {
-    DAE_CHECK_ARG((excl_indptr == nullptr) == (excl_items == nullptr),
-                  "topk_similarity: excl_indptr and excl_items go together (exactly one of them is NULL)");
-    DAE_CHECK_ARG((win_lo == nullptr) == (win_hi == nullptr),
-                  "topk_similarity: win_lo and win_hi go together (exactly one of them is NULL)");
+    if (int rc = sweep_filter_check("topk_similarity", f, seq)) return rc;
     DAE_CHECK_ARG(Q && idx && score && workspace && Nq > 0 && D > 0 && ldq >= D, "topk_similarity: bad input");
     DAE_CHECK_ARG(k >= 1 && k <= TOPK_MAX, "topk_similarity: k must be in 1..%d (got %d)", TOPK_MAX, k);
-    DAE_CHECK_ARG(!exclude_self || !C, "topk_similarity: exclude_self needs C == NULL (the corpus is Q itself)");
+    DAE_CHECK_ARG(!f.exclude_self || !C, "topk_similarity: exclude_self needs C == NULL (the corpus is Q itself)");
     DAE_CHECK_ARG(ldk >= k, "topk_similarity: ldk (%lld) must be >= k (%d)", (long long)ldk, k);
     hipStream_t st = (hipStream_t)stream;
     SweepOperands o;
@@ -275,20 +228,11 @@ static int topk_run(const float* Q, int64_t ldq, int32_t Nq, const float* C, int
     TopkParams p;
     memset(&p, 0, sizeof(p));
     p.g = o.g;
-    p.Nq = Nq; p.Nc = Nc; p.Nqp = (int)o.Nqp; p.k = k; p.exclude_self = exclude_self ? 1 : 0; p.splits = splits;
+    p.Nq = Nq; p.Nc = Nc; p.Nqp = (int)o.Nqp; p.k = k; p.splits = splits;
     p.ctiles = (int)(o.Ncp / BN);
     p.part = (uint64_t*)o.rest; p.part_n = (int*)(o.rest + al256((uint64_t)splits * o.Nqp * k * 8));
-    p.excl_indptr = excl_indptr; p.excl_items = excl_items; p.win_lo = win_lo; p.win_hi = win_hi;
-    p.list_stamps = list_stamps; p.row_list = row_list; p.row_limit = row_limit; p.n_lists = n_lists;
-    const int64_t grid = o.Nqp / BM * splits;
-    int rc;
-    if (list_stamps) rc = win_lo ? sweep_launch<topk_tiles_kernel<true, true, true>>(grid, TOPK_WIN_LDS, TOPK_WIN_LDS, st, p)
-                                 : sweep_launch<topk_tiles_kernel<true, false, true>>(grid, TOPK_LDS, TOPK_LDS, st, p);
-    else if (win_lo) rc = excl_indptr ? sweep_launch<topk_tiles_kernel<true, true>>(grid, TOPK_WIN_LDS, TOPK_WIN_LDS, st, p)
-                                 : sweep_launch<topk_tiles_kernel<false, true>>(grid, TOPK_WIN_LDS, TOPK_WIN_LDS, st, p);
-    else rc = excl_indptr ? sweep_launch<topk_tiles_kernel<true, false>>(grid, TOPK_LDS, TOPK_LDS, st, p)
-                          : sweep_launch<topk_tiles_kernel<false, false>>(grid, TOPK_LDS, TOPK_LDS, st, p);
-    if (rc) return rc;
+    p.f = f;
+    if (int rc = DAE_SWEEP_LAUNCH_FILTERED(topk_tiles_kernel, f, TOPK_LDS, TOPK_WIN_LDS, o.Nqp / BM * splits, st, p)) return rc;
     DAE_LAUNCH(topk_merge_kernel, dim3(Nq), dim3(256), 0, st, p.part, p.part_n, p.Nqp, splits, k, idx, score, ldk);
     DAE_CHECK_LAUNCH();
     return 0;
@@ -298,8 +242,8 @@ extern "C" int dae_topk_similarity_win(const float* Q, int64_t ldq, int32_t Nq, 
                                        int32_t norm, int32_t metric, int32_t k, int32_t exclude_self, const int64_t* excl_indptr,
                                        const int32_t* excl_items, const int32_t* win_lo, const int32_t* win_hi, int32_t* idx,
                                        float* score, int64_t ldk, void* workspace, uint64_t workspace_bytes, void* stream) {
-    return topk_run(Q, ldq, Nq, C, ldc, Nc, D, norm, metric, k, exclude_self, excl_indptr, excl_items, nullptr, 0, nullptr, nullptr,
-                    win_lo, win_hi, idx, score, ldk, workspace, workspace_bytes, stream);
+    const RowFilter f = {exclude_self, excl_indptr, excl_items, win_lo, win_hi, nullptr, nullptr, nullptr, 0};
+    return topk_run(Q, ldq, Nq, C, ldc, Nc, D, norm, metric, k, f, false, idx, score, ldk, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dae_topk_similarity_seq(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
@@ -307,13 +251,8 @@ extern "C" int dae_topk_similarity_seq(const float* Q, int64_t ldq, int32_t Nq, 
                                        const int32_t* list_items, const int32_t* list_stamps, int32_t n_lists, const int32_t* row_list,
                                        const int32_t* row_limit, const int32_t* win_lo, const int32_t* win_hi, int32_t* idx,
                                        float* score, int64_t ldk, void* workspace, uint64_t workspace_bytes, void* stream) {
-    const int given = (list_indptr != nullptr) + (list_items != nullptr) + (list_stamps != nullptr) + (row_list != nullptr) +
-                      (row_limit != nullptr);
-    DAE_CHECK_ARG(given == 0 || given == 5,
-                  "topk_similarity: list_indptr, list_items, list_stamps, row_list and row_limit go together (%d of the 5 are NULL)", 5 - given);
-    DAE_CHECK_ARG(given == 0 || n_lists >= 0, "topk_similarity: n_lists must not be negative (got %d)", n_lists);
-    return topk_run(Q, ldq, Nq, C, ldc, Nc, D, norm, metric, k, exclude_self, list_indptr, list_items, list_stamps, given ? n_lists : 0,
-                    row_list, row_limit, win_lo, win_hi, idx, score, ldk, workspace, workspace_bytes, stream);
+    const RowFilter f = {exclude_self, list_indptr, list_items, win_lo, win_hi, list_stamps, row_list, row_limit, n_lists};
+    return topk_run(Q, ldq, Nq, C, ldc, Nc, D, norm, metric, k, f, true, idx, score, ldk, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dae_topk_similarity_ex(const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,

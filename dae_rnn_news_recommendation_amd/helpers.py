@@ -226,15 +226,6 @@ def _workspace(dev, nbytes):
     return ctypes.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256), ws
 
 
-def _upload_exclusions(xp, xi, dev):
-    """The exclusion CSR of ``normalize_exclusions`` on the device (``(None, None)`` without one).  The library tells "no lists" from
-    "empty lists" by the pointers, so an empty item array is still uploaded as one element: never a NULL pointer."""
-    import torch
-    if xp is None:
-        return None, None
-    return torch.from_numpy(xp).to(dev), torch.from_numpy(xi if xi.size else np.zeros(1, dtype=np.int32)).to(dev)
-
-
 def _csr_lists(lists, what="histories"):
     """``(indptr int64 [n + 1], items int64 [nnz])`` of a list of index sequences, or of an ``(indptr, items)`` pair -- a *tuple* of
     two arrays; a list is always taken as one sequence per row."""
@@ -313,12 +304,6 @@ def normalize_shared_exclusions(exclude_shared, n_rows, n_candidates):
     return indptr, np.ascontiguousarray(items.astype(np.int32)), np.ascontiguousarray(st), out[0], out[1]
 
 
-def _upload_shared(shared, dev):
-    """The five arrays of ``normalize_shared_exclusions`` on the device; empty item arrays go up as one element: never a NULL pointer."""
-    import torch
-    return tuple(torch.from_numpy(a if a.size else np.zeros(1, dtype=a.dtype)).to(dev) for a in shared)
-
-
 def _n_rows(data):
     """The number of rows of a container ``_device_matrix`` takes, without touching it."""
     shape = getattr(data, "shape", None)
@@ -367,6 +352,76 @@ def _permute_csr(indptr, items, perm):
     out_ptr[1:] = np.cumsum(n)
     take = np.repeat(indptr[:-1][perm] - out_ptr[:-1], n) + np.arange(int(out_ptr[-1]), dtype=np.int64)
     return out_ptr, items[take]
+
+
+class _RowFilter:
+    """Which candidates may compete in which query row -- the part ``most_similar`` and ``target_ranks`` share: ``exclude_self``,
+    the per-row lists ``(xp, xi)`` of ``normalize_exclusions`` or the shared stamped lists ``shared`` of
+    ``normalize_shared_exclusions``, and the pair ``window`` of ``normalize_window`` (each None: no such term), all in the caller's
+    row order.  ``place`` hands them to the device, ``entry`` / ``args`` are then the suffix of the entry point that takes them and
+    its arguments from ``exclude_self`` to ``win_hi``, and ``restore`` puts a result back in the caller's order."""
+
+    def __init__(self, exclude_self, window, shared, exclude):
+        self.exclude_self, self.window, self.shared, self.exclude = bool(exclude_self), window, shared, exclude
+        self.xp = self.xi = self.perm_d = None
+
+    def lists(self, Nq, Nc):
+        """``(xp, xi)``; a raw ``exclude`` is normalised at the first call, i.e. where its errors have always been raised: behind the
+        checks of the operands (and of the targets)."""
+        if self.exclude is not None:
+            (self.xp, self.xi), self.exclude = normalize_exclusions(self.exclude, Nq, Nc), None
+        return self.xp, self.xi
+
+    def place(self, Q, Cm, dev, *per_row):
+        """Uploads the filter.  With windows and ``candidates`` (``Cm``) the rows go in the stable order of ``(lo, hi)``
+        (``_window_order``): returns ``Q`` and the ``per_row`` device tensors in the order the kernel gets them."""
+        import torch
+        xp, xi = self.lists(int(Q.shape[0]), int(Q.shape[0]) if Cm is None else int(Cm.shape[0]))
+        shared, lo_d, hi_d = self.shared, None, None
+        if self.window is not None:
+            wlo, whi = self.window
+            perm = None if Cm is None else _window_order(wlo, whi)    # the corpus is Q itself: its rows stay where they are
+            if perm is not None:
+                self.perm_d = torch.from_numpy(perm).to(dev)
+                Q, wlo, whi = Q[self.perm_d].contiguous(), wlo[perm], whi[perm]
+                per_row = tuple(t[self.perm_d].contiguous() for t in per_row)
+                if xp is not None:
+                    xp, xi = _permute_csr(xp, xi, perm)
+                if shared is not None:
+                    shared = shared[:3] + (np.ascontiguousarray(shared[3][perm]), np.ascontiguousarray(shared[4][perm]))
+            lo_d, hi_d = torch.from_numpy(np.ascontiguousarray(wlo)).to(dev), torch.from_numpy(np.ascontiguousarray(whi)).to(dev)
+        # the library tells "no lists" from "empty lists" by the pointers: an empty array still goes up as one element, never as NULL
+        up = lambda a: None if a is None else torch.from_numpy(a if a.size else np.zeros(1, dtype=a.dtype)).to(dev)      # noqa: E731
+        if shared is not None:
+            d = tuple(up(a) for a in shared)
+            self.entry, lists = "_seq", (L.ptr(d[0]), L.ptr(d[1]), L.ptr(d[2]), int(shared[0].size - 1), L.ptr(d[3]), L.ptr(d[4]))
+        else:
+            d = (up(xp), up(xi))
+            self.entry, lists = "_win", (L.ptr(d[0]), L.ptr(d[1]))
+        self._device = (d, lo_d, hi_d)                                # the pointers in args stay valid as long as the filter lives
+        self.args = (1 if self.exclude_self else 0,) + lists + (L.ptr(lo_d), L.ptr(hi_d))
+        return (Q,) + per_row
+
+    def restore(self, *outs):
+        """Per-row device results of a call on the rows of ``place``, in the caller's row order."""
+        import torch
+        if self.perm_d is None:
+            return outs
+        return tuple(torch.empty_like(t).index_copy_(0, self.perm_d, t) for t in outs)
+
+
+def _row_filter(in_df, candidates, exclude_self, exclude, exclude_shared, window):
+    """The ``_RowFilter`` of the arguments of ``most_similar`` / ``target_ranks``: the default and the error of ``exclude_self``,
+    ``exclude`` against ``exclude_shared``, and ``window`` / ``exclude_shared`` normalised -- all before the library is touched."""
+    if exclude_self is None:
+        exclude_self = candidates is None
+    elif exclude_self and candidates is not None:
+        raise ValueError("exclude_self=True needs candidates=None (the self pair exists only when the corpus is in_df itself)")
+    if exclude is not None and exclude_shared is not None:
+        raise ValueError("exclude and exclude_shared do not go together")
+    n = lambda: (_n_rows(in_df), _n_rows(in_df if candidates is None else candidates))      # noqa: E731
+    return _RowFilter(exclude_self, None if window is None else normalize_window(window, *n()),
+                      None if exclude_shared is None else normalize_shared_exclusions(exclude_shared, *n()), exclude)
 
 
 def candidate_windows(query_times, publish_times, max_age=None):
@@ -422,53 +477,20 @@ def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candi
     ``row_limit[i]`` (``normalize_shared_exclusions``, ``dae_topk_similarity_seq``).  The result equals, bit for bit, that of
     ``exclude`` with those items listed row by row."""
     import torch
-    if exclude_self is None:
-        exclude_self = candidates is None
-    elif exclude_self and candidates is not None:
-        raise ValueError("exclude_self=True needs candidates=None (the self pair exists only when the corpus is in_df itself)")
-    if exclude is not None and exclude_shared is not None:
-        raise ValueError("exclude and exclude_shared do not go together")
-    if window is not None:
-        window = normalize_window(window, _n_rows(in_df), _n_rows(in_df if candidates is None else candidates))
-    shared = None
-    if exclude_shared is not None:
-        shared = normalize_shared_exclusions(exclude_shared, _n_rows(in_df), _n_rows(in_df if candidates is None else candidates))
+    flt = _row_filter(in_df, candidates, exclude_self, exclude, exclude_shared, window)
     lib, dev, Q, Cm, Nq, Nc, D = _sweep_inputs(in_df, candidates, norm, metric, device)
     k = int(k)
     idx = torch.empty((Nq, max(k, 1)), dtype=torch.int32, device=dev)
     score = torch.empty((Nq, max(k, 1)), dtype=torch.float32, device=dev)
     ws_bytes = int(lib.dae_topk_similarity_workspace(Nq, Nc, D, k))
     ws_p, ws = _workspace(dev, ws_bytes)
-    xp = xi = perm = perm_d = lo_d = hi_d = None
-    if exclude is not None:
-        xp, xi = normalize_exclusions(exclude, Nq, Nc)
-    if window is not None:
-        wlo, whi = window
-        perm = None if Cm is None else _window_order(wlo, whi)        # the corpus is Q itself: its rows stay where they are
-        if perm is not None:
-            perm_d = torch.from_numpy(perm).to(dev)
-            Q, wlo, whi = Q[perm_d].contiguous(), wlo[perm], whi[perm]
-            if xp is not None:
-                xp, xi = _permute_csr(xp, xi, perm)
-            if shared is not None:
-                shared = shared[:3] + (np.ascontiguousarray(shared[3][perm]), np.ascontiguousarray(shared[4][perm]))
-        lo_d, hi_d = torch.from_numpy(np.ascontiguousarray(wlo)).to(dev), torch.from_numpy(np.ascontiguousarray(whi)).to(dev)
-    xp_d, xi_d = _upload_exclusions(xp, xi, dev)
-    if shared is not None:
-        if Nq > 0:
-            sh_d = _upload_shared(shared, dev)
-            with torch.cuda.device(dev):
-                L.call("dae_topk_similarity_seq", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
-                       _NORMS[norm], _METRICS[metric], k, 1 if exclude_self else 0, L.ptr(sh_d[0]), L.ptr(sh_d[1]), L.ptr(sh_d[2]),
-                       int(shared[0].size - 1), L.ptr(sh_d[3]), L.ptr(sh_d[4]), L.ptr(lo_d), L.ptr(hi_d), L.ptr(idx), L.ptr(score),
-                       idx.stride(0), ws_p, ws_bytes, L.current_stream())
-    elif Nq > 0 or window is None:                                    # without rows only the windowed call is skipped
+    (Q,) = flt.place(Q, Cm, dev)
+    if Nq > 0 or (flt.window is None and flt.shared is None):         # without rows only the windowed and the shared call are skipped
         with torch.cuda.device(dev):
-            L.call("dae_topk_similarity_win", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
-                   _NORMS[norm], _METRICS[metric], k, 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(lo_d), L.ptr(hi_d),
-                   L.ptr(idx), L.ptr(score), idx.stride(0), ws_p, ws_bytes, L.current_stream())
-    if perm_d is not None:
-        idx, score = torch.empty_like(idx).index_copy_(0, perm_d, idx), torch.empty_like(score).index_copy_(0, perm_d, score)
+            L.call("dae_topk_similarity" + flt.entry, L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
+                   _NORMS[norm], _METRICS[metric], k, *flt.args, L.ptr(idx), L.ptr(score), idx.stride(0), ws_p, ws_bytes,
+                   L.current_stream())
+    idx, score = flt.restore(idx, score)
     idx = idx.long()
     if return_tensor:
         return idx, score
@@ -1301,17 +1323,7 @@ def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, ca
     ``row_list[i]`` whose stamp is at most ``row_limit[i]``, and the result equals that of ``exclude`` with those items bit for
     bit."""
     import torch
-    if exclude_self is None:
-        exclude_self = candidates is None
-    elif exclude_self and candidates is not None:
-        raise ValueError("exclude_self=True needs candidates=None (the self pair exists only when the corpus is in_df itself)")
-    if exclude is not None and exclude_shared is not None:
-        raise ValueError("exclude and exclude_shared do not go together")
-    if window is not None:
-        window = normalize_window(window, _n_rows(in_df), _n_rows(in_df if candidates is None else candidates))
-    shared = None
-    if exclude_shared is not None:
-        shared = normalize_shared_exclusions(exclude_shared, _n_rows(in_df), _n_rows(in_df if candidates is None else candidates))
+    flt = _row_filter(in_df, candidates, exclude_self, exclude, exclude_shared, window)
     lib, dev, Q, Cm, Nq, Nc, D = _sweep_inputs(in_df, candidates, norm, metric, device)
     tgt = targets.detach().cpu().numpy() if isinstance(targets, torch.Tensor) else np.asarray(targets)
     tgt = tgt.ravel()
@@ -1322,10 +1334,7 @@ def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, ca
         raise ValueError(f"{tgt.shape[0]} targets for {Nq} queries")
     if tgt.size and int(tgt.max()) >= Nc:
         raise ValueError(f"targets must be below {Nc} (got {int(tgt.max())})")
-    xp = xi = None
-    if exclude is not None:
-        xp, xi = normalize_exclusions(exclude, Nq, Nc)
-    n_cand, barred = _competitors(tgt, Nq, Nc, exclude_self, xp, xi, window, shared)
+    n_cand, barred = _competitors(tgt, Nq, Nc, flt.exclude_self, *flt.lists(Nq, Nc), flt.window, flt.shared)
     rank = torch.empty(Nq, dtype=torch.int32, device=dev)
     score = torch.empty(Nq, dtype=torch.float32, device=dev)
     if Nq == 0:
@@ -1333,33 +1342,11 @@ def target_ranks(in_df, targets, norm="", metric="cosine", exclude_self=None, ca
         return out if return_tensor else tuple(t.cpu().numpy() for t in out)
     ws_bytes = int(lib.dae_rank_similarity_workspace(Nq, Nc, D))
     ws_p, ws = _workspace(dev, ws_bytes)
-    t_d = torch.from_numpy(np.where(tgt >= 0, tgt, -1).astype(np.int32)).to(dev)
-    perm = perm_d = lo_d = hi_d = None
-    if window is not None:
-        wlo, whi = window
-        perm = None if Cm is None else _window_order(wlo, whi)        # the corpus is Q itself: its rows stay where they are
-        if perm is not None:
-            perm_d = torch.from_numpy(perm).to(dev)
-            Q, wlo, whi, t_d = Q[perm_d].contiguous(), wlo[perm], whi[perm], t_d[perm_d].contiguous()
-            if xp is not None:
-                xp, xi = _permute_csr(xp, xi, perm)
-            if shared is not None:
-                shared = shared[:3] + (np.ascontiguousarray(shared[3][perm]), np.ascontiguousarray(shared[4][perm]))
-        lo_d, hi_d = torch.from_numpy(np.ascontiguousarray(wlo)).to(dev), torch.from_numpy(np.ascontiguousarray(whi)).to(dev)
-    xp_d, xi_d = _upload_exclusions(xp, xi, dev)
+    Q, t_d = flt.place(Q, Cm, dev, torch.from_numpy(np.where(tgt >= 0, tgt, -1).astype(np.int32)).to(dev))
     with torch.cuda.device(dev):
-        if shared is not None:
-            sh_d = _upload_shared(shared, dev)
-            L.call("dae_rank_similarity_seq", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
-                   _NORMS[norm], _METRICS[metric], 1 if exclude_self else 0, L.ptr(sh_d[0]), L.ptr(sh_d[1]), L.ptr(sh_d[2]),
-                   int(shared[0].size - 1), L.ptr(sh_d[3]), L.ptr(sh_d[4]), L.ptr(lo_d), L.ptr(hi_d), L.ptr(t_d), L.ptr(rank),
-                   L.ptr(score), ws_p, ws_bytes, L.current_stream())
-        else:
-            L.call("dae_rank_similarity_win", L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
-                   _NORMS[norm], _METRICS[metric], 1 if exclude_self else 0, L.ptr(xp_d), L.ptr(xi_d), L.ptr(lo_d), L.ptr(hi_d),
-                   L.ptr(t_d), L.ptr(rank), L.ptr(score), ws_p, ws_bytes, L.current_stream())
-    if perm_d is not None:
-        rank, score = torch.empty_like(rank).index_copy_(0, perm_d, rank), torch.empty_like(score).index_copy_(0, perm_d, score)
+        L.call("dae_rank_similarity" + flt.entry, L.ptr(Q), Q.stride(0), Nq, L.ptr(Cm), 0 if Cm is None else Cm.stride(0), Nc, D,
+               _NORMS[norm], _METRICS[metric], *flt.args, L.ptr(t_d), L.ptr(rank), L.ptr(score), ws_p, ws_bytes, L.current_stream())
+    rank, score = flt.restore(rank, score)
     rank = rank.long()
     if barred.any():
         rank[torch.from_numpy(barred).to(dev)] = 0

@@ -181,6 +181,94 @@ def test_exact_truth_on_integer_valued_data(base):
         assert n_ranked >= 60 and n_barred >= 5
 
 
+@pytest.fixture(scope="module")
+def six_forms():
+    """One small problem for all six (EXCL, WIN, SEQ) forms of both kernels: 130 query rows (two query tiles, the second with 2
+    rows), 300 candidates (three corpus tiles, the last partial), 24 features, integers in [-3, 3] -- every fp32 product sum is
+    exact, so the float64 brute force is the truth bit for bit.  17 shared stamped lists of 0..40 items; per row the list it reads
+    (-1 and 17: none) and a limit, and the same content as per-row lists of 0..40 items."""
+    rng = np.random.default_rng(21)
+    Nq, Nc, D, n_lists = 130, 300, 24, 17
+    Q = rng.integers(-3, 4, (Nq, D)).astype(np.float32)
+    E = rng.integers(-3, 4, (Nc, D)).astype(np.float32)
+    sizes = rng.integers(0, 41, n_lists)
+    sizes[:3] = [0, 40, 1]
+    items = [np.sort(rng.choice(Nc, n, replace=False)) for n in sizes]
+    items[1][[0, -1]] = [0, 299]                                                    # the corpus' first and last column are listed
+    stamps = [rng.permutation(n) for n in sizes]
+    rl = rng.integers(0, n_lists, Nq)
+    rl[[3, 64, 129]], rl[[5, 128]] = -1, n_lists                                   # no list, on either side of [0, n_lists)
+    rm = rng.integers(-1, 41, Nq)
+    rl[[0, 127]], rm[[0, 127]] = 1, 40                                             # the whole 40-item list, in both query tiles
+    rl[7] = 0                                                                      # an empty list
+    lists = _materialise(np.concatenate([[0], np.cumsum(sizes)]), np.concatenate(items), np.concatenate(stamps), rl, rm)
+    assert {0, 40} <= {len(x) for x in lists} and max(len(x) for x in lists) == 40
+    tgt = rng.integers(0, Nc, Nq)
+    tgt[::9] = -1
+    for i in range(1, Nq, 6):                                                      # targets from the row's own list
+        if len(lists[i]):
+            tgt[i] = lists[i][rng.integers(len(lists[i]))]
+    lo = rng.integers(0, Nc, Nq)
+    hi = np.minimum(lo + rng.integers(1, 200, Nq), Nc)
+    near = (rng.random(Nq) < 0.7) & (tgt >= 0)                                      # most targets inside their window
+    lo[near] = np.maximum(tgt[near] - rng.integers(0, 100, Nq)[near], 0)
+    hi[near] = np.minimum(tgt[near] + 1 + rng.integers(0, 100, Nq)[near], Nc)
+    lo[:5], hi[:5] = [0, 50, 0, 140, 260], [300, 50, 120, 290, 300]                # all, empty, misses tiles 1-2, ends inside the last tile, inside it
+    lo[128:], hi[128:] = [0, 256], [128, 300]                                      # exactly the first tile, and only the last
+    S = Q.astype(np.float64) @ E.astype(np.float64).T
+    cols = np.arange(Nc)[None, :]
+    listed, outside = np.zeros((Nq, Nc), dtype=bool), (cols < lo[:, None]) | (cols >= hi[:, None])
+    for i, x in enumerate(lists):
+        listed[i, x] = True
+    return dict(Q=Q, E=E, S=S, tgt=tgt, lists=lists, shared=((items, stamps, rl, rm)), win=(lo, hi), listed=listed, outside=outside)
+
+
+def _six_forms(d):
+    """(name, arguments of most_similar / target_ranks, the columns a row may not return) per form; the two SEQ forms last."""
+    for win in (False, True):
+        w, out = (d["win"], d["outside"]) if win else (None, np.zeros_like(d["outside"]))
+        yield f"<false, {win}>", dict(window=w), out
+        yield f"<true, {win}>", dict(window=w, exclude=d["lists"]), out | d["listed"]
+        yield f"<true, {win}, true>", dict(window=w, exclude_shared=d["shared"]), out | d["listed"]
+
+
+@pytest.mark.parametrize("k", [1, 128])
+def test_six_forms_topk_equals_the_brute_force(six_forms, k):
+    from dae_rnn_news_recommendation_amd import helpers
+    d, per_row = six_forms, None
+    for name, kw, barred in _six_forms(d):
+        R = np.where(barred, -np.inf, d["S"])
+        want = np.argsort(-R, axis=1, kind="stable")[:, :k]                         # score descending, ties by index ascending
+        ws = np.take_along_axis(R, want, 1)
+        idx, sc = helpers.most_similar(d["Q"], k=k, metric="linear kernel", norm="", candidates=d["E"], **kw)
+        assert np.array_equal(idx, np.where(np.isneginf(ws), -1, want)), name
+        assert np.array_equal(_u32(sc), _u32(ws.astype(np.float32))), name
+        if "exclude" in kw:
+            per_row = (idx, sc)
+        elif "exclude_shared" in kw:                                                # the per-row and the shared form of one filter
+            assert np.array_equal(idx, per_row[0]) and np.array_equal(_u32(sc), _u32(per_row[1])), name
+
+
+def test_six_forms_rank_equals_the_brute_force(six_forms):
+    from dae_rnn_news_recommendation_amd import helpers
+    d, per_row = six_forms, None
+    tgt, S = d["tgt"], d["S"]
+    has = tgt >= 0
+    st = S[np.arange(tgt.size), np.maximum(tgt, 0)]
+    ahead = (S > st[:, None]) | ((S == st[:, None]) & (np.arange(S.shape[1])[None, :] < tgt[:, None]))
+    for name, kw, barred in _six_forms(d):
+        ok = has & ~barred[np.arange(tgt.size), np.maximum(tgt, 0)]                 # the target itself may be returned
+        want = np.where(ok, 1 + (ahead & ~barred).sum(axis=1), 0)
+        rank, score, _ = helpers.target_ranks(d["Q"], tgt, metric="linear kernel", norm="", candidates=d["E"], **kw)
+        assert np.array_equal(rank, want), name
+        assert np.array_equal(_u32(score), _u32(np.where(has, st, -np.inf).astype(np.float32))), name
+        assert ok.sum() >= 40 and (not barred.any() or (has & ~ok).sum() >= 5), name          # ranked targets, and barred ones
+        if "exclude" in kw:
+            per_row = (rank, score)
+        elif "exclude_shared" in kw:
+            assert np.array_equal(rank, per_row[0]) and np.array_equal(_u32(score), _u32(per_row[1])), name
+
+
 def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
