@@ -1031,6 +1031,10 @@ extern "C" int dae_triplet_batch_hard_rows(const float* D_slabs, int32_t d_split
     hipStream_t st = (hipStream_t)stream;
     DAE_CHECK_HIP(hipMemsetAsync(dw, 0, (size_t)Bp * sizeof(int32_t), st));
     const size_t lds = (size_t)Bp * 4 + 64;
+    // Bp = 16384 needs 65 600 B, above the 64 KiB a kernel may take without asking: raise the limit once per process (as launch_batch_all does)
+    static const int attr_rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(batch_hard_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                        4 * TRIP_MAX_B * 4 + 64);
+    DAE_CHECK_ARG(attr_rc == 0, "batch_hard: hipFuncSetAttribute failed (%d)", attr_rc);
     DAE_LAUNCH(batch_hard_kernel, dim3(n_anchors), dim3(TRIP_THREADS), lds, st, D_slabs, d_splits, slab_stride, ldd, labels, B, Bp,
                        loss_part, cnt_part, dw, G, a0);
     DAE_CHECK_LAUNCH();

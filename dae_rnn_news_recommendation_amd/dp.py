@@ -584,7 +584,9 @@ class GlobalMiner:
         self.Mp = L.pad(self.per_max)
         self.Gp = L.pad(self.per_max * self.world)
         # the miners hold one D row of the GLOBAL batch per workgroup in LDS: dae_triplet_batch_all_rows up to 4096 padded columns,
-        # dae_triplet_batch_hard_rows up to 16384 -- fail here, not at the first step of the fit
+        # dae_triplet_batch_hard_rows up to 16384 -- fail here, not at the first step of the fit.  (With DAE_MINER_POS_ONLY batch_all's
+        # limit is 3072: its role counts take 52 instead of 32 B of LDS per column.  The estimator cannot reach that mode -- it never
+        # sets pos_triplets_only, as the reference's estimator does not, and mine() below passes mode 0 -- so 4096 is the limit here.)
         limit = 4096 if strategy == "batch_all" else 16384
         if self.Gp > limit:
             raise ValueError("dp_mining='global' with %s supports a padded global batch of at most %d rows (got %d = %d ranks x %d); "

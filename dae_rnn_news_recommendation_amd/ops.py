@@ -189,6 +189,51 @@ def triplet_batch_hard(D_slabs, labels, B):
     return loss_part, cnt, dw, G
 
 
+def _rows_operand(D_rows, n_anchors, B):
+    """(S, slab_stride, ldd) of a D given as [S x rows x cols] (or [rows x cols]): `rows` >= n_anchors, unit column stride."""
+    _dev(D_rows)
+    if D_rows.dim() == 2:
+        D_rows = D_rows.unsqueeze(0)
+    S, rows, cols = D_rows.shape
+    if D_rows.dtype != torch.float32 or D_rows.stride(-1) != 1 or rows < n_anchors or cols < B:
+        raise ValueError("D_rows must be float32 [S x >= n_anchors x >= B] with unit column stride")
+    return D_rows, S, D_rows.stride(0) if S > 1 else 0, D_rows.stride(-2)
+
+
+def triplet_batch_all_rows(D_rows, labels, B, a0, n_anchors, pos_only=False, fast=False, out=None):
+    """batch_all for the anchors [a0, a0 + n_anchors) of a batch of B: row r of D_rows belongs to batch element a0 + r and its
+    columns are the whole batch.  D is taken as given (S slabs of stride D.stride(0), ldd = D.stride(-2)); the outputs are
+    [n_anchors] and [n_anchors x Bp].  `out` = (loss_part, npos, G, role) hands in the buffers instead (role None unless pos_only)."""
+    D_rows, S, slab_stride, ldd = _rows_operand(D_rows, n_anchors, B)
+    Bp = L.pad(B)
+    dev = D_rows.device
+    if out is None:
+        n = max(int(n_anchors), 0)
+        out = (torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev),
+               torch.zeros((n, Bp), dtype=torch.float32, device=dev),
+               torch.zeros((n, Bp), dtype=torch.int32, device=dev) if pos_only else None)
+    loss_part, npos, G, role = out
+    L.call("dae_triplet_batch_all_rows", L.ptr(D_rows), S, slab_stride, ldd, L.ptr(labels), B, Bp, a0, n_anchors,
+           int(pos_only) | (2 if fast else 0), L.ptr(loss_part), L.ptr(npos), L.ptr(G), L.ptr(role), L.current_stream())
+    return loss_part, npos, G, role
+
+
+def triplet_batch_hard_rows(D_rows, labels, B, a0, n_anchors, out=None):
+    """batch_hard for the anchors [a0, a0 + n_anchors) (see triplet_batch_all_rows).  dw[Bp] holds THIS call's anchors' contributions
+    only (the library zeroes it in every call).  `out` = (loss_part, cnt, dw, G) hands in the buffers instead."""
+    D_rows, S, slab_stride, ldd = _rows_operand(D_rows, n_anchors, B)
+    Bp = L.pad(B)
+    dev = D_rows.device
+    if out is None:
+        n = max(int(n_anchors), 0)
+        out = (torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev),
+               torch.zeros(Bp, dtype=torch.int32, device=dev), torch.zeros((n, Bp), dtype=torch.float32, device=dev))
+    loss_part, cnt, dw, G = out
+    L.call("dae_triplet_batch_hard_rows", L.ptr(D_rows), S, slab_stride, ldd, L.ptr(labels), B, Bp, a0, n_anchors,
+           L.ptr(loss_part), L.ptr(cnt), L.ptr(dw), L.ptr(G), L.current_stream())
+    return loss_part, cnt, dw, G
+
+
 def triplet_finalize(triplet, pos_only, B, alpha, loss_part, cnt_part, nvalid, dw_i32, role_cnt, cw):
     Bp = loss_part.shape[0]
     dev = loss_part.device

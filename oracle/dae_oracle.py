@@ -18,7 +18,7 @@ from scipy import sparse
 __all__ = [
     "act", "act_grad_from_output", "softplus_tf", "sigmoid",
     "get_anchor_positive_triplet_mask", "get_anchor_negative_triplet_mask", "get_triplet_mask",
-    "batch_all_triplet_loss", "batch_all_triplet_loss_loops", "batch_all_closed_form",
+    "batch_all_triplet_loss", "batch_all_triplet_loss_literal", "batch_all_triplet_loss_loops", "batch_all_closed_form",
     "batch_hard_triplet_loss", "batch_hard_triplet_loss_loops",
     "weighted_loss", "weighted_loss_rows",
     "encode", "decode", "forward_backward", "explicit_triplet_forward_backward",
@@ -118,8 +118,60 @@ def batch_all_closed_form(labels):
 
 def batch_all_triplet_loss(labels, h, pos_triplets_only=False, dt=np.float32, chunk=32,
                            return_grad=False, D=None):
-    """triplet_loss_utils.py:79-131, evaluated anchor-chunk by anchor-chunk (arithmetically the
-    same sums as the B^3 broadcast; chunking only bounds memory).
+    """triplet_loss_utils.py:79-131 on the VALID entries only: the anchors of one class share their positives (the class, minus
+    the anchor itself) and their negatives (everyone else), so a chunk of same-class anchors is a dense [anchors x |class| x
+    |others|] block -- the terms of ``batch_all_triplet_loss_literal``, element for element in the same arithmetic, without the
+    invalid (masked-to-zero) part of the B^3 broadcast.  Sums are accumulated in float64 in another order than there.
+
+    Returns (loss, data_weight[B], fraction, num_pos) and, if ``return_grad``, also
+    G = d loss / d D (gradient wrt the Gram matrix; masks carry no gradient)."""
+    labels = np.asarray(labels)
+    h = np.asarray(h, dtype=dt)
+    B = labels.shape[0]
+    if D is None:
+        D = h @ h.T                                        # :93
+    D = np.asarray(D, dtype=dt)
+    num_valid = 0
+    num_pos = 0
+    loss_sum = 0.0                                         # python float == fp64 accumulator
+    dw = np.zeros(B, np.int64)
+    G = np.zeros((B, B), np.float64) if return_grad else None      # un-normalised until the counts are known
+    for c in np.unique(labels):
+        Pc = np.flatnonzero(labels == c)
+        Nc = np.flatnonzero(labels != c)
+        if len(Pc) < 2 or len(Nc) == 0:
+            continue
+        for i0 in range(0, len(Pc), chunk):
+            A = Pc[i0:i0 + chunk]                                             # anchors of this block
+            Da = D[A]
+            T = (-Da[:, Pc][:, :, None] + Da[:, Nc][:, None, :]).astype(dt)   # :96-106  T[a,p,n] = D[a,n] - D[a,p]
+            valid = np.broadcast_to((Pc[None, :] != A[:, None])[:, :, None], T.shape)   # :110 (a != p; labels by construction)
+            pos = valid & (T > dt(EPS))                                       # :114 (valid*T > 1e-16)
+            num_valid += int(valid.sum())
+            num_pos += int(pos.sum())
+            m = pos if pos_triplets_only else valid                           # :118-123
+            loss_sum += float(np.sum(np.where(m, softplus_tf(T), dt(0)), dtype=np.float64))   # :126
+            dw[A] += m.sum(axis=(1, 2))                                       # anchor role  :129 sum[1,2]
+            dw[Nc] += m.sum(axis=(0, 1))                                      # negative role sum[0,1]
+            dw[Pc] += m.sum(axis=(0, 2))                                      # positive role sum[0,2]
+            if return_grad:
+                sg = np.where(m, sigmoid(T.astype(np.float64)), 0.0)          # SoftplusGrad = sigmoid
+                G[np.ix_(A, Nc)] += sg.sum(axis=1)                            # d/dD[i,k] (negative role)
+                G[np.ix_(A, Pc)] -= sg.sum(axis=2)                            # d/dD[i,j] (positive role)
+    num_triplet = num_pos if pos_triplets_only else num_valid
+    loss = dt(loss_sum) / (dt(num_triplet) + dt(EPS))                     # :127
+    data_weight = dw.astype(dt)
+    frac = dt(num_pos) / (dt(num_valid) + dt(EPS))
+    if not return_grad:
+        return loss, data_weight, frac, dt(num_pos)
+    return loss, data_weight, frac, dt(num_pos), (G * (1.0 / (float(num_triplet) + EPS))).astype(dt)
+
+
+def batch_all_triplet_loss_literal(labels, h, pos_triplets_only=False, dt=np.float32, chunk=32,
+                           return_grad=False, D=None):
+    """triplet_loss_utils.py:79-131, evaluated anchor-chunk by anchor-chunk over the full B x B rectangle of every anchor
+    (arithmetically the same sums as the B^3 broadcast; chunking only bounds memory).  ``batch_all_triplet_loss`` evaluates the
+    same terms on the valid entries only and is pinned to this function (tests/test_oracle.py).
 
     Returns (loss, data_weight[B], fraction, num_pos) and, if ``return_grad``, also
     G = d loss / d D (gradient wrt the Gram matrix; masks carry no gradient)."""
@@ -346,9 +398,12 @@ def decode(h, W, bv, dec_act="sigmoid", dt=np.float32):
 
 def forward_backward(W, bh, bv, x, x_corr, labels=None, *, enc_act="sigmoid", dec_act="sigmoid",
                      loss_func="cross_entropy", triplet_strategy="none", alpha=1.0, dt=np.float32,
-                     want_grads=True):
+                     want_grads=True, pos_triplets_only=False):
     """One training step's forward + hand-derived backward, i.e. what
     ``tf_session.run([train_step, ...])`` (autoencoder.py:233) evaluates, minus the optimizer.
+
+    ``pos_triplets_only`` (batch_all only, triplet_loss_utils.py:118-123): the loss, its normaliser and the
+    data_weight that feeds the weighted reconstruction loss count the positive triplets only.
 
     Returns dict(cost, ae_loss, triplet_loss, fraction, num, data_weight, h, y, D, G,
                  dW, dbh, dbv, delta1, delta2, dh)."""
@@ -363,7 +418,7 @@ def forward_backward(W, bh, bv, x, x_corr, labels=None, *, enc_act="sigmoid", de
     if triplet_strategy != "none":                                         # autoencoder.py:424-438
         D = (h @ h.T).astype(dt)
         if triplet_strategy == "batch_all":
-            tl, dw, frac, num, G = batch_all_triplet_loss(labels, h, False, dt, return_grad=True, D=D)
+            tl, dw, frac, num, G = batch_all_triplet_loss(labels, h, bool(pos_triplets_only), dt, return_grad=True, D=D)
         elif triplet_strategy == "batch_hard":
             tl, dw, frac, num, G = batch_hard_triplet_loss(labels, h, dt, return_grad=True, D=D)
         else:

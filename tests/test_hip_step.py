@@ -71,7 +71,8 @@ def _run_case(dtype, strategy, loss_func, acts, opt, *, N=400, F=700, H=90, B=15
         torch.cuda.synchronize()
         xb = m[idx].toarray(); xcb = (xc_all[idx] if dense else xc_all[idx].toarray()) * scale
         r = O.forward_backward(W, bh, bv, xb, xcb, lab[idx], enc_act=acts[0], dec_act=acts[1], loss_func=loss_func,
-                               triplet_strategy=strategy, alpha=alpha, dt=np.float64)
+                               triplet_strategy=strategy, alpha=alpha, dt=np.float64,
+                               pos_triplets_only=bool((engine_kw or {}).get("pos_triplets_only", False)))
         dWg, dbhg, dbvg = eng.grads()
         out.append((r, stats[s].cpu().numpy(), dWg, dbhg, dbvg))
         O.opt_apply(st, [W, bh, bv], [r["dW"], r["dbh"], r["dbv"]], 0.05, 0.5, np.float64)
@@ -129,6 +130,36 @@ def test_step_bf16x3_matches_oracle(strategy, opt):
     if opt == "gradient_descent":          # (Adam moves a weight by ~lr * sign(g): no max-norm bound through a near-zero gradient element)
         for a, b in zip(got, ref):
             assert _rel(a, b) < 2e-4, _rel(a, b)
+
+
+@pytest.mark.parametrize("sort_by_label", [False, True])
+@pytest.mark.parametrize("B", [150, 800])
+@pytest.mark.parametrize("dtype", ["fp32", "bf16x3"])
+def test_step_pos_triplets_only_matches_oracle(dtype, B, sort_by_label):
+    """The whole step with pos_triplets_only (batch_all_kernel<POS_ONLY>: role counts, dae_triplet_finalize's data weights and
+    normaliser, G through sym_scale into dh) against the float64 oracle, with the tolerances of test_step_fp32_matches_oracle /
+    test_step_bf16x3_matches_oracle.  A class-sorted batch reaches the class-range prologue with POS_ONLY; B = 800 two chunks of
+    negatives and snake packing.  One derived change: the loss normaliser is now the positive count, which the existing test lets
+    differ by up to 3 near-tie flips between the fp32 and the fp64 Gram matrix; a flipped triplet has T ~ 0 and moves a sum of
+    `num` terms by ~ln 2, so the triplet-loss and cost tolerances get + 3 / num relative (num >= 1e5 is asserted: < 3e-5)."""
+    out, ref, got = _run_case(dtype, "batch_all", "cross_entropy", ("sigmoid", "sigmoid"), "gradient_descent", B=B, N=max(400, 2 * B),
+                              steps=1 if B == 800 else 2, engine_kw=dict(pos_triplets_only=True), sort_by_label=sort_by_label)
+    tol = 2e-5
+    for r, st, dW, dbh, dbv in out:
+        num = float(r["num"])
+        assert num >= 1e5 and 0.1 <= r["fraction"] <= 0.9
+        flips = 3.0 / num
+        # the statistic is a float32: above 2^24 (B = 800: 4.8e7 positive triplets) it carries the count rounded to its spacing
+        assert abs(float(st[4]) - num) <= 3 + 0.5 * float(np.spacing(np.float32(num))), (st[4], num)
+        assert abs(st[3] - r["fraction"]) <= 1e-4
+        assert abs(st[1] - r["ae_loss"]) <= tol * abs(r["ae_loss"]), (st[1], r["ae_loss"])
+        assert abs(st[2] - r["triplet_loss"]) <= (tol + flips) * abs(r["triplet_loss"]) + 1e-9, (st[2], r["triplet_loss"])
+        assert abs(st[0] - r["cost"]) <= (tol + flips) * abs(r["cost"]), (st[0], r["cost"])
+        gtol = 5e-5 if dtype == "fp32" else 1e-4                 # (the gradient gate of this file's other split-bf16 tests)
+        e = (_rel(dW, r["dW"]), _rel(dbh, r["dbh"]), _rel(dbv, r["dbv"]))
+        assert max(e) < gtol, e
+    for a, b in zip(got, ref):
+        assert _rel(a, b) < (1e-5 if dtype == "fp32" else 2e-4), _rel(a, b)
 
 
 @pytest.mark.parametrize("loss_func,acts,scale,strategy", [("mean_squared", ("tanh", "none"), 1.0, "batch_all"),

@@ -231,6 +231,55 @@ def test_finite_difference_gradient():
     assert np.allclose(fd, r["dbh"][1], rtol=1e-5, atol=1e-9)
 
 
+@pytest.mark.parametrize("pos_only", [False, True])
+@pytest.mark.parametrize("B,classes", [(150, 4), (97, 1), (120, 40)])
+def test_batch_all_on_valid_entries_equals_literal_broadcast(B, classes, pos_only):
+    """batch_all_triplet_loss walks the valid entries class by class; the literal form walks every anchor's full B x B rectangle.
+    Same elements, same arithmetic: integers identical, float32 results identical, float64 sums equal to rounding."""
+    rng = np.random.default_rng(B + classes)
+    h = (rng.random((B, 11)) - 0.5) * 2.0
+    h[7] = h[3]                                                          # duplicated rows: exact ties, never positive triplets
+    lab = rng.integers(0, classes, B)
+    for dt in (np.float32, np.float64):
+        D = (h @ h.T).astype(dt)
+        D[:, 7] = D[:, 3]
+        a = O.batch_all_triplet_loss(lab, h, pos_only, dt, return_grad=True, D=D)
+        b = O.batch_all_triplet_loss_literal(lab, h, pos_only, dt, return_grad=True, D=D)
+        assert np.array_equal(a[1], b[1]) and a[2] == b[2] and a[3] == b[3]
+        tol = 1e-6 if dt == np.float32 else 1e-13
+        assert np.allclose(a[0], b[0], rtol=tol, atol=0)
+        assert np.allclose(a[4], b[4], rtol=0, atol=tol * max(np.abs(b[4]).max(), 1e-300))
+
+
+def test_forward_backward_pos_triplets_only():
+    """pos_triplets_only through the whole step: the triplet loss, its normaliser and the data weight of the reconstruction loss are
+    the positive-triplet variants of the executable spec (the triple loop), and the gradient is the cost's (finite differences; the
+    positive mask is piecewise constant)."""
+    rng = np.random.default_rng(23)
+    B, F, H = 10, 16, 5
+    W = rng.uniform(-0.4, 0.4, (F, H)); bh = rng.uniform(-0.3, 0.3, H); bv = rng.uniform(-0.3, 0.3, F)
+    x = (rng.random((B, F)) < 0.3).astype(np.float64); xc = x * (rng.random((B, F)) >= 0.3)
+    lab = _labels(rng, B, 2)
+    kw = dict(loss_func="cross_entropy", triplet_strategy="batch_all", alpha=0.8, dt=np.float64, pos_triplets_only=True)
+    r = O.forward_backward(W, bh, bv, x, xc, lab, **kw)
+    spec = O.batch_all_triplet_loss_loops(lab, r["h"])
+    assert 0 < spec["num_pos"] < spec["num_valid"]                       # the two variants differ on this batch
+    assert r["num"] == spec["num_pos"] and np.array_equal(r["data_weight"], spec["dw_pos"])
+    assert np.allclose(r["triplet_loss"], spec["loss_pos"], rtol=1e-12)
+    assert np.allclose(r["fraction"], spec["num_pos"] / spec["num_valid"], rtol=1e-12)
+    assert np.allclose(r["ae_loss"], O.weighted_loss(x, r["y"], "cross_entropy", spec["dw_pos"], np.float64), rtol=1e-12)
+    assert np.allclose(r["cost"], r["ae_loss"] + 0.8 * spec["loss_pos"], rtol=1e-12)
+    rv = O.forward_backward(W, bh, bv, x, xc, lab, **dict(kw, pos_triplets_only=False))
+    assert np.array_equal(rv["data_weight"], spec["dw_valid"]) and np.allclose(rv["triplet_loss"], spec["loss_valid"], rtol=1e-12)
+    e = 1e-6
+    for (i, j) in [(0, 0), (3, 2), (15, 4)]:
+        Wp = W.copy(); Wp[i, j] += e; Wm = W.copy(); Wm[i, j] -= e
+        fp = O.forward_backward(Wp, bh, bv, x, xc, lab, want_grads=False, **kw)
+        fm = O.forward_backward(Wm, bh, bv, x, xc, lab, want_grads=False, **kw)
+        assert fp["num"] == fm["num"] == r["num"]                        # no triplet changed sides inside the difference
+        assert np.allclose((fp["cost"] - fm["cost"]) / (2 * e), r["dW"][i, j], rtol=1e-5, atol=1e-9)
+
+
 @pytest.mark.parametrize("opt", ["gradient_descent", "ada_grad", "momentum", "adam"])
 def test_optimizers_vs_torch(opt):
     rng = np.random.default_rng(2)
