@@ -81,6 +81,36 @@ def gather_csr_bits(indptr, indices, row_idx, B, F, dtype, *, corr_mode=L.CORR_N
     return x, bits, xct
 
 
+def encode_csr(indptr, indices, values, row_idx, B, F, H, dtype, W_lo, bh, enc_act, *, corr_mode=L.CORR_NONE, keep_bits=None,
+               seed=0, rng_stream=0, corr_frac=0.0, scale=1.0, want_h_f32=True, want_h_lo=True, want_h_t=True, want_hcat_a=False,
+               want_hcat_b=False, want_x_bits=False, want_xct=True, want_rowsq=False, ldt=None):
+    """Fused corrupt + gather + encode of CSR rows (dae_encode_csr): W_lo [Fp x >= Hp] in `dtype`, bh [Hp] fp32.  Returns a dict of the
+    images asked for (None otherwise): h_f32 / h_lo [Bp x Hp], h_t [Hp x Bp], hcat_a / hcat_b [Bp x 3 Hp] bf16, x_bits [Bp x Fp/32]
+    int32, xct [Fp x ldt], rowsq [Bp].  Every image is handed over NaN- resp. sentinel-filled, so that an element the kernel does not
+    write shows -- except xct, which the kernel's contract wants pre-zeroed (only kept entries are scattered into it)."""
+    _dev(indptr)
+    Bp, Fp, Hp = L.pad(B), L.pad(F), L.pad(H)
+    td = tdtype(dtype)
+    dev = indptr.device
+    if W_lo.dtype != td or W_lo.shape[0] < Fp or W_lo.stride(1) != 1 or bh.dtype != torch.float32 or bh.numel() < Hp:
+        raise ValueError("encode_csr: W_lo must be [Fp x >= Hp] of the activation dtype and bh fp32 [Hp]")
+    nan = float("nan")
+
+    def filled(shape, dt, on=True):
+        return torch.full(shape, nan, dtype=dt, device=dev) if on else None
+
+    ldt = Bp if ldt is None else int(ldt)
+    out = dict(h_f32=filled((Bp, Hp), torch.float32, want_h_f32), h_lo=filled((Bp, Hp), td, want_h_lo), h_t=filled((Hp, Bp), td, want_h_t),
+               hcat_a=filled((Bp, 3 * Hp), torch.bfloat16, want_hcat_a), hcat_b=filled((Bp, 3 * Hp), torch.bfloat16, want_hcat_b),
+               x_bits=torch.full((Bp, Fp // 32), 0x5A5A5A5A, dtype=torch.int32, device=dev) if want_x_bits else None,
+               xct=torch.zeros((Fp, ldt), dtype=td, device=dev) if want_xct else None, rowsq=filled((Bp,), torch.float32, want_rowsq))
+    L.call("dae_encode_csr", L.ptr(indptr), L.ptr(indices), L.ptr(values), L.ptr(row_idx), B, F, H, dtype, L.ptr(W_lo), W_lo.stride(0),
+           L.ptr(bh), enc_act, corr_mode, L.ptr(keep_bits), seed, rng_stream, corr_frac, scale, L.ptr(out["h_f32"]), L.ptr(out["h_lo"]),
+           Hp, L.ptr(out["h_t"]), Bp, L.ptr(out["hcat_a"]), L.ptr(out["hcat_b"]), L.ptr(out["x_bits"]), Fp // 32, L.ptr(out["xct"]), ldt,
+           L.ptr(out["rowsq"]), L.current_stream())
+    return out
+
+
 def encode_bits(bits, Wt_lo, splits=1):
     """slabs[s] = bits(x~) . Wt_lo^T  (bf16 MFMA, A expanded from the bit image in LDS)."""
     Bp, Fp, Hp = bits.shape[0], bits.shape[1] * 32, Wt_lo.shape[0]

@@ -26,14 +26,19 @@ def _keep_bits(keep):
 
 
 def _run_case(dtype, strategy, loss_func, acts, opt, *, N=400, F=700, H=90, B=150, steps=2, seed=0, dense=False,
-              alpha=0.7, tol=None, options=None, scale=1.0, phase=0, engine_kw=None, sort_by_label=False):
+              alpha=0.7, tol=None, options=None, scale=1.0, phase=0, engine_kw=None, sort_by_label=False, m=None, w0=0.3, first_rows=0,
+              after_step=None):
+    # m: a prebuilt CSR train set (N, F from it) instead of a random one; w0: bound of the uniform W0; first_rows: rows [0, first_rows) are in every batch;
+    # after_step(eng, step): called behind every step
     from dae_rnn_news_recommendation_amd import _lib as L
     from dae_rnn_news_recommendation_amd.engine import Engine
     rng = np.random.default_rng(seed)
     binary = loss_func == "cross_entropy"
-    m = _mk(rng, N, F, binary)
+    if m is None:
+        m = _mk(rng, N, F, binary)
+    N, F = m.shape
     lab = rng.integers(0, 4, N)
-    W0 = rng.uniform(-0.3, 0.3, (F, H)).astype(np.float32)
+    W0 = rng.uniform(-w0, w0, (F, H)).astype(np.float32)
     bh0 = (rng.standard_normal(H) * 0.1).astype(np.float32); bv0 = (rng.standard_normal(F) * 0.1).astype(np.float32)
     if dtype == "bf16":
         W0 = torch.as_tensor(W0).to(torch.bfloat16).float().numpy()     # start from bf16-representable weights
@@ -52,6 +57,8 @@ def _run_case(dtype, strategy, loss_func, acts, opt, *, N=400, F=700, H=90, B=15
     out = []
     for s in range(steps):
         idx = rng.permutation(N)[:B]
+        if first_rows:
+            idx = np.concatenate([np.arange(first_rows), first_rows + rng.permutation(N - first_rows)])[:B]
         if sort_by_label:                                   # a class-sorted mini-batch (what fit() hands over: utils.class_sort_batches)
             idx = idx[np.argsort(lab[idx], kind="stable")]
         if dense:
@@ -69,6 +76,8 @@ def _run_case(dtype, strategy, loss_func, acts, opt, *, N=400, F=700, H=90, B=15
         if phase == 1:
             eng.apply()
         torch.cuda.synchronize()
+        if after_step is not None:
+            after_step(eng, s)
         xb = m[idx].toarray(); xcb = (xc_all[idx] if dense else xc_all[idx].toarray()) * scale
         r = O.forward_backward(W, bh, bv, xb, xcb, lab[idx], enc_act=acts[0], dec_act=acts[1], loss_func=loss_func,
                                triplet_strategy=strategy, alpha=alpha, dt=np.float64,
@@ -797,3 +806,160 @@ def test_apply_in_row_bands_equals_one_apply(dtype, opt):
         res.append(imgs)
     for a, b in zip(*res):
         assert torch.equal(a, b)
+
+
+# ----------------------------------------------------------------------------------------------- #
+# rows longer than one 256-entry pass of the CSR front end (tests/csr_cases.py)
+# ----------------------------------------------------------------------------------------------- #
+X3T_XV = 1 << 10          # split modes: lo image of x~^T present (csrc/dae_kernels.h)
+
+
+def _assert_scatter_clean(eng, step):
+    """Behind a step the x~^T operand (and its lo image) holds no non-zero element: the step tail zeroed exactly what the encode launch scattered."""
+    it = torch.int32 if eng.td == torch.float32 else torch.int16
+    assert int(eng.buffer("xct", (eng.Fp, eng.Bpm), it).ne(0).sum().item()) == 0, step
+    if eng.x3 and eng.info()["x3_terms"] & X3T_XV:
+        assert int(eng.buffer("xct_2", (eng.Fp, eng.Bpm), torch.int16).ne(0).sum().item()) == 0, step
+
+
+def _long_rows_case(dtype, loss_func, *, options=None, seed=0, B=40, **kw):
+    """Two steps on the long-row matrix (rows of 0 .. 700 stored entries; the first 8-row group -- empty, 700 and 1 entries -- in every batch),
+    random keep bits, W0 in +-0.05; x~^T checked clean behind each step."""
+    import csr_cases as CC
+    m, _ = CC.long_row_csr(np.random.default_rng(100 + seed), 1000, loss_func != "cross_entropy")
+    strategy = "batch_all" if loss_func == "cross_entropy" else "none"
+    return strategy, _run_case(dtype, strategy, loss_func, ("sigmoid", "sigmoid"), "gradient_descent", m=m, H=90, B=B, steps=2, seed=seed, w0=0.05,
+                               first_rows=8, options=options, after_step=_assert_scatter_clean, **kw)
+
+
+@pytest.mark.parametrize("loss_func", ["cross_entropy", "cosine_proximity"])
+def test_step_fp32_long_rows_matches_oracle(loss_func):
+    """fp32 steps on rows of up to 700 stored entries (binary / cross_entropy with batch_all, valued / cosine_proximity with its row squares), at the
+    tolerances of test_step_fp32_matches_oracle."""
+    strategy, (out, ref, got) = _long_rows_case("fp32", loss_func)
+    for r, st, dW, dbh, dbv in out:
+        assert abs(st[0] - r["cost"]) <= 2e-5 * abs(r["cost"]), (st, r["cost"])
+        assert abs(st[1] - r["ae_loss"]) <= 2e-5 * abs(r["ae_loss"])
+        if strategy != "none":
+            assert abs(st[2] - r["triplet_loss"]) <= 2e-5 * abs(r["triplet_loss"]) + 1e-9
+            assert abs(st[4] - r["num"]) <= 3
+            assert abs(st[3] - r["fraction"]) <= 1e-4
+        assert _rel(dW, r["dW"]) < 5e-5, _rel(dW, r["dW"])
+        assert _rel(dbh, r["dbh"]) < 5e-5 and _rel(dbv, r["dbv"]) < 5e-5
+    for a, b in zip(got, ref):
+        assert _rel(a, b) < 1e-5
+
+
+@pytest.mark.parametrize("dw_tr", [0, 1])
+@pytest.mark.parametrize("loss_func", ["cross_entropy", "cosine_proximity"])
+def test_step_bf16_long_rows_matches_oracle(loss_func, dw_tr):
+    """bf16 steps on the long rows at the tolerances of test_step_bf16_matches_oracle, on the 160 x 128 dW kernel with the transposed (dw_tr = 0)
+    and the row-major (dw_tr = 1) x~ scatter: the step tail must un-scatter either layout (tests/test_hip_encode_csr.py asserts the layouts)."""
+    from dae_rnn_news_recommendation_amd import _lib as L
+    lib = L.load()
+    lib.dae_set_glds(-5)
+    try:
+        strategy, (out, ref, got) = _long_rows_case("bf16", loss_func, options={"dw_tr": dw_tr}, seed=1)
+    finally:
+        lib.dae_set_glds(-4)
+    for r, st, dW, dbh, dbv in out:
+        assert abs(st[1] - r["ae_loss"]) <= 1e-4 * abs(r["ae_loss"]), (st[1], r["ae_loss"])
+        if strategy == "batch_all":
+            assert abs(st[2] - r["triplet_loss"]) <= 1e-4 * abs(r["triplet_loss"])
+            assert abs(st[4] - r["num"]) <= 2e-3 * r["num"]
+        assert abs(st[0] - r["cost"]) <= 2e-4 * abs(r["cost"])
+        assert _rel(dW, r["dW"]) < 2e-2 and _rel(dbh, r["dbh"]) < 2e-2 and _rel(dbv, r["dbv"]) < 2e-2
+
+
+@pytest.mark.parametrize("loss_func", ["cross_entropy", "cosine_proximity"])
+def test_step_bf16x3_long_rows_matches_oracle(loss_func):
+    """Split-bf16 steps on the long rows at the tolerances of test_step_bf16x3_matches_oracle; the valued case scatters (and the tail clears) the
+    lo image of x~^T as well."""
+    strategy, (out, ref, got) = _long_rows_case("bf16x3", loss_func, seed=2)
+    for r, st, dW, dbh, dbv in out:
+        e = (_rel(dW, r["dW"]), _rel(dbh, r["dbh"]), _rel(dbv, r["dbv"]))
+        print(f"[bf16x3 long rows] {loss_func}: gradient deviations {e}")
+        assert abs(st[1] - r["ae_loss"]) <= 2e-5 * abs(r["ae_loss"]), (st[1], r["ae_loss"])
+        assert abs(st[0] - r["cost"]) <= 2e-5 * abs(r["cost"])
+        if strategy == "batch_all":
+            assert abs(st[2] - r["triplet_loss"]) <= 2e-5 * abs(r["triplet_loss"])
+        assert max(e) < 1e-4, e                                  # (the gradient gate of this file's other split-bf16 tests)
+    for a, b in zip(got, ref):
+        assert _rel(a, b) < 2e-4, _rel(a, b)
+
+
+def test_step_f16x2_long_rows_matches_oracle():
+    """The fp16 build's row reader (two v_cvt_f32_f16 per packed pair) on the long rows, at the tolerances of test_hip_f16.py::test_step_f16x2_matches_oracle."""
+    strategy, (out, ref, got) = _long_rows_case("f16x2", "cross_entropy", seed=3)
+    for r, st, dW, dbh, dbv in out:
+        assert abs(st[1] - r["ae_loss"]) <= 5e-5 * abs(r["ae_loss"]), (st[1], r["ae_loss"])
+        assert abs(st[0] - r["cost"]) <= 5e-5 * abs(r["cost"])
+        assert max(_rel(dW, r["dW"]), _rel(dbh, r["dbh"]), _rel(dbv, r["dbv"])) < 1.5e-3
+    for a, b in zip(got, ref):
+        assert _rel(a, b) < 2e-3, _rel(a, b)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16x3"])
+def test_encode_rows_long_rows_matches_oracle(dtype):
+    """transform()'s kernel path on the long rows, at the tolerance of test_encode_rows_matches_oracle."""
+    import csr_cases as CC
+    from dae_rnn_news_recommendation_amd.engine import Engine
+    rng = np.random.default_rng(6)
+    F, H = 1000, 77
+    m, _ = CC.long_row_csr(rng, F, True)
+    N = m.shape[0]
+    W0 = rng.uniform(-0.05, 0.05, (F, H)).astype(np.float32); bh0 = (rng.standard_normal(H) * 0.1).astype(np.float32)
+    eng = Engine(F, H, 40, dtype=dtype)
+    eng.upload_csr(m); eng.set_params(W0, bh0)
+    out = torch.zeros((N, H), device="cuda")
+    for i0 in range(0, N, 40):
+        idx = torch.arange(i0, min(N, i0 + 40), dtype=torch.int32, device="cuda")
+        eng.encode_rows(idx, out[i0:i0 + idx.numel()], scale=0.7)
+    want, _ = O.encode(m.toarray() * 0.7, W0, bh0, "sigmoid", np.float64)
+    assert _rel(out.cpu().numpy(), want) < 1e-5
+    per_row = np.abs(out.cpu().numpy() - want).max(1)
+    assert per_row.max() < 1e-5 * np.abs(want).max(), int(per_row.argmax())
+
+
+@pytest.mark.parametrize("binary", [True, False])
+def test_salt_pepper_on_long_rows_and_step(binary):
+    """dae_salt_pepper_batch with v = 300 on the long rows: output rows go past 256 and 512 entries and the empty row gains entries; exactly the
+    oracle's corrupted rows.  Then one step with that corrupted copy against the oracle (fp32 tolerances of test_step_fp32_matches_oracle)."""
+    import csr_cases as CC
+    from dae_rnn_news_recommendation_amd.engine import Engine
+    rng = np.random.default_rng(9)
+    F, H, B, v = 1000, 90, 40, 300
+    m, _ = CC.long_row_csr(rng, F, not binary)
+    N = m.shape[0]
+    loss_func = "cross_entropy" if binary else "mean_squared"
+    W0 = rng.uniform(-0.05, 0.05, (F, H)).astype(np.float32)
+    bh0 = (rng.standard_normal(H) * 0.1).astype(np.float32); bv0 = (rng.standard_normal(F) * 0.1).astype(np.float32)
+    eng = Engine(F, H, B, dtype="fp32", loss_func=loss_func, learning_rate=0.05)
+    eng.upload_csr(m); eng.set_params(W0, bh0, bv0)
+    rows = np.concatenate([np.arange(8), 8 + rng.permutation(N - 8)])[:B].astype(np.int32)
+    lo, hi = 0.0, float(m.data.max())
+    seed, stream = 0x1234ABCD5678, 3
+    c = eng.salt_pepper_batch(torch.from_numpy(rows).cuda(), v, lo, hi, seed=seed, rng_stream=stream)
+    torch.cuda.synchronize()
+    span = c["indptr"].cpu().numpy(); ci = c["indices"].cpu().numpy(); cv = c["values"].cpu().numpy()
+    want = O.salt_and_pepper_philox(m, rows, v, seed, stream, lo=lo, hi=hi)
+    got = np.zeros((B, F))
+    lens = []
+    for i in range(B):
+        s0, e0 = span[2 * i], span[2 * i + 1]
+        cols = ci[s0:e0]
+        lens.append(e0 - s0)
+        assert (np.diff(cols) > 0).all() and (cv[s0:e0] != 0).all()
+        got[i, cols] = cv[s0:e0]
+    assert np.array_equal(got.astype(np.float32), want.astype(np.float32))
+    assert lens[0] > 64 and max(lens) > 512 and m[rows[0]].nnz == 0          # the empty row gained entries; output rows of three 256-entry passes
+    stats = torch.zeros(8, device="cuda")
+    eng.train_step(torch.from_numpy(rows).cuda(), None, stats, corrupted_csr=c, phase=0)
+    torch.cuda.synchronize()
+    _assert_scatter_clean(eng, 0)
+    r = O.forward_backward(W0.astype(np.float64), bh0.astype(np.float64), bv0.astype(np.float64), m[rows].toarray(), want, None, loss_func=loss_func,
+                           triplet_strategy="none", dt=np.float64)
+    st = stats.cpu().numpy()
+    dW, dbh, dbv = eng.grads()
+    assert abs(st[0] - r["cost"]) <= 2e-5 * abs(r["cost"]), (st[0], r["cost"])
+    assert _rel(dW, r["dW"]) < 5e-5 and _rel(dbh, r["dbh"]) < 5e-5 and _rel(dbv, r["dbv"]) < 5e-5, (_rel(dW, r["dW"]), _rel(dbh, r["dbh"]), _rel(dbv, r["dbv"]))
