@@ -145,6 +145,16 @@ SIGNATURES = {
     "dae_pair_hist_max_bins": (i32, []),
     "dae_pair_hist_workspace": (u64, [i32, i32, i32, i32]),
     "dae_pair_hist": (i32, [vp, i64, i32, vp, vp, i64, i32, vp, i32, i32, i32, f32, f32, i32, vp, vp, vp, u64, vp]),
+    "dae_sweep_image_bytes": (u64, [i32, i32]),
+    "dae_sweep_image_dense": (i32, [vp, i64, i32, i32, i32, i32, vp, u64, vp]),
+    "dae_sweep_image_csr": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, u64, vp]),
+    "dae_sweep_image_norm2_max_workspace": (u64, []),
+    "dae_sweep_image_norm2_max": (i32, [vp, i32, i32, vp, vp, u64, vp]),
+    "dae_topk_carry_bytes": (u64, [i32, i32]),
+    "dae_topk_images_workspace": (u64, [i32, i32, i32]),
+    "dae_topk_images": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, u64, vp]),
+    "dae_pair_hist_images_workspace": (u64, [i32, i32, i32]),
+    "dae_pair_hist_images": (i32, [vp, i32, vp, vp, i32, vp, i32, f32, f32, i32, vp, vp, vp, u64, vp]),
     "dae_pair_stats_workspace": (u64, [i32]),
     "dae_pair_stats": (i32, [vp, i64, vp, i32, vp, vp, u64, vp]),
     "dae_gemm_trace": (i32, [i32, i32, i32, vp, i64, vp, i64, i32, vp, i64, vp, i64, i32, vp, i64, i32, i64, i32, vp, vp]),

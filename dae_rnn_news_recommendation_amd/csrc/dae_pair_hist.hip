@@ -17,6 +17,11 @@
 // LDS counters go to the global uint64[2][bins] histogram by atomic adds -- integers, so the result is bit-identical run to
 // run and independent of the grid -- and the lanes' running values are reduced over the wave and the workgroup into one
 // record per workgroup; the host folds the records in index order (the fp64 sums are therefore bit-identical run to run).
+//
+// dae_pair_hist_images runs the same kernel, unchanged, on images the caller built (dae_sweep_image.hip) with an explicit range:
+// the strict lower triangle of an operand swept in row chunks is its diagonal blocks in self mode plus the blocks below them in
+// full mode; counts add as integers, min / max combine, the caller adds the fp64 sums block by block.  dae_sweep_image_norm2_max
+// exposes row_norm2_max_kernel so that the automatic range of the linear kernel can be rebuilt from the chunks (a maximum).
 #include "dae_score_sweep.h"
 
 #include <cmath>
@@ -166,71 +171,61 @@ using namespace dae;
 
 extern "C" int32_t dae_pair_hist_max_bins(void) { return PAIR_HIST_MAX_BINS; }
 
-extern "C" uint64_t dae_pair_hist_workspace(int32_t Nq, int32_t Nc, int32_t D, int32_t bins) {
-    if (Nq <= 0 || Nc <= 0 || D <= 0 || bins <= 0) return 0;
-    const uint64_t Nqp = pad128(Nq), Ncp = pad128(Nc);
-    // operand images, labels, global histogram, per-workgroup records, norm partials of the automatic range
-    return sweep_images_bytes(Nq, Nc, D) + al256(Nqp * 4) + al256(Ncp * 4) + al256(2 * (uint64_t)bins * 8) +
-           al256(PAIR_HIST_MAX_GRID * sizeof(PairHistRecord)) + al256(2 * PAIR_NORM_BLOCKS * 8);
+// the workspace of pair_hist_sweep: labels, global histogram, per-workgroup records
+static uint64_t pair_hist_sweep_bytes(int32_t Nq, int32_t Nc, int32_t bins) {
+    return al256(pad128(Nq) * 4) + al256(pad128(Nc) * 4) + al256(2 * (uint64_t)bins * 8) + al256(PAIR_HIST_MAX_GRID * sizeof(PairHistRecord));
 }
 
-extern "C" int dae_pair_hist(const float* Q, int64_t ldq, int32_t Nq, const int32_t* labels_q_host, const float* C, int64_t ldc,
-                             int32_t Nc, const int32_t* labels_c_host, int32_t D, int32_t norm, int32_t metric, float lo, float hi,
-                             int32_t bins, uint64_t* hist_host, double* out16_host, void* workspace, uint64_t workspace_bytes,
-                             void* stream) {
-    DAE_CHECK_ARG(Q && labels_q_host && workspace && Nq > 0 && D > 0, "pair_hist: bad input");
-    DAE_CHECK_ARG(hist_host && out16_host, "pair_hist: hist / out16 are NULL");
-    DAE_CHECK_ARG(ldq >= D, "pair_hist: ldq (%lld) must be >= D (%d)", (long long)ldq, D);
-    DAE_CHECK_ARG(C ? (Nc > 0 && ldc >= D && labels_c_host) : Nc == Nq,
-                  "pair_hist: bad corpus (C == NULL means the corpus is Q: pass Nc == Nq; with C, labels_c is needed)");
-    DAE_CHECK_ARG(bins >= 2 && bins <= PAIR_HIST_MAX_BINS, "pair_hist: bins must be in 2..%d (got %d)", PAIR_HIST_MAX_BINS, bins);
-    DAE_CHECK_ARG(std::isfinite(lo) && std::isfinite(hi), "pair_hist: lo / hi must be finite (lo >= hi asks for the automatic range)");
-    DAE_CHECK_ARG(lo >= hi || std::isfinite(hi - lo), "pair_hist: hi - lo overflows fp32");
-    const int self = C ? 0 : 1;
+extern "C" uint64_t dae_pair_hist_workspace(int32_t Nq, int32_t Nc, int32_t D, int32_t bins) {
+    if (Nq <= 0 || Nc <= 0 || D <= 0 || bins <= 0) return 0;
+    // operand images, the sweep's share, norm partials of the automatic range
+    return sweep_images_bytes(Nq, Nc, D) + pair_hist_sweep_bytes(Nq, Nc, bins) + al256(2 * PAIR_NORM_BLOCKS * 8);
+}
+
+extern "C" uint64_t dae_pair_hist_images_workspace(int32_t Nq, int32_t Nc, int32_t bins) {
+    if (Nq <= 0 || Nc <= 0 || bins <= 0) return 0;
+    return pair_hist_sweep_bytes(Nq, Nc, bins);
+}
+
+extern "C" uint64_t dae_sweep_image_norm2_max_workspace(void) { return al256(PAIR_NORM_BLOCKS * 8); }
+
+// the largest squared row 2-norm (fp64) of the first `rows` rows of an image of width Dp, from the partials of row_norm2_max_kernel
+static int image_norm2_max(const float* image, int32_t rows, int64_t Dp, double* npart, double* out_host, hipStream_t st) {
+    DAE_LAUNCH(row_norm2_max_kernel, dim3(PAIR_NORM_BLOCKS), dim3(256), 0, st, image, Dp, (int)rows, (int)Dp, npart);
+    DAE_CHECK_LAUNCH();
+    double h[PAIR_NORM_BLOCKS];
+    DAE_CHECK_HIP(hipMemcpyAsync(h, npart, PAIR_NORM_BLOCKS * 8, hipMemcpyDeviceToHost, st));
+    DAE_CHECK_HIP(hipStreamSynchronize(st));
+    double m = 0.0;
+    for (int k = 0; k < PAIR_NORM_BLOCKS; ++k) m = std::fmax(m, h[k]);
+    *out_host = m;
+    return 0;
+}
+
+extern "C" int dae_sweep_image_norm2_max(const float* image, int32_t rows, int32_t D, double* out_host, void* workspace,
+                                         uint64_t workspace_bytes, void* stream) {
+    DAE_CHECK_ARG(image && out_host && workspace, "sweep_image_norm2_max: image / out / workspace are NULL");
+    DAE_CHECK_ARG(rows > 0 && D > 0, "sweep_image_norm2_max: rows and D must be positive (got %d, %d)", rows, D);
+    DAE_CHECK_ARG(pad128(rows) * pad128(D) * 4 < (1ll << 32), "sweep_image_norm2_max: an operand image exceeds 4 GiB");
+    DAE_CHECK_ARG(workspace_bytes >= dae_sweep_image_norm2_max_workspace() && ((uintptr_t)workspace % 256) == 0,
+                  "sweep_image_norm2_max: workspace too small / unaligned");
+    return image_norm2_max(image, rows, pad128(D), (double*)workspace, out_host, (hipStream_t)stream);
+}
+
+// The sweep of dae_pair_hist and dae_pair_hist_images over two prepared images (g), lo < hi: labels up, histogram cleared,
+// pair_hist_tiles_kernel, and the host's fold of the records into out16.  w: pair_hist_sweep_bytes of workspace.
+static int pair_hist_sweep(const GemmParams& g, int32_t Nq, const int32_t* labels_q_host, int self, int32_t Nc, const int32_t* labels_c_host,
+                           float lo, float hi, int32_t bins, uint64_t* hist_host, double* out16_host, char* w, hipStream_t st) {
     const int64_t Nqp = pad128(Nq), Ncp = pad128(Nc), qtiles = Nqp / BM, ctiles = Ncp / BN;
     const int64_t tiles = self ? qtiles * (qtiles + 1) / 2 : qtiles * ctiles;
-    DAE_CHECK_ARG(tiles < (1ll << 31), "pair_hist: %lld tiles exceed the enumeration", (long long)tiles);
-    hipStream_t st = (hipStream_t)stream;
-    SweepOperands o;
-    if (int rc = sweep_prepare("pair_hist", Q, ldq, Nq, C, ldc, Nc, D, norm, metric, workspace, workspace_bytes,
-                               dae_pair_hist_workspace(Nq, Nc, D, bins), st, o))
-        return rc;
     for (int k = 0; k < 16; ++k) out16_host[k] = std::nan("");
-    const float *Qi = o.Qi, *Ci = o.Ci;
-    const int64_t Dp = o.Dp;
-    const int cosine = metric == 0 ? 1 : 0;
-    char* w = o.rest;
     int32_t* lq = (int32_t*)w;                  w += al256(Nqp * 4);
-    int32_t* lc = C ? (int32_t*)w : lq;         w += al256(Ncp * 4);
+    int32_t* lc = self ? lq : (int32_t*)w;      w += al256(Ncp * 4);
     unsigned long long* hist = (unsigned long long*)w;   w += al256(2 * (uint64_t)bins * 8);
-    PairHistRecord* rec = (PairHistRecord*)w;   w += al256(PAIR_HIST_MAX_GRID * sizeof(PairHistRecord));
-    double* npart = (double*)w;
+    PairHistRecord* rec = (PairHistRecord*)w;
     DAE_CHECK_HIP(hipMemcpyAsync(lq, labels_q_host, (size_t)Nq * 4, hipMemcpyHostToDevice, st));
-    if (C) DAE_CHECK_HIP(hipMemcpyAsync(lc, labels_c_host, (size_t)Nc * 4, hipMemcpyHostToDevice, st));
+    if (!self) DAE_CHECK_HIP(hipMemcpyAsync(lc, labels_c_host, (size_t)Nc * 4, hipMemcpyHostToDevice, st));
     DAE_CHECK_HIP(hipMemsetAsync(hist, 0, 2 * (size_t)bins * 8, st));
-    if (lo >= hi) {                                             // the automatic range
-        if (cosine) { lo = -1.f; hi = 1.f; }
-        else {
-            // Cauchy-Schwarz: |score| <= (largest row norm of Qi) x (largest row norm of Ci), rounded up by one part in 2^20
-            DAE_LAUNCH(row_norm2_max_kernel, dim3(PAIR_NORM_BLOCKS), dim3(256), 0, st, Qi, Dp, (int)Nq, (int)Dp, npart);
-            DAE_CHECK_LAUNCH();
-            if (C) {
-                DAE_LAUNCH(row_norm2_max_kernel, dim3(PAIR_NORM_BLOCKS), dim3(256), 0, st, Ci, Dp, (int)Nc, (int)Dp, npart + PAIR_NORM_BLOCKS);
-                DAE_CHECK_LAUNCH();
-            }
-            std::vector<double> h(2 * PAIR_NORM_BLOCKS, 0.0);
-            DAE_CHECK_HIP(hipMemcpyAsync(h.data(), npart, (C ? 2 : 1) * PAIR_NORM_BLOCKS * 8, hipMemcpyDeviceToHost, st));
-            DAE_CHECK_HIP(hipStreamSynchronize(st));
-            double mq = 0.0, mc = 0.0;
-            for (int k = 0; k < PAIR_NORM_BLOCKS; ++k) { mq = std::fmax(mq, h[k]); mc = std::fmax(mc, h[PAIR_NORM_BLOCKS + k]); }
-            if (!C) mc = mq;
-            const double M = std::sqrt(mq) * std::sqrt(mc) * (1.0 + 1.0 / 1048576.0);
-            float Mf = (float)M;
-            if ((double)Mf < M) Mf = std::nextafterf(Mf, INFINITY);
-            if (!(Mf > 0.f) || !std::isfinite(Mf)) Mf = 1.f;    // all-zero rows (every score is 0) / overflowing norms
-            lo = -Mf; hi = Mf;
-        }
-    }
     static int cus = 0;
     if (cus == 0) {
         int dev = 0, n = 0;
@@ -243,7 +238,7 @@ extern "C" int dae_pair_hist(const float* Q, int64_t ldq, int32_t Nq, const int3
     if (grid > tiles) grid = tiles;
     PairHistParams p;
     memset(&p, 0, sizeof(p));
-    p.g = o.g;
+    p.g = g;
     p.Nq = Nq; p.Nc = Nc; p.self = self; p.ctiles = (int)ctiles; p.bins = bins; p.tiles = tiles;
     p.lo = lo; p.span = hi - lo; p.fbins = (float)bins;
     p.labels_q = lq; p.labels_c = lc; p.hist = hist; p.rec = rec;
@@ -276,4 +271,64 @@ extern "C" int dae_pair_hist(const float* Q, int64_t ldq, int32_t Nq, const int3
     out16_host[9] = (double)lo; out16_host[10] = (double)hi;
     out16_host[11] = (double)grid; out16_host[12] = (double)tiles;
     return 0;
+}
+
+extern "C" int dae_pair_hist_images(const float* Qi, int32_t Nq, const int32_t* labels_q_host, const float* Ci, int32_t Nc,
+                                    const int32_t* labels_c_host, int32_t D, float lo, float hi, int32_t bins, uint64_t* hist_host,
+                                    double* out16_host, void* workspace, uint64_t workspace_bytes, void* stream) {
+    DAE_CHECK_ARG(labels_q_host && hist_host && out16_host, "pair_hist_images: labels_q / hist / out16 are NULL");
+    DAE_CHECK_ARG(!Ci || labels_c_host, "pair_hist_images: with Ci, labels_c is needed");
+    DAE_CHECK_ARG(bins >= 2 && bins <= PAIR_HIST_MAX_BINS, "pair_hist_images: bins must be in 2..%d (got %d)", PAIR_HIST_MAX_BINS, bins);
+    DAE_CHECK_ARG(std::isfinite(lo) && std::isfinite(hi) && lo < hi && std::isfinite(hi - lo),
+                  "pair_hist_images: lo / hi must be finite with lo < hi (there is no automatic range here) and hi - lo must not overflow fp32");
+    SweepOperands o;
+    if (int rc = sweep_prepare_images("pair_hist_images", Qi, Nq, Ci, Nc, D, workspace, workspace_bytes,
+                                      dae_pair_hist_images_workspace(Nq, Nc, bins), o))
+        return rc;
+    const int64_t qtiles = o.Nqp / BM, ctiles = o.Ncp / BN;
+    DAE_CHECK_ARG((Ci ? qtiles * ctiles : qtiles * (qtiles + 1) / 2) < (1ll << 31), "pair_hist_images: the tiles exceed the enumeration");
+    return pair_hist_sweep(o.g, Nq, labels_q_host, Ci ? 0 : 1, Nc, labels_c_host, lo, hi, bins, hist_host, out16_host, o.rest, (hipStream_t)stream);
+}
+
+extern "C" int dae_pair_hist(const float* Q, int64_t ldq, int32_t Nq, const int32_t* labels_q_host, const float* C, int64_t ldc,
+                             int32_t Nc, const int32_t* labels_c_host, int32_t D, int32_t norm, int32_t metric, float lo, float hi,
+                             int32_t bins, uint64_t* hist_host, double* out16_host, void* workspace, uint64_t workspace_bytes,
+                             void* stream) {
+    DAE_CHECK_ARG(Q && labels_q_host && workspace && Nq > 0 && D > 0, "pair_hist: bad input");
+    DAE_CHECK_ARG(hist_host && out16_host, "pair_hist: hist / out16 are NULL");
+    DAE_CHECK_ARG(ldq >= D, "pair_hist: ldq (%lld) must be >= D (%d)", (long long)ldq, D);
+    DAE_CHECK_ARG(C ? (Nc > 0 && ldc >= D && labels_c_host) : Nc == Nq,
+                  "pair_hist: bad corpus (C == NULL means the corpus is Q: pass Nc == Nq; with C, labels_c is needed)");
+    DAE_CHECK_ARG(bins >= 2 && bins <= PAIR_HIST_MAX_BINS, "pair_hist: bins must be in 2..%d (got %d)", PAIR_HIST_MAX_BINS, bins);
+    DAE_CHECK_ARG(std::isfinite(lo) && std::isfinite(hi), "pair_hist: lo / hi must be finite (lo >= hi asks for the automatic range)");
+    DAE_CHECK_ARG(lo >= hi || std::isfinite(hi - lo), "pair_hist: hi - lo overflows fp32");
+    const int self = C ? 0 : 1;
+    const int64_t Nqp = pad128(Nq), Ncp = pad128(Nc), qtiles = Nqp / BM, ctiles = Ncp / BN;
+    const int64_t tiles = self ? qtiles * (qtiles + 1) / 2 : qtiles * ctiles;
+    DAE_CHECK_ARG(tiles < (1ll << 31), "pair_hist: %lld tiles exceed the enumeration", (long long)tiles);
+    hipStream_t st = (hipStream_t)stream;
+    SweepOperands o;
+    if (int rc = sweep_prepare("pair_hist", Q, ldq, Nq, C, ldc, Nc, D, norm, metric, workspace, workspace_bytes,
+                               dae_pair_hist_workspace(Nq, Nc, D, bins), st, o))
+        return rc;
+    for (int k = 0; k < 16; ++k) out16_host[k] = std::nan("");
+    const float *Qi = o.Qi, *Ci = o.Ci;
+    const int64_t Dp = o.Dp;
+    if (lo >= hi) {                                             // the automatic range
+        if (metric == 0) { lo = -1.f; hi = 1.f; }
+        else {
+            // Cauchy-Schwarz: |score| <= (largest row norm of Qi) x (largest row norm of Ci), rounded up by one part in 2^20
+            double* npart = (double*)(o.rest + pair_hist_sweep_bytes(Nq, Nc, bins));
+            double mq = 0.0, mc = 0.0;
+            if (int rc = image_norm2_max(Qi, Nq, Dp, npart, &mq, st)) return rc;
+            if (C) { if (int rc = image_norm2_max(Ci, Nc, Dp, npart + PAIR_NORM_BLOCKS, &mc, st)) return rc; }
+            else mc = mq;
+            const double M = std::sqrt(mq) * std::sqrt(mc) * (1.0 + 1.0 / 1048576.0);
+            float Mf = (float)M;
+            if ((double)Mf < M) Mf = std::nextafterf(Mf, INFINITY);
+            if (!(Mf > 0.f) || !std::isfinite(Mf)) Mf = 1.f;    // all-zero rows (every score is 0) / overflowing norms
+            lo = -Mf; hi = Mf;
+        }
+    }
+    return pair_hist_sweep(o.g, Nq, labels_q_host, self, Nc, labels_c_host, lo, hi, bins, hist_host, out16_host, o.rest, st);
 }

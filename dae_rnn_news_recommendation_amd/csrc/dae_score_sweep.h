@@ -3,6 +3,8 @@
 // only in the epilogue.  Here: the order-preserving keys, the score tile in LDS, the tile enumerations, the row filter of top-k and
 // rank (exclusion lists, stamped lists, candidate windows: its fields, the list a row reads, the window prologue, its checks and
 // its launch), and the host prologue (argument checks, workspace carve, normalisation, GemmParams) and launch of every entry.
+// The *_images entries (dae_topk_images, dae_pair_hist_images) sweep images their caller built chunk by chunk
+// (dae_sweep_image.hip: from dense rows or straight from CSR rows); their prologue is sweep_prepare_images.
 #pragma once
 #include "dae_gemm_tile.h"
 
@@ -150,6 +152,15 @@ struct SweepOperands {
     char* rest;                   // the workspace behind the images
 };
 
+// the K loop over two images of width Dp: one K segment, A = Qi, Bt = Ci
+static inline void sweep_gemm_params(const float* Qi, const float* Ci, int64_t Dp, GemmParams& g) {
+    memset(&g, 0, sizeof(g));
+    g.seg[0].A = (const char*)Qi; g.seg[0].Bt = (const char*)Ci;
+    g.seg[0].lda_b = g.seg[0].ldb_b = Dp * 4;
+    g.seg[0].ktiles = g.ktiles_total = (int)(Dp * 4 / BKB);
+    g.nseg = 1; g.splits = 1; g.out_scale = 1.f;
+}
+
 // The prologue of every entry point: the argument checks they share (messages prefixed with `who`; `need` is the entry's
 // *_workspace), the images carved from the workspace and filled by row_normalize_kernel, and the K loop's parameters.
 static inline int sweep_prepare(const char* who, const float* Q, int64_t ldq, int32_t Nq, const float* C, int64_t ldc, int32_t Nc, int32_t D,
@@ -171,11 +182,26 @@ static inline int sweep_prepare(const char* who, const float* Q, int64_t ldq, in
     if (int rc = launch_row_normalize(Q, ldq, Nq, D, norm, cosine, o.Qi, o.Dp, (int)o.Dp, (int)o.Nqp, st)) return rc;
     if (C)
         if (int rc = launch_row_normalize(C, ldc, Nc, D, norm, cosine, o.Ci, o.Dp, (int)o.Dp, (int)o.Ncp, st)) return rc;
-    memset(&o.g, 0, sizeof(o.g));
-    o.g.seg[0].A = (const char*)o.Qi; o.g.seg[0].Bt = (const char*)o.Ci;
-    o.g.seg[0].lda_b = o.g.seg[0].ldb_b = o.Dp * 4;
-    o.g.seg[0].ktiles = o.g.ktiles_total = (int)(o.Dp * 4 / BKB);
-    o.g.nseg = 1; o.g.splits = 1; o.g.out_scale = 1.f;
+    sweep_gemm_params(o.Qi, o.Ci, o.Dp, o.g);
+    return 0;
+}
+
+// The prologue of the *_images entries, whose caller built the images (dae_sweep_image.hip): the checks of the two images
+// [pad128(Nq) x pad128(D)], [pad128(Nc) x pad128(D)] (Ci == NULL: the corpus is Qi, pass Nc == Nq) and of the workspace, and the
+// K loop's parameters.  No HIP call.
+static inline int sweep_prepare_images(const char* who, const float* Qi, int32_t Nq, const float* Ci, int32_t Nc, int32_t D, void* workspace,
+                                       uint64_t workspace_bytes, uint64_t need, SweepOperands& o) {
+    DAE_CHECK_ARG(Qi && workspace && Nq > 0 && D > 0, "%s: bad input", who);
+    DAE_CHECK_ARG(Ci ? Nc > 0 : Nc == Nq, "%s: bad corpus (Ci == NULL means the corpus is Qi: pass Nc == Nq)", who);
+    o.Nqp = pad128(Nq); o.Ncp = pad128(Nc); o.Dp = pad128(D);
+    DAE_CHECK_ARG(o.Nqp * o.Dp * 4 < (1ll << 32) && o.Ncp * o.Dp * 4 < (1ll << 32), "%s: an operand image exceeds 4 GiB", who);
+    DAE_CHECK_ARG(workspace_bytes >= need, "%s: workspace too small (%llu < %llu bytes)", who, (unsigned long long)workspace_bytes,
+                  (unsigned long long)need);
+    DAE_CHECK_ARG(((uintptr_t)workspace % 256) == 0 && ((uintptr_t)Qi % 256) == 0 && ((uintptr_t)Ci % 256) == 0,
+                  "%s: workspace and images must be 256-byte aligned", who);
+    o.Qi = const_cast<float*>(Qi); o.Ci = const_cast<float*>(Ci ? Ci : Qi);
+    o.rest = (char*)workspace;
+    sweep_gemm_params(o.Qi, o.Ci, o.Dp, o.g);
     return 0;
 }
 

@@ -35,6 +35,15 @@
 // Shared stamped lists (dae_topk_similarity_seq, topk_tiles_kernel<true, *, true>): the same lookup in the list the row shares with
 // the other states of its user, an item counting up to its stamp.  Neighbouring rows read the same list addresses; nothing is
 // staged in LDS, the budget is unchanged.  topk_tiles_kernel<*, *, false> is the kernel as it was.
+//
+// Corpus chunks (dae_topk_images): the two operand images are built by the caller (dae_sweep_image.hip) and hold rows
+// row0 .. row0 + Nq of the queries and col0 .. col0 + Nc of the corpus; the keys, the self test and the exclusion lookup use
+// those global ids (TopkParams::row0 / col0; zero in every other entry).  Each row's sorted keys are carried from one corpus
+// chunk to the next: phase A seeds a row's threshold with the k-th key of a full carry, so a candidate that cannot enter the
+// final list loses at the first compare and the partial lists hold only keys above it; phase B merges the carry as one more
+// list (33 x 128 keys of LDS), writes the merged row back to the carry and idx / score from it.  The order is total, so after
+// the last chunk the row is the one the one-shot sweep returns, bit for bit.  All of it sits behind the template flags CHUNK
+// (topk_tiles_kernel) and CARRY (topk_merge_kernel): the instantiations of the other entries are the kernels as they were.
 #include "dae_score_sweep.h"
 
 namespace dae {
@@ -62,11 +71,18 @@ struct TopkParams {
     uint64_t* part;               // [splits][Nqp][k] sorted keys
     int* part_n;                  // [splits][Nqp] valid keys per list
     RowFilter f;                  // which columns may compete in a row (dae_score_sweep.h)
+    // dae_topk_images (topk_tiles_kernel<*, *, *, true> only): image row i is query row0 + i, image column j is candidate col0 + j --
+    // the ids in the keys, in the self test and in the exclusion items (excl_indptr is already offset to the image's first row)
+    int row0, col0;
+    uint64_t* carry;              // [Nqp][k] each row's sorted keys over the corpus chunks before this one, or NULL
+    int* carry_n;                 // [Nqp] valid keys per row
 };
 
-template <bool EXCL, bool WIN, bool SEQ = false>
+template <bool EXCL, bool WIN, bool SEQ = false, bool CHUNK = false>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams p) {
     static_assert(EXCL || !SEQ, "the shared lists are a form of the exclusion lists");
+    static_assert(!CHUNK || (!WIN && !SEQ), "dae_topk_images takes neither windows nor shared lists");
+    const int row0 = CHUNK ? p.row0 : 0, col0 = CHUNK ? p.col0 : 0;     // <*, *, *, false>: the kernel as it was
     extern __shared__ __attribute__((aligned(16))) char lds[];
     float* tile = reinterpret_cast<float*>(lds);
     uint64_t* th = reinterpret_cast<uint64_t*>(lds + TOPK_TILE_BYTES);
@@ -78,6 +94,11 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams 
     int ct0 = (int)((int64_t)p.ctiles * split / p.splits), ct1 = (int)((int64_t)p.ctiles * (split + 1) / p.splits);
     const int k = p.k;
     if (tid < 128) { th[tid] = 0; len[tid] = 0; }
+    if constexpr (CHUNK) {
+        // a full carry: its k-th key is the threshold from the first tile on, so a candidate needs one compare to lose
+        const int gi = qt * BM + tid;
+        if (tid < 128 && gi < p.Nq && p.carry_n[gi] == k) th[tid] = p.carry[(int64_t)gi * k + k - 1];
+    }
     int* wlo = reinterpret_cast<int*>(lds + TOPK_LDS);          // the query tile's windows (WIN only; behind the merge scratch)
     int* whi = wlo + 128;
     if constexpr (WIN) window_prologue(p.f.win_lo, p.f.win_hi, p.Nq, p.Nc, qt, split, p.splits, wlo, whi, whi + 128, ct0, ct1);
@@ -90,6 +111,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams 
         acc_to_tile(acc, tile, wm, wn, g, c);
         __syncthreads();
         const int j0 = ct * BN + lane, j1 = j0 + 64;
+        const int gj0 = col0 + j0, gj1 = col0 + j1;          // the candidates' ids
         for (int rr = 0; rr < 32; ++rr) {
             const int row = wave * 32 + rr, gi = qt * BM + row;
             if (gi >= p.Nq) break;
@@ -99,17 +121,17 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams 
                 if (wh <= ct * BN || wl >= (ct + 1) * BN) continue;      // the row's window misses this tile (wave-uniform)
             }
             const uint64_t t = th[row];
-            const bool ok0 = j0 < p.Nc && !(p.f.exclude_self && j0 == gi) && (!WIN || (j0 >= wl && j0 < wh)),
-                       ok1 = j1 < p.Nc && !(p.f.exclude_self && j1 == gi) && (!WIN || (j1 >= wl && j1 < wh));
-            const uint64_t c0 = ok0 ? pair_key(tile[row * BN + lane], j0) : 0, c1 = ok1 ? pair_key(tile[row * BN + 64 + lane], j1) : 0;
+            const bool ok0 = j0 < p.Nc && !(p.f.exclude_self && gj0 == row0 + gi) && (!WIN || (j0 >= wl && j0 < wh)),
+                       ok1 = j1 < p.Nc && !(p.f.exclude_self && gj1 == row0 + gi) && (!WIN || (j1 >= wl && j1 < wh));
+            const uint64_t c0 = ok0 ? pair_key(tile[row * BN + lane], gj0) : 0, c1 = ok1 ? pair_key(tile[row * BN + 64 + lane], gj1) : 0;
             bool in0 = c0 > t, in1 = c1 > t;
             uint64_t b0 = __ballot(in0), b1 = __ballot(in1);
             if ((b0 | b1) == 0) continue;
             if constexpr (EXCL) {                               // drop the candidates the row's list bars, then ballot again
                 const RowList l = row_list_of<SEQ>(p.f, gi);
                 if (l.n > 0) {
-                    if (in0 && list_has<SEQ>(l, j0)) in0 = false;
-                    if (in1 && list_has<SEQ>(l, j1)) in1 = false;
+                    if (in0 && list_has<SEQ>(l, gj0)) in0 = false;
+                    if (in1 && list_has<SEQ>(l, gj1)) in1 = false;
                     b0 = __ballot(in0); b1 = __ballot(in1);
                     if ((b0 | b1) == 0) continue;
                 }
@@ -152,23 +174,27 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams 
     if (tid < 128 && qt * BM + tid < p.Nq) p.part_n[(int64_t)split * p.Nqp + qt * BM + tid] = len[tid];
 }
 
+template <bool CARRY>
 __global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* __restrict__ part, const int* __restrict__ part_n, int Nqp,
                                                          int splits, int k, int32_t* __restrict__ idx, float* __restrict__ score,
-                                                         int64_t ldk) {
-    __shared__ uint64_t keys[TOPK_MAX_SPLITS * TOPK_MAX];
-    __shared__ int off[TOPK_MAX_SPLITS + 1];
+                                                         int64_t ldk, uint64_t* carry, int* carry_n) {
+    // CARRY (dae_topk_images): the carry is one more list, list `splits`, and the merged row is written back to it
+    __shared__ uint64_t keys[(TOPK_MAX_SPLITS + (CARRY ? 1 : 0)) * TOPK_MAX];
+    __shared__ int off[TOPK_MAX_SPLITS + 2];
     const int row = blockIdx.x, tid = threadIdx.x;
+    const int lists = splits + (CARRY ? 1 : 0);
     if (tid == 0) {
         off[0] = 0;
         for (int s = 0; s < splits; ++s) off[s + 1] = off[s] + part_n[(int64_t)s * Nqp + row];
+        if constexpr (CARRY) off[lists] = off[splits] + min(max(carry_n[row], 0), k);
     }
     __syncthreads();
-    const int total = off[splits];
-    for (int s = 0; s < splits; ++s) {
-        const uint64_t* L = part + ((int64_t)s * Nqp + row) * k;
+    const int total = off[lists];
+    for (int s = 0; s < lists; ++s) {
+        const uint64_t* L = !CARRY || s < splits ? part + ((int64_t)s * Nqp + row) * k : carry + (int64_t)row * k;
         for (int p = tid; p < off[s + 1] - off[s]; p += 256) keys[off[s] + p] = L[p];
     }
-    __syncthreads();
+    __syncthreads();                                            // the carry is in LDS: its row may be overwritten
     int32_t* oi = idx + (int64_t)row * ldk;
     float* os = score + (int64_t)row * ldk;
     for (int e = tid; e < total; e += 256) {
@@ -176,14 +202,16 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* __restr
         while (e >= off[s + 1]) ++s;
         const uint64_t x = keys[e];
         int rank = e - off[s];
-        for (int t = 0; t < splits; ++t)
+        for (int t = 0; t < lists; ++t)
             if (t != s) rank += keys_above(keys + off[t], off[t + 1] - off[t], x);
         if (rank < k) {
             oi[rank] = pair_key_index(x);
             os[rank] = pair_key_score(x);
+            if constexpr (CARRY) carry[(int64_t)row * k + rank] = x;
         }
     }
     for (int r = total + tid; r < k; r += 256) { oi[r] = -1; os[r] = -__builtin_inff(); }
+    if (CARRY && tid == 0) carry_n[row] = min(total, k);
 }
 
 static int topk_splits(int Nq, int Nc) { return sweep_splits(Nq, Nc, TOPK_SLOTS, TOPK_MAX_SPLITS); }
@@ -233,7 +261,52 @@ static int topk_run(const float* Q, int64_t ldq, int32_t Nq, const float* C, int
     p.part = (uint64_t*)o.rest; p.part_n = (int*)(o.rest + al256((uint64_t)splits * o.Nqp * k * 8));
     p.f = f;
     if (int rc = DAE_SWEEP_LAUNCH_FILTERED(topk_tiles_kernel, f, TOPK_LDS, TOPK_WIN_LDS, o.Nqp / BM * splits, st, p)) return rc;
-    DAE_LAUNCH(topk_merge_kernel, dim3(Nq), dim3(256), 0, st, p.part, p.part_n, p.Nqp, splits, k, idx, score, ldk);
+    DAE_LAUNCH(topk_merge_kernel<false>, dim3(Nq), dim3(256), 0, st, p.part, p.part_n, p.Nqp, splits, k, idx, score, ldk, (uint64_t*)nullptr,
+               (int*)nullptr);
+    DAE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" uint64_t dae_topk_carry_bytes(int32_t Nq, int32_t k) {
+    if (Nq <= 0 || k <= 0) return 0;
+    return al256((uint64_t)pad128(Nq) * (uint64_t)k * 8) + al256((uint64_t)pad128(Nq) * 4);
+}
+
+extern "C" uint64_t dae_topk_images_workspace(int32_t Nq, int32_t Nc, int32_t k) {
+    if (Nq <= 0 || Nc <= 0 || k <= 0) return 0;
+    const uint64_t Nqp = pad128(Nq), s = topk_splits(Nq, Nc);
+    return al256(s * Nqp * (uint64_t)k * 8) + al256(s * Nqp * 4);
+}
+
+extern "C" int dae_topk_images(const float* Qi, int32_t Nq, int32_t row0, const float* Ci, int32_t Nc, int32_t col0, int32_t D, int32_t k,
+                               int32_t exclude_self, const int64_t* excl_indptr, const int32_t* excl_items, void* carry, int32_t* idx,
+                               float* score, int64_t ldk, void* workspace, uint64_t workspace_bytes, void* stream) {
+    RowFilter f = {exclude_self, excl_indptr, excl_items, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    if (int rc = sweep_filter_check("topk_images", f, false)) return rc;
+    DAE_CHECK_ARG(idx && score && carry, "topk_images: idx / score / carry are NULL");
+    DAE_CHECK_ARG(k >= 1 && k <= TOPK_MAX, "topk_images: k must be in 1..%d (got %d)", TOPK_MAX, k);
+    DAE_CHECK_ARG(ldk >= k, "topk_images: ldk (%lld) must be >= k (%d)", (long long)ldk, k);
+    DAE_CHECK_ARG(row0 >= 0 && col0 >= 0 && (int64_t)row0 + Nq <= INT32_MAX && (int64_t)col0 + Nc <= INT32_MAX,
+                  "topk_images: row0 / col0 must not be negative, and the global ids must fit 31 bits");
+    DAE_CHECK_ARG(((uintptr_t)carry % 256) == 0, "topk_images: carry must be 256-byte aligned");
+    SweepOperands o;
+    if (int rc = sweep_prepare_images("topk_images", Qi, Nq, Ci, Nc, D, workspace, workspace_bytes, dae_topk_images_workspace(Nq, Nc, k), o))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int splits = topk_splits(Nq, Nc);
+    TopkParams p;
+    memset(&p, 0, sizeof(p));
+    p.g = o.g;
+    p.Nq = Nq; p.Nc = Nc; p.Nqp = (int)o.Nqp; p.k = k; p.splits = splits;
+    p.ctiles = (int)(o.Ncp / BN);
+    p.part = (uint64_t*)o.rest; p.part_n = (int*)(o.rest + al256((uint64_t)splits * o.Nqp * k * 8));
+    p.f = f;
+    p.row0 = row0; p.col0 = col0;
+    p.carry = (uint64_t*)carry; p.carry_n = (int*)((char*)carry + al256((uint64_t)o.Nqp * k * 8));
+    if (int rc = f.excl_indptr ? sweep_launch<topk_tiles_kernel<true, false, false, true>>(o.Nqp / BM * splits, TOPK_LDS, TOPK_LDS, st, p)
+                               : sweep_launch<topk_tiles_kernel<false, false, false, true>>(o.Nqp / BM * splits, TOPK_LDS, TOPK_LDS, st, p))
+        return rc;
+    DAE_LAUNCH(topk_merge_kernel<true>, dim3(Nq), dim3(256), 0, st, p.part, p.part_n, p.Nqp, splits, k, idx, score, ldk, p.carry, p.carry_n);
     DAE_CHECK_LAUNCH();
     return 0;
 }

@@ -16,6 +16,10 @@ library / a GPU this raises.
 * ``label_similarity_stats`` -- the related-vs-unrelated AUROC and box-plot numbers of ``visualize_pairwise_similarity``
   without the N x N matrix: ``dae_pair_hist`` reduces the score tiles into one histogram per class, and
   ``stats_from_histograms`` (host code) derives the AUROC with a bracket that certifies it, and the quartiles.
+* ``chunk_rows=`` of ``most_similar`` / ``label_similarity_stats`` -- the same results from operands swept a bounded number of rows
+  at a time: a scipy.sparse input stays CSR on the device and its operand images are built chunk by chunk
+  (``dae_sweep_image_csr``, ``dae_topk_images``, ``dae_pair_hist_images``); ``sweep_chunk_rows``, ``sweep_chunk_plan`` and
+  ``label_stats_blocks`` (host code) are the chunk plan.
 * ``user_states`` -- the decaying user model of "Embedding-based News Recommendation for Millions of Users": a decay-weighted
   mean of the embeddings of the articles a user has read (``dae_user_states``); ``recommend`` -- the top-k articles by
   ``user . article`` that the user has not read yet (``most_similar(exclude=...)``, ``dae_topk_similarity_ex``);
@@ -224,6 +228,161 @@ def _workspace(dev, nbytes):
     import torch
     ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
     return ctypes.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256), ws
+
+
+# chunk_rows="auto": the largest chunk whose operand image stays within this many bytes.  NOT measured: 1 GiB is a round figure
+# that keeps two images far below the memory of one device while a chunk still holds thousands of rows at a 50 000-word vocabulary.
+SWEEP_AUTO_IMAGE_BYTES = 1 << 30
+
+
+def sweep_chunk_rows(chunk_rows, n_features):
+    """The rows per chunk of a chunked sweep (``most_similar`` / ``label_similarity_stats`` with ``chunk_rows=``): None stays None
+    (the one-shot route), an integer >= 1 is rounded up to a multiple of 128 (the tile height: a chunk's image has no padding
+    rows inside the operand), and ``"auto"`` is the largest multiple of 128 whose fp32 image of ``n_features`` columns (padded to
+    128) is at most ``SWEEP_AUTO_IMAGE_BYTES``, and at least 128.  Host code."""
+    if chunk_rows is None:
+        return None
+    if isinstance(chunk_rows, str):
+        if chunk_rows != "auto":
+            raise ValueError(f"chunk_rows must be None, a positive integer or 'auto' (got {chunk_rows!r})")
+        return max(SWEEP_AUTO_IMAGE_BYTES // (L.pad(max(int(n_features), 1)) * 4) // L.PAD * L.PAD, L.PAD)
+    c = int(chunk_rows)
+    if c < 1:
+        raise ValueError(f"chunk_rows must be None, a positive integer or 'auto' (got {chunk_rows!r})")
+    return L.pad(c)
+
+
+def sweep_chunk_plan(n_rows, chunk_rows):
+    """The row ranges ``[(start, stop), ...]`` of ``n_rows`` rows in chunks of ``chunk_rows`` (a multiple of 128, from
+    ``sweep_chunk_rows``); the last one may be ragged, and ``chunk_rows >= n_rows`` gives one chunk.  Host code."""
+    n, c = int(n_rows), int(chunk_rows)
+    if c < 1 or c % L.PAD:
+        raise ValueError(f"chunk_rows must be a positive multiple of {L.PAD} (got {chunk_rows})")
+    return [(a, min(a + c, n)) for a in range(0, n, c)]
+
+
+def label_stats_blocks(n_query_chunks, n_corpus_chunks=None):
+    """The blocks ``[(a, b, self_mode), ...]`` a chunked ``label_similarity_stats`` sweeps, in the order their sums are added.
+    Without candidates (``n_corpus_chunks=None``) the pairs are ``j < i`` of one operand: per query chunk ``a`` the blocks
+    ``b < a`` in full (every pair of an earlier chunk lies below the diagonal), then the diagonal block ``(a, a)`` in self mode;
+    the blocks ``b > a`` hold no pair and are skipped.  With candidates every ``(a, b)``.  Host code."""
+    if n_corpus_chunks is None:
+        return [(a, b, b == a) for a in range(int(n_query_chunks)) for b in range(a + 1)]
+    return [(a, b, False) for a in range(int(n_query_chunks)) for b in range(int(n_corpus_chunks))]
+
+
+class _SweepOperand:
+    """One operand of a chunked sweep on the device, in the form it came in: a scipy.sparse matrix as canonical CSR (duplicates
+    summed, column ids ascending), uploaded once -- no dense array of it exists on either side; a CUDA tensor as it is; anything
+    else as a host float32 array whose row slices go up chunk by chunk.  ``image`` writes the normalised operand image of the rows
+    ``[a0, a1)`` (``dae_sweep_image_csr`` / ``dae_sweep_image_dense``).  ``uploaded`` counts the bytes sent to the device."""
+
+    def __init__(self, torch, data, dev):
+        import scipy.sparse as sp
+        self.dev, self.csr, self.X, self.host, self.uploaded = dev, None, None, None, 0
+        if isinstance(data, torch.Tensor):
+            if data.dim() != 2:
+                raise ValueError("Expected 2D array")
+            X = data.to(device=dev, dtype=torch.float32)
+            self.X = X if X.stride(1) == 1 or X.shape[1] <= 1 else X.contiguous()
+            self.shape = (int(X.shape[0]), int(X.shape[1]))
+        elif sp.issparse(data):
+            m = data.tocsr().astype(np.float32)                        # astype copies: the caller's matrix is not touched
+            m.sum_duplicates()
+            m.sort_indices()
+            self.shape = (int(m.shape[0]), int(m.shape[1]))
+            parts = (m.indptr.astype(np.int64), m.indices.astype(np.int32), m.data.astype(np.float32, copy=False))
+            parts = tuple(np.ascontiguousarray(p if p.size else np.zeros(1, dtype=p.dtype)) for p in parts)
+            self.uploaded = sum(p.nbytes for p in parts)
+            self.csr = tuple(torch.from_numpy(p).to(dev) for p in parts)
+        else:
+            self.host = np.asarray(data, dtype=np.float32)
+            if self.host.ndim != 2:
+                raise ValueError("Expected 2D array")
+            self.shape = (int(self.host.shape[0]), int(self.host.shape[1]))
+
+    def image(self, torch, a0, a1, image_p, image_bytes, norm, metric):
+        import ctypes
+        rows, D = a1 - a0, self.shape[1]
+        if self.csr is not None:
+            ip, ix, vl = self.csr
+            L.call("dae_sweep_image_csr", ctypes.c_void_p(ip.data_ptr() + 8 * a0), L.ptr(ix), L.ptr(vl), rows, D, _NORMS[norm],
+                   _METRICS[metric], image_p, image_bytes, L.current_stream())
+            return
+        if self.X is not None:
+            X = self.X[a0:a1]
+        else:
+            X = torch.from_numpy(np.ascontiguousarray(self.host[a0:a1])).to(self.dev)
+            self.uploaded += X.numel() * 4
+        L.call("dae_sweep_image_dense", L.ptr(X), max(int(X.stride(0)), D), rows, D, _NORMS[norm], _METRICS[metric], image_p, image_bytes,
+               L.current_stream())
+
+
+def _chunked_operands(in_df, candidates, norm, metric, device):
+    """The start of a chunked sweep, as ``_sweep_inputs`` is of a one-shot one: ``(lib, dev, Qo, Co, Nq, Nc, D)`` with the operands
+    as ``_SweepOperand`` (``Co`` None: the corpus is ``in_df`` itself)."""
+    import torch
+    assert metric in ["cosine", "linear kernel"]                      # helpers.py:34
+    if norm not in _NORMS:
+        raise ValueError(f"'{norm}' is not a supported norm")         # sklearn.preprocessing.normalize's message
+    lib = L.load()
+    dev = torch.device("cuda" if device is None else device)
+    Qo = _SweepOperand(torch, in_df, dev)
+    Co = None if candidates is None else _SweepOperand(torch, candidates, dev)
+    Nq, D = Qo.shape
+    if Co is not None and Co.shape[1] != D:
+        raise ValueError(f"candidates have {Co.shape[1]} columns, in_df has {D}")
+    Nc = Nq if Co is None else Co.shape[0]
+    if Nq < 1 or Nc < 1 or D < 1:
+        raise ValueError(f"a chunked sweep needs rows, candidates and columns (got {Nq} x {D} against {Nc} candidates)")
+    return lib, dev, Qo, Co, Nq, Nc, D
+
+
+def _most_similar_chunked(in_df, candidates, k, norm, metric, flt, chunk_rows, return_tensor, device):
+    """``most_similar(chunk_rows=...)``: the outer loop walks the query chunks with one image and one carry (each row's running
+    top-k as sorted 64-bit keys), the inner loop the corpus chunks with a second image; ``dae_topk_images`` merges a corpus chunk
+    into the carry.  In self mode the diagonal block reuses the query image."""
+    import ctypes
+    import torch
+    lib, dev, Qo, Co, Nq, Nc, D = _chunked_operands(in_df, candidates, norm, metric, device)
+    k = int(k)
+    c = sweep_chunk_rows(chunk_rows, D)
+    idx = torch.empty((Nq, max(k, 1)), dtype=torch.int32, device=dev)
+    score = torch.empty((Nq, max(k, 1)), dtype=torch.float32, device=dev)
+    xp, xi = flt.lists(Nq, Nc)
+    xp_d = xi_d = None
+    if xp is not None:
+        xp_d = torch.from_numpy(xp).to(dev)
+        xi_d = torch.from_numpy(xi if xi.size else np.zeros(1, dtype=np.int32)).to(dev)
+    cq, cc = min(c, L.pad(Nq)), min(c, L.pad(Nc))
+    qb, cb = int(lib.dae_sweep_image_bytes(cq, D)), int(lib.dae_sweep_image_bytes(cc, D))
+    q_p, q_t = _workspace(dev, qb)
+    c_p, c_t = _workspace(dev, cb)
+    carry_bytes = int(lib.dae_topk_carry_bytes(cq, max(k, 1)))
+    carry = torch.empty(carry_bytes + 256, dtype=torch.uint8, device=dev)
+    carry_p = ctypes.c_void_p(carry.data_ptr() + (-carry.data_ptr()) % 256)
+    q_plan, c_plan = sweep_chunk_plan(Nq, c), sweep_chunk_plan(Nc, c)
+    # a ragged last chunk has fewer query tiles and may get MORE corpus slices than a full one: size the workspace for every block shape
+    ws_bytes = max(int(lib.dae_topk_images_workspace(nq, nc, max(k, 1))) for nq in {q_plan[0][1], q_plan[-1][1] - q_plan[-1][0]}
+                   for nc in {c_plan[0][1], c_plan[-1][1] - c_plan[-1][0]})
+    ws_p, ws = _workspace(dev, ws_bytes)
+    with torch.cuda.device(dev):
+        for q0, q1 in q_plan:
+            Qo.image(torch, q0, q1, q_p, qb, norm, metric)
+            carry.zero_()                                             # all-zero bytes: an empty carry
+            for c0, c1 in c_plan:
+                diag = Co is None and c0 == q0
+                if not diag:
+                    (Qo if Co is None else Co).image(torch, c0, c1, c_p, cb, norm, metric)
+                L.call("dae_topk_images", q_p, q1 - q0, q0, None if diag else c_p, c1 - c0, c0, D, k, 1 if flt.exclude_self else 0,
+                       None if xp_d is None else ctypes.c_void_p(xp_d.data_ptr() + 8 * q0), L.ptr(xi_d), carry_p,
+                       ctypes.c_void_p(idx.data_ptr() + 4 * q0 * idx.stride(0)), ctypes.c_void_p(score.data_ptr() + 4 * q0 * score.stride(0)),
+                       idx.stride(0), ws_p, ws_bytes, L.current_stream())
+    del q_t, c_t, ws
+    idx = idx.long()
+    if return_tensor:
+        return idx, score
+    return idx.cpu().numpy(), score.cpu().numpy()
 
 
 def _csr_lists(lists, what="histories"):
@@ -449,7 +608,7 @@ def candidate_windows(query_times, publish_times, max_age=None):
 
 
 def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candidates=None, *, exclude=None, exclude_shared=None,
-                 window=None, return_tensor=False, device=None):
+                 window=None, chunk_rows=None, return_tensor=False, device=None):
     """The ``k`` most similar rows of ``candidates`` (default: ``in_df`` itself) for every row of ``in_df``, by the scores
     ``pairwise_similarity`` would give (same ``norm`` / ``metric``, same exact-fp32 products), without the N x N matrix:
     ``dae_topk_similarity`` keeps a running top-k per row inside the GEMM's epilogue.
@@ -475,9 +634,20 @@ def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candi
     successive states of one user: one list per USER with a stamp per item (``click_prefix_lists``), and per query row the list
     it reads and its stamp limit (``every_click_rows``); row i skips the items of list ``row_list[i]`` whose stamp is at most
     ``row_limit[i]`` (``normalize_shared_exclusions``, ``dae_topk_similarity_seq``).  The result equals, bit for bit, that of
-    ``exclude`` with those items listed row by row."""
+    ``exclude`` with those items listed row by row.
+
+    ``chunk_rows`` (default None: both operands whole, as dense fp32 images -- each must stay below 4 GiB) sweeps the operands a
+    bounded number of rows at a time: an integer (rounded up to a multiple of 128) or ``"auto"`` (``sweep_chunk_rows``).  A
+    scipy.sparse input then goes to the device once, as CSR, and its images are built chunk by chunk straight from the CSR rows
+    (``dae_sweep_image_csr``); dense inputs are cut into row slices.  Each row's running top-k is carried from one corpus chunk
+    to the next (``dae_topk_images``), and the result equals that of ``chunk_rows=None`` bit for bit.  ``exclude_self`` and
+    ``exclude`` are supported; ``window`` or ``exclude_shared`` with ``chunk_rows`` is a ``ValueError``."""
     import torch
+    if chunk_rows is not None and (window is not None or exclude_shared is not None):
+        raise ValueError("chunk_rows does not go with window= or exclude_shared= (the chunked sweep takes exclude_self and exclude only)")
     flt = _row_filter(in_df, candidates, exclude_self, exclude, exclude_shared, window)
+    if chunk_rows is not None:
+        return _most_similar_chunked(in_df, candidates, k, norm, metric, flt, chunk_rows, return_tensor, device)
     lib, dev, Q, Cm, Nq, Nc, D = _sweep_inputs(in_df, candidates, norm, metric, device)
     k = int(k)
     idx = torch.empty((Nq, max(k, 1)), dtype=torch.int32, device=dev)
@@ -1971,8 +2141,103 @@ def stats_from_histograms(hist_related, hist_unrelated, score_range, *, min_rela
     return res
 
 
+def _label_stats_chunked(in_df, labels, candidates, candidate_labels, norm, metric, bins, chunk_rows, device):
+    """``label_similarity_stats(chunk_rows=...)``: returns ``sweep(lo, hi) -> (out16 as a list, hist uint64 [2 x bins])``, the
+    numbers one ``dae_pair_hist`` call returns, summed over the blocks of ``label_stats_blocks`` (``dae_pair_hist_images``; one
+    query image and one corpus image at a time).  Histograms, counts and ``n_nan`` add as integers, min / max combine, the fp64
+    sums add in block order.  The automatic range of the linear kernel is rebuilt from the largest squared row norm of every
+    chunk image (``dae_sweep_image_norm2_max``; a maximum does not depend on the chunking), with ``dae_pair_hist``'s arithmetic."""
+    import ctypes
+    import math
+    import torch
+    lib, dev, Qo, Co, Nq, Nc, D = _chunked_operands(in_df, candidates, norm, metric, device)
+    lq = _label_ids(labels, Nq)
+    lc = lq if Co is None else _label_ids(candidate_labels, Nc)
+    c = sweep_chunk_rows(chunk_rows, D)
+    cq, cc = min(c, L.pad(Nq)), min(c, L.pad(Nc))
+    qb, cb = int(lib.dae_sweep_image_bytes(cq, D)), int(lib.dae_sweep_image_bytes(cc, D))
+    q_p, q_t = _workspace(dev, qb)
+    c_p, c_t = _workspace(dev, cb)
+    ws_bytes = max(int(lib.dae_pair_hist_images_workspace(cq, cc, bins)), int(lib.dae_sweep_image_norm2_max_workspace()))
+    ws_p, ws = _workspace(dev, ws_bytes)
+    q_plan, c_plan = sweep_chunk_plan(Nq, c), sweep_chunk_plan(Nc, c)
+    blocks = label_stats_blocks(len(q_plan), None if Co is None else len(c_plan))
+    auto = {}
+
+    def norm2_max(op, plan, image_p, image_bytes):
+        best, out = 0.0, ctypes.c_double()
+        for a0, a1 in plan:
+            op.image(torch, a0, a1, image_p, image_bytes, norm, metric)
+            L.call("dae_sweep_image_norm2_max", image_p, a1 - a0, D, ctypes.byref(out), ws_p, ws_bytes, L.current_stream())
+            best = max(best, float(out.value))
+        return best
+
+    def auto_range():
+        if metric == "cosine":
+            return -1.0, 1.0
+        if not auto:
+            mq = norm2_max(Qo, q_plan, q_p, qb)
+            mc = mq if Co is None else norm2_max(Co, c_plan, c_p, cb)
+            M = math.sqrt(mq) * math.sqrt(mc) * (1.0 + 1.0 / 1048576.0)
+            with np.errstate(over="ignore"):
+                Mf = np.float32(M)
+            if float(Mf) < M:
+                Mf = np.nextafter(Mf, np.float32(np.inf))
+            if not (Mf > 0 and np.isfinite(Mf)):
+                Mf = np.float32(1.0)                                      # all-zero rows (every score is 0) / overflowing norms
+            auto["M"] = float(Mf)
+        return -auto["M"], auto["M"]
+
+    def sweep(lo, hi):
+        if lo >= hi:
+            lo, hi = auto_range()
+        total = np.zeros((2, bins), dtype=np.uint64)
+        hist = np.zeros((2, bins), dtype=np.uint64)
+        out = (ctypes.c_double * 16)()
+        nan = float("nan")
+        n, n_nan, sums, mins, maxs, tiles, rng = [0, 0], 0, [0.0, 0.0], [nan, nan], [nan, nan], 0.0, (lo, hi)
+        have = None
+        with torch.cuda.device(dev):
+            for a, b, self_mode in blocks:
+                q0, q1 = q_plan[a]
+                if have != a:
+                    Qo.image(torch, q0, q1, q_p, qb, norm, metric)
+                    have = a
+                if self_mode:
+                    c0, c1 = q0, q1
+                else:
+                    c0, c1 = c_plan[b]
+                    (Qo if Co is None else Co).image(torch, c0, c1, c_p, cb, norm, metric)
+                lqa, lcb = np.ascontiguousarray(lq[q0:q1]), np.ascontiguousarray(lc[c0:c1])
+                L.call("dae_pair_hist_images", q_p, q1 - q0, lqa.ctypes.data_as(ctypes.c_void_p), None if self_mode else c_p, c1 - c0,
+                       lcb.ctypes.data_as(ctypes.c_void_p), D, lo, hi, bins, hist.ctypes.data_as(ctypes.c_void_p),
+                       ctypes.cast(out, ctypes.c_void_p), ws_p, ws_bytes, L.current_stream())
+                v = [float(x) for x in out]
+                total += hist
+                n_nan += int(v[2])
+                tiles += v[12]
+                rng = (v[9], v[10])
+                for cls in range(2):
+                    if v[cls] > 0:
+                        n[cls] += int(v[cls])
+                        sums[cls] += v[3 + cls]
+                        mins[cls] = v[5 + 2 * cls] if mins[cls] != mins[cls] else min(mins[cls], v[5 + 2 * cls])
+                        maxs[cls] = v[6 + 2 * cls] if maxs[cls] != maxs[cls] else max(maxs[cls], v[6 + 2 * cls])
+        v = [nan] * 16
+        v[0], v[1], v[2] = float(n[0]), float(n[1]), float(n_nan)
+        for cls in range(2):
+            if n[cls]:
+                v[3 + cls], v[5 + 2 * cls], v[6 + 2 * cls] = sums[cls], mins[cls], maxs[cls]
+        v[9], v[10], v[11], v[12] = rng[0], rng[1], float(len(blocks)), tiles
+        return v, total
+
+    sweep.keep = (q_t, c_t, ws)
+    return sweep
+
+
 def label_similarity_stats(in_df, labels, norm="", metric="cosine", candidates=None, candidate_labels=None, *, bins=2048,
-                           score_range=None, refine=False, return_histograms=False, save_path=None, title=None, device=None):
+                           score_range=None, refine=False, return_histograms=False, save_path=None, title=None, chunk_rows=None,
+                           device=None):
     """The numbers of ``visualize_pairwise_similarity(labels, pairwise_similarity(in_df, norm, metric))`` without the N x N matrix:
     ``dae_pair_hist`` bins every pair's score (same ``norm`` / ``metric``, same exact-fp32 products as ``similar_pairs``) into one
     histogram per class inside the GEMM's epilogue, and ``stats_from_histograms`` derives the statistics.
@@ -1994,7 +2259,12 @@ def label_similarity_stats(in_df, labels, norm="", metric="cosine", candidates=N
     long row); the first call's bracket is kept under ``first_pass``.  ``return_histograms=True`` adds ``hist_related``,
     ``hist_unrelated`` (uint64) and ``bin_edges`` (float64, bins + 1): enough to draw the ROC curve and the box plot.
     ``save_path`` writes the dict (without the arrays) as JSON with the ``.png`` -> ``.json`` rule of
-    ``visualize_pairwise_similarity``."""
+    ``visualize_pairwise_similarity``.
+
+    ``chunk_rows`` (default None: both operands whole, as dense fp32 images -- each must stay below 4 GiB) as in ``most_similar``:
+    the operands are swept in blocks of that many rows, a scipy.sparse input as CSR (``_label_stats_chunked``).  Histograms,
+    counts, ``n_nan``, ``min``, ``max`` and the score range equal those of ``chunk_rows=None`` exactly; the fp64 score sums are added
+    block by block, so the means agree to rounding (1e-12 relative), not bit for bit."""
     import ctypes
     import json
     import torch
@@ -2010,21 +2280,27 @@ def label_similarity_stats(in_df, labels, norm="", metric="cosine", candidates=N
         lo, hi = float(score_range[0]), float(score_range[1])
         if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
             raise ValueError("score_range must be finite with lo < hi")
-    lib, dev, Q, Cm, Nq, Nc, D = _sweep_inputs(in_df, candidates, norm, metric, device)
-    lq = _label_ids(labels, Nq)
-    lc = None if Cm is None else _label_ids(candidate_labels, Nc)
-    ws_bytes = int(lib.dae_pair_hist_workspace(Nq, Nc, D, bins))
-    ws_p, ws = _workspace(dev, ws_bytes)
+    if chunk_rows is not None:
+        sweep = _label_stats_chunked(in_df, labels, candidates, candidate_labels, norm, metric, bins, chunk_rows, device)
+    else:
+        lib, dev, Q, Cm, Nq, Nc, D = _sweep_inputs(in_df, candidates, norm, metric, device)
+        lq = _label_ids(labels, Nq)
+        lc = None if Cm is None else _label_ids(candidate_labels, Nc)
+        ws_bytes = int(lib.dae_pair_hist_workspace(Nq, Nc, D, bins))
+        ws_p, ws = _workspace(dev, ws_bytes)
+
+        def sweep(lo, hi):
+            hist = np.zeros((2, bins), dtype=np.uint64)
+            out = (ctypes.c_double * 16)()
+            with torch.cuda.device(dev):
+                L.call("dae_pair_hist", L.ptr(Q), Q.stride(0), Nq, lq.ctypes.data_as(ctypes.c_void_p), L.ptr(Cm),
+                       0 if Cm is None else Cm.stride(0), Nc, None if lc is None else lc.ctypes.data_as(ctypes.c_void_p), D, _NORMS[norm],
+                       _METRICS[metric], lo, hi, bins, hist.ctypes.data_as(ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p),
+                       ws_p, ws_bytes, L.current_stream())
+            return [float(x) for x in out], hist
 
     def run(lo, hi):
-        hist = np.zeros((2, bins), dtype=np.uint64)
-        out = (ctypes.c_double * 16)()
-        with torch.cuda.device(dev):
-            L.call("dae_pair_hist", L.ptr(Q), Q.stride(0), Nq, lq.ctypes.data_as(ctypes.c_void_p), L.ptr(Cm),
-                   0 if Cm is None else Cm.stride(0), Nc, None if lc is None else lc.ctypes.data_as(ctypes.c_void_p), D, _NORMS[norm],
-                   _METRICS[metric], lo, hi, bins, hist.ctypes.data_as(ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p),
-                   ws_p, ws_bytes, L.current_stream())
-        v = [float(x) for x in out]
+        v, hist = sweep(lo, hi)
         have_r, have_u = v[0] > 0, v[1] > 0
         st = stats_from_histograms(hist[0], hist[1], (v[9], v[10]),
                                    min_related=v[5] if have_r else None, max_related=v[6] if have_r else None,

@@ -731,6 +731,55 @@ int dae_pair_hist(const float* Q, int64_t ldq, int32_t Nq, const int32_t* labels
                   int32_t bins, uint64_t* hist_host, double* out16_host, void* workspace, uint64_t workspace_bytes,
                   void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Sparse and chunked operands for top-k and label statistics (helpers.most_similar / label_similarity_stats with chunk_rows=).
+ * Every sweep above builds its two normalised, zero-padded fp32 operand images [dae_pad(rows) x dae_pad(D)] inside the call,
+ * from dense fp32 rows, and so needs the whole operand dense and below 4 GiB.  The entries here split that: the caller builds
+ * the image of a CHUNK of rows -- from dense rows or straight from CSR rows -- and sweeps pairs of images; top-k carries each
+ * row's running list from one corpus chunk to the next, the histograms add.  Scores do not depend on the tiling, the top-k
+ * order is total and the counts are integers, so the chunked results equal the one-shot ones bit for bit (the fp64 score sums
+ * of the label statistics are folded in another order).
+ *   dae_sweep_image_bytes(rows, D): the bytes of one image, a multiple of 256.
+ *   dae_sweep_image_dense: the image of X [rows x ldx] by the kernel the plain entries use.  dae_sweep_image_csr: the same image,
+ *   bit for bit, of CSR rows: indptr int64[rows + 1] points at the chunk's first row and holds offsets into indices int32 / values
+ *   fp32 (values NULL: every stored entry is 1); column ids ascending and unique within a row and inside [0, D) (an entry that
+ *   is not is dropped, never written).  norm / metric as dae_pairwise_similarity.  image: 256-byte aligned, image_bytes >=
+ *   dae_sweep_image_bytes(rows, D), below 4 GiB.  Rows past `rows` are zero.
+ *   dae_sweep_image_norm2_max: the largest squared row 2-norm of an image's first `rows` rows in fp64 (host; synchronises).  The
+ *   maximum over chunks is the maximum over the operand, so the automatic linear-kernel range of dae_pair_hist can be rebuilt on
+ *   the host: M = sqrt(max_q) * sqrt(max_c) * (1 + 2^-20), rounded up to fp32 (1 when that is not positive and finite).
+ *   workspace: dae_sweep_image_norm2_max_workspace() bytes, 256-byte aligned.
+ *   dae_topk_images: dae_topk_similarity_ex over two prepared images (Ci == NULL: the corpus is Qi, pass Nc == Nq).  Image row i
+ *   is query row0 + i and image column j is candidate col0 + j: those global ids are the ones in idx, in the self test
+ *   (exclude_self may go with Ci here) and in excl_items; excl_indptr points at the entry of query row0 (offsets into the whole
+ *   excl_items).  carry: dae_topk_carry_bytes(Nq, k) bytes, 256-byte aligned -- each row's k sorted keys, then its count; all-zero
+ *   bytes are an empty carry.  The call merges the carry with this corpus chunk's candidates, writes the carry back and writes
+ *   idx / score from it, so after the last corpus chunk idx / score are those of the one-shot call.  The same k in every call
+ *   on one carry.  A full carry's k-th key is the threshold from the first tile on.  Windows and shared lists are not taken.
+ *   workspace: dae_topk_images_workspace(Nq, Nc, k) bytes -- NOT monotone in Nq (fewer query tiles get more corpus slices): a caller
+ *   that reuses one workspace asks for every block shape it sweeps.
+ *   dae_pair_hist_images: dae_pair_hist over two prepared images (Ci == NULL: self mode, the pairs j < i of Qi) with an explicit
+ *   range lo < hi; hist_host / out16_host as there.  For the strict lower triangle of a chunked operand: self mode on the
+ *   diagonal blocks, Ci = an earlier chunk for the blocks below it.  workspace: dae_pair_hist_images_workspace(Nq, Nc, bins).
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_sweep_image_bytes(int32_t rows, int32_t D);
+int dae_sweep_image_dense(const float* X, int64_t ldx, int32_t rows, int32_t D, int32_t norm, int32_t metric, float* image,
+                          uint64_t image_bytes, void* stream);
+int dae_sweep_image_csr(const int64_t* indptr, const int32_t* indices, const float* values, int32_t rows, int32_t D,
+                        int32_t norm, int32_t metric, float* image, uint64_t image_bytes, void* stream);
+uint64_t dae_sweep_image_norm2_max_workspace(void);
+int dae_sweep_image_norm2_max(const float* image, int32_t rows, int32_t D, double* out_host, void* workspace,
+                              uint64_t workspace_bytes, void* stream);
+uint64_t dae_topk_carry_bytes(int32_t Nq, int32_t k);
+uint64_t dae_topk_images_workspace(int32_t Nq, int32_t Nc, int32_t k);
+int dae_topk_images(const float* Qi, int32_t Nq, int32_t row0, const float* Ci, int32_t Nc, int32_t col0, int32_t D, int32_t k,
+                    int32_t exclude_self, const int64_t* excl_indptr, const int32_t* excl_items, void* carry, int32_t* idx,
+                    float* score, int64_t ldk, void* workspace, uint64_t workspace_bytes, void* stream);
+uint64_t dae_pair_hist_images_workspace(int32_t Nq, int32_t Nc, int32_t bins);
+int dae_pair_hist_images(const float* Qi, int32_t Nq, const int32_t* labels_q_host, const float* Ci, int32_t Nc,
+                         const int32_t* labels_c_host, int32_t D, float lo, float hi, int32_t bins, uint64_t* hist_host,
+                         double* out16_host, void* workspace, uint64_t workspace_bytes, void* stream);
+
 /* Related / unrelated pair statistics of an N x N similarity matrix: the numbers behind
  * helpers.visualize_pairwise_similarity (helpers.py:79-135) -- AUROC of "same label" vs "different label" over the strict
  * lower triangle (labels < 0 are missing and drop their pairs; ties count half, as sklearn's roc_curve + auc do) and the

@@ -97,6 +97,11 @@ def build_parser():
                    help="after training (needs labels): the related-vs-unrelated AUROC, with a bracket that certifies it, and the box-plot "
                         "numbers of the input vectors and of the embeddings, written to similarity_stats_<name>.json (per-class score "
                         "histograms, no N x N matrix: works with --similarity False)")
+    p.add_argument("--sweep_chunk_rows", type=int, default=0,
+                   help="rows per chunk of the sweeps of --top_k and --label_stats: 0 (default) sweeps every operand whole, as a dense fp32 "
+                        "image below 4 GiB; N > 0 sweeps N rows (rounded up to a multiple of 128) at a time and keeps the bag-of-words / "
+                        "tf-idf matrix on the device as CSR (same results; for corpora whose dense image does not fit); -1 picks N so that "
+                        "a chunk's image is at most 1 GiB")
     p.add_argument("--sessions", default="",
                    help="click logs for --recommend: an .npz with `indptr` (int64, users + 1), `items` (train article indices, every user's clicks "
                         "oldest first) and optionally `timestamps` (one per click), or the word `synthetic` (seeded logs in which a user reads "
@@ -220,6 +225,13 @@ def evaluate_similarity(a, trX, vlX, trY, vlY, emb, emb_v, plot_dir=None):
     return rows
 
 
+def sweep_chunk_rows_arg(a):
+    """--sweep_chunk_rows as the ``chunk_rows`` of helpers.most_similar / label_similarity_stats: 0 -> None, -1 -> 'auto'."""
+    n = int(getattr(a, 'sweep_chunk_rows', 0) or 0)
+    assert n >= -1, "--sweep_chunk_rows must be 0, -1 (auto) or a positive row count"
+    return None if n == 0 else 'auto' if n < 0 else n
+
+
 def evaluate_label_stats(a, trX, vlX, trY, vlY, emb, emb_v, plot_dir=None):
     """--label_stats: the four jobs of evaluate_similarity through helpers.label_similarity_stats (dae_pair_hist: per-class score
     histograms in the GEMM's epilogue, no N x N matrix).  Prints the same per-job line with the AUROC's bracket appended and, with
@@ -236,7 +248,7 @@ def evaluate_label_stats(a, trX, vlX, trY, vlY, emb, emb_v, plot_dir=None):
     rows = []
     for name, M, metric, y, stem in jobs:
         ids = np.unique(np.asarray(y), return_inverse=True)[1]
-        st = helpers.label_similarity_stats(M, ids, metric=metric, title=name,
+        st = helpers.label_similarity_stats(M, ids, metric=metric, title=name, chunk_rows=sweep_chunk_rows_arg(a),
                                             save_path=None if plot_dir is None else plot_dir + 'similarity_stats_' + stem + '.png')
         print('  %-26s %5d x %-5d  AUROC %.4f  median sim related %.4f  unrelated %.4f  (%d / %d pairs)  AUROC in [%.6f, %.6f]' % (
             name, M.shape[0], M.shape[0], st['auroc'], st['related']['median'], st['unrelated']['median'], st['n_related'],
@@ -260,12 +272,12 @@ def evaluate_top_k(a, trX, vlX, trY, vlY, emb, emb_v, data_dir):
         sets.append(('validate', vlX, emb_v, vlY, trX, emb, trY, 'article_encoded_validate_top%d.npz' % K))
     out = {}
     for name, X, E, y, Xc, Ec, yc, fname in sets:
-        idx, score = helpers.most_similar(E, k=K, candidates=Ec)
+        idx, score = helpers.most_similar(E, k=K, candidates=Ec, chunk_rows=sweep_chunk_rows_arg(a))
         np.savez(data_dir + fname, indices=idx, scores=score)
         out[name] = idx
         print('  %-9s %5d queries -> %s' % (name, idx.shape[0], fname))
         if y is not None:
-            idx_in, _ = helpers.most_similar(X, k=K, metric=metric_in, candidates=Xc)
+            idx_in, _ = helpers.most_similar(X, k=K, metric=metric_in, candidates=Xc, chunk_rows=sweep_chunk_rows_arg(a))
             p_in, n = helpers.label_precision_at_k(idx_in, y, yc)
             p_emb, _ = helpers.label_precision_at_k(idx, y, yc)
             print('  precision@%d %-9s input vectors %.4f  embedding %.4f  (%d queries)' % (K, name, p_in, p_emb, n))
