@@ -24,6 +24,9 @@ library / a GPU this raises.
   mean of the embeddings of the articles a user has read (``dae_user_states``); ``recommend`` -- the top-k articles by
   ``user . article`` that the user has not read yet (``most_similar(exclude=...)``, ``dae_topk_similarity_ex``);
   ``next_click_metrics`` (host code) scores such a list against one held-out click per user.
+* ``dedup_lists`` -- the pipeline's last stage: walk each recommendation list best first and skip an article whose similarity to
+  one already selected reaches a threshold (``dae_dedup_lists``: one 128 x 128 score tile per list); ``recommend`` /
+  ``most_similar`` with ``dedup_threshold=`` retrieve a larger pool and run it.
 * ``target_ranks`` / ``recommend_ranks`` -- the position of the held-out article among ALL candidates, without the users x
   articles matrix (``dae_rank_similarity``); ``rank_metrics`` (host code) turns the ranks into AUC, mean / median rank,
   untruncated MRR / nDCG and hit / MRR / nDCG at any number of cut-offs from one pass.
@@ -608,7 +611,8 @@ def candidate_windows(query_times, publish_times, max_age=None):
 
 
 def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candidates=None, *, exclude=None, exclude_shared=None,
-                 window=None, chunk_rows=None, return_tensor=False, device=None):
+                 window=None, chunk_rows=None, return_tensor=False, device=None, dedup_threshold=None, dedup_pool=None, dedup_norm="",
+                 dedup_metric="cosine"):
     """The ``k`` most similar rows of ``candidates`` (default: ``in_df`` itself) for every row of ``in_df``, by the scores
     ``pairwise_similarity`` would give (same ``norm`` / ``metric``, same exact-fp32 products), without the N x N matrix:
     ``dae_topk_similarity`` keeps a running top-k per row inside the GEMM's epilogue.
@@ -641,10 +645,29 @@ def most_similar(in_df, k=10, norm="", metric="cosine", exclude_self=None, candi
     scipy.sparse input then goes to the device once, as CSR, and its images are built chunk by chunk straight from the CSR rows
     (``dae_sweep_image_csr``); dense inputs are cut into row slices.  Each row's running top-k is carried from one corpus chunk
     to the next (``dae_topk_images``), and the result equals that of ``chunk_rows=None`` bit for bit.  ``exclude_self`` and
-    ``exclude`` are supported; ``window`` or ``exclude_shared`` with ``chunk_rows`` is a ``ValueError``."""
+    ``exclude`` are supported; ``window`` or ``exclude_shared`` with ``chunk_rows`` is a ``ValueError``.
+
+    ``dedup_threshold`` (default None: the call is what it was) de-duplicates every row: ``dedup_pool`` candidates (default
+    ``min(128, 4 * k)``; ``k <= dedup_pool <= 128``) are retrieved with every filter above, and ``dedup_lists`` walks them down
+    to ``k`` -- a candidate is skipped when its ``dedup_norm`` / ``dedup_metric`` similarity (default cosine) to a candidate
+    already selected reaches the threshold.  The scores returned are the retrieval's; a row whose pool runs out ends in -1 / -inf.
+    ``chunk_rows`` with ``dedup_threshold`` is a ``ValueError``."""
     import torch
     if chunk_rows is not None and (window is not None or exclude_shared is not None):
         raise ValueError("chunk_rows does not go with window= or exclude_shared= (the chunked sweep takes exclude_self and exclude only)")
+    if dedup_threshold is not None:
+        k = int(k)
+        pool = min(128, 4 * k) if dedup_pool is None else int(dedup_pool)
+        if chunk_rows is not None:
+            raise ValueError("chunk_rows does not go with dedup_threshold=")
+        if pool < k or pool > 128:
+            raise ValueError(f"dedup_pool must be in k..128 = {k}..128 (got {pool})")
+        dev = torch.device("cuda" if device is None else device)
+        corpus = _device_matrix(torch, in_df if candidates is None else candidates, dev)      # once, for both calls
+        idx, score = most_similar(corpus if candidates is None else in_df, pool, norm, metric, exclude_self, None if candidates is None else corpus,
+                                  exclude=exclude, exclude_shared=exclude_shared, window=window, return_tensor=True, device=device)
+        return dedup_lists(idx, corpus, k, dedup_threshold, scores=score, norm=dedup_norm, metric=dedup_metric, return_tensor=return_tensor,
+                           device=device)
     flt = _row_filter(in_df, candidates, exclude_self, exclude, exclude_shared, window)
     if chunk_rows is not None:
         return _most_similar_chunked(in_df, candidates, k, norm, metric, flt, chunk_rows, return_tensor, device)
@@ -1349,17 +1372,91 @@ def fit_gru_user_model(histories, embeddings, *, epochs=5, batch_users=256, n_ne
     return GRUUserModel(*final, history=np.asarray(history, dtype=np.float64), validation=scored if validation is not None else None)
 
 
+def dedup_lists(indices, embeddings, k, threshold, *, scores=None, norm="", metric="cosine", return_counts=False, return_tensor=False,
+                device=None):
+    """Greedy de-duplication of recommendation lists on the device (``dae_dedup_lists``).  ``indices`` ``[Nr x L]`` (ndarray or
+    CUDA tensor, ``L <= 128``) holds per row candidate rows of ``embeddings``, best first, as ``most_similar`` returns them.
+    Each row is walked front to back: a candidate is kept iff no candidate kept before it scores ``>= threshold`` against it,
+    by the score ``pairwise_similarity(embeddings, norm, metric)`` gives the two (same normalisation, same exact-fp32
+    products); the walk stops after ``k`` kept (``1 <= k <= L``).  Entries < 0 or past the last row of ``embeddings`` are
+    skipped.  An index that occurs twice in a row is, under cosine, a duplicate of itself.
+
+    Returns ``(indices int64 [Nr x k], scores)``: the kept candidates in the row's order, -1 where fewer than ``k`` survive;
+    ``scores`` (``[Nr x L]``, e.g. the relevance ``most_similar`` returned) are gathered alongside as float32 ``[Nr x k]``
+    with a tail of -inf, or None when not given.  With ``return_counts`` a third item ``(n_kept, n_dup_pairs_topk)`` (int64
+    ``[Nr]`` each): how many were kept, and how many pairs among the first ``min(k, L)`` candidates reach the threshold -- the
+    duplicate pairs the plain top-k would have shown.  ndarrays, or CUDA tensors with ``return_tensor=True``."""
+    import torch
+    assert metric in ["cosine", "linear kernel"]                      # helpers.py:34
+    if norm not in _NORMS:
+        raise ValueError(f"'{norm}' is not a supported norm")
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("threshold is NaN")
+    shape = tuple(indices.shape) if hasattr(indices, "shape") else np.asarray(indices).shape
+    if len(shape) != 2:
+        raise ValueError("indices must be [n_rows x L]")
+    Nr, Ll = int(shape[0]), int(shape[1])
+    k = int(k)
+    if Ll > 128:
+        raise ValueError(f"a list holds at most 128 candidates (got {Ll})")
+    if k < 1 or k > Ll:
+        raise ValueError(f"k must be in 1..L = 1..{Ll} (got {k})")
+    if scores is not None and tuple(scores.shape) != (Nr, Ll):
+        raise ValueError(f"scores must have the shape of indices {(Nr, Ll)} (got {tuple(scores.shape)})")
+    lib = L.load()
+    dev = torch.device("cuda" if device is None else device)
+    E = _device_matrix(torch, embeddings, dev)
+    Na, D = int(E.shape[0]), int(E.shape[1])
+    if isinstance(indices, torch.Tensor):
+        lists = indices.to(device=dev)
+    else:
+        lists = torch.as_tensor(np.ascontiguousarray(np.asarray(indices))).to(dev)
+    big = torch.iinfo(torch.int32).max
+    lists = lists.clamp(min=-1, max=big).to(torch.int32).contiguous()           # (an index beyond int32 is beyond every corpus)
+    out_idx = torch.empty((Nr, k), dtype=torch.int32, device=dev)
+    out_pos = torch.empty((Nr, k), dtype=torch.int32, device=dev)
+    counts = torch.empty((Nr, 2), dtype=torch.int32, device=dev)
+    if Nr > 0:
+        if Na == 0:
+            raise ValueError("embeddings has no rows")
+        ws_bytes = int(lib.dae_dedup_lists_workspace(Nr, Na, D, Ll))
+        ws_p, ws = _workspace(dev, ws_bytes)
+        with torch.cuda.device(dev):
+            L.call("dae_dedup_lists", L.ptr(E), E.stride(0), Na, D, _NORMS[norm], _METRICS[metric], L.ptr(lists), lists.stride(0), Nr, Ll, k,
+                   threshold, L.ptr(out_idx), L.ptr(out_pos), out_idx.stride(0), L.ptr(counts), ws_p, ws_bytes, L.current_stream())
+    out_s = None
+    if scores is not None:
+        s = scores.to(device=dev, dtype=torch.float32) if isinstance(scores, torch.Tensor) else \
+            torch.as_tensor(np.asarray(scores, dtype=np.float32)).to(dev)
+        pos = out_pos.long()
+        out_s = torch.gather(s, 1, pos.clamp(min=0)).masked_fill(pos < 0, float("-inf"))
+    out = (out_idx.long(), out_s)
+    if return_counts:
+        out = out + ((counts[:, 0].long(), counts[:, 1].long()),)
+    if return_tensor:
+        return out
+    host = lambda t: None if t is None else t.cpu().numpy()
+    return (host(out[0]), host(out[1])) + (((host(out[2][0]), host(out[2][1])),) if return_counts else ())
+
+
 def recommend(user_vectors, embeddings, k=10, seen=None, norm="", metric="linear kernel", *, window=None, return_tensor=False,
-              device=None):
+              device=None, dedup_threshold=None, dedup_pool=None, dedup_norm="", dedup_metric="cosine"):
     """The ``k`` articles (rows of ``embeddings``) with the largest relevance to every user vector (e.g. from ``user_states``)
     among those the user has not read: ``most_similar(user_vectors, candidates=embeddings, exclude=seen)``.  ``seen``: per
     user the indices already read (a list of sequences or an ``(indptr, items)`` tuple -- a history as given to ``user_states``
     will do; order and repeats do not matter), or None.  The default ``metric`` is the paper's relevance, the inner product;
     ``'cosine'`` and ``norm`` are those of ``most_similar``, and so is ``window``: per user the range of articles that may be
     shown at all (``candidate_windows``: those published by the time of the click, and not too long before).  Returns
-    ``(indices, scores)`` as ``most_similar`` does."""
+    ``(indices, scores)`` as ``most_similar`` does.
+
+    ``dedup_threshold`` (default None: no de-duplication, the call is what it was) drops near-duplicates from every list:
+    ``dedup_pool`` unseen, in-window candidates (default ``min(128, 4 * k)``) are retrieved and ``dedup_lists`` walks them down
+    to ``k``, skipping an article whose ``dedup_norm`` / ``dedup_metric`` similarity (default cosine) to one already selected
+    reaches the threshold.  ``dedup_pool < k`` or ``> 128`` is a ``ValueError``."""
     return most_similar(user_vectors, k=k, norm=norm, metric=metric, candidates=embeddings, exclude=seen, window=window,
-                        return_tensor=return_tensor, device=device)
+                        return_tensor=return_tensor, device=device, dedup_threshold=dedup_threshold, dedup_pool=dedup_pool,
+                        dedup_norm=dedup_norm, dedup_metric=dedup_metric)
 
 
 def next_click_metrics(indices, targets):

@@ -702,6 +702,31 @@ int dae_threshold_pairs(const float* Q, int64_t ldq, int32_t Nq, const float* C,
                         uint64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------------------------------------------------
+ * De-duplication of recommendation lists: the greedy "skip an article too similar to one already selected" pass over every
+ * row of a [Nr x L] table of candidate article indices, best first (helpers.dedup_lists; recommend(dedup_threshold=)).
+ *   E, lde, Na, D, norm, metric: the article vectors, exactly as the corpus of dae_pairwise_similarity, and the same scores:
+ *   s(p, q) of a row is the score dae_pairwise_similarity gives row lists[p] against column lists[q] (the same normalised
+ *   image, the same exact-fp32 products over the whole K range -- a score does not depend on where its tile lies).
+ *   lists int32 [Nr x ldl], L <= 128 entries per row.  Walking a row front to back, the entry at position p is kept iff no entry
+ *   kept at a position q < p has s(p, q) >= threshold (a pair AT the threshold is a duplicate, as in dae_threshold_pairs); the
+ *   walk stops after k kept, 1 <= k <= L.  Entries < 0 (the -1 tail of a short row) or >= Na are skipped and never kept.  An
+ *   index that occurs twice is compared like any other pair (under cosine: a duplicate of itself).  A NaN score never
+ *   qualifies; a NaN threshold is an argument error.
+ *   out_idx / out_pos int32 [Nr x ldo], ldo >= k: the kept articles and their positions in the input row, in the row's order;
+ *   -1 where fewer than k survive.  counts int32 [Nr x 2]: [2 i] the number kept; [2 i + 1] the number of pairs
+ *   q < p < min(k, L) of valid entries with s(p, q) >= threshold -- the duplicate pairs the plain top-k would have shown.
+ *   Deterministic: bit-identical run to run, independent of the grid and of the chunking below.
+ *   workspace: 256-byte aligned.  It holds the corpus image (below 4 GiB) and the gathered rows of a chunk of lists
+ *   (128 x dae_pad(D) x 4 bytes each); dae_dedup_lists_workspace(Nr, Na, D, L) asks for min(Nr, R0) lists, R0 the number whose
+ *   rows fill 256 MiB.  Any workspace that holds the image and one list -- dae_dedup_lists_workspace(1, Na, D, L) -- is
+ *   accepted: the rows are walked in chunks of as many lists as fit, with the same result.
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_dedup_lists_workspace(int32_t Nr, int32_t Na, int32_t D, int32_t L);
+int dae_dedup_lists(const float* E, int64_t lde, int32_t Na, int32_t D, int32_t norm, int32_t metric, const int32_t* lists,
+                    int64_t ldl, int32_t Nr, int32_t L, int32_t k, float threshold, int32_t* out_idx, int32_t* out_pos,
+                    int64_t ldo, int32_t* counts, void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
  * Label statistics without an N x N matrix: the per-class score histograms of all row pairs (helpers.label_similarity_stats).
  *   Q, ldq, Nq, C, ldc, Nc, D, norm, metric: exactly as dae_threshold_pairs, and the same scores.  labels_q_host int32[Nq] and,
  *   with C, labels_c_host int32[Nc] on the HOST (with C == NULL the corpus and its labels are Q's; labels_c_host is ignored).

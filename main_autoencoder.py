@@ -17,6 +17,7 @@ examples:
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rank_metrics --max_age 48 --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --fit_user_model --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --every_click --similarity False
+  python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rec_dedup 0.9 --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --every_click --user_model gru --fit_gru --gru_validation 0.2 --similarity False
 """
 import argparse
@@ -110,6 +111,14 @@ def build_parser():
                    help="K > 0 (needs --sessions): after training, hold out every user's last click, build decayed user states from the rest "
                         "on the train embeddings, recommend K unseen articles per user to article_encoded_recommend{K}.npz, and print hit@K / "
                         "MRR / nDCG beside a most-clicked-unseen popularity baseline (no users x articles matrix: works with --similarity False)")
+    p.add_argument("--rec_dedup", type=float, default=None,
+                   help="T (only with --recommend K): ALSO de-duplicated lists -- per user --rec_dedup_pool unseen candidates are "
+                        "retrieved and walked best first, skipping an article whose cosine similarity to one already selected is at "
+                        "least T (helpers.recommend(dedup_threshold=T)); prints hit@K / MRR / nDCG of those lists and the mean number of "
+                        "duplicate pairs per list before and after, and saves article_encoded_recommend{K}_dedup.npz.  The other "
+                        "output and files stay what they are")
+    p.add_argument("--rec_dedup_pool", type=int, default=0,
+                   help="candidates per user that --rec_dedup T starts from, K..128 (0, the default: min(128, 4 K))")
     p.add_argument("--rank_metrics", default=False, **b,
                    help="with --recommend K: also the rank of every held-out click among ALL unseen articles (no users x articles matrix), "
                         "saved to article_encoded_ranks.npz, and AUC, full MRR, mean / median rank and hit@{1, 10, 100} per model")
@@ -164,6 +173,9 @@ def validate(a):
     assert a.recommend == 0 or a.sessions != '', "--recommend needs --sessions"
     assert 0. <= a.session_decay <= 1.
     assert not a.rank_metrics or a.recommend > 0, "--rank_metrics needs --recommend K"
+    assert a.rec_dedup is None or a.recommend > 0, "--rec_dedup needs --recommend K"
+    assert a.rec_dedup_pool == 0 or a.rec_dedup is not None, "--rec_dedup_pool needs --rec_dedup T"
+    assert a.rec_dedup_pool == 0 or a.recommend <= a.rec_dedup_pool <= 128, "--rec_dedup_pool is a number in K..128"
     assert not a.fit_user_model or (a.sessions != '' and a.recommend > 0), "--fit_user_model needs --sessions S --recommend K"
     assert a.user_model == 'decay' or (a.sessions != '' and a.recommend > 0 and (a.gru_weights != '' or a.fit_gru)), \
         "--user_model gru needs --sessions S --recommend K and --gru_weights PATH or --fit_gru"
@@ -361,6 +373,8 @@ def evaluate_recommend(a, trY, emb, data_dir):
     print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'decayed user state', m['hit'], m['mrr'], m['ndcg']))
     print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'most clicked unseen', b['hit'], b['mrr'], b['ndcg']))
     print('calculate recommend %d done' % K)
+    if a.rec_dedup is not None:
+        evaluate_recommend_dedup(a, states, emb, hist, targets, data_dir)
     models = {}
     if a.rank_metrics:
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir)
@@ -371,6 +385,31 @@ def evaluate_recommend(a, trY, emb, data_dir):
     if a.every_click:
         evaluate_every_click(a, emb, (indptr, items), t, None, models, data_dir)
     return idx, score, targets
+
+
+def evaluate_recommend_dedup(a, states, emb, hist, targets, data_dir, window=None):
+    """--rec_dedup T: the lists of evaluate_recommend once more with the pipeline's last stage, near-duplicates dropped
+    (helpers.recommend(dedup_threshold=T): --rec_dedup_pool candidates per user, walked best first down to K; cosine similarity of
+    the embeddings).  Prints hit@K / MRR@K / nDCG@K of those lists and the mean number of duplicate pairs per list before -- among
+    the plain top-K -- and after: the de-duplicated lists handed to helpers.dedup_lists again, which must find none.  Saves
+    ``indices`` / ``scores`` / ``targets`` / ``n_kept`` / ``dup_pairs_before`` to article_encoded_recommend{K}[_window]_dedup.npz."""
+    from dae_rnn_news_recommendation_amd import helpers
+    K, T = a.recommend, a.rec_dedup
+    pool = a.rec_dedup_pool if a.rec_dedup_pool > 0 else min(128, 4 * K)
+    name = 'article_encoded_recommend%d%s_dedup.npz' % (K, '' if window is None else '_window')
+    print('calculate recommend %d dedup %g' % (K, T))
+    cand, cand_score = helpers.recommend(states, emb, k=pool, seen=hist, window=window, return_tensor=True)
+    idx, score, (n_kept, before) = helpers.dedup_lists(cand, emb, K, T, scores=cand_score, return_counts=True)
+    _, _, (_, after) = helpers.dedup_lists(idx, emb, K, T, return_counts=True)
+    np.savez(data_dir + name, indices=idx, scores=score, targets=targets, n_kept=n_kept, dup_pairs_before=before)
+    m = helpers.next_click_metrics(idx, targets)
+    print('  pool %d, cosine >= %g: %.2f kept per list -> %s' % (pool, T, float(n_kept.mean()) if n_kept.size else 0.0, name))
+    print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'dedup user state', m['hit'], m['mrr'], m['ndcg']))
+    print('  duplicate pairs per list: before %.4f  after %.4f' % (float(before.mean()) if before.size else 0.0,
+                                                                  float(after.mean()) if after.size else 0.0))
+    assert int(after.sum()) == 0, "a de-duplicated list still holds a duplicate pair"
+    print('calculate recommend %d dedup done' % K)
+    return idx, score
 
 
 def evaluate_recommend_window(a, trY, emb, data_dir):
@@ -405,6 +444,8 @@ def evaluate_recommend_window(a, trY, emb, data_dir):
     print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'decayed user state', m['hit'], m['mrr'], m['ndcg']))
     print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'most clicked unseen', b['hit'], b['mrr'], b['ndcg']))
     print('calculate recommend %d done' % K)
+    if a.rec_dedup is not None:
+        evaluate_recommend_dedup(a, states, emb, hist, targets, data_dir, window=window)
     models = {}
     if a.rank_metrics:
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir, window=window, max_age=a.max_age)
