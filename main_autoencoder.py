@@ -502,8 +502,8 @@ def evaluate_gru_user_model(a, emb, hist, targets, n, data_dir, window=None, mod
         seed = a.seed if a.seed >= 0 else 1234
         if a.gru_validation > 0:
             held = np.random.default_rng(seed).random(hist[0].size - 1) < a.gru_validation
-            val = helpers._permute_csr(hist[0], hist[1], np.flatnonzero(held))
-            model = helpers.fit_gru_user_model(helpers._permute_csr(hist[0], hist[1], np.flatnonzero(~held)), emb, epochs=a.gru_epochs,
+            val = helpers.permute_histories(hist[0], hist[1], np.flatnonzero(held))
+            model = helpers.fit_gru_user_model(helpers.permute_histories(hist[0], hist[1], np.flatnonzero(~held)), emb, epochs=a.gru_epochs,
                                                seed=seed, init=model, validation=val)
         else:
             model = helpers.fit_gru_user_model(hist, emb, epochs=a.gru_epochs, seed=seed, init=model)

@@ -40,8 +40,8 @@ def materialise(np, helpers, lists, row_list, row_limit):
     counts = np.zeros(n_rows, np.int64)
     parts = []
     lim = row_limit.astype(np.int64)
-    for a, b in helpers._shared_row_chunks(np.diff(lp)[row_list]):
-        rows, places = helpers._shared_pairs(lp, row_list, a, b)
+    for a, b in helpers.shared_row_chunks(np.diff(lp)[row_list]):
+        rows, places = helpers.shared_pairs(lp, row_list, a, b)
         keep = ls[places] <= lim[rows]
         counts[a:b] = np.bincount(rows[keep] - a, minlength=b - a)
         parts.append(li[places[keep]])                                          # ascending within a row, as the shared list is

@@ -48,7 +48,7 @@ def image_line(torch, L, helpers, m, rows):
     row_normalize_kernel (cosine, no norm; HIP events around 5 launches each), and the bytes of the image they write."""
     lib = L.load()
     F = m.shape[1]
-    op = helpers._SweepOperand(torch, m[:rows], torch.device("cuda"))
+    op = helpers.SweepOperand(torch, m[:rows], torch.device("cuda"))
     X = torch.from_numpy(m[:rows].toarray()).cuda()
     nb = int(lib.dae_sweep_image_bytes(rows, F))
     img = torch.empty(nb, dtype=torch.uint8, device="cuda")

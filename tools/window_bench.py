@@ -84,7 +84,7 @@ def main(argv=None):
     U = torch.randn((M, H), device="cuda", generator=g)                     # users in random order
     xp, xi = helpers.normalize_exclusions((indptr, items), M, Na)
     perm = np.lexsort((hi, lo))                                             # the helpers' order: stable by (lo, hi)
-    xp_s, xi_s = helpers._permute_csr(xp, xi, perm)
+    xp_s, xi_s = helpers.permute_histories(xp, xi, perm)
     dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()        # noqa: E731
     xp_d, xi_d, xp_sd, xi_sd = dev(xp), dev(xi), dev(xp_s), dev(xi_s)
     perm_d = dev(perm)
