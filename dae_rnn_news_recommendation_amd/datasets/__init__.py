@@ -1,2 +1,3 @@
-"""Host-side mirror of the one function of the reference's ``datasets`` package the explicit-triplet path needs."""
-from .articles import similar_articles  # noqa: F401
+"""Mirror of the functions of the reference's ``datasets`` package the training paths need: ``similar_articles`` (host code, the
+explicit-triplet path) and ``tfidf_transform`` (the count matrix to tf-idf, on the device)."""
+from .articles import similar_articles, tfidf_transform  # noqa: F401

@@ -1,7 +1,9 @@
 """``similar_articles`` -- reference ``datasets/articles.py:83-128``: give every article a positive (another article of
 the same category) and a negative (an article of another category) for the explicit-triplet trainer
 (``main_autoencoder_triplet.py:44``).  Host code (pandas + NumPy), same arguments, column names, RNG consumption and
-quirks; the parquet / jieba / CountVectorizer parts of that module are out of scope.
+quirks.  ``tfidf_transform`` -- reference ``datasets/articles.py:160-174``: fit a TfidfTransformer on a count matrix and return it
+with the transformed matrix; here the transformer is ``helpers.TfidfTransformer`` and the work runs on the device.  The parquet /
+jieba tokenising parts of that module are out of scope.
 
 Semantics kept from the reference:
   * categories are visited in ``value_counts()`` order, only those with ``min_cate <= count <= max_cate``;
@@ -14,6 +16,15 @@ Semantics kept from the reference:
 from __future__ import annotations
 
 import numpy as np
+
+
+def tfidf_transform(in_df, **param_tfidf_transformer):
+    """``(transformer, X)``: a ``helpers.TfidfTransformer(**param_tfidf_transformer)`` (norm, use_idf, smooth_idf, sublinear_tf)
+    fitted on the count matrix ``in_df`` (scipy sparse, or a device CSR dict) and its tf-idf matrix as scipy CSR."""
+    from ..helpers import TfidfTransformer
+    tfidf_transformer = TfidfTransformer(**param_tfidf_transformer)
+    X = tfidf_transformer.fit_transform(in_df)
+    return tfidf_transformer, X
 
 
 def similar_articles(out_df, id_colname='article_id', cate_colname='main_category_id', min_cate=2, max_cate=None):

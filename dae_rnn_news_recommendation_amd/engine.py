@@ -93,7 +93,10 @@ class Engine:
 
     # ------------------------------------------------------------------ data
     def upload_csr(self, m):
-        """Make a scipy CSR matrix resident in HBM (canonical form: sorted, no duplicates)."""
+        """Make a scipy CSR matrix resident in HBM (canonical form: sorted, no duplicates).  A device CSR dict (the keys of
+        ``to_device_csr``; ``values`` None or all ones: a binary matrix) is bound where it is, without a round trip."""
+        if isinstance(m, dict):
+            return self._upload_device_csr(m)
         from scipy import sparse
         m = sparse.csr_matrix(m)
         if not m.has_canonical_format:
@@ -107,6 +110,22 @@ class Engine:
             values=None if binary else torch.from_numpy(m.data.astype(np.float32)).to(dev),
             n_rows=m.shape[0], nnz=int(m.nnz))
         self._max_row_nnz = int(np.diff(m.indptr).max()) if m.shape[0] else 0
+        self._sp = None
+        self.dense = None
+        self._bind()
+        return self.csr
+
+    def _upload_device_csr(self, d):
+        """upload_csr of a device CSR dict: the tensors are bound as they are (they must be canonical and on this engine's device)."""
+        n_rows, nnz = int(d["n_rows"]), int(d["nnz"])
+        ip, ix, vl = d["indptr"], d["indices"], d.get("values")
+        assert d.get("n_cols", self.F) == self.F, (d.get("n_cols"), self.F)
+        assert ip.dtype == torch.int64 and ix.dtype == torch.int32 and (vl is None or vl.dtype == torch.float32), "int64 / int32 / float32"
+        assert all(t is None or (t.device == self.device and t.is_contiguous()) for t in (ip, ix, vl)), "contiguous tensors on the engine's device"
+        assert ip.numel() == n_rows + 1 and ix.numel() >= nnz and (vl is None or vl.numel() >= nnz), (ip.numel(), ix.numel(), n_rows, nnz)
+        binary = bool(vl is None or nnz == 0 or bool((vl[:nnz] == 1).all()))
+        self.csr = dict(indptr=ip, indices=ix, values=None if binary else vl, n_rows=n_rows, nnz=nnz)
+        self._max_row_nnz = int((ip[1:] - ip[:-1]).max()) if n_rows else 0
         self._sp = None
         self.dense = None
         self._bind()
@@ -133,7 +152,8 @@ class Engine:
             m = m.copy(); m.sum_duplicates(); m.sort_indices()
         return dict(indptr=torch.from_numpy(m.indptr.astype(np.int64)).to(device),
                     indices=torch.from_numpy(m.indices.astype(np.int32)).to(device),
-                    values=torch.from_numpy(m.data.astype(np.float32)).to(device), n_rows=m.shape[0], nnz=int(m.nnz))
+                    values=torch.from_numpy(m.data.astype(np.float32)).to(device), n_rows=m.shape[0], nnz=int(m.nnz),
+                    n_cols=m.shape[1])
 
     def _bind(self):
         b = L.dae_buffers()

@@ -19,6 +19,9 @@ is importable from here; the code lives by subject:
   (``popularity_recommend``, ``popularity_ranks``), and the every-click protocol (``click_prefix_lists``, ``every_click_rows``,
   ``recommend_every_click``, ``recommend_ranks_every_click``, ``evaluate_every_click``, ``rank_metrics_by_position``,
   ``popularity_ranks_every_click``).
+* ``vectorize`` -- the stage in front of training (main_autoencoder.py:206-240) on a raw count matrix that stays on the device as
+  CSR: ``column_stats`` (df and tf per column), ``limit_features`` / ``limit_features_columns`` / ``select_columns``
+  (``CountVectorizer._limit_features``), ``TfidfTransformer`` (sklearn's, fitted on train, applied to validation), ``binarize``.
 * ``_device`` -- what every device call starts and ends with, once: device and library, the ``norm`` / ``metric`` check, the
   matrix and history intakes, uploads, workspaces, the result tail.
 
@@ -37,3 +40,5 @@ from .sweeps import (SWEEP_AUTO_IMAGE_BYTES, SweepOperand, candidate_windows, de
                      shared_pairs, shared_row_chunks, similar_pairs, sweep_chunk_plan, sweep_chunk_rows, target_ranks)
 from .user_models import (GRUUserModel, UserModel, decay_factor_derivatives, decay_factors, fit_gru_user_model, fit_user_model,
                           gru_pair_loss, gru_schedule, gru_user_states, sample_negatives, trim_histories, user_pair_loss, user_states)
+from .vectorize import (TfidfTransformer, binarize, column_stats, device_csr_to_scipy, limit_features, limit_features_columns,
+                        select_columns)

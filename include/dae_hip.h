@@ -805,6 +805,44 @@ int dae_pair_hist_images(const float* Qi, int32_t Nq, const int32_t* labels_q_ho
                          const int32_t* labels_c_host, int32_t D, float lo, float hi, int32_t bins, uint64_t* hist_host,
                          double* out16_host, void* workspace, uint64_t workspace_bytes, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * From a count matrix to the training input (helpers.column_stats / limit_features / select_columns / TfidfTransformer): what
+ * sklearn's CountVectorizer._limit_features and TfidfTransformer do to a bag of words, on CSR rows that stay on the device.
+ * CSR as dae_sweep_image_csr: indptr int64[rows + 1] points at the chunk's first row and holds offsets into indices int32 /
+ * values fp32 (values NULL: every stored entry is 1); column ids ascending and unique within a row.  An entry whose column
+ * lies outside [0, F) is dropped and counted.  Every call returns host numbers and so synchronises the stream.
+ *   dae_csr_column_stats: df[c] += stored entries of column c (explicit zeros count, as sklearn's _document_frequency counts
+ *   them), tf[c] += sum of the column's counts; both int64[F] on the device.  The call ADDS, so a corpus can be passed in row
+ *   chunks: zero both before the first.  The counts are added as integers by integer atomics: exact, independent of scheduling.
+ *   counts2_host (host, uint64[2]): [0] entries in range whose value is not an integer in [0, 2^24] (nothing is added to tf for
+ *   them; df counts them), [1] entries dropped for their column (not looked at further).
+ *   workspace: dae_csr_column_stats_workspace() bytes, 256-byte aligned.
+ *   dae_csr_select_columns: the rows with the columns renumbered by remap int32[F] (device; -1: the column is dropped; the kept
+ *   columns map increasingly, so a row stays ascending): count per row, exclusive scan, fill.  out_indptr int64[rows + 1] is
+ *   always written; out_indices int32 / out_values fp32 hold `capacity` entries (out_values may be NULL: the structure alone;
+ *   values NULL writes ones).  out2_host (host, int64[2]): [0] the new nnz, [1] entries dropped for their column.  When the
+ *   new nnz exceeds capacity the call returns 1 with out2_host set and writes nothing to out_indices / out_values; it never
+ *   writes past them.  workspace: dae_csr_select_columns_workspace(rows) bytes, 256-byte aligned.
+ *   dae_tfidf_transform: sklearn's TfidfTransformer.transform.  idf fp32[F] on the device (NULL: use_idf=False) -- computed
+ *   on the host in fp64 from the integer df and rounded once; sublinear 0 | 1; norm 0 none, 1 l1, 2 l2.  Per entry
+ *   v = fl32(t * idf[c]) with t the count, or fl32(1 + log((double) count)) when sublinear; the row norm (sum |v|, or the
+ *   square root of the sum of v^2) is summed in fp64 in an order fixed by the row alone; the result is fl32((double) v / norm).
+ *   A row whose norm is 0 or not finite keeps its v.  A dropped entry takes no part in the norm and its output is 0.
+ *   out_values fp32 (as long as values) may be values.  Bit-identical from run to run.  dropped_host (host, uint64[1]).
+ *   workspace: dae_tfidf_transform_workspace() bytes, 256-byte aligned.
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_csr_column_stats_workspace(void);
+int dae_csr_column_stats(const int64_t* indptr, const int32_t* indices, const float* values, int32_t rows, int32_t F, int64_t* df,
+                         int64_t* tf, uint64_t* counts2_host, void* workspace, uint64_t workspace_bytes, void* stream);
+uint64_t dae_csr_select_columns_workspace(int32_t rows);
+int dae_csr_select_columns(const int64_t* indptr, const int32_t* indices, const float* values, int32_t rows, int32_t F,
+                           const int32_t* remap, int64_t* out_indptr, int32_t* out_indices, float* out_values, uint64_t capacity,
+                           int64_t* out2_host, void* workspace, uint64_t workspace_bytes, void* stream);
+uint64_t dae_tfidf_transform_workspace(void);
+int dae_tfidf_transform(const int64_t* indptr, const int32_t* indices, const float* values, int32_t rows, int32_t F,
+                        const float* idf, int32_t sublinear, int32_t norm, float* out_values, uint64_t* dropped_host,
+                        void* workspace, uint64_t workspace_bytes, void* stream);
+
 /* Related / unrelated pair statistics of an N x N similarity matrix: the numbers behind
  * helpers.visualize_pairwise_similarity (helpers.py:79-135) -- AUROC of "same label" vs "different label" over the strict
  * lower triangle (labels < 0 are missing and drop their pairs; ties count half, as sklearn's roc_curve + auc do) and the

@@ -5,13 +5,15 @@ MI355X-native estimator.
 Kept: flag names, defaults, choices and the validation asserts (:94-109), ``main_dir`` defaulting to
 ``model_name`` (:111), the fit -> transform(decay-compensated) sequence (:277-290), parameter.txt, the saved
 artefact names under results/<algo>/<main_dir>/data/.  Not kept (out of the hot path): the parquet /
-jieba / CountVectorizer preprocessing and the matplotlib ROC plots -- the UCI dataset blob is absent from the
+jieba tokenising and the matplotlib ROC plots -- the UCI dataset blob is absent from the
 reference checkout (.MISSING_LARGE_BLOBS:2), so data comes from ``--data <matrix.npz> [--labels <labels.npy>]``
-(scipy CSR / dense .npy) or from the seeded synthetic generator (default).
+(scipy CSR / dense .npy) or from the seeded synthetic generator (default).  With ``--vectorize`` the file is a raw count
+matrix and the CountVectorizer pruning / TfidfTransformer steps (:206-240) run on the device.
 
 examples:
   python main_autoencoder.py --model_name demo --num_epochs 5 --verbose --verbose_step 1
   python main_autoencoder.py --model_name uci --data X.npz --labels y.npy --triplet_strategy batch_hard
+  python main_autoencoder.py --model_name bow --data counts.npz --vectorize --validation --min_df 0.001 --max_features 10000
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rank_metrics --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rank_metrics --max_age 48 --similarity False
@@ -49,7 +51,7 @@ def build_parser():
     p.add_argument("--save_tsv", default=False, **b)
     p.add_argument("--train_row", type=int, default=8000)
     p.add_argument("--validate_row", type=int, default=2000)
-    # Count-vectorizer parameters (:47-50); only max_features matters for synthetic data
+    # Count-vectorizer parameters (:47-50); only max_features matters for synthetic data; with --vectorize all three prune --data
     p.add_argument("--restore_previous_data", default=False, **b)
     p.add_argument("--min_df", type=float, default=0)
     p.add_argument("--max_df", type=float, default=0.99)
@@ -82,6 +84,14 @@ def build_parser():
     p.add_argument("--rng", default="numpy", choices=["numpy", "philox"])
     p.add_argument("--data", default="", help="scipy-sparse .npz or dense .npy feature matrix (rows = articles)")
     p.add_argument("--labels", default="", help=".npy label vector aligned with --data")
+    p.add_argument("--vectorize", default=False, **b,
+                   help="--data is a RAW count matrix (scipy .npz): on the device, the first train_row rows fit the vocabulary (--min_df, "
+                        "--max_df, --max_features: CountVectorizer's rule) and the idf; the validation rows go through both; "
+                        "--input_format picks the binary or the tf-idf matrix for training.  --min_df / --max_df are parsed as floats in "
+                        "[0, 1] (the reference's flags), so only shares of the train rows are accepted here; absolute counts are taken by "
+                        "helpers.limit_features.  Saves article_[binary_]count_vectorized, "
+                        "article_tfidf_vectorized (and their _validate forms), vocabulary_kept.npy and tfidf_transformer.npz.  Off: "
+                        "--data is trained on as it is")
     p.add_argument("--data_parallel", default=False, **b)
     p.add_argument("--similarity", default=True, **b,
                    help="after training: the N x N cosine similarities the reference computes (:307-317), on the device")
@@ -618,6 +628,46 @@ def _artefact(kind, a, validate=False):
     return "article_label_" + a.label + suffix + ".pkl"
 
 
+def vectorize_data(a, data_dir, helpers):
+    """--vectorize: ``--data`` is a RAW count matrix (scipy .npz; rows = articles, columns = the whole vocabulary), and the stage
+    the reference runs in front of training (:206-240) runs on the device (helpers.vectorize).  The first ``train_row`` rows fit the
+    vocabulary -- ``CountVectorizer``'s ``min_df`` / ``max_df`` / ``max_features`` rule on the count matrix (helpers.limit_features) --
+    and the idf (helpers.TfidfTransformer); the validation rows go through both.  With ``data_dir`` the count, binary and tf-idf
+    matrices are saved under the reference's names (:233-240), with the kept columns (vocabulary_kept.npy) and the fitted
+    transformer (tfidf_transformer.npz) where the reference pickles its two sklearn objects.  Returns the matrices
+    ``--input_format`` selects and the labels.  The matrices come back as host scipy copies -- the artefacts are saved from them, and
+    the estimator's ``fit`` / ``transform`` and the evaluation steps take host matrices -- so the CLI uploads the chosen one once more
+    for training; a caller that wants no round trip hands ``return_device=True`` results to ``Engine.upload_csr`` itself."""
+    assert a.data.endswith(".npz"), "--vectorize needs --data <counts.npz>, a scipy sparse count matrix"
+    from dae_rnn_news_recommendation_amd.engine import Engine
+    n = a.train_row + (a.validate_row if a.validation else 0)
+    X = sparse.load_npz(a.data).tocsr()[:n]
+    y = np.load(a.labels, allow_pickle=True)[:n] if a.labels else None
+    n_train = min(a.train_row, X.shape[0])
+    parts = [('', Engine.to_device_csr(X[:n_train], 'cuda'))]
+    if a.validation and X.shape[0] > n_train:
+        parts.append(('_validate', Engine.to_device_csr(X[n_train:], 'cuda')))
+    counts, kept = helpers.limit_features(parts[0][1], a.min_df, a.max_df, a.max_features, return_device=True)
+    tfidf = helpers.TfidfTransformer().fit(counts)
+    out = {}
+    for suffix, raw in parts:
+        c = counts if suffix == '' else helpers.select_columns(raw, kept, return_device=True)
+        forms = {'count': helpers.device_csr_to_scipy(c)}
+        forms['binary_count'] = helpers.binarize(forms['count'])
+        forms['tfidf'] = tfidf.transform(c)
+        out[suffix] = forms['tfidf' if a.input_format == 'tfidf' else 'binary_count']
+        if data_dir is not None:
+            for stem, M in forms.items():
+                helpers.save_file(M, data_dir + 'article_' + stem + '_vectorized' + suffix + '.npz')
+    if data_dir is not None:
+        np.save(data_dir + 'vocabulary_kept.npy', kept)
+        tfidf.save(data_dir + 'tfidf_transformer.npz')
+    print('vectorize: %d of %d columns kept, fitted on %d rows' % (kept.size, X.shape[1], n_train))
+    trY = None if y is None else np.asarray(y[:n_train])
+    vlY = None if (y is None or '_validate' not in out) else np.asarray(y[n_train:])
+    return out[''], out.get('_validate'), trY, vlY
+
+
 def load_or_restore(a, data_dir, helpers):
     """Train / validation matrices and label vectors: restored from the model's data directory
     (``--restore_previous_data``, reference :161-174) or built by ``load_data`` and saved there under the reference's
@@ -629,15 +679,18 @@ def load_or_restore(a, data_dir, helpers):
         trY = helpers.read_file(data_dir + _artefact("label", a), data_type='pandas_series').to_numpy()
         vlY = helpers.read_file(data_dir + _artefact("label", a, True), data_type='pandas_series').to_numpy() if a.validation else None
         return trX, vlX, trY, vlY
-    X, y = load_data(a)
-    trX, vlX = X[:a.train_row], (X[a.train_row:a.train_row + a.validate_row] if a.validation else None)
-    trY = None if y is None else np.asarray(y[:a.train_row])
-    vlY = None if (y is None or not a.validation) else np.asarray(y[a.train_row:a.train_row + a.validate_row])
     from dae_rnn_news_recommendation_amd import dp
+    if a.vectorize:
+        trX, vlX, trY, vlY = vectorize_data(a, data_dir if dp.rank() == 0 else None, helpers)
+    else:
+        X, y = load_data(a)
+        trX, vlX = X[:a.train_row], (X[a.train_row:a.train_row + a.validate_row] if a.validation else None)
+        trY = None if y is None else np.asarray(y[:a.train_row])
+        vlY = None if (y is None or not a.validation) else np.asarray(y[a.train_row:a.train_row + a.validate_row])
     if dp.rank() != 0:                     # data parallel: rank 0 is the only writer of the shared artefact directory
         return trX, vlX, trY, vlY
     for M, val in ((trX, False), (vlX, True)):
-        if M is not None:
+        if M is not None and not a.vectorize:                           # vectorize_data has saved all three forms
             helpers.save_file(M if sparse.issparse(M) else np.asarray(M), data_dir + (_artefact("features", a, val) if sparse.issparse(M)
                               else _artefact("features", a, val).replace(".npz", ".npy")))
     for v, val in ((trY, False), (vlY, True)):
