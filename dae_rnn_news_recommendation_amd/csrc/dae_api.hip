@@ -286,6 +286,12 @@ extern "C" int dae_plan_set_option(dae_plan* p, const char* name, int32_t value)
     else if (!strcmp(name, "gram_fused")) set_use_glds(on ? -20 : -19);    // process-wide: the split Gram's three products per K tile in one LDS stage (gram64f_kernel; default on), 0 = the K-concatenated walk (gram64_kernel)
     else if (!strcmp(name, "decode_x3")) set_use_glds(on ? -18 : -17);     // process-wide: the split modes' decode on the K loops that keep the hi stage's fragments in registers (mainloop_n64_x3 / _c2; default on, binary input)
     else if (!strcmp(name, "pad_skip")) set_use_glds(on ? -12 : -11);      // process-wide: 0 = multiply / evaluate the all-padding 32-row blocks of the last batch tile too (A/B)
+    else if (!strcmp(name, "decode_bm")) {                                  // tile height of the decode kernel: 0 auto (batch_route), 128, 160 (gemm_decode_loss_160)
+        DAE_CHECK_ARG(value == 0 || value == 128 || value == 160, "plan_set_option: decode_bm is 0 (auto), 128 or 160");
+        DAE_CHECK_ARG(value != 160 || plan_dec_bm160_form(p, p->xbits_ok),
+                      "plan_set_option: decode_bm = 160 needs the three-term 16-bit decode with a bit image of x (f16x2h on a binary CSR train set; no cosine loss, no lo images of delta2 / x, decode_bn 64)");
+        p->dec_bm = value;
+    }
     else if (!strcmp(name, "miner_order")) p->miner_order_ok = on;
     else if (!strcmp(name, "miner_ranges")) p->miner_ranges_ok = on;
     else if (!strcmp(name, "miner_pack")) set_miner_pack(on);        // process-wide (the launcher's choice), like dae_set_glds

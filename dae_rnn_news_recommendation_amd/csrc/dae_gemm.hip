@@ -874,6 +874,8 @@ __global__ __launch_bounds__(GEMM_THREADS, wg_per_cu_for(NST)) void gemm_nt_trac
 // Tile geometry of the decode kernel: 128 rows x BN_T columns.  BN_T = 64 (bf16) gives 7 x 158 = 1106 tiles of 48 KB LDS
 // and <= 168 VGPRs, i.e. THREE workgroups per CU and 768 resident slots: the 128 x 128 form had 553 tiles on 512 slots
 // (2 per CU), so 41 stragglers doubled the kernel time (rocprofv3: wave lifetime 15.6 us, kernel 32 us).
+// The three-term decode of a B = 800 batch does not run on this geometry any more: 160-row tiles (Dec160 / gemm_decode_loss_160 below) make it 474
+// workgroups on the 512 slots of two per CU, one resident round -- 40.7 us against 44.2 (profiles/decode_bm160.md); batch_route picks the tile height.
 template <int BN_T> struct DecGeo {
     static constexpr int NTB = BN_T / 64;                  // 32-column MFMA blocks per wave along N (waves are 2 x 2)
     static constexpr int WCOLS = BN_T / 2;                 // columns per wave
@@ -1755,9 +1757,361 @@ __global__ __launch_bounds__(GEMM_THREADS, DecGeo<BN_T>::WG_PER_CU) void gemm_de
 }
 
 // ------------------------------------------------------------------------------------------------
+// 160 x 128 decode tile (16-bit storage, binary input as a bit image, three-term K loop): B = 800 is five exact row panels, so the c2 shape
+// is 6 x 79 = 474 workgroups (the sixth panel, rows 800..895 of Bp, is pure padding and only writes zeros) on 2 x 256 = 512 resident slots:
+// ONE round instead of 1.44, and the h tile is streamed for 79 column tiles instead of 158.  Waves 1 x 4 as in gemm_dw_pc's consumer: wave w
+// owns all 160 rows x columns [32 w, +32) = 5 accumulators, 5 A fragments + 1 B fragment per k step.  K loop: mainloop_n64_x3's two stages
+// per K tile in the same term order (hi.hi; then per k step hi.lo, lo.hi), so every logit is the bit pattern the 128 x 64 kernel computes;
+// the hi stage's 24 fragments stay in registers (96 VGPRs) and the lo stage reads its fragments one k step ahead (2 x 24 VGPRs) -- 80 + 96 +
+// 48 = 224 under the 256 of two workgroups per CU.  Epilogue: delta2 [160][P0] and delta2^T [128][P1] are staged ONE AFTER THE OTHER in the
+// same LDS region (side by side they would be 86 KiB); the transposed image waits in 40 packed registers.  Row panels may overhang Bp (a
+// multiple of 128, not of 160): the h rows are clamped (dma_src), every other access beyond Bp is guarded.
+// Partial sums: rowloss_part [Fp/32][Bp] as the 64-column kernel, dbv_part ONE row per tile row (tiles_m x Fp), tile_part [tiles_m x tiles_n].
+// ------------------------------------------------------------------------------------------------
+struct Dec160 {
+    static constexpr int ROWS = 160, COLS = 128, MT = ROWS / 32;
+    static constexpr int A_BYTES = ROWS * BKB;                     // 20 KiB
+    static constexpr int STAGE = A_BYTES + COLS * BKB;             // + 16 KiB
+    static constexpr int LOOP_BYTES = 2 * STAGE;                   // 72 KiB
+    static constexpr int P0 = COLS * 2 + 16;                       // staged row pitch of the [160][128] delta2 tile
+    static constexpr int P1 = ROWS * 2 + 16;                       // ... of the [128][160] delta2^T tile
+    static constexpr int R_BYTES = ROWS * P0 > COLS * P1 ? ROWS * P0 : COLS * P1;
+    static constexpr int AUX_FLOATS = ROWS + COLS + 4 * ROWS + COLS + 4;
+    static constexpr int EPI_BYTES = R_BYTES + AUX_FLOATS * 4;
+    static_assert(EPI_BYTES <= LOOP_BYTES, "the epilogue reuses the stage ring");
+    static constexpr int XB_OFF = LOOP_BYTES;                      // bit image of the clean-input tile [160][4 words]: lands by LDS-DMA while the K loop runs, so behind the ring
+    static constexpr int XB_PIECES = ROWS * (COLS / 32) / 64;      // 256-byte pieces (one dword per lane)
+    static constexpr int LDS_BYTES = XB_OFF + ROWS * (COLS / 32) * 4;
+    static_assert(LDS_BYTES <= 80 * 1024, "two workgroups per CU");
+    static_assert(P0 % 16 == 0 && P1 % 16 == 0, "16-byte pieces of the staged tiles");
+};
+template <int OFF> __device__ __forceinline__ i32x4 lds_read_b128_at(uint32_t addr) {     // OFF: any immediate byte offset (the stage slot and the 32-row block)
+    static_assert(OFF >= 0 && OFF < 65536 && OFF % 16 == 0, "a 16-bit immediate");
+    i32x4 v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(v) : "v"(addr), "n"(OFF));
+    return v;
+}
+// Fragments of k step KK of the stage at byte SLOT: the wave's 5 A blocks and its B block.  a_row / b_row: the lane's row in the A tile / in the wave's
+// B block (slot 0), so0 = frag_slot(0, lane).  frag_slot(kk) = so0 ^ (kk << 5) (kk sits above the lane's half g in the slot index), formed here by an
+// opaque v_xad_u32 per operand: as loop invariants the 16 addresses of the two slots would cost 16 VGPRs the loop does not have.
+template <int KK, int SLOT> __device__ __forceinline__ void dec160_read(uint32_t a_row, uint32_t b_row, uint32_t so0, i32x4 (&fa)[5], i32x4 (&fb)[1]) {
+    static_assert(frag_slot(KK, 0) == (frag_slot(0, 0) ^ (KK << 5)) && frag_slot(KK, 63) == (frag_slot(0, 63) ^ (KK << 5)), "k step as an XOR on the slot offset");
+    uint32_t a, b;
+    if constexpr (KK == 0) { a = a_row + so0; b = b_row + so0; }
+    else {
+        asm volatile("v_xad_u32 %0, %1, %2, %3" : "=v"(a) : "v"(so0), "s"(KK << 5), "v"(a_row));
+        asm volatile("v_xad_u32 %0, %1, %2, %3" : "=v"(b) : "v"(so0), "s"(KK << 5), "v"(b_row));
+    }
+    fa[0] = lds_read_b128_at<SLOT>(a);
+    fa[1] = lds_read_b128_at<SLOT + FRAG_BLOCK>(a);
+    fa[2] = lds_read_b128_at<SLOT + 2 * FRAG_BLOCK>(a);
+    fa[3] = lds_read_b128_at<SLOT + 3 * FRAG_BLOCK>(a);
+    fa[4] = lds_read_b128_at<SLOT + 4 * FRAG_BLOCK>(a);
+    fb[0] = lds_read_b128_at<SLOT>(b);
+}
+__device__ __forceinline__ void mainloop_160_x3(const GemmParams& p, int tm, int tn, int Bp, char* lds, f32x16 (&acc)[5][1]) {
+    using T = bf16_t;
+    constexpr int STAGE = Dec160::STAGE, A_BYTES = Dec160::A_BYTES;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    zero_acc(acc);
+    const int nk = p.seg[0].ktiles;                    // the three segments: the same K extent and leading dimensions (checked by the launcher)
+    if (nk <= 0) return;
+    // LDS-DMA addressing: piece i of this wave is piece 4 i + wave of a tile, 32 i rows below the wave's first piece -- the swizzle has period 16 rows, so the
+    // lane's 16 bytes sit at ONE offset (vA / vB) from the piece's first row and the pieces differ by a uniform (SGPR) row offset.  A piece of the h tile that
+    // lies beyond Bp (whole pieces: Bp is a multiple of 8) re-reads the panel's last 8 rows; nothing of those rows is used.
+    static_assert(piece_slot(4, 9) == piece_slot(0, 9) && piece_slot(17, 60) == piece_slot(1, 60) && PIECE_ROWS == 8, "the piece swizzle repeats every 16 rows");
+    const uint32_t lda = (uint32_t)p.seg[0].lda_b, ldb = (uint32_t)p.seg[0].ldb_b;
+    const uint32_t slot16 = (uint32_t)(piece_slot(wave, lane) << 4);
+    const uint32_t vA = (uint32_t)(lane >> 3) * lda + slot16, vB = (uint32_t)(lane >> 3) * ldb + slot16;
+    int64_t rA[5], rB[4];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) rA[i] = (int64_t)min(tm * Dec160::ROWS + (4 * i + wave) * PIECE_ROWS, Bp - PIECE_ROWS) * lda;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rB[i] = (int64_t)(tn * Dec160::COLS + (4 * i + wave) * PIECE_ROWS) * ldb;
+    auto dma = [&](char* slot, const char* gA, const char* gB) {       // 9 pieces per wave
+#pragma unroll
+        for (int i = 0; i < 5; ++i) glds_piece<4>(i, wave, gA + rA[i] + vA, slot);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) glds_piece<4>(i, wave, gB + rB[i] + vB, slot + A_BYTES);
+    };
+    const uint32_t lbase = lds_addr(lds);
+    const uint32_t a_row = lbase + frag_row(0, lane), b_row = lbase + A_BYTES + frag_row(wave * 32, lane);
+    const uint32_t so0 = frag_slot(0, lane);
+    // segments as the launcher lists them: 0 = (h_hi, W_hi), 1 = (h_hi, W_lo), 2 = (h_lo, W_hi)
+    const char *gAh = p.seg[0].A, *gBh = p.seg[0].Bt, *gAl = p.seg[2].A, *gBl = p.seg[1].Bt;
+    // Both stages of K tile 0 go out at once; from then on a slot is refilled THE MOMENT its fragments sit in registers -- the barrier behind the last landed
+    // read, not behind the MFMAs that consume them -- so the hi stage of K tile i + 1 is in flight through the last hi MFMAs and the whole lo stage of K tile
+    // i, and the lo stage of K tile i + 1 from the last lo MFMAs on.  vmcnt: the stage waited for always has exactly one younger stage (9 pieces) behind it.
+    dma(lds, gAh, gBh);
+    dma(lds + STAGE, gAl, gBl);
+    for (int i = 0; i < nk; ++i) {
+        const bool more = i + 1 < nk;
+        // ---- hi stage (slot 0)
+        wait_vm<9>();
+        __builtin_amdgcn_s_barrier();                  // the hi stage landed for every wave
+        asm volatile("" ::: "memory");
+        i32x4 fah[4][5], fbh[4][1];
+        // (at most 12 reads in flight: lgkmcnt is a 4-bit counter)
+        dec160_read<0, 0>(a_row, b_row, so0, fah[0], fbh[0]);
+        dec160_read<1, 0>(a_row, b_row, so0, fah[1], fbh[1]);
+        mma_group<T, 6>(fah[0], fbh[0], acc);
+        __builtin_amdgcn_sched_barrier(0);
+        dec160_read<2, 0>(a_row, b_row, so0, fah[2], fbh[2]);
+        mma_group<T, 6>(fah[1], fbh[1], acc);
+        __builtin_amdgcn_sched_barrier(0);
+        dec160_read<3, 0>(a_row, b_row, so0, fah[3], fbh[3]);
+        mma_group<T, 6>(fah[2], fbh[2], acc);
+        __builtin_amdgcn_sched_barrier(0);
+        wait_lgkm<0>();
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();                  // every wave holds slot 0 in registers: the next K tile's hi stage refills it
+        asm volatile("" ::: "memory");
+        if (more) {
+            gAh += BKB; gBh += BKB;
+            dma(lds, gAh, gBh);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        mma_block<T>(fah[3], fbh[3], acc);
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- lo stage (slot 1): its fragments one k step ahead of the MFMAs, the hi fragments from registers
+        if (more) wait_vm<9>();
+        else wait_vm<0>();
+        __builtin_amdgcn_s_barrier();                  // the lo stage landed for every wave
+        asm volatile("" ::: "memory");
+        i32x4 fal[2][5], fbl[2][1];
+        dec160_read<0, STAGE>(a_row, b_row, so0, fal[0], fbl[0]);
+        dec160_read<1, STAGE>(a_row, b_row, so0, fal[1], fbl[1]);
+        mma_group<T, 6>(fah[0], fbl[0], acc); mma_block<T>(fal[0], fbh[0], acc);
+        __builtin_amdgcn_sched_barrier(0);
+        dec160_read<2, STAGE>(a_row, b_row, so0, fal[0], fbl[0]);
+        mma_group<T, 6>(fah[1], fbl[1], acc); mma_block<T>(fal[1], fbh[1], acc);
+        __builtin_amdgcn_sched_barrier(0);
+        dec160_read<3, STAGE>(a_row, b_row, so0, fal[1], fbl[1]);
+        mma_group<T, 6>(fah[2], fbl[0], acc); mma_block<T>(fal[0], fbh[2], acc);
+        __builtin_amdgcn_sched_barrier(0);
+        wait_lgkm<0>();
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();                  // every wave has read slot 1: the next K tile's lo stage refills it
+        asm volatile("" ::: "memory");
+        if (more) {
+            gAl += BKB; gBl += BKB;
+            dma(lds + STAGE, gAl, gBl);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        mma_block<T>(fah[3], fbl[1], acc); mma_block<T>(fal[1], fbh[3], acc);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+template <int LOSS, int ACT>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_decode_loss_160(GemmParams p, DecodeEpi e) {
+    static_assert(LOSS != DAE_LOSS_COSINE, "the cosine passes stay on the 128-row kernels");
+    using T = bf16_t;
+    using Geo = Dec160;
+    constexpr int ROWS = Geo::ROWS, COLS = Geo::COLS, MT = Geo::MT, P0 = Geo::P0, P1 = Geo::P1, WPR = COLS / 32;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    if (e.sym_G && (int)blockIdx.x >= e.sym_first) {   // rider workgroups: the symmetrised triplet gradient (see DecodeEpi)
+        const int t = (int)blockIdx.x - e.sym_first, nt = e.sym_Bp / 64;
+        sym_scale_tile<T>(e.sym_G, e.sym_B, e.sym_Bp, e.sym_scalars, reinterpret_cast<T*>(e.sym_Gs), t % nt, t / nt,
+                          reinterpret_cast<float(*)[65]>(lds), e.op_scale);
+        return;
+    }
+    int tm, tn, split, kt0, kt1;
+    if (!block_to_tile(p, tm, tn, split, kt0, kt1)) return;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int g = lane >> 5, c = lane & 31;
+    const int row0 = tm * ROWS;
+    T* D2 = reinterpret_cast<T*>(e.delta2);
+    T* D2T = reinterpret_cast<T*>(e.delta2_t);
+
+    // ---- the bit image of the clean-input tile (160 rows x 4 words) goes to LDS by DMA, one dword per lane, ahead of the K loop's stages: no register
+    //      waits for it through the loop.  Rows beyond Bp re-read row Bp - 1 (nothing of them is used).
+    uint32_t* xb_l = reinterpret_cast<uint32_t*>(lds + Geo::XB_OFF);      // [160][WPR]
+    {
+        const int wv = __builtin_amdgcn_readfirstlane(wave);
+#pragma unroll
+        for (int i = 0; i < (Geo::XB_PIECES + 3) / 4; ++i) {
+            const int piece = 4 * i + wv;
+            if (piece < Geo::XB_PIECES) {
+                const int idx = piece * 64 + lane, row = min(row0 + (idx >> 2), e.Bp - 1);
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(e.x_bits + (int64_t)row * e.ldxb + tn * WPR + (idx & 3)),
+                                                 (__attribute__((address_space(3))) void*)(xb_l + piece * 64), 4, 0, 0);
+            }
+        }
+    }
+
+    f32x16 acc[MT][1];
+    // 32-row blocks of this tile that hold a real batch row (0..5); a tile without one (the panel behind the batch) skips the K loop
+    const int vblk = e.no_pad_skip ? MT : max(0, min(MT, (e.B - row0 + 31) >> 5));
+    if (vblk > 0) mainloop_160_x3(p, tm, tn, e.Bp, lds, acc);
+    else zero_acc(acc);
+    wait_vm<0>();                                      // (a tile without a K loop: the bit image)
+    __syncthreads();                                   // every wave is done with the K-loop stages
+
+    char* R = lds;                                     // delta2 [160][P0], then delta2^T [128][P1]
+    float* aux = reinterpret_cast<float*>(lds + Geo::R_BYTES);
+    float* cw_l = aux;                                 // [160] row weights
+    float* bv_l = aux + ROWS;                          // [128] visible bias
+    float* rowsum_l = bv_l + COLS;                     // [4 (wave)][160]
+    float* colsum_l = rowsum_l + 4 * ROWS;             // [128]
+    float* wl_l = colsum_l + COLS;                     // [4]
+    if (tid < ROWS) cw_l[tid] = (row0 + tid) < e.Bp ? e.cw[row0 + tid] : 0.f;      // zero beyond B by construction
+    if (tid < COLS) bv_l[tid] = (tn * COLS + tid) < e.F ? e.bv[tn * COLS + tid] : 0.f;
+    __syncthreads();
+
+    const int lcol0 = wave * 32 + c;                   // local column: acc_col(0, c) of the wave's 32
+    const int lrow0 = 4 * g;                           // local row of (mt = 0, r = 0)
+    const float eps = 1e-16f;
+    const float cm = (tn * COLS + lcol0) < e.F ? 1.f : 0.f;     // column mask as a multiplier: padded features contribute nothing
+    const float bvv = bv_l[lcol0];
+    float colsum = 0.f;
+    char* r0_lane = R + lrow0 * P0 + lcol0 * 2;
+    char* r1_lane = R + lcol0 * P1 + lrow0 * 2;
+    const bool want_rows = e.rowloss_part != nullptr;
+    const float osc = e.op_scale;
+    float wl_acc = 0.f;                                // this lane's share of sum_i cw_i * loss_if
+    uint32_t tp[MT * 4][2];                            // packed 16-bit delta2 of this lane's elements for the transposed image, block (mt, r4) at mt * 4 + r4
+    // (the arithmetic of gemm_decode_loss's epi_block for the staged 16-bit kernel with a bit image, element for element)
+    auto epi_block = [&](auto MTV, auto R4, auto FASTV) {
+        constexpr int mt = decltype(MTV)::value, r4 = decltype(R4)::value;
+        constexpr bool FAST = decltype(FASTV)::value;
+        constexpr int rloc = acc_row(mt, 4 * r4, 0);
+        float d2v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int lrow = lrow0 + rloc + q;
+            const float cwi = cw_l[lrow];
+            const float z = acc[mt][0][r4 * 4 + q] + bvv;
+            const float x = (float)((xb_l[lrow * WPR + wave] >> c) & 1u);
+            float rl, d2;
+            if constexpr (FAST) {
+                const float en = __builtin_amdgcn_exp2f(-fabsf(z) * kLog2e);          // exp(-|z|)
+                const float op = 1.0f + en;
+                const float rr = __builtin_amdgcn_rcpf(op);
+                const float yv = z >= 0.f ? rr : en * rr;
+                const float l = kLn2 * __builtin_amdgcn_logf(op) + fmaxf(z, 0.f) - x * z;
+                d2 = (cwi * cm) * (yv - x);
+                rl = cm * l;
+            } else {
+                const float y = act_fwd<ACT>(z);
+                float l, dy;
+                if constexpr (LOSS == DAE_LOSS_CROSS_ENTROPY) {
+                    const float a = y + eps, b = (1.0f - y) + eps;          // reference op order: (1.-y)+1e-16
+                    const float la = __builtin_amdgcn_logf(a), lb = __builtin_amdgcn_logf(b);
+                    l = -kLn2 * (x * la + (1.0f - x) * lb);
+                    dy = (1.0f - x) * __builtin_amdgcn_rcpf(b) - x * __builtin_amdgcn_rcpf(a);
+                } else {
+                    const float d = x - y;
+                    l = d * d;
+                    dy = -2.0f * d;
+                }
+                d2 = (cwi * cm) * dy * act_bwd<ACT>(y);                     // cw is 0 on padded rows
+                rl = cm * l;
+            }
+            colsum += d2;
+            const float d2s = sat16(d2 * osc);                              // the 16-bit images hold op_scale * delta2
+            d2v[q] = d2s;
+            *reinterpret_cast<bf16_t*>(r0_lane + (rloc + q) * P0) = f2bf_hw(d2s);
+            wl_acc += cwi * rl;
+            if (want_rows) {
+                rl = half32_sum_hi(rl);                                     // the 32 lanes that share this row; lanes 31 / 63 hold it
+                if (c == 31) rowsum_l[wave * ROWS + lrow] = rl;
+            }
+        }
+        tp[mt * 4 + r4][0] = f2bf_pack_hw(d2v[0], d2v[1]);
+        tp[mt * 4 + r4][1] = f2bf_pack_hw(d2v[2], d2v[3]);
+    };
+    // a 32-row block of pure padding (rows >= B): delta2 = 0 without evaluating the loss
+    auto zero_block = [&](auto MTV) {
+        constexpr int mt = decltype(MTV)::value;
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+            const int rloc = acc_row(mt, 4 * r4, 0);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                *reinterpret_cast<bf16_t*>(r0_lane + (rloc + q) * P0) = (bf16_t)0;
+                if (want_rows && c == 31) rowsum_l[wave * ROWS + lrow0 + rloc + q] = 0.f;
+            }
+            tp[mt * 4 + r4][0] = 0u; tp[mt * 4 + r4][1] = 0u;
+        }
+    };
+#define DAE_EPI160_ROWS(MTV, FV)                                                                                           \
+    if (MTV < vblk) {                                                                                                      \
+    epi_block(std::integral_constant<int, MTV>{}, std::integral_constant<int, 0>{}, std::integral_constant<bool, FV>{});   \
+    epi_block(std::integral_constant<int, MTV>{}, std::integral_constant<int, 1>{}, std::integral_constant<bool, FV>{});   \
+    epi_block(std::integral_constant<int, MTV>{}, std::integral_constant<int, 2>{}, std::integral_constant<bool, FV>{});   \
+    epi_block(std::integral_constant<int, MTV>{}, std::integral_constant<int, 3>{}, std::integral_constant<bool, FV>{});   \
+    } else zero_block(std::integral_constant<int, MTV>{});
+#define DAE_EPI160_ALL(FV) DAE_EPI160_ROWS(0, FV) DAE_EPI160_ROWS(1, FV) DAE_EPI160_ROWS(2, FV) DAE_EPI160_ROWS(3, FV) DAE_EPI160_ROWS(4, FV)
+    bool fast = false;
+    if constexpr (LOSS == DAE_LOSS_CROSS_ENTROPY && ACT == DAE_ACT_SIGMOID) {
+        float zmax = 0.f;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) zmax = fmaxf(zmax, fabsf(acc[mt][0][r] + bvv));
+        fast = __builtin_amdgcn_ballot_w64(!(zmax < CE_FAST_ZMAX)) == 0ull && !e.ce_literal;   // NaN logits take the literal path
+    }
+    if (fast) {
+        if constexpr (LOSS == DAE_LOSS_CROSS_ENTROPY && ACT == DAE_ACT_SIGMOID) { DAE_EPI160_ALL(true) }
+    } else {
+        DAE_EPI160_ALL(false)
+    }
+#undef DAE_EPI160_ALL
+#undef DAE_EPI160_ROWS
+    {                                                   // column sums: rows of g = 0 and g = 1, then one lane per column
+        const float v = colsum + __shfl_xor(colsum, 32, 64);
+        if (g == 0) colsum_l[lcol0] = v;
+    }
+    if (e.tile_part) {                                  // this tile's share of sum_i cw_i * rowloss_i (4 waves, fixed order)
+        const float v = wave64_sum_hi(wl_acc);
+        if (lane == 63) wl_l[wave] = v;
+    }
+    __syncthreads();
+
+    // ---- leave the CU: delta2 as coalesced 16-byte row pieces ----
+    if (D2) {
+#pragma unroll
+        for (int i = 0; i < ROWS * (COLS / 8) / GEMM_THREADS; ++i) {
+            const int ch = tid + GEMM_THREADS * i, row = ch >> 4, c16 = ch & 15;
+            if (row0 + row < e.Bp)
+                *reinterpret_cast<i32x4*>(D2 + (int64_t)(row0 + row) * e.ldd + tn * COLS + c16 * 8) = *reinterpret_cast<const i32x4*>(R + row * P0 + c16 * 16);
+        }
+    }
+    if (D2T) {                                          // (NULL: the dW kernel reads delta2 row-major, no transposed image -- gemm_dw_pc<TRA>)
+        __syncthreads();                                // every piece of the delta2 tile has been read: the region takes delta2^T
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int r4 = 0; r4 < 4; ++r4) {
+                uint2 v; v.x = tp[mt * 4 + r4][0]; v.y = tp[mt * 4 + r4][1];
+                *reinterpret_cast<uint2*>(r1_lane + acc_row(mt, 4 * r4, 0) * 2) = v;
+            }
+        __syncthreads();
+        static_assert(COLS * (ROWS / 8) % GEMM_THREADS == 0, "whole rounds of 16-byte pieces");
+#pragma unroll
+        for (int i = 0; i < COLS * (ROWS / 8) / GEMM_THREADS; ++i) {
+            const int ch = tid + GEMM_THREADS * i, row = ch / (ROWS / 8), c16 = ch % (ROWS / 8);
+            if (row0 + c16 * 8 < e.Bp)
+                *reinterpret_cast<i32x4*>(D2T + (int64_t)(tn * COLS + row) * e.lddt + row0 + c16 * 8) = *reinterpret_cast<const i32x4*>(R + row * P1 + c16 * 16);
+        }
+    }
+    if (want_rows) {
+        for (int i = tid; i < 4 * ROWS; i += GEMM_THREADS) {
+            const int w = i / ROWS, k = i % ROWS;
+            if (row0 + k < e.Bp) e.rowloss_part[(int64_t)(tn * 4 + w) * e.Bp + row0 + k] = (row0 + k) < e.B ? rowsum_l[i] : 0.f;
+        }
+    }
+    if (e.dbv_part && tid < COLS) e.dbv_part[(int64_t)tm * e.Fp + tn * COLS + tid] = colsum_l[tid];
+    if (e.tile_part && tid == 0) e.tile_part[tm * p.tiles_n + tn] = (wl_l[0] + wl_l[1]) + (wl_l[2] + wl_l[3]);
+}
+
+// ------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------
-static int g_nst = 2;   // staging variant of the plain GEMM: 0 register-staged, 2/3/4 global_load_lds ring depth
+static int g_nst = 2;  // staging variant of the plain GEMM: 0 register-staged, 2/3/4 global_load_lds ring depth
 
 // one K segment of a contraction as the host hands it over: A_seg [M x K], Bt_seg [N x K], both K-contiguous, leading dimensions in elements
 static int fill_params_n(GemmParams& p, int dtype, int M, int N, const GemmSegDesc* segs, int nsegs, int splits, int bn = BN, bool a_is_k_by_m = false) {
@@ -1883,7 +2237,26 @@ static decode_fn decode_kernel_c2(int loss, int act, bool res) {
 #undef DAE_DKC
     return nullptr;
 }
+// the 160 x 128 tile with the same three-term loop (gemm_decode_loss_160); the cosine passes stay on the 128-row kernels
+static decode_fn decode_kernel_160(int loss, int act) {
+#define DAE_DK160(LV, AV) if (loss == LV && act == AV) return gemm_decode_loss_160<LV, AV>;
+    DAE_DK160(0, 0) DAE_DK160(0, 1) DAE_DK160(0, 2) DAE_DK160(1, 0) DAE_DK160(1, 1) DAE_DK160(1, 2)
+#undef DAE_DK160
+    return nullptr;
+}
 static int g_decode_x3 = 1;        // dae_set_glds(-17) off / (-18) on; plan option "decode_x3": the three-term decode (f16x2h) on mainloop_n64_x3 instead of three K segments
+// Does the 160-row decode kernel exist for this launch?  (16-bit storage, 64-column layout of the partial sums, bit image of x, all three product terms,
+// no lo images of delta2 / x, not cosine, whole 128-column tiles)
+bool decode_bm160_form(int dtype, int bn, bool x_bits, bool three_terms, bool lo_images, int loss_func, int Fp) {
+    return g_decode_x3 && dtype == DAE_BF16 && bn == DECODE_BN_BF16 && x_bits && three_terms && !lo_images && loss_func != DAE_LOSS_COSINE && Fp % Dec160::COLS == 0;
+}
+static int gemm_init();
+// ... and does it pay by the tile count alone?  One resident round (2 workgroups per CU) where the 128 x 64 grid (3 per CU) needs more than one.
+bool decode_bm160_one_round(int Bp, int Fp) {
+    if (gemm_init() || g_cus <= 0) return false;
+    const int t160 = ((Bp + Dec160::ROWS - 1) / Dec160::ROWS) * (Fp / Dec160::COLS), t64 = (Bp / BM) * (Fp / DECODE_BN_BF16);
+    return t160 <= 2 * g_cus && t64 > 3 * g_cus;
+}
 template <typename T> static decode_fn decode_kernel(int loss, int act) {
 #define DAE_DK(LV, AV) if (loss == LV && act == AV) return gemm_decode_loss<T, LV, AV, false, (sizeof(T) == 2 ? DECODE_BN_BF16 : BN)>;
     DAE_DK(0, 0) DAE_DK(0, 1) DAE_DK(0, 2) DAE_DK(1, 0) DAE_DK(1, 1) DAE_DK(1, 2) DAE_DK(2, 0) DAE_DK(2, 1) DAE_DK(2, 2)
@@ -2216,6 +2589,31 @@ int launch_decode_loss_n(int dtype, int Bp, int Fp, const GemmSegDesc* segs, int
     }
     if (e.op_scale == 0.f) e.op_scale = 1.f;
     e.no_pad_skip = g_pad_skip ? 0 : 1;
+    DAE_CHECK_ARG(e.bm == 0 || e.bm == BM || e.bm == Dec160::ROWS, "decode_loss: tile height %d (0, 128 or 160)", e.bm);
+    if (e.bm == Dec160::ROWS) {                         // 160 x 128 tiles: the route took them (batch_route), the launcher only checks that the form exists
+        DAE_CHECK_ARG(x3d && e.loss_func != DAE_LOSS_COSINE && !e.z_io && Fp % Dec160::COLS == 0 && e.Bp == Bp && e.Fp == Fp && e.ldxb >= Fp / 32,
+                      "decode_loss: the 160-row tile exists for the three-term 16-bit decode with a bit image of x (no cosine loss, no lo images)");
+        static int rc160 = [] {
+            int rc = 0;
+            for (int l = 0; l < 2; ++l)
+                for (int a = 0; a < 3; ++a)
+                    rc |= (int)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_kernel_160(l, a)), hipFuncAttributeMaxDynamicSharedMemorySize, Dec160::LDS_BYTES);
+            return rc;
+        }();
+        DAE_CHECK_ARG(rc160 == 0, "decode_loss: hipFuncSetAttribute failed");
+        GemmParams q = p;
+        q.tiles_m = (Bp + Dec160::ROWS - 1) / Dec160::ROWS; q.tiles_n = Fp / Dec160::COLS;
+        int nblocks = grid_blocks(q);
+        if (e.sym_G) {
+            DAE_CHECK_ARG(e.sym_scalars && e.sym_Gs && e.sym_Bp % 64 == 0 && e.sym_B <= e.sym_Bp, "decode_loss: bad sym_scale rider");
+            e.sym_first = nblocks;
+            nblocks += (e.sym_Bp / 64) * (e.sym_Bp / 64);
+        }
+        static_assert(Dec160::LDS_BYTES >= 64 * 65 * 4, "rider tile must fit the decode LDS");
+        DAE_LAUNCH(decode_kernel_160(e.loss_func, e.dec_act), dim3(nblocks), dim3(GEMM_THREADS), Dec160::LDS_BYTES, st, q, e);
+        DAE_CHECK_LAUNCH();
+        return 0;
+    }
     if (wide) {
         k = decode_kernel_wide(e.loss_func, e.dec_act, e.x_bits != nullptr);
         static int wide_rc = [] {

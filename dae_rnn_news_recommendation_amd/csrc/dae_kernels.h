@@ -36,7 +36,12 @@ struct DecodeEpi {
     int z_mode;               // z_mode 2: pass 2 LOADS them instead of running the K loop again (the same fp32 values the recomputation would produce); 0 / NULL: recompute
     int bn;                   // tile width (columns of y per workgroup): 0 = the mode's default (decode_tile_n), 128 = the wide 16-bit kernel; the partial-sum arrays
                               // (rowloss_part / cos_part: 2 * Fp / bn rows; tile_part: (Bp / 128) * (Fp / bn)) are laid out by it
+    int bm;                   // tile height: 0 / 128 = the kernels above, 160 = gemm_decode_loss_160 (160 x 128 tiles over ceil(Bp / 160) row panels: dbv_part holds ONE
+                              // row per panel, tile_part ceil(Bp / 160) * (Fp / 128) entries, rowloss_part Fp / 32 rows as with bn = 64); an error where that form does not exist
 };
+// the 160-row decode tile: does the kernel exist for such a launch, and does the shape fit one resident round where the 128 x 64 grid needs more? (dae_gemm.hip)
+bool decode_bm160_form(int dtype, int bn, bool x_bits, bool three_terms, bool lo_images, int loss_func, int Fp);
+bool decode_bm160_one_round(int Bp, int Fp);
 
 // lo product terms of the split 16-bit mode (dae_config.dtype = DAE_BF16X3; plan option "x3_terms"): each bit keeps one (hi, lo) / (lo, hi) product of one
 // contraction -- and with it the lo image it reads.  bf16 storage needs them all (profiles/r04_precision_terms.txt); fp16 storage holds the 1e-4 curve

@@ -57,6 +57,8 @@ struct dae_plan {
     float op_scale;
     int dec_bn;                      // tile width of the decode kernel: decode_tile_n(dtype), or 128 in the 16-bit modes when the 64-column tiles would be more than
                                      // DEC_WIDE_ROUNDS rounds of the chip's 768 slots (option "decode_bn" = 64 | 128 | 0 auto; before dae_plan_bind)
+    int dec_bm;                      // option "decode_bm": tile height of the decode kernel, 0 = auto (batch_route: 160 where the 160 x 128 form exists and fits one resident
+                                     // round that the 128 x 64 grid does not), 128, 160 (an error where the form does not exist for the plan's mode / loss)
     bool dw_pair_ok;                 // option "dw_pair": split-bf16 dW kernel streams x~^T resp. delta2^T_hi ONCE for the hi and lo image of delta1^T resp. h^T
     bool xct2_clean;
     bool enc_w32_ok;                 // option "encode_w32": bf16 mode encodes from the fp32 MASTER weights (h fp32-accurate); 0 = from W_lo
@@ -96,6 +98,13 @@ static int plan_dec_bn(const dae_plan* p) {
     if (p->dec_bn == 64 || p->dec_bn == 128) return p->dec_bn;
     const int64_t tiles64 = (int64_t)(p->Bpm / 128) * (p->Fp / 64);
     return tiles64 > 4 * 768 ? 128 : def;             // F = 50000: 5474 tiles of 128 x 64 = 7.1 rounds of 768 slots -> 2737 wide tiles
+}
+
+// does the 160 x 128 decode kernel exist for this plan's mode, terms and loss (x_bits: the clean rows reach the decode as a bit image)?
+static bool plan_dec_bm160_form(const dae_plan* p, bool x_bits) {
+    const uint32_t T = p->x3 ? p->terms : 0u;
+    return decode_bm160_form(p->cfg.dtype, plan_dec_bn(p), x_bits, (T & X3T_DEC_WLO) && (T & X3T_DEC_HLO), (T & (X3T_DH_D2LO | X3T_DW_D2LO | X3T_XV)) != 0,
+                             p->cfg.loss_func, p->Fp);
 }
 
 #define RC(expr) do { if (int rc__ = (expr)) return rc__; } while (0)
@@ -212,6 +221,7 @@ struct BatchRoute {
     bool sym_ride;              // the decode launch also scales G + G^T (sym_scale)
     // ---- decode
     int dbn;                    // tile width
+    int dbm;                    // tile height: 128, or 160 (gemm_decode_loss_160; lays out dbv_part / tile_part, see DecodeEpi::bm)
     bool is_cos;
     bool zstore;                // cosine: the second pass reads the first pass's accumulators back
     // ---- dh

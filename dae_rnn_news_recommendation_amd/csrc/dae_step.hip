@@ -54,6 +54,9 @@ static BatchRoute batch_route(const dae_plan& p, const PhaseClass& k, int B, con
     r.fold_finalize = (c.triplet == DAE_TRIPLET_BATCH_ALL && !c.pos_triplets_only) && !k.ext_mine;
     r.sym_ride = r.mined && k.backward && p.sym_ride_ok;
     r.dbn = plan_dec_bn(&p);
+    // 160 x 128 tiles: forced by option "decode_bm" (the launcher refuses where the form does not exist), or where the form exists and the grid is one
+    // resident round that the 128 x 64 grid is not (B = 800: 474 tiles on 512 slots instead of 1106 on 768)
+    r.dbm = (p.dec_bm == 160 || (p.dec_bm == 0 && plan_dec_bm160_form(&p, r.use_xbits) && decode_bm160_one_round(r.Bp, Fp))) ? 160 : 128;
     r.is_cos = c.loss_func == DAE_LOSS_COSINE;
     r.zstore = r.is_cos && k.backward && p.cos_zstore_ok && p.zbuf;
     r.s_dh = (p.x3 && r.dense_in) ? p.s_dh3 : p.s_dh;
@@ -299,7 +302,7 @@ static int stage_decode(dae_plan* p, const dae_step*, const StepRoute& r, hipStr
     e.dbv_part = backward ? p->dbv_part : nullptr; e.cos_part = p->cos_part;
     e.delta2 = backward ? p->delta2 : nullptr; e.ldd = Fp; e.delta2_t = (backward && !r.dw_tr) ? p->delta2_t : nullptr; e.lddt = p->Bpm;
     e.B = B; e.F = p->F; e.Bp = Bp; e.Fp = Fp; e.dec_act = c.dec_act; e.loss_func = c.loss_func; e.ce_literal = p->ce_literal ? 1 : 0;
-    e.op_scale = r.osc; e.bn = r.dbn;
+    e.op_scale = r.osc; e.bn = r.dbn; e.bm = r.dbm;
     if (r.sym_ride) { e.sym_G = p->G; e.sym_scalars = p->tri_scalars; e.sym_Gs = p->Gs; e.sym_B = B; e.sym_Bp = Bp; }
     // z2 = h W^T: one K segment, or -- split-bf16 -- (h_hi, W_hi) (h_hi, W_lo) (h_lo, W_hi); the row-major h_hi / h_lo are the first and
     // third block of the Gram operand hcat_a = [hi | hi | lo] (leading dimension 3 Hp)
@@ -331,7 +334,7 @@ static int stage_decode(dae_plan* p, const dae_step*, const StepRoute& r, hipStr
 // 8. statistics of this step (autoencoder.py:233 fetch list): their own launch, or a rider of the step tail
 static StatsArgs stats_args(const dae_plan* p, const dae_step* s, const StepRoute& r) {
     const dae_config& c = p->cfg;
-    return StatsArgs{r.is_cos ? p->rowloss_part : nullptr, 1, r.is_cos ? nullptr : p->tile_part, (r.Bp / 128) * (p->Fp / r.dbn), p->cw, r.B, r.Bp,
+    return StatsArgs{r.is_cos ? p->rowloss_part : nullptr, 1, r.is_cos ? nullptr : p->tile_part, r.dbm == 160 ? ((r.Bp + 159) / 160) * (p->Fp / 128) : (r.Bp / 128) * (p->Fp / r.dbn), p->cw, r.B, r.Bp,
                      c.triplet == 3 ? DAE_TRIPLET_BATCH_HARD : c.triplet, c.alpha, p->tri_scalars,
                      (c.triplet == DAE_TRIPLET_BATCH_ALL && !r.ext_mine) ? p->nvalid : nullptr, s->stats, r.fold_finalize ? p->loss_part : nullptr,
                      r.fold_finalize ? p->cnt_part : nullptr};
@@ -413,7 +416,7 @@ static int stage_tail(dae_plan* p, const dae_step* s, const StepRoute& r, hipStr
     const dae_config& c = p->cfg;
     const int B = r.B, Bp = r.Bp, F = p->F, H = p->H, Fp = p->Fp, Hp = p->Hp;
     float* g_bh = p->b.grad + (int64_t)Fp * Hp;
-    const BiasArgs ba{p->dbv_part, 2 * Bp / 128, p->colsum_part, Bp / 32, p->b.bh, H, Hp, F, Fp, c.enc_act, g_bh, g_bh + Hp,
+    const BiasArgs ba{p->dbv_part, r.dbm == 160 ? (Bp + 159) / 160 : 2 * Bp / 128, p->colsum_part, Bp / 32, p->b.bh, H, Hp, F, Fp, c.enc_act, g_bh, g_bh + Hp,
                       r.fuse_bias ? 1 : 0, c.opt, plan_lr(p, s->adam_t), c.momentum, s->grad_scale, p->b.bv,
                       plan_bias_slot(p, p->b.opt_s1), plan_bias_slot(p, p->b.opt_s2)};
     if (r.tail) {

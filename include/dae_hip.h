@@ -887,7 +887,9 @@ int      dae_plan_sync_shadows(dae_plan* p, void* stream);
  * log2 of the largest power of two <= 16 * max_batch (at most 14) for fp16 storage, whose normal range ends at 6.1e-5), "gram64" (16-bit modes, before
  * dae_plan_bind: the split Gram matrix on 64 x 64 tiles over the whole K, ONE slab -- default 1; 0 = 128 x 128 tiles, split-K slabs summed by the miner),
  * "decode_bn" (16-bit modes, before dae_plan_bind: tile width of the decode kernel, 64 | 128 | 0 = by tile count: 128 once the 64-column tiles are more than
- * four rounds of the chip, i.e. F = 50000), "dw_tr" (-1 | 0 | 1: the dW kernel reads x~ and delta2 row-major through transposing LDS reads, so that
+ * four rounds of the chip, i.e. F = 50000), "decode_bm" (tile height of the decode kernel, 0 | 128 | 160: 160 = the 160 x 128 tiles of the three-term 16-bit
+ * decode with a bit image of x, an error for a plan whose mode or loss has no such kernel; 0 = 160 where that kernel exists and its grid is one resident
+ * round of the chip while the 128 x 64 grid is not, e.g. B = 800 at F = 10000), "dw_tr" (-1 | 0 | 1: the dW kernel reads x~ and delta2 row-major through transposing LDS reads, so that
  * delta2^T / x~^T are never written; -1 = for dense train sets only, where it was measured faster), "dw_rounds" (process-wide: rounds of the chip the fused
  * 160 x 128 dW + optimizer kernel may take, default 16 for the split modes / 1 otherwise), "pad_skip" (process-wide, default 1: the decode epilogue does not
  * evaluate the loss of 32-row blocks that are pure batch padding).  Unknown names are an error. */
