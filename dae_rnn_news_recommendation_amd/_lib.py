@@ -144,6 +144,9 @@ SIGNATURES = {
     "dae_threshold_pairs": (i32, [vp, i64, i32, vp, i64, i32, i32, i32, i32, f32, vp, vp, vp, u64, vp, vp, u64, vp]),
     "dae_dedup_lists_workspace": (u64, [i32, i32, i32, i32]),
     "dae_dedup_lists": (i32, [vp, i64, i32, i32, i32, i32, vp, i64, i32, i32, i32, f32, vp, vp, i64, vp, vp, u64, vp]),
+    "dae_mmr_lists_workspace": (u64, [i32, i32, i32, i32]),
+    "dae_mmr_lists": (i32, [vp, i64, i32, i32, i32, i32, vp, i64, vp, i64, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, i64, vp, vp, u64,
+                            vp]),
     "dae_pair_hist_max_bins": (i32, []),
     "dae_pair_hist_workspace": (u64, [i32, i32, i32, i32]),
     "dae_pair_hist": (i32, [vp, i64, i32, vp, vp, i64, i32, vp, i32, i32, i32, f32, f32, i32, vp, vp, vp, u64, vp]),

@@ -34,29 +34,15 @@
 // Chunking.  The workspace is the image, the gather buffer and the validity masks.  dae_dedup_lists_workspace asks for min(Nr, R0)
 // lists, R0 the number whose gather buffer stays within DEDUP_GATHER_BYTES; the entry accepts any workspace that holds the image
 // and one list and walks the rows in chunks of as many lists as fit (never more than R0: the K loop addresses the buffer with
-// 32-bit byte offsets).
-#include "dae_score_sweep.h"
+// 32-bit byte offsets).  The sizes, the carve with its checks and the gather launch live in dae_list_tile.h: dae_mmr.hip (dae_mmr_lists)
+// runs another epilogue on the same gather buffer and the same tile.
+#include "dae_list_tile.h"
 
 #include <cmath>
 
 namespace dae {
 
-constexpr int DEDUP_MAX = 128;                                 // one score tile per list
-// The gather buffer of one chunk.  256 MiB is a GUESS, not a measurement: large enough that a chunk fills the chip many times over
-// (1024 lists at D = 512), small beside the memory of one device.
-constexpr uint64_t DEDUP_GATHER_BYTES = 256ull << 20;
-constexpr int DEDUP_TILE_BYTES = BM * BN * 4;
 constexpr int DEDUP_LDS = DEDUP_TILE_BYTES + 128 * 2 * 8 + 128 * 4;
-
-static inline uint64_t dedup_list_bytes(int64_t Dp) { return (uint64_t)DEDUP_MAX * (uint64_t)Dp * 4; }
-static inline int64_t dedup_r0(int64_t Dp) {
-    const int64_t r = (int64_t)(DEDUP_GATHER_BYTES / dedup_list_bytes(Dp));
-    return r < 1 ? 1 : r;
-}
-// image + gather buffer + validity masks of R lists
-static inline uint64_t dedup_bytes(int64_t Nap, int64_t Dp, int64_t R) {
-    return al256((uint64_t)Nap * Dp * 4) + (uint64_t)R * dedup_list_bytes(Dp) + al256((uint64_t)R * 16);
-}
 
 // grid = 2 R: workgroup b copies the 64 rows of half (b & 1) of list (b >> 1), 16 rows per wave, 16 bytes per lane and step
 __global__ __launch_bounds__(256) void dedup_gather_kernel(const float* __restrict__ image, int Dp, int Na, const int32_t* __restrict__ lists,
@@ -84,6 +70,13 @@ __global__ __launch_bounds__(256) void dedup_gather_kernel(const float* __restri
         const int id = ids[wave * 16 + row];
         dst[e] = id >= 0 ? src[(int64_t)id * q4 + c] : zero;
     }
+}
+
+int launch_list_gather(const float* image, int Dp, int Na, const int32_t* lists, int64_t ldl, int L, int64_t n, float* gathered,
+                       unsigned long long* valid, hipStream_t st) {
+    DAE_LAUNCH(dedup_gather_kernel, dim3((unsigned)(2 * n)), dim3(256), 0, st, image, Dp, Na, lists, ldl, L, gathered, valid);
+    DAE_CHECK_LAUNCH();
+    return 0;
 }
 
 struct DedupParams {
@@ -176,11 +169,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void dedup_tiles_kernel(DedupParam
 
 using namespace dae;
 
-extern "C" uint64_t dae_dedup_lists_workspace(int32_t Nr, int32_t Na, int32_t D, int32_t L) {
-    if (Nr <= 0 || Na <= 0 || D <= 0 || L <= 0) return 0;
-    const int64_t Dp = pad128(D), R0 = dedup_r0(Dp);
-    return dedup_bytes(pad128(Na), Dp, Nr < R0 ? Nr : R0);
-}
+extern "C" uint64_t dae_dedup_lists_workspace(int32_t Nr, int32_t Na, int32_t D, int32_t L) { return list_workspace_bytes(Nr, Na, D, L); }
 
 extern "C" int dae_dedup_lists(const float* E, int64_t lde, int32_t Na, int32_t D, int32_t norm, int32_t metric, const int32_t* lists,
                                int64_t ldl, int32_t Nr, int32_t L, int32_t k, float threshold, int32_t* out_idx, int32_t* out_pos,
@@ -193,24 +182,13 @@ extern "C" int dae_dedup_lists(const float* E, int64_t lde, int32_t Na, int32_t 
     DAE_CHECK_ARG(!std::isnan(threshold), "dedup_lists: threshold is NaN");
     DAE_CHECK_ARG(ldl >= L, "dedup_lists: ldl (%lld) must be >= L (%d)", (long long)ldl, L);
     DAE_CHECK_ARG(ldo >= k, "dedup_lists: ldo (%lld) must be >= k (%d)", (long long)ldo, k);
-    const int64_t Nap = pad128(Na), Dp = pad128(D);
-    DAE_CHECK_ARG(Nap * Dp * 4 < (1ll << 32), "dedup_lists: the corpus image exceeds 4 GiB");
-    const uint64_t least = dedup_bytes(Nap, Dp, 1);
-    DAE_CHECK_ARG(workspace_bytes >= least, "dedup_lists: workspace too small (%llu < %llu bytes: the corpus image and one list)",
-                  (unsigned long long)workspace_bytes, (unsigned long long)least);
-    DAE_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "dedup_lists: workspace must be 256-byte aligned");
-    // lists per chunk: as many as the workspace holds, at most R0 and Nr
-    int64_t R = (int64_t)((workspace_bytes - al256((uint64_t)Nap * Dp * 4)) / (dedup_list_bytes(Dp) + 16));
-    const int64_t R0 = dedup_r0(Dp);
-    if (R > R0) R = R0;
-    if (R > Nr) R = Nr;
-    while (R > 1 && dedup_bytes(Nap, Dp, R) > workspace_bytes) --R;
+    ListWorkspace w;
+    if (int rc = list_workspace_carve("dedup_lists", Na, D, Nr, workspace, workspace_bytes, w)) return rc;
+    const int64_t Dp = w.Dp, R = w.R;
     hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)workspace;
-    float* image = (float*)w;                       w += al256((uint64_t)Nap * Dp * 4);
-    float* gathered = (float*)w;                    w += (uint64_t)R * dedup_list_bytes(Dp);
-    unsigned long long* valid = (unsigned long long*)w;
-    if (int rc = launch_row_normalize(E, lde, Na, D, norm, metric == 0 ? 1 : 0, image, Dp, (int)Dp, (int)Nap, st)) return rc;
+    float* image = w.image; float* gathered = w.gathered;
+    unsigned long long* valid = w.valid;
+    if (int rc = launch_row_normalize(E, lde, Na, D, norm, metric == 0 ? 1 : 0, image, Dp, (int)Dp, (int)w.Nap, st)) return rc;
     DedupParams p;
     memset(&p, 0, sizeof(p));
     sweep_gemm_params(gathered, gathered, Dp, p.g);
@@ -219,9 +197,7 @@ extern "C" int dae_dedup_lists(const float* E, int64_t lde, int32_t Na, int32_t 
         const int64_t n = Nr - i0 < R ? Nr - i0 : R;
         p.lists = lists + i0 * ldl;
         p.out_idx = out_idx + i0 * ldo; p.out_pos = out_pos + i0 * ldo; p.counts = counts + 2 * i0;
-        DAE_LAUNCH(dedup_gather_kernel, dim3((unsigned)(2 * n)), dim3(256), 0, st, (const float*)image, (int)Dp, Na, p.lists, ldl, L, gathered,
-                   valid);
-        DAE_CHECK_LAUNCH();
+        if (int rc = launch_list_gather(image, (int)Dp, Na, p.lists, ldl, L, n, gathered, valid, st)) return rc;
         if (int rc = sweep_launch<dedup_tiles_kernel>(n, DEDUP_LDS, DEDUP_LDS, st, p)) return rc;
     }
     return 0;

@@ -5,8 +5,8 @@ is importable from here; the code lives by subject:
 * ``sweeps`` -- ``pairwise_similarity`` (helpers.py:11-50; the evaluation step ``main_autoencoder.py:307-317`` runs six times right
   after training) and the sweeps by the same scores without the N x N matrix: ``most_similar`` (top-k; ``exclude``,
   ``exclude_shared``, ``window`` / ``candidate_windows``, ``chunk_rows=``, ``dedup_threshold=``), ``target_ranks`` (full rank of one
-  target per row), ``similar_pairs`` (near-duplicate search) and ``dedup_lists`` (greedy de-duplication of recommendation lists);
-  the ``normalize_*`` forms of the row filter; the chunk plan (``sweep_chunk_rows``, ``sweep_chunk_plan``, ``label_stats_blocks``)
+  target per row), ``similar_pairs`` (near-duplicate search), ``dedup_lists`` (greedy de-duplication of recommendation lists) and
+  ``diversify_lists`` (MMR re-ranking of such lists for diversity, with a de-dup threshold and a cap per label); the ``normalize_*`` forms of the row filter; the chunk plan (``sweep_chunk_rows``, ``sweep_chunk_plan``, ``label_stats_blocks``)
   and ``SweepOperand``, one operand of a sweep in the form it came in.
 * ``label_stats`` -- ``visualize_pairwise_similarity`` (helpers.py:79-135) and ``label_similarity_stats``, the same AUROC and box-plot
   numbers without the N x N matrix (``stats_from_histograms``); ``label_precision_at_k``, ``duplicate_groups`` and
@@ -15,7 +15,8 @@ is importable from here; the code lives by subject:
   ``decay_factors``), ``fit_user_model`` / ``UserModel`` on ``user_pair_loss`` (``sample_negatives``,
   ``decay_factor_derivatives``); ``GRUUserModel``, ``gru_user_states`` (``gru_schedule``, ``trim_histories``),
   ``fit_gru_user_model`` on ``gru_pair_loss``.
-* ``evaluation`` -- ``recommend`` / ``recommend_ranks`` with ``next_click_metrics`` / ``rank_metrics``, the popularity baseline
+* ``evaluation`` -- ``recommend`` / ``recommend_ranks`` with ``next_click_metrics`` / ``rank_metrics``, ``recommend_diverse``
+  (``recommend`` + ``diversify_lists``) with ``list_diversity`` (nearest similarity, labels per list), the popularity baseline
   (``popularity_recommend``, ``popularity_ranks``), and the every-click protocol (``click_prefix_lists``, ``every_click_rows``,
   ``recommend_every_click``, ``recommend_ranks_every_click``, ``evaluate_every_click``, ``rank_metrics_by_position``,
   ``popularity_ranks_every_click``).
@@ -27,15 +28,15 @@ is importable from here; the code lives by subject:
 
 The device functions have no CPU implementation: without the built library / a GPU they raise.  torch, scipy and pandas are
 imported inside the functions that need them; importing this package needs numpy alone."""
-from .evaluation import (click_prefix_lists, evaluate_every_click, every_click_rows, next_click_metrics, popularity_ranks,
-                         popularity_ranks_every_click, popularity_recommend, rank_metrics, rank_metrics_by_position, recommend,
-                         recommend_every_click, recommend_ranks, recommend_ranks_every_click)
+from .evaluation import (click_prefix_lists, evaluate_every_click, every_click_rows, list_diversity, next_click_metrics,
+                         popularity_ranks, popularity_ranks_every_click, popularity_recommend, rank_metrics, rank_metrics_by_position,
+                         recommend, recommend_diverse, recommend_every_click, recommend_ranks, recommend_ranks_every_click)
 from .io import read_file, save_file
 from .label_stats import _STAT_KEYS  # noqa: F401  (the tests read it)
 from .label_stats import (duplicate_groups, duplicate_pair_precision, label_precision_at_k, label_similarity_stats,
                           stats_from_histograms, visualize_pairwise_similarity)
 from .sweeps import competitors as _competitors  # noqa: F401  (the tests call it by its earlier name)
-from .sweeps import (SWEEP_AUTO_IMAGE_BYTES, SweepOperand, candidate_windows, dedup_lists, label_stats_blocks, most_similar,
+from .sweeps import (SWEEP_AUTO_IMAGE_BYTES, SweepOperand, candidate_windows, dedup_lists, diversify_lists, label_stats_blocks, most_similar,
                      normalize_exclusions, normalize_shared_exclusions, normalize_window, pairwise_similarity, permute_histories,
                      shared_pairs, shared_row_chunks, similar_pairs, sweep_chunk_plan, sweep_chunk_rows, target_ranks)
 from .user_models import (GRUUserModel, UserModel, decay_factor_derivatives, decay_factors, fit_gru_user_model, fit_user_model,

@@ -1,5 +1,6 @@
 """Recommendation and its evaluation on top of the sweeps and the user models: ``recommend`` / ``recommend_ranks`` (a user's unseen
-articles by relevance; the full rank of the held-out one) with ``next_click_metrics`` and ``rank_metrics``; the popularity
+articles by relevance; the full rank of the held-out one) with ``next_click_metrics`` and ``rank_metrics``; ``recommend_diverse``
+(retrieval, then the MMR re-rank of ``diversify_lists``) with ``list_diversity``; the popularity
 baseline (``popularity_recommend``, ``popularity_ranks``); and the every-click protocol -- ``click_prefix_lists``,
 ``every_click_rows``, ``recommend_every_click``, ``recommend_ranks_every_click``, ``evaluate_every_click``,
 ``rank_metrics_by_position``, ``popularity_ranks_every_click``."""
@@ -8,7 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 from ._device import check_item_range, csr_lists, device_and_library, device_matrix, event_times, history_csr, result, row_count
-from .sweeps import (competitors, most_similar, normalize_exclusions, normalize_window, shared_pairs, shared_row_chunks,
+from .sweeps import (competitors, diversify_lists, most_similar, normalize_exclusions, normalize_window, shared_pairs, shared_row_chunks,
                      target_ranks)
 from .user_models import GRUUserModel, UserModel, gru_user_states, user_states
 
@@ -30,6 +31,76 @@ def recommend(user_vectors, embeddings, k=10, seen=None, norm="", metric="linear
     return most_similar(user_vectors, k=k, norm=norm, metric=metric, candidates=embeddings, exclude=seen, window=window,
                         return_tensor=return_tensor, device=device, dedup_threshold=dedup_threshold, dedup_pool=dedup_pool,
                         dedup_norm=dedup_norm, dedup_metric=dedup_metric)
+
+
+def recommend_diverse(user_vectors, embeddings, k=10, seen=None, lam=0.7, pool=None, norm="", metric="linear kernel", *, window=None,
+                      labels=None, max_per_label=None, dedup_threshold=None, diversity_norm="", diversity_metric="cosine",
+                      scale_relevance="minmax", return_details=False, return_tensor=False, device=None):
+    """``recommend`` followed by ``diversify_lists``: per user ``pool`` unseen, in-window candidates (default ``min(128, 4 * k)``;
+    ``k <= pool <= 128``) are retrieved by relevance (``norm`` / ``metric``, as in ``recommend``) and re-ranked down to ``k`` by
+    Maximal Marginal Relevance with weight ``lam``, the similarity between articles by ``diversity_norm`` / ``diversity_metric``
+    (default cosine), optionally with ``dedup_threshold`` and ``labels`` / ``max_per_label``.  The relevance is rescaled per list
+    to ``[0, 1]`` by default (``scale_relevance``): the inner product is unbounded, the similarity penalty is not.  The corpus
+    goes to the device once for both calls.  Returns what ``diversify_lists`` returns; the relevance is the retrieval's."""
+    k = int(k)
+    pool = min(128, 4 * k) if pool is None else int(pool)
+    if pool < k or pool > 128:
+        raise ValueError(f"pool must be in k..128 = {k}..128 (got {pool})")
+    if not 0.0 <= float(lam) <= 1.0:
+        raise ValueError(f"lam must be in [0, 1] (got {lam})")
+    if max_per_label is not None and (int(max_per_label) < 1 or labels is None):
+        raise ValueError("max_per_label must be at least 1 and needs labels")
+    if scale_relevance not in (None, "minmax"):
+        raise ValueError(f"scale_relevance must be None or 'minmax' (got {scale_relevance!r})")
+    torch, _, dev = device_and_library(device)
+    corpus = device_matrix(torch, embeddings, dev)                       # once, for both calls
+    idx, score = most_similar(user_vectors, k=pool, norm=norm, metric=metric, candidates=corpus, exclude=seen, window=window,
+                              return_tensor=True, device=device)
+    return diversify_lists(idx, score, corpus, k, lam, labels=labels, max_per_label=max_per_label, dedup_threshold=dedup_threshold,
+                           norm=diversity_norm, metric=diversity_metric, scale_relevance=scale_relevance, return_details=return_details,
+                           return_tensor=return_tensor, device=device)
+
+
+def list_diversity(indices, nearest=None, labels=None):
+    """How diverse recommendation lists are.  Host code.  ``indices`` ``[n x k]``, -1 where a list is short; ``nearest`` (same
+    shape, e.g. ``diversify_lists(..., return_details=True)['nearest']``): per entry the similarity to the nearest entry before
+    it; ``labels``: one integer per article.  Returns a dict with, per list (``[n]`` arrays) and averaged over the lists where
+    the figure exists (NaN where none does): ``nearest`` / ``mean_nearest`` -- the mean of ``nearest`` over a list's entries from
+    the second on (NaN for a list of fewer than two); ``n_labels`` / ``mean_n_labels`` -- the number of distinct labels;
+    ``max_label_share`` / ``mean_max_label_share`` -- the largest share of a list one label holds (NaN for an empty list).  The
+    first pair needs ``nearest``, the other two ``labels``; what cannot be computed is left out."""
+    idx = np.asarray(indices)
+    if idx.ndim != 2:
+        raise ValueError("indices must be [n_lists x k]")
+    ok = idx >= 0
+    out = {}
+
+    def mean(x):
+        x = x[~np.isnan(x)]
+        return float(x.mean()) if x.size else float("nan")
+
+    if nearest is not None:
+        near = np.asarray(nearest, dtype=np.float64)
+        if near.shape != idx.shape:
+            raise ValueError(f"nearest must have the shape of indices {idx.shape} (got {near.shape})")
+        later = ok & (np.cumsum(ok, axis=1) > 1)                          # a list's selected entries from the second on
+        n = later.sum(axis=1)
+        per = np.where(n > 0, np.where(later, near, 0.0).sum(axis=1) / np.maximum(n, 1), np.nan)
+        out["nearest"], out["mean_nearest"] = per, mean(per)
+    if labels is not None:
+        lab = np.asarray(labels).ravel()
+        if idx.size and ok.any() and int(idx.max()) >= lab.size:
+            raise ValueError(f"labels holds {lab.size} entries, the lists name article {int(idx.max())}")
+        n_labels = np.zeros(idx.shape[0], dtype=np.int64)
+        share = np.full(idx.shape[0], np.nan)
+        for i in range(idx.shape[0]):
+            row = lab[idx[i][ok[i]]]
+            if row.size:
+                _, c = np.unique(row, return_counts=True)
+                n_labels[i], share[i] = c.size, c.max() / row.size
+        out["n_labels"], out["mean_n_labels"] = n_labels, float(n_labels.mean()) if n_labels.size else float("nan")
+        out["max_label_share"], out["mean_max_label_share"] = share, mean(share)
+    return out
 
 
 def next_click_metrics(indices, targets):

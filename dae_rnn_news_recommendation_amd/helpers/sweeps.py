@@ -1,6 +1,7 @@
 """The score sweeps over two sets of rows, by the scores of ``pairwise_similarity`` (the reference's helpers.py:11-50) and without
 its N x N matrix: ``most_similar`` (top-k), ``target_ranks`` (full rank of one target per row), ``similar_pairs`` (every pair over a
-threshold) and ``dedup_lists`` (greedy de-duplication of such lists); the row filter the first two share (``normalize_exclusions``,
+threshold), ``dedup_lists`` (greedy de-duplication of such lists) and ``diversify_lists`` (MMR re-ranking with a de-dup threshold and
+a per-label cap); the row filter the first two share (``normalize_exclusions``,
 ``normalize_shared_exclusions``, ``normalize_window``, ``candidate_windows``); and the start of every sweep: the chunk plan
 (``sweep_chunk_rows``, ``sweep_chunk_plan``, ``label_stats_blocks``), ``SweepOperand`` and ``sweep_start``."""
 from __future__ import annotations
@@ -8,8 +9,8 @@ from __future__ import annotations
 import numpy as np
 
 from .. import _lib as L
-from ._device import (container, csr_lists, dense_on_device, device_and_library, device_matrix, norm_metric, result, row_count, upload,
-                      workspace)
+from ._device import (container, csr_lists, dense_on_device, device_and_library, device_matrix, matrix_shape, norm_metric, result, row_count,
+                      upload, workspace)
 
 
 def pairwise_similarity(in_df, norm="", metric="cosine", set_diagonal_zero=True, *, return_tensor=False, device=None):
@@ -489,12 +490,7 @@ def dedup_lists(indices, embeddings, k, threshold, *, scores=None, norm="", metr
     torch, lib, dev = device_and_library(device)
     E = device_matrix(torch, embeddings, dev)
     Na, D = int(E.shape[0]), int(E.shape[1])
-    if isinstance(indices, torch.Tensor):
-        lists = indices.to(device=dev)
-    else:
-        lists = torch.as_tensor(np.ascontiguousarray(np.asarray(indices))).to(dev)
-    big = torch.iinfo(torch.int32).max
-    lists = lists.clamp(min=-1, max=big).to(torch.int32).contiguous()           # (an index beyond int32 is beyond every corpus)
+    lists = _list_table(torch, indices, dev)
     out_idx = torch.empty((Nr, k), dtype=torch.int32, device=dev)
     out_pos = torch.empty((Nr, k), dtype=torch.int32, device=dev)
     counts = torch.empty((Nr, 2), dtype=torch.int32, device=dev)
@@ -516,6 +512,111 @@ def dedup_lists(indices, embeddings, k, threshold, *, scores=None, norm="", metr
     if return_counts:
         out = out + ((counts[:, 0].long(), counts[:, 1].long()),)
     return result(out, return_tensor)
+
+
+def _list_table(torch, indices, dev):
+    """The int32 device table of a ``[Nr x L]`` index container (an index beyond int32 is beyond every corpus)."""
+    if isinstance(indices, torch.Tensor):
+        lists = indices.to(device=dev)
+    else:
+        lists = torch.as_tensor(np.ascontiguousarray(np.asarray(indices))).to(dev)
+    return lists.clamp(min=-1, max=torch.iinfo(torch.int32).max).to(torch.int32).contiguous()
+
+
+def diversify_lists(indices, relevance, embeddings, k, lam=0.7, *, labels=None, max_per_label=None, dedup_threshold=None, norm="",
+                    metric="cosine", scale_relevance=None, return_details=False, return_tensor=False, device=None):
+    """Re-ranks recommendation lists for diversity on the device (``dae_mmr_lists``): Maximal Marginal Relevance, optionally with
+    the de-dup rule and a cap on the articles of one label.  ``indices`` ``[Nr x L]`` (ndarray or CUDA tensor, ``L <= 128``) holds
+    per row candidate rows of ``embeddings``, ``relevance`` (same shape) one relevance each -- normally what ``most_similar`` /
+    ``recommend`` returned; no order is assumed.  An entry < 0, past the last row of ``embeddings`` or with a non-finite relevance
+    is never selected.  Each of at most ``k`` steps (``1 <= k <= L``) selects the candidate with the largest
+    ``lam * relevance - (1 - lam) * max(0, similarity to the nearest article already selected)`` (both products and the difference
+    rounded to float32 one by one; equal values: the lowest position), the similarity that of
+    ``pairwise_similarity(embeddings, norm, metric)``.  ``0 <= lam <= 1``: 1 is the stable sort by relevance, 0 looks at relevance
+    for the first pick alone.  ``dedup_threshold`` (default None: off) also drops every candidate whose similarity to a selected
+    article reaches it, as ``dedup_lists`` does; ``max_per_label`` (default None: off; needs ``labels``, one integer per row of
+    ``embeddings``) lets at most that many articles of one label into a list -- labels < 0 are never capped.
+
+    ``scale_relevance="minmax"`` first rescales each row's relevances (the finite ones of entries inside the corpus) to ``[0, 1]``
+    in float32, ``(rel - min) / (max - min)``, a row with ``max == min`` to all 1: the inner product is unbounded while the
+    similarity penalty lives in ``[0, 1]``.
+
+    Returns ``(indices int64 [Nr x k], relevance float32 [Nr x k])`` in selection order: the selected articles, -1 where the
+    row ran out, and the CALLER's relevance of each, tail -inf.  With ``return_details`` a third item, a dict: ``positions`` (in
+    the input row), ``value`` (the criterion at selection), ``nearest`` (the similarity penalty at selection: 0 for the first
+    pick), ``n_selected``, ``n_beyond_topk`` (how many of a row's selected are not among its first ``k`` valid entries) and
+    ``relevance_used`` (``[Nr x L]``, what the rule saw).  ndarrays, or CUDA tensors with ``return_tensor=True``."""
+    nm = norm_metric(norm, metric)
+    shape = tuple(indices.shape) if hasattr(indices, "shape") else np.asarray(indices).shape
+    if len(shape) != 2:
+        raise ValueError("indices must be [n_rows x L]")
+    Nr, Ll = int(shape[0]), int(shape[1])
+    rshape = tuple(relevance.shape) if hasattr(relevance, "shape") else np.asarray(relevance).shape
+    if rshape != (Nr, Ll):
+        raise ValueError(f"relevance must have the shape of indices {(Nr, Ll)} (got {rshape})")
+    k = int(k)
+    if Ll > 128:
+        raise ValueError(f"a list holds at most 128 candidates (got {Ll})")
+    if k < 1 or k > Ll:
+        raise ValueError(f"k must be in 1..L = 1..{Ll} (got {k})")
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:                                             # (false for NaN)
+        raise ValueError(f"lam must be in [0, 1] (got {lam})")
+    threshold = float("inf") if dedup_threshold is None else float(dedup_threshold)
+    if threshold != threshold:
+        raise ValueError("dedup_threshold is NaN")
+    Na, D = matrix_shape(embeddings)
+    cap = 0
+    if max_per_label is not None:
+        cap = int(max_per_label)
+        if cap < 1:
+            raise ValueError(f"max_per_label must be at least 1 (got {max_per_label})")
+        if labels is None:
+            raise ValueError("max_per_label needs labels")
+    if labels is not None and row_count(labels) < Na:
+        raise ValueError(f"labels must hold one entry per row of embeddings ({Na}; got {row_count(labels)})")
+    if scale_relevance not in (None, "minmax"):
+        raise ValueError(f"scale_relevance must be None or 'minmax' (got {scale_relevance!r})")
+    torch, lib, dev = device_and_library(device)
+    E = device_matrix(torch, embeddings, dev)
+    lists = _list_table(torch, indices, dev)
+    rel = relevance.to(device=dev, dtype=torch.float32) if isinstance(relevance, torch.Tensor) else \
+        torch.as_tensor(np.asarray(relevance, dtype=np.float32)).to(dev)
+    rel = rel.contiguous()
+    used = rel
+    if scale_relevance == "minmax" and Nr > 0:
+        ok = (lists >= 0) & (lists < Na) & torch.isfinite(rel)
+        inf = float("inf")
+        lo = rel.masked_fill(~ok, inf).amin(dim=1, keepdim=True)
+        hi = rel.masked_fill(~ok, -inf).amax(dim=1, keepdim=True)
+        flat = hi == lo
+        used = torch.where(ok, torch.where(flat, torch.ones_like(rel), (rel - lo) / (hi - lo).masked_fill(flat, 1.0)), rel).contiguous()
+    lab = None
+    if labels is not None:
+        lab = labels.to(device=dev) if isinstance(labels, torch.Tensor) else torch.as_tensor(np.asarray(labels)).to(dev)
+        lab = lab.reshape(-1).clamp(min=-1, max=torch.iinfo(torch.int32).max).to(torch.int32).contiguous()
+    out_idx = torch.empty((Nr, k), dtype=torch.int32, device=dev)
+    out_pos = torch.empty((Nr, k), dtype=torch.int32, device=dev)
+    out_val = torch.empty((Nr, k), dtype=torch.float32, device=dev)
+    out_near = torch.empty((Nr, k), dtype=torch.float32, device=dev)
+    counts = torch.empty((Nr, 2), dtype=torch.int32, device=dev)
+    if Nr > 0:
+        if Na == 0:
+            raise ValueError("embeddings has no rows")
+        ws_bytes = int(lib.dae_mmr_lists_workspace(Nr, Na, D, Ll))
+        ws_p, ws = workspace(dev, ws_bytes)
+        with torch.cuda.device(dev):
+            L.call("dae_mmr_lists", L.ptr(E), E.stride(0), Na, D, *nm, L.ptr(lists), lists.stride(0), L.ptr(used), used.stride(0), L.ptr(lab),
+                   cap, Nr, Ll, k, lam, threshold, L.ptr(out_idx), L.ptr(out_pos), L.ptr(out_val), L.ptr(out_near), out_idx.stride(0),
+                   L.ptr(counts), ws_p, ws_bytes, L.current_stream())
+    pos = out_pos.long()
+    out_r = torch.gather(rel, 1, pos.clamp(min=0)).masked_fill(pos < 0, float("-inf"))
+    out = result((out_idx.long(), out_r), return_tensor)
+    if return_details:
+        details = {"positions": pos, "value": out_val, "nearest": out_near, "n_selected": counts[:, 0].long(),
+                   "n_beyond_topk": counts[:, 1].long(), "relevance_used": used}
+        out = out + ({name: result(t, return_tensor) for name, t in details.items()},)
+    return out
 
 
 def shared_row_chunks(n, max_pairs=1 << 22):

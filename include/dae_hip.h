@@ -727,6 +727,47 @@ int dae_dedup_lists(const float* E, int64_t lde, int32_t Na, int32_t D, int32_t 
                     int64_t ldo, int32_t* counts, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------------------------------------------------
+ * Diversification of recommendation lists: Maximal Marginal Relevance over every row of a [Nr x L] table of candidate article
+ * indices, with an optional de-dup threshold and an optional cap on the articles of one label (helpers.diversify_lists,
+ * helpers.recommend_diverse).
+ *   E, lde, Na, D, norm, metric: the article vectors, exactly as the corpus of dae_pairwise_similarity, and the same scores:
+ *   s(q, p) of a row is the score dae_pairwise_similarity gives row lists[q] against column lists[p] (the same normalised image,
+ *   the same exact-fp32 products over the whole K range, as in dae_dedup_lists).  The orientation is fixed: row = the selected
+ *   article, column = the candidate.
+ *   lists int32 [Nr x ldl] and rel fp32 [Nr x ldr], L <= 128 entries per row: the candidates and their relevance, normally what
+ *   dae_topk_similarity returned, best first; the rule does not assume that order.  Position p is VALID iff
+ *   0 <= lists[p] < Na and rel[p] is finite (NaN and +-inf make it invalid); an invalid position is never selected and never
+ *   influences anything.  labels int32 [Na] or NULL; max_per_label >= 0, and > 0 needs labels.
+ *   State: m[p] = 0.0f for every position, selected = {}, alive[p] = valid[p].  Each of at most k steps, 1 <= k <= L:
+ *     - for every alive p, v[p] = (lambda (x) rel[p]) (-) ((1 (-) lambda) (x) m[p]), (x) and (-) single correctly rounded fp32
+ *       operations (no fused multiply-add), 0 <= lambda <= 1;
+ *     - the alive p with the largest v[p] is selected, equal values go to the lowest position; val = v[p], near = m[p];
+ *       alive[p] = false;
+ *     - for every alive p', m[p'] = fmaxf(m[p'], s(p, p')): a NaN score leaves m unchanged, so the penalty is
+ *       max(0, max over the selected of s) -- the first pick is the most relevant, a negative similarity earns no bonus;
+ *     - threshold finite (+inf: off; NaN is an argument error): every alive p' with s(p, p') >= threshold, an fp32 compare, becomes
+ *       not alive -- the rule of dae_dedup_lists as a side condition;
+ *     - max_per_label > 0 and c = labels[lists[p]] >= 0: once the number of selected entries with label c equals max_per_label,
+ *       every alive p' with that label becomes not alive.  Labels < 0 are never capped;
+ *     - stop after k selections or when nothing is alive.
+ *   Outputs per row, in selection order, [Nr x ldo], ldo >= k: out_idx (the articles) and out_pos (their positions in the input
+ *   row) int32, tail -1; out_val (val) and out_near (near) fp32, tail -inf.  Nothing past column k is written.  counts int32
+ *   [Nr x 2]: [2 i] the number selected; [2 i + 1] how many of the selected are NOT among the first k valid positions of the row --
+ *   how far the re-rank reached past the plain top-k.
+ *   With lambda = 1, no threshold and no cap the result is the stable sort by relevance; with lambda = 1, a threshold T and a
+ *   best-first row the selected set is that of dae_dedup_lists.  Deterministic: a row's result depends on its own score tile
+ *   alone, bit-identical run to run, independent of the grid and of the chunking below.
+ *   workspace: 256-byte aligned; the layout, the size and the chunking of dae_dedup_lists: dae_mmr_lists_workspace(Nr, Na, D, L)
+ *   asks for the corpus image (below 4 GiB) and min(Nr, R0) lists, and any workspace that holds the image and one list --
+ *   dae_mmr_lists_workspace(1, Na, D, L) -- is accepted, with the same result.
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_mmr_lists_workspace(int32_t Nr, int32_t Na, int32_t D, int32_t L);
+int dae_mmr_lists(const float* E, int64_t lde, int32_t Na, int32_t D, int32_t norm, int32_t metric, const int32_t* lists,
+                  int64_t ldl, const float* rel, int64_t ldr, const int32_t* labels, int32_t max_per_label, int32_t Nr, int32_t L,
+                  int32_t k, float lambda, float threshold, int32_t* out_idx, int32_t* out_pos, float* out_val, float* out_near,
+                  int64_t ldo, int32_t* counts, void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
  * Label statistics without an N x N matrix: the per-class score histograms of all row pairs (helpers.label_similarity_stats).
  *   Q, ldq, Nq, C, ldc, Nc, D, norm, metric: exactly as dae_threshold_pairs, and the same scores.  labels_q_host int32[Nq] and,
  *   with C, labels_c_host int32[Nc] on the HOST (with C == NULL the corpus and its labels are Q's; labels_c_host is ignored).

@@ -20,6 +20,7 @@ examples:
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --fit_user_model --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --every_click --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rec_dedup 0.9 --similarity False
+  python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rec_mmr 0.7 --rec_max_per_label 3 --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --every_click --user_model gru --fit_gru --gru_validation 0.2 --similarity False
 """
 import argparse
@@ -129,6 +130,16 @@ def build_parser():
                         "output and files stay what they are")
     p.add_argument("--rec_dedup_pool", type=int, default=0,
                    help="candidates per user that --rec_dedup T starts from, K..128 (0, the default: min(128, 4 K))")
+    p.add_argument("--rec_mmr", type=float, default=None,
+                   help="LAMBDA in [0, 1] (only with --recommend K): ALSO lists re-ranked for diversity -- per user --rec_mmr_pool unseen "
+                        "candidates are retrieved and K of them selected one by one by Maximal Marginal Relevance, LAMBDA x relevance - "
+                        "(1 - LAMBDA) x cosine similarity to the nearest article already selected (helpers.diversify_lists); prints "
+                        "hit@K / MRR / nDCG and the diversity of the plain and the re-ranked lists and saves "
+                        "article_encoded_recommend{K}_mmr.npz.  The other output and files stay what they are")
+    p.add_argument("--rec_mmr_pool", type=int, default=0,
+                   help="candidates per user that --rec_mmr LAMBDA starts from, K..128 (0, the default: min(128, 4 K))")
+    p.add_argument("--rec_max_per_label", type=int, default=0,
+                   help="N > 0 (only with --rec_mmr LAMBDA): at most N articles of one label (the one --label names) per re-ranked list")
     p.add_argument("--rank_metrics", default=False, **b,
                    help="with --recommend K: also the rank of every held-out click among ALL unseen articles (no users x articles matrix), "
                         "saved to article_encoded_ranks.npz, and AUC, full MRR, mean / median rank and hit@{1, 10, 100} per model")
@@ -186,6 +197,10 @@ def validate(a):
     assert a.rec_dedup is None or a.recommend > 0, "--rec_dedup needs --recommend K"
     assert a.rec_dedup_pool == 0 or a.rec_dedup is not None, "--rec_dedup_pool needs --rec_dedup T"
     assert a.rec_dedup_pool == 0 or a.recommend <= a.rec_dedup_pool <= 128, "--rec_dedup_pool is a number in K..128"
+    assert a.rec_mmr is None or (a.recommend > 0 and 0. <= a.rec_mmr <= 1.), "--rec_mmr LAMBDA needs --recommend K and LAMBDA in [0, 1]"
+    assert a.rec_mmr_pool == 0 or a.rec_mmr is not None, "--rec_mmr_pool needs --rec_mmr LAMBDA"
+    assert a.rec_mmr_pool == 0 or a.recommend <= a.rec_mmr_pool <= 128, "--rec_mmr_pool is a number in K..128"
+    assert a.rec_max_per_label >= 0 and (a.rec_max_per_label == 0 or a.rec_mmr is not None), "--rec_max_per_label N needs --rec_mmr LAMBDA"
     assert not a.fit_user_model or (a.sessions != '' and a.recommend > 0), "--fit_user_model needs --sessions S --recommend K"
     assert a.user_model == 'decay' or (a.sessions != '' and a.recommend > 0 and (a.gru_weights != '' or a.fit_gru)), \
         "--user_model gru needs --sessions S --recommend K and --gru_weights PATH or --fit_gru"
@@ -385,6 +400,8 @@ def evaluate_recommend(a, trY, emb, data_dir):
     print('calculate recommend %d done' % K)
     if a.rec_dedup is not None:
         evaluate_recommend_dedup(a, states, emb, hist, targets, data_dir)
+    if a.rec_mmr is not None:
+        evaluate_recommend_mmr(a, trY, states, emb, hist, targets, data_dir)
     models = {}
     if a.rank_metrics:
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir)
@@ -422,6 +439,42 @@ def evaluate_recommend_dedup(a, states, emb, hist, targets, data_dir, window=Non
     return idx, score
 
 
+def evaluate_recommend_mmr(a, trY, states, emb, hist, targets, data_dir, window=None):
+    """--rec_mmr LAMBDA: the lists of evaluate_recommend once more, re-ranked for diversity (helpers.diversify_lists: Maximal
+    Marginal Relevance with weight LAMBDA over --rec_mmr_pool candidates per user, their relevance rescaled per list to [0, 1],
+    cosine similarity of the embeddings; with --rec_max_per_label N at most N articles of one --label per list).  Prints
+    hit@K / MRR@K / nDCG@K of the plain and the diversified lists and helpers.list_diversity of both: the mean similarity of a
+    list's entries to the nearest entry before them and, with labels, the labels per list and the largest share of one label.
+    Saves ``indices`` / ``scores`` / ``targets`` / ``n_selected`` / ``n_beyond_topk`` / ``nearest`` to
+    article_encoded_recommend{K}[_window]_mmr.npz."""
+    from dae_rnn_news_recommendation_amd import helpers
+    K, lam, cap = a.recommend, a.rec_mmr, a.rec_max_per_label
+    pool = a.rec_mmr_pool if a.rec_mmr_pool > 0 else min(128, 4 * K)
+    name = 'article_encoded_recommend%d%s_mmr.npz' % (K, '' if window is None else '_window')
+    labels = None if trY is None else np.unique(np.asarray(trY), return_inverse=True)[1]
+    assert cap == 0 or labels is not None, "--rec_max_per_label needs labels"
+    print('calculate recommend %d mmr %g' % (K, lam))
+    cand, cand_score = helpers.recommend(states, emb, k=pool, seen=hist, window=window, return_tensor=True)
+    plain, _, p = helpers.diversify_lists(cand, cand_score, emb, K, 1.0, return_details=True)       # lambda = 1: the plain top-K
+    idx, score, d = helpers.diversify_lists(cand, cand_score, emb, K, lam, labels=labels, max_per_label=cap if cap > 0 else None,
+                                            scale_relevance='minmax', return_details=True)
+    np.savez(data_dir + name, indices=idx, scores=score, targets=targets, n_selected=d['n_selected'], n_beyond_topk=d['n_beyond_topk'],
+             nearest=d['nearest'])
+    mean = lambda x: float(x.mean()) if x.size else 0.0
+    before, after = helpers.list_diversity(plain, p['nearest'], labels), helpers.list_diversity(idx, d['nearest'], labels)
+    m0, m = helpers.next_click_metrics(plain, targets), helpers.next_click_metrics(idx, targets)
+    print('  pool %d, lambda %g%s: %.2f selected per list, %.2f of them from beyond the top %d -> %s' % (
+        pool, lam, ', at most %d per label' % cap if cap > 0 else '', mean(d['n_selected']), mean(d['n_beyond_topk']), K, name))
+    print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'plain user state', m0['hit'], m0['mrr'], m0['ndcg']))
+    print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'mmr user state', m['hit'], m['mrr'], m['ndcg']))
+    print('  nearest similarity in a list: before %.4f  after %.4f' % (before['mean_nearest'], after['mean_nearest']))
+    if labels is not None:
+        print('  labels per list: before %.2f  after %.2f; largest label share: before %.4f  after %.4f' % (
+            before['mean_n_labels'], after['mean_n_labels'], before['mean_max_label_share'], after['mean_max_label_share']))
+    print('calculate recommend %d mmr done' % K)
+    return idx, score
+
+
 def evaluate_recommend_window(a, trY, emb, data_dir):
     """--max_age HOURS: evaluate_recommend inside per-user candidate windows (see there)."""
     from dae_rnn_news_recommendation_amd import helpers
@@ -456,6 +509,8 @@ def evaluate_recommend_window(a, trY, emb, data_dir):
     print('calculate recommend %d done' % K)
     if a.rec_dedup is not None:
         evaluate_recommend_dedup(a, states, emb, hist, targets, data_dir, window=window)
+    if a.rec_mmr is not None:
+        evaluate_recommend_mmr(a, trY, states, emb, hist, targets, data_dir, window=window)
     models = {}
     if a.rank_metrics:
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir, window=window, max_age=a.max_age)
