@@ -160,6 +160,10 @@ SIGNATURES = {
     "dae_topk_images": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, u64, vp]),
     "dae_pair_hist_images_workspace": (u64, [i32, i32, i32]),
     "dae_pair_hist_images": (i32, [vp, i32, vp, vp, i32, vp, i32, f32, f32, i32, vp, vp, vp, u64, vp]),
+    "dae_kmeans_assign_workspace": (u64, [i32, i32]),
+    "dae_kmeans_assign": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, u64, vp]),
+    "dae_kmeans_update_workspace": (u64, [i32, i32, i32]),
+    "dae_kmeans_update": (i32, [vp, i32, i32, vp, i32, vp, i64, vp, vp, vp, vp, vp, u64, vp]),
     "dae_csr_column_stats_workspace": (u64, []),
     "dae_csr_column_stats": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, u64, vp]),
     "dae_csr_select_columns_workspace": (u64, [i32]),

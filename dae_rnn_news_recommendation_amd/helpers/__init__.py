@@ -23,11 +23,16 @@ is importable from here; the code lives by subject:
 * ``vectorize`` -- the stage in front of training (main_autoencoder.py:206-240) on a raw count matrix that stays on the device as
   CSR: ``column_stats`` (df and tf per column), ``limit_features`` / ``limit_features_columns`` / ``select_columns``
   (``CountVectorizer._limit_features``), ``TfidfTransformer`` (sklearn's, fitted on train, applied to validation), ``binarize``.
+* ``clustering`` -- spherical k-means on the device (``kmeans`` -> ``KMeansResult``, ``kmeans_assign``, ``relocation_rows``),
+  ``cluster_label_scores`` (purity / NMI / ARI against labels; host code) and ``ClusterIndex``, cluster-probed top-k on the windowed
+  ``most_similar`` (``merge_probe_lists``).
 * ``_device`` -- what every device call starts and ends with, once: device and library, the ``norm`` / ``metric`` check, the
   matrix and history intakes, uploads, workspaces, the result tail.
 
 The device functions have no CPU implementation: without the built library / a GPU they raise.  torch, scipy and pandas are
 imported inside the functions that need them; importing this package needs numpy alone."""
+from .clustering import (ClusterIndex, KMeansResult, cluster_label_scores, kmeans, kmeans_assign, merge_probe_lists,
+                         relocation_rows)
 from .evaluation import (click_prefix_lists, evaluate_every_click, every_click_rows, list_diversity, next_click_metrics,
                          popularity_ranks, popularity_ranks_every_click, popularity_recommend, rank_metrics, rank_metrics_by_position,
                          recommend, recommend_diverse, recommend_every_click, recommend_ranks, recommend_ranks_every_click)

@@ -847,6 +847,37 @@ int dae_pair_hist_images(const float* Qi, int32_t Nq, const int32_t* labels_q_ho
                          double* out16_host, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------------------------------------------------
+ * Spherical k-means on the device (helpers.kmeans / kmeans_assign / ClusterIndex): one Lloyd iteration is dae_kmeans_assign
+ * followed by dae_kmeans_update.  Both read sweep images the caller built (dae_sweep_image_dense / dae_sweep_image_csr):
+ * Xi [dae_pad(N) x dae_pad(D)] of the rows, Ci [dae_pad(K) x dae_pad(D)] of the centroids, 256-byte aligned, each below 4 GiB.
+ * Both return host numbers and so synchronise the stream.
+ *   dae_kmeans_assign: labels[i] int32 = the centroid j < K with the largest score Xi[i] . Ci[j] (the exact-fp32 products of the
+ *   other sweeps), ties to the lower j with -0 and +0 one score (the order of dae_topk_similarity), scores[i] fp32 = that score;
+ *   a padded centroid row never wins.  A row whose scores are all -inf or NaN gets label -1, score -inf (dae_topk_similarity
+ *   returns a column for -inf and lets a NaN win; on finite scores the two agree bit for bit).  prev_labels int32[N] or NULL.
+ *   out_host (host, double[4]): [0] the fp64 sum of scores, folded in a fixed order (a fixed tree per 128 rows, then the tiles
+ *   ascending by thread and a fixed tree), [1] the rows whose label differs from prev_labels (N when it is NULL), [2] the grid of
+ *   the sweep, [3] its centroid slices per row tile.  Bit-identical from run to run.
+ *   workspace: dae_kmeans_assign_workspace(N, K) bytes, 256-byte aligned.
+ *   dae_kmeans_update: counts int32[K], offsets int64[K + 1] (the exclusive scan of counts) and order int32[N] -- the row ids
+ *   sorted by (label, row id), a stable sort; rows whose label is outside [0, K) take no part and form the tail of order.  For
+ *   every cluster with members, s_d = the fp64 sum of its image rows in a fixed order (segments of at most 256 consecutive
+ *   members of order, each summed ascending, the segment sums added ascending), n2 = the fp64 sum of s_d^2 in a fixed order, and
+ *   centroids[c][d] = fl32(s_d / sqrt(n2)) for d < D (centroids fp32 [K x ldc], ldc >= D).  A cluster without members, or with
+ *   n2 == 0, keeps its row.  centroids == NULL: counts / offsets / order alone.  No floating-point atomics: bit-identical from run
+ *   to run.  out_host (host, double[4]): [0] rows left out, [1] clusters without members, [2] clusters with members and n2 == 0,
+ *   [3] segments.  workspace: dae_kmeans_update_workspace(N, K, D) bytes, 256-byte aligned; the size includes the scratch
+ *   rocprim asks for on the current device, so ask on the device that runs the call (0: the query failed, and so will the call).
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_kmeans_assign_workspace(int32_t N, int32_t K);
+int dae_kmeans_assign(const float* Xi, int32_t N, const float* Ci, int32_t K, int32_t D, const int32_t* prev_labels,
+                      int32_t* labels, float* scores, double* out_host, void* workspace, uint64_t workspace_bytes, void* stream);
+uint64_t dae_kmeans_update_workspace(int32_t N, int32_t K, int32_t D);
+int dae_kmeans_update(const float* Xi, int32_t N, int32_t D, const int32_t* labels, int32_t K, float* centroids, int64_t ldc,
+                      int32_t* counts, int32_t* order, int64_t* offsets, double* out_host, void* workspace,
+                      uint64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
  * From a count matrix to the training input (helpers.column_stats / limit_features / select_columns / TfidfTransformer): what
  * sklearn's CountVectorizer._limit_features and TfidfTransformer do to a bag of words, on CSR rows that stay on the device.
  * CSR as dae_sweep_image_csr: indptr int64[rows + 1] points at the chunk's first row and holds offsets into indices int32 /

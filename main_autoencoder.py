@@ -21,6 +21,8 @@ examples:
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --every_click --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rec_dedup 0.9 --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rec_mmr 0.7 --rec_max_per_label 3 --similarity False
+  python main_autoencoder.py --model_name topics --cluster 40 --validation --similarity False
+  python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --ann_clusters 64 --ann_probe 8 --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --every_click --user_model gru --fit_gru --gru_validation 0.2 --similarity False
 """
 import argparse
@@ -176,6 +178,19 @@ def build_parser():
     p.add_argument("--gru_validation", type=float, default=0.,
                    help="FRACTION in (0, 1) with --fit_gru: hold out that share of the users (drawn by the fit's seed), train on the rest and "
                         "print the every-click MRR of the held-out users after every epoch (helpers.fit_gru_user_model(validation=...))")
+    p.add_argument("--cluster", type=int, default=0,
+                   help="K > 0: after encoding, spherical k-means of the train embeddings into K clusters on the device (helpers.kmeans): "
+                        "iterations, mean score, cluster sizes and, with labels, purity / NMI / ARI against them; labels, centroids, counts "
+                        "and history go to article_encoded_clusters.npz; with --validation the validation embeddings are assigned to the "
+                        "same centroids")
+    p.add_argument("--cluster_iters", type=int, default=50, help="centroid updates of --cluster K at the most")
+    p.add_argument("--cluster_seed", type=int, default=0, help="seed of --cluster K's random start")
+    p.add_argument("--cluster_n_init", type=int, default=1, help="restarts of --cluster K (seeds S, S + 1, ...); the best mean score is kept")
+    p.add_argument("--ann_clusters", type=int, default=0,
+                   help="C > 0 (only with --recommend K): ALSO the lists of a cluster index (helpers.ClusterIndex: k-means into C clusters, "
+                        "every user scored against the articles of the --ann_probe nearest clusters only): recall@K against the exact "
+                        "lists, hit / MRR / nDCG and the share of the corpus scored per user; saves article_encoded_recommend{K}_ann.npz")
+    p.add_argument("--ann_probe", type=int, default=8, help="clusters probed per user by --ann_clusters C, 1..128")
     return p
 
 
@@ -210,6 +225,10 @@ def validate(a):
     assert 0. <= a.gru_validation < 1., "--gru_validation is a fraction in [0, 1)"
     assert a.gru_validation == 0. or a.fit_gru, "--gru_validation needs --fit_gru"
     assert a.max_age >= 0., "--max_age is a number of hours"
+    assert a.cluster >= 0 and a.cluster_iters >= 0 and a.cluster_n_init >= 1, "--cluster K, --cluster_iters I >= 0, --cluster_n_init R >= 1"
+    assert a.ann_clusters == 0 or (a.ann_clusters > 0 and a.recommend > 0 and a.max_age == 0.), \
+        "--ann_clusters C needs --recommend K (and does not go with --max_age: an index takes no windows)"
+    assert 1 <= a.ann_probe <= 128, "--ann_probe is a number in 1..128"
     assert a.max_age == 0. or (a.sessions == 'synthetic' and a.recommend > 0), "--max_age needs --sessions synthetic --recommend K"
     return a
 
@@ -402,6 +421,8 @@ def evaluate_recommend(a, trY, emb, data_dir):
         evaluate_recommend_dedup(a, states, emb, hist, targets, data_dir)
     if a.rec_mmr is not None:
         evaluate_recommend_mmr(a, trY, states, emb, hist, targets, data_dir)
+    if a.ann_clusters > 0:
+        evaluate_recommend_ann(a, states, emb, hist, idx, targets, data_dir)
     models = {}
     if a.rank_metrics:
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir)
@@ -412,6 +433,61 @@ def evaluate_recommend(a, trY, emb, data_dir):
     if a.every_click:
         evaluate_every_click(a, emb, (indptr, items), t, None, models, data_dir)
     return idx, score, targets
+
+
+def evaluate_recommend_ann(a, states, emb, hist, exact, targets, data_dir):
+    """--ann_clusters C [--ann_probe P]: the lists of evaluate_recommend once more through a cluster index (helpers.ClusterIndex:
+    k-means of the train embeddings into C clusters; every user state is scored against the unseen articles of its P nearest
+    clusters only -- for the inner product the choice of clusters is a heuristic).  Prints recall@K against the exact lists, hit@K /
+    MRR@K / nDCG@K and the share of the corpus scored per user; saves ``indices`` / ``scores`` / ``targets`` / ``order`` / ``offsets``
+    / ``centroids`` to article_encoded_recommend{K}_ann.npz."""
+    from dae_rnn_news_recommendation_amd import helpers
+    K, C, P = a.recommend, min(a.ann_clusters, emb.shape[0]), a.ann_probe
+    print('calculate recommend %d through %d clusters, %d probed' % (K, C, P))
+    index = helpers.ClusterIndex.build(emb, C, '', 'linear kernel', max_iter=a.cluster_iters, seed=a.cluster_seed)
+    idx, score = index.search(states, K, n_probe=P, exclude=hist)
+    exact = np.asarray(exact)
+    found = ((idx[:, :, None] == exact[:, None, :]) & (idx[:, :, None] >= 0)).any(axis=2).sum()
+    recall = found / max(int((exact >= 0).sum()), 1)
+    name = 'article_encoded_recommend%d_ann.npz' % K
+    np.savez(data_dir + name, indices=idx, scores=score, targets=targets, order=index.order, offsets=index.offsets, centroids=index.centroids,
+             n_probe=np.int64(P))
+    m = helpers.next_click_metrics(idx, targets)
+    print('  recall@%d against the exact lists %.4f, %.4f of the corpus scored per user -> %s' % (K, recall, index.probed_fraction(states, P), name))
+    print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'cluster index', m['hit'], m['mrr'], m['ndcg']))
+    print('calculate recommend through clusters done')
+    return idx, score
+
+
+def evaluate_clusters(a, trY, vlY, emb, emb_v, data_dir):
+    """--cluster K: spherical k-means of the train embeddings (helpers.kmeans, on the device): iterations, mean score, the largest
+    and the smallest cluster and the empty clusters relocated; with labels purity / NMI / ARI against them
+    (helpers.cluster_label_scores).  ``labels`` / ``centroids`` / ``counts`` / ``scores`` / ``history`` go to
+    article_encoded_clusters.npz.  The validation embeddings are assigned to the same centroids (helpers.kmeans_assign) and scored the
+    same way; their ``labels`` / ``scores`` go to article_encoded_validate_clusters.npz."""
+    from dae_rnn_news_recommendation_amd import helpers
+    K = min(a.cluster, emb.shape[0])
+    print('calculate clusters %d' % K)
+    res = helpers.kmeans(emb, K, max_iter=a.cluster_iters, seed=a.cluster_seed, n_init=a.cluster_n_init)
+    np.savez(data_dir + 'article_encoded_clusters.npz', labels=res.labels, centroids=res.centroids, counts=res.counts, scores=res.scores,
+             history=np.asarray(res.history, dtype=np.float64))
+
+    def against(labels, true):
+        if true is None:
+            return ''
+        s = helpers.cluster_label_scores(labels, np.unique(np.asarray(true), return_inverse=True)[1])
+        return '  purity %.4f  NMI %.4f  ARI %.4f (%d articles, %d labels)' % (s['purity'], s['nmi'], s['ari'], s['n'], s['n_labels'])
+    print('  train     %d iterations, mean score %.6f, clusters of %d .. %d articles, %d empty clusters relocated%s -> '
+          'article_encoded_clusters.npz' % (res.n_iter, res.mean_score, int(res.counts.min()), int(res.counts.max()), res.relocated,
+                                            against(res.labels, trY)))
+    if emb_v is not None:
+        lab_v, score_v = helpers.kmeans_assign(emb_v, res.centroids)
+        np.savez(data_dir + 'article_encoded_validate_clusters.npz', labels=lab_v, scores=score_v)
+        sizes = np.bincount(lab_v, minlength=K)
+        print('  validate  mean score %.6f, clusters of %d .. %d articles%s -> article_encoded_validate_clusters.npz'
+              % (float(score_v.astype(np.float64).mean()), int(sizes.min()), int(sizes.max()), against(lab_v, vlY)))
+    print('calculate clusters done')
+    return res
 
 
 def evaluate_recommend_dedup(a, states, emb, hist, targets, data_dir, window=None):
@@ -800,6 +876,8 @@ def main(argv=None):
         evaluate_top_k(a, trX, vlX, trY, vlY, emb, emb_v, model.data_dir)
     if a.dup_threshold > 0 and dp.rank() == 0:
         evaluate_duplicates(a, trY, vlY, emb, emb_v, model.data_dir)
+    if a.cluster > 0 and dp.rank() == 0:
+        evaluate_clusters(a, trY, vlY, emb, emb_v, model.data_dir)
     if a.recommend > 0 and dp.rank() == 0:
         evaluate_recommend(a, trY, emb, model.data_dir)
     if model.samples_per_sec:
