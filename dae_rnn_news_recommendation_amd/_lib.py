@@ -137,6 +137,12 @@ SIGNATURES = {
     "dae_gru_user_states_workspace": (u64, [i32, i32, i32, i64]),
     "dae_gru_user_states": (i32, [vp, i64, i32, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, i64, i32, vp, i64,
                                   vp, u64, vp]),
+    "dae_lstm_user_states_workspace": (u64, [i32, i32, i32, i64]),
+    "dae_lstm_user_states": (i32, [vp, i64, i32, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, i64, vp, i64, i32,
+                                   vp, i64, vp, i64, vp, u64, vp]),
+    "dae_rnn_user_states_workspace": (u64, [i32, i32, i32, i64]),
+    "dae_rnn_user_states": (i32, [vp, i64, i32, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, i64, i32, vp, i64,
+                                  vp, u64, vp]),
     "dae_gru_pair_loss_workspace": (u64, [i32, i32, i64, i64, i32, i32]),
     "dae_gru_pair_loss": (i32, [vp, i64, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, i32, vp, vp, vp, i64, vp, i64,
                                 vp, vp, vp, vp, u64, vp]),

@@ -11,7 +11,7 @@ import numpy as np
 from ._device import check_item_range, csr_lists, device_and_library, device_matrix, event_times, history_csr, result, row_count
 from .sweeps import (competitors, diversify_lists, most_similar, normalize_exclusions, normalize_window, shared_pairs, shared_row_chunks,
                      target_ranks)
-from .user_models import GRUUserModel, UserModel, gru_user_states, user_states
+from .user_models import GRUUserModel, LSTMUserModel, RNNUserModel, UserModel, user_states
 
 
 def recommend(user_vectors, embeddings, k=10, seen=None, norm="", metric="linear kernel", *, window=None, return_tensor=False,
@@ -355,13 +355,16 @@ def recommend_ranks_every_click(states, embeddings, histories, *, window=None, b
                   return_tensor)
 
 
+_RECURRENT = (GRUUserModel, LSTMUserModel, RNNUserModel)
+
+
 def evaluate_every_click(histories, embeddings, model, *, timestamps=None, time_unit=None, window=None, batch_users=4096,
                          ks=(1, 5, 10, 50, 100), device=None):
     """Next-click evaluation at EVERY click of every history (the per-position protocol of session-based recommendation), where
     the last-click protocol scores one click per user: the state after each event is ranked against the event that follows,
     among all the articles the user had not clicked by then (``recommend_ranks_every_click``).
 
-    ``model``: a ``GRUUserModel`` (states of ``gru_user_states``), a fitted ``UserModel`` (``alpha *`` the states of ``user_states``
+    ``model``: a ``GRUUserModel``, ``LSTMUserModel`` or ``RNNUserModel`` (the ``all_states`` rows of its ``.states``), a fitted ``UserModel`` (``alpha *`` the states of ``user_states``
     with its ``beta`` and ``time_unit``, as ``UserModel.states`` applies them) or a float ``beta`` (``user_states``; ``time_unit``
     as there).  ``timestamps`` (one per event) drive the decay of the two decay forms; ``window`` is a pair ``(lo, hi)`` per EVENT.
     The states are produced for ``batch_users`` users at a time and ranked at once, so [events x H] never exists whole.
@@ -377,7 +380,7 @@ def evaluate_every_click(histories, embeddings, model, *, timestamps=None, time_
         raise ValueError(f"{t.size} timestamps for {nnz} events")
     if window is not None:
         window = normalize_window(window, nnz, row_count(embeddings))
-    if not isinstance(model, (GRUUserModel, UserModel)):
+    if not isinstance(model, _RECURRENT + (UserModel,)):
         model = float(model)
     torch, _, dev = device_and_library(device)
     E = device_matrix(torch, embeddings, dev, in_place=True)
@@ -390,8 +393,8 @@ def evaluate_every_click(histories, embeddings, model, *, timestamps=None, time_
             continue
         hist = (indptr[u0:u1 + 1] - a, items[a:b])
         tb = None if t is None else t[a:b]
-        if isinstance(model, GRUUserModel):
-            S = gru_user_states(hist, E, model, all_states=True, return_tensor=True, device=device)
+        if isinstance(model, _RECURRENT):
+            S = model.states(hist, E, all_states=True, return_tensor=True, device=device)
         elif isinstance(model, UserModel):
             S = user_states(hist, E, model.beta, timestamps=tb, time_unit=model.time_unit, all_states=True, return_tensor=True,
                             device=device) * alpha

@@ -2,7 +2,8 @@
 model: ``user_states`` (``decay_factors``), and its trained form ``fit_user_model`` -> ``UserModel`` on the loss and gradients of
 ``user_pair_loss`` (``sample_negatives``, ``decay_factor_derivatives``).  The recurrent model: ``GRUUserModel`` (weights in the
 layout of ``torch.nn.GRU``), ``gru_user_states`` (``gru_schedule``, ``trim_histories``), and its training ``fit_gru_user_model`` on
-``gru_pair_loss`` (back-propagation through time on the device)."""
+``gru_pair_loss`` (back-propagation through time on the device).  The paper's other two recurrent cells, states from given
+weights: ``LSTMUserModel`` / ``lstm_user_states`` and ``RNNUserModel`` / ``rnn_user_states``."""
 from __future__ import annotations
 
 import numpy as np
@@ -168,6 +169,82 @@ def trim_histories(histories, max_events):
     return out, items[pos]
 
 
+def _recurrent_user_states(cell, cls, histories, embeddings, model, initial, max_events, all_states, batch_users, return_tensor, device,
+                           return_cell=False):
+    """The intake, chunk loop and schedule shared by ``gru_user_states``, ``lstm_user_states`` and ``rnn_user_states``:
+    ``dae_{cell}_user_states`` on the weights of ``model`` (a ``cls``).  ``initial``: a tuple of start states, ``(h,)`` or, for the
+    LSTM, ``(h, c)``, each ``[users x H]`` or None.  Returns ``(U, C)``; ``C`` (LSTM with ``return_cell``) is the cell state after
+    every user's last event, else None."""
+    import torch
+    if not isinstance(model, cls):
+        raise TypeError(f"model must be a {cls.__name__} ({cls.__name__}.load / from_torch)")
+    if max_events is not None and all_states:
+        raise ValueError("max_events and all_states do not go together: the rows of all_states are the caller's events")
+    if int(batch_users) < 1:
+        raise ValueError(f"batch_users must be positive (got {batch_users})")
+    indptr, items = history_csr(histories)
+    if max_events is not None:
+        indptr, items = trim_histories((indptr, items), max_events)
+    H, D = model.hidden_size, model.input_size
+    M, nnz = int(indptr.size - 1), int(items.size)
+
+    def check_embeddings(shape):
+        if int(shape[1]) != D:
+            raise ValueError(f"embeddings have {int(shape[1])} columns, the model's weight_ih has {D}")
+        check_item_range(items, int(shape[0]))
+    if not isinstance(embeddings, torch.Tensor):                        # a host container: refused before any device work
+        check_embeddings(matrix_shape(embeddings))
+    initial = list(initial)
+    for k, name in enumerate(("initial", "initial c")[:len(initial)]):
+        if initial[k] is not None and not isinstance(initial[k], torch.Tensor):
+            initial[k] = np.asarray(initial[k], dtype=np.float32)
+        if initial[k] is not None and tuple(initial[k].shape) != (M, H):
+            raise ValueError(f"{name} must be [users x H] = [{M} x {H}] (got {tuple(initial[k].shape)})")
+    _, lib, dev = device_and_library(device)
+    E = device_matrix(torch, embeddings, dev, in_place=True)
+    Na = int(E.shape[0])
+    check_embeddings(E.shape)
+    rows = nnz if all_states else M
+    U = torch.empty((rows, H), dtype=torch.float32, device=dev)
+
+    def on_device(x):
+        return (x.to(device=dev, dtype=torch.float32) if isinstance(x, torch.Tensor) else torch.as_tensor(x).to(dev)).contiguous()
+    if rows == 0:                                                       # no row of U; C is the initial c, or zeros
+        C = None
+        if return_cell:
+            C = on_device(initial[1]).clone() if initial[1] is not None else torch.zeros((M, H), dtype=torch.float32, device=dev)
+        return result(U, return_tensor), (None if C is None else result(C, return_tensor))
+    if Na == 0:
+        raise ValueError("embeddings hold no articles")
+    start = [None if x is None else on_device(x) for x in initial]
+    C = torch.empty((M, H), dtype=torch.float32, device=dev) if return_cell else None     # every row is written: last step, or the init kernel
+    w = [torch.from_numpy(getattr(model, n)).to(dev) for n in cls.NAMES]
+    it_d = upload(items.astype(np.int32), dev)
+    chunk = min(int(batch_users), M)
+    ws_bytes = int(getattr(lib, f"dae_{cell}_user_states_workspace")(Na, D, H, chunk))
+    ws_ptr, ws = workspace(dev, ws_bytes)
+    import ctypes
+    with torch.cuda.device(dev):
+        for c0 in range(0, M, chunk):
+            c1 = min(c0 + chunk, M)
+            e0, e1 = int(indptr[c0]), int(indptr[c1])
+            ip = np.ascontiguousarray(indptr[c0:c1 + 1] - e0)
+            order, active = gru_schedule(ip)
+            ip_d, or_d = torch.from_numpy(ip).to(dev), torch.from_numpy(order).to(dev)
+            Uc = U[e0:e1] if all_states else U[c0:c1]
+            first = []                                                  # (h0, ldh0) and, for the LSTM, (c0, ldc0)
+            for x in start:
+                first += [L.ptr(None if x is None else x[c0:c1]), H]
+            out = [ctypes.c_void_p(Uc.data_ptr()), U.stride(0)]         # (U, ldu) and, for the LSTM, (C, ldc)
+            if cell == "lstm":
+                out += [None if C is None else ctypes.c_void_p(C[c0:c1].data_ptr()), H]
+            L.call(f"dae_{cell}_user_states", L.ptr(E), E.stride(0), Na, D, H, L.ptr(w[0]), D, L.ptr(w[1]), H, L.ptr(w[2]), L.ptr(w[3]),
+                   L.ptr(ip_d), ctypes.c_void_p(it_d.data_ptr() + 4 * e0), L.ptr(or_d), c1 - c0, e1 - e0, int(active.size),
+                   active.ctypes.data_as(ctypes.c_void_p), *first, 1 if all_states else 0, *out, ws_ptr, ws_bytes, L.current_stream())
+    del ws
+    return result(U, return_tensor), (None if C is None else result(C, return_tensor))
+
+
 def gru_user_states(histories, embeddings, model, *, initial=None, max_events=None, all_states=False, batch_users=262144,
                     return_tensor=False, device=None):
     """User states from browsing histories by the recurrent (GRU) user model of "Embedding-based News Recommendation for Millions
@@ -190,64 +267,145 @@ def gru_user_states(histories, embeddings, model, *, initial=None, max_events=No
     Returns float32 ``[users x H]``: the state after each user's last event (zeros, or the ``initial`` row, for an empty
     history); with ``all_states=True`` ``[events x H]``: row e is the state after event e, the one that predicts event e + 1,
     and the row of a user's last event equals that user's row of the default form bit for bit."""
-    import torch
-    if not isinstance(model, GRUUserModel):
-        raise TypeError("model must be a GRUUserModel (GRUUserModel.load / from_torch)")
-    if max_events is not None and all_states:
-        raise ValueError("max_events and all_states do not go together: the rows of all_states are the caller's events")
-    if int(batch_users) < 1:
-        raise ValueError(f"batch_users must be positive (got {batch_users})")
-    indptr, items = history_csr(histories)
-    if max_events is not None:
-        indptr, items = trim_histories((indptr, items), max_events)
-    H, D = model.hidden_size, model.input_size
-    M, nnz = int(indptr.size - 1), int(items.size)
+    return _recurrent_user_states("gru", GRUUserModel, histories, embeddings, model, (initial,), max_events, all_states, batch_users,
+                                  return_tensor, device)[0]
 
-    def check_embeddings(shape):
-        if int(shape[1]) != D:
-            raise ValueError(f"embeddings have {int(shape[1])} columns, the model's weight_ih has {D}")
-        check_item_range(items, int(shape[0]))
-    if not isinstance(embeddings, torch.Tensor):                        # a host container: refused before any device work
-        check_embeddings(matrix_shape(embeddings))
-    if initial is not None and not isinstance(initial, torch.Tensor):
-        initial = np.asarray(initial, dtype=np.float32)
-    if initial is not None and tuple(initial.shape) != (M, H):
-        raise ValueError(f"initial must be [users x H] = [{M} x {H}] (got {tuple(initial.shape)})")
-    _, lib, dev = device_and_library(device)
-    E = device_matrix(torch, embeddings, dev, in_place=True)
-    Na = int(E.shape[0])
-    check_embeddings(E.shape)
-    rows = nnz if all_states else M
-    U = torch.empty((rows, H), dtype=torch.float32, device=dev)
-    if rows == 0:
-        return result(U, return_tensor)
-    if Na == 0:
-        raise ValueError("embeddings hold no articles")
-    h0 = None
-    if initial is not None:
-        h0 = (initial.to(device=dev, dtype=torch.float32) if isinstance(initial, torch.Tensor)
-              else torch.as_tensor(np.asarray(initial, dtype=np.float32)).to(dev)).contiguous()
-    w = [torch.from_numpy(getattr(model, n)).to(dev) for n in GRUUserModel.NAMES]
-    it_d = upload(items.astype(np.int32), dev)
-    chunk = min(int(batch_users), M)
-    ws_bytes = int(lib.dae_gru_user_states_workspace(Na, D, H, chunk))
-    ws_ptr, ws = workspace(dev, ws_bytes)
-    import ctypes
-    with torch.cuda.device(dev):
-        for c0 in range(0, M, chunk):
-            c1 = min(c0 + chunk, M)
-            e0, e1 = int(indptr[c0]), int(indptr[c1])
-            ip = np.ascontiguousarray(indptr[c0:c1 + 1] - e0)
-            order, active = gru_schedule(ip)
-            ip_d, or_d = torch.from_numpy(ip).to(dev), torch.from_numpy(order).to(dev)
-            Uc = U[e0:e1] if all_states else U[c0:c1]
-            h0c = None if h0 is None else h0[c0:c1]
-            L.call("dae_gru_user_states", L.ptr(E), E.stride(0), Na, D, H, L.ptr(w[0]), D, L.ptr(w[1]), H, L.ptr(w[2]), L.ptr(w[3]),
-                   L.ptr(ip_d), ctypes.c_void_p(it_d.data_ptr() + 4 * e0), L.ptr(or_d), c1 - c0, e1 - e0, int(active.size),
-                   active.ctypes.data_as(ctypes.c_void_p), L.ptr(h0c), H, 1 if all_states else 0,
-                   ctypes.c_void_p(Uc.data_ptr()), U.stride(0), ws_ptr, ws_bytes, L.current_stream())
-    del ws
-    return result(U, return_tensor)
+
+class _TorchCellUserModel:
+    """What ``LSTMUserModel`` and ``RNNUserModel`` share: float32 weights in the layout of the ``torch.nn`` module ``MODULE`` (one
+    layer, unidirectional, with bias; ``GATES`` row blocks of H rows), ``save`` / ``load`` in an ``.npz`` under the four ``NAMES``,
+    ``from_torch``.  Host code."""
+    NAMES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
+    GATES, MODULE = 0, ""
+
+    def __init__(self, weight_ih, weight_hh, bias_ih, bias_hh):
+        G, rows = self.GATES, ("%dH" % self.GATES if self.GATES > 1 else "H")
+        w = [np.ascontiguousarray(np.asarray(a, dtype=np.float32)) for a in (weight_ih, weight_hh, bias_ih, bias_hh)]
+        self.weight_ih, self.weight_hh, self.bias_ih, self.bias_hh = w
+        if self.weight_hh.ndim != 2 or self.weight_hh.shape[0] != G * self.weight_hh.shape[1] or self.weight_hh.shape[1] < 1:
+            raise ValueError(f"weight_hh of an {self.MODULE} must be [{rows} x H] (got {self.weight_hh.shape})")
+        H = int(self.weight_hh.shape[1])
+        if self.weight_ih.ndim != 2 or self.weight_ih.shape[0] != G * H or self.weight_ih.shape[1] < 1:
+            raise ValueError(f"weight_ih must be [{rows} x D] with H = {H} (got {self.weight_ih.shape})")
+        if self.bias_ih.shape != (G * H,) or self.bias_hh.shape != (G * H,):
+            raise ValueError(f"bias_ih and bias_hh must be [{rows}] with H = {H} (got {self.bias_ih.shape}, {self.bias_hh.shape})")
+        if not all(np.isfinite(a).all() for a in w):
+            raise ValueError(f"{self.MODULE} weights must be finite")
+
+    @property
+    def hidden_size(self):
+        return int(self.weight_hh.shape[1])
+
+    @property
+    def input_size(self):
+        return int(self.weight_ih.shape[1])
+
+    def save(self, path):
+        with open(path, "wb") as f:
+            np.savez(f, **{n: getattr(self, n) for n in self.NAMES})
+
+    @classmethod
+    def load(cls, path):
+        """From an ``.npz`` of the four arrays.  The row multiple of ``weight_hh`` tells the cells apart: a file of another cell
+        (a GRU file handed to ``LSTMUserModel``, say) is a ``ValueError``."""
+        with np.load(path) as z:
+            missing = [n for n in cls.NAMES if n not in z.files]
+            if missing:
+                raise ValueError(f"{path}: no array named {missing[0]} (an {cls.MODULE} weight file holds {', '.join(cls.NAMES)})")
+            return cls(*(z[n] for n in cls.NAMES))
+
+    @classmethod
+    def from_torch(cls, x):
+        """From the ``torch.nn`` module of the cell (one layer, unidirectional, with bias, no projection, tanh) or its state dict."""
+        if hasattr(x, "state_dict"):
+            if type(x).__name__ != cls.MODULE:
+                raise ValueError(f"from_torch takes a torch.nn.{cls.MODULE} (got {type(x).__name__})")
+            if getattr(x, "num_layers", 1) != 1 or getattr(x, "bidirectional", False) or not getattr(x, "bias", True):
+                raise ValueError(f"from_torch takes a one-layer, unidirectional {cls.MODULE} with bias")
+            if getattr(x, "proj_size", 0) != 0:
+                raise ValueError(f"from_torch takes an {cls.MODULE} without projection (proj_size = {x.proj_size})")
+            if getattr(x, "nonlinearity", "tanh") != "tanh":
+                raise ValueError(f"from_torch takes an {cls.MODULE} with nonlinearity='tanh' (got {x.nonlinearity!r})")
+            x = x.state_dict()
+        keys = [n + "_l0" for n in cls.NAMES]
+        extra = [k for k in x if k not in keys]
+        if extra or any(k not in x for k in keys):
+            raise ValueError(f"a one-layer, unidirectional {cls.MODULE} with bias has the entries {keys} (got {sorted(x)})")
+        return cls(*(x[k].detach().cpu().numpy() if hasattr(x[k], "detach") else x[k] for k in keys))
+
+
+class LSTMUserModel(_TorchCellUserModel):
+    """The weights of the LSTM user model, float32 in the layout of ``torch.nn.LSTM`` (one layer, gate row blocks i, f, g, o):
+    ``weight_ih`` [4H x D], ``weight_hh`` [4H x H], ``bias_ih`` and ``bias_hh`` [4H].  ``save`` / ``load`` keep them in an ``.npz`` under
+    those four names (``tools/gru_fit_torch.py --cell lstm`` writes the file).  Host code; the states come from
+    ``lstm_user_states`` (or ``.states``)."""
+    GATES, MODULE = 4, "LSTM"
+
+    def states(self, histories, embeddings, **kw):
+        return lstm_user_states(histories, embeddings, self, **kw)
+
+
+class RNNUserModel(_TorchCellUserModel):
+    """The weights of the plain-RNN user model, float32 in the layout of ``torch.nn.RNN(nonlinearity='tanh')`` (one layer):
+    ``weight_ih`` [H x D], ``weight_hh`` [H x H], ``bias_ih`` and ``bias_hh`` [H].  ``save`` / ``load`` keep them in an ``.npz`` under
+    those four names (``tools/gru_fit_torch.py --cell rnn`` writes the file).  Host code; the states come from
+    ``rnn_user_states`` (or ``.states``)."""
+    GATES, MODULE = 1, "RNN"
+
+    def states(self, histories, embeddings, **kw):
+        return rnn_user_states(histories, embeddings, self, **kw)
+
+
+def rnn_user_states(histories, embeddings, model, *, initial=None, max_events=None, all_states=False, batch_users=262144,
+                    return_tensor=False, device=None):
+    """User states from browsing histories by the plain recurrent user model of "Embedding-based News Recommendation for Millions
+    of Users" (KDD'17): per user, over the events oldest first, with ``x = E[item]`` and the weights of ``model`` (an
+    ``RNNUserModel``; the form of ``torch.nn.RNN(nonlinearity='tanh')``)
+
+        h' = tanh(W_ih x + b_ih + W_hh h + b_hh)
+
+    (``dae_rnn_user_states``: time-major, one exact-fp32 MFMA GEMM launch per step over the users still active; fixed order, no
+    atomics: bit-identical run to run and independent of the other users of the call and of their order).
+
+    ``histories`` and ``embeddings`` [articles x D] as for ``user_states``; ``model.input_size`` must be D.  The states have
+    ``H = model.hidden_size`` columns (``recommend`` needs H = D).  ``h`` starts at zero, or at the rows of ``initial``
+    [users x H]: the states of an earlier call, continued with the new clicks without replaying the history.  ``max_events``
+    keeps every user's most recent events (trimmed on the host; with ``all_states`` a ``ValueError``: the rows would no longer
+    be the caller's events).  The users are processed in chunks of at most ``batch_users``, which bounds the workspace; the
+    chunking does not change a bit of the result.  An item outside ``[0, articles)`` raises ``ValueError``.
+
+    Returns float32 ``[users x H]``: the state after each user's last event (zeros, or the ``initial`` row, for an empty
+    history); with ``all_states=True`` ``[events x H]``: row e is the state after event e, the one that predicts event e + 1,
+    and the row of a user's last event equals that user's row of the default form bit for bit."""
+    return _recurrent_user_states("rnn", RNNUserModel, histories, embeddings, model, (initial,), max_events, all_states, batch_users,
+                                  return_tensor, device)[0]
+
+
+def lstm_user_states(histories, embeddings, model, *, initial=None, max_events=None, all_states=False, batch_users=262144,
+                     return_tensor=False, return_cell=False, device=None):
+    """User states from browsing histories by the LSTM user model of "Embedding-based News Recommendation for Millions of Users"
+    (KDD'17): per user, over the events oldest first, with ``x = E[item]`` and the weights of ``model`` (an ``LSTMUserModel``;
+    gate order of ``torch.nn.LSTM``)
+
+        i = sigmoid(W_ii x + b_ii + W_hi h + b_hi)   f = sigmoid(W_if x + b_if + W_hf h + b_hf)   o = sigmoid(W_io x + b_io + W_ho h + b_ho)
+        g = tanh(W_ig x + b_ig + W_hg h + b_hg)   c' = f * c + i * g   h' = o * tanh(c')
+
+    (``dae_lstm_user_states``: time-major, one launch per step over the users still active, the exact-fp32 MFMA K loop once per
+    gate; fixed order, no atomics: bit-identical run to run and independent of the other users of the call and of their order).
+
+    The contract of ``gru_user_states`` -- ``histories``, ``embeddings`` [articles x D], ``max_events``, ``all_states``,
+    ``batch_users``, ``return_tensor``, the errors and the returned ``[users x H]`` / ``[events x H]`` states ``h`` -- with two
+    additions.  ``initial`` is a pair ``(h, c)`` of ``[users x H]`` start states, either of which may be None (zeros).
+    ``return_cell=True`` returns ``(U, C)``: ``C`` float32 ``[users x H]`` is every user's cell state after their last event (the
+    ``c`` row of ``initial``, or zeros, for an empty history), whatever ``all_states``.  The last states and ``C`` of one call,
+    handed to the next as ``initial=(U, C)``, continue the histories to the bits of the unsplit run."""
+    if initial is None:
+        initial = (None, None)
+    if not isinstance(initial, (tuple, list)) or len(initial) != 2:
+        raise ValueError("initial must be a pair (h, c); either may be None")
+    U, C = _recurrent_user_states("lstm", LSTMUserModel, histories, embeddings, model, tuple(initial), max_events, all_states, batch_users,
+                                  return_tensor, device, return_cell=bool(return_cell))
+    return (U, C) if return_cell else U
 
 
 def decay_factor_derivatives(indptr, timestamps, beta, time_unit=None):

@@ -635,6 +635,45 @@ int dae_gru_user_states(const float* E, int64_t lde, int32_t Na, int32_t D, int3
                         int64_t ldu, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------------------------------------------------
+ * LSTM and plain-RNN user states: the other two recurrent user models of the same paper, inference only
+ * (helpers.lstm_user_states, helpers.rnn_user_states), from weights in the layout of torch.nn.LSTM (gate row blocks
+ * i, f, g, o: W_ih [4H x ldwi], W_hh [4H x ldwh], b_ih, b_hh float[4H]) and of torch.nn.RNN(nonlinearity='tanh') (one
+ * block: W_ih [H x ldwi], W_hh [H x ldwh], b_ih, b_hh float[H]).  Per user, events oldest first, x = E[items[e]]:
+ *       LSTM:  i = sigmoid(W_ii x + b_ii + W_hi h + b_hi)   f, o likewise   g = tanh(W_ig x + b_ig + W_hg h + b_hg)
+ *              c' = f * c + i * g      h' = o * tanh(c')
+ *       RNN:   h' = tanh(W_ih x + b_ih + W_hh h + b_hh)
+ *   Every argument dae_rnn_user_states shares with dae_gru_user_states means what it means there: E, the history CSR, the
+ *   schedule (order, active_host, T), h0 / ldh0, all_states, U / ldu, workspace, stream.  dae_lstm_user_states adds
+ *       c0 [M x ldc0] (device) or NULL: the cell state every user starts from (zero when NULL), with or without h0;
+ *       C [M x ldc] (device) or NULL: receives every user's cell state after their last event; for an empty history its
+ *       c0 row, or zeros.  (h, c) = (U, C) of a call, handed back as (h0, c0), continue the histories.
+ *   fp32 throughout, exact-fp32 MFMA chains in a fixed k order, expf / tanhf and IEEE division in the gates, no atomics:
+ *   bit-identical run to run; a user's states do not depend on the other users of the call, on their order or on
+ *   all_states, and continuing from stored states gives the bits of the unsplit history.  Without h0 the first step
+ *   skips the recurrent product (h = 0) and gives the bits of a call with a zero h0.
+ *   Preconditions, not reported: as dae_gru_user_states.
+ *   workspace, 256-byte aligned, with pad = round up to 128, al = round up to 256 and G = 4 (LSTM) or 1 (RNN):
+ *       al(4 pad(Na) pad(D)) + al(4 G pad(H) pad(D)) + al(4 G pad(H) pad(H)) + al(4 G pad(Na) pad(H)) + S al(4 pad(M) pad(H))
+ *   bytes -- the images of E, W_ih and W_hh, the input projection of every article, and S = 2 state buffers (RNN) or
+ *   S = 3, two state buffers and the cell buffer (LSTM).  No events x H term; linear in M.  Every image must stay below
+ *   4 GiB (split the users into several calls).  M == 0 returns 0 without a launch.  Every argument error is reported
+ *   before any HIP call.  lde, ldwi >= D; ldwh, ldu, ldh0, ldc0, ldc >= H.
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_lstm_user_states_workspace(int32_t Na, int32_t D, int32_t H, int64_t M);
+int dae_lstm_user_states(const float* E, int64_t lde, int32_t Na, int32_t D, int32_t H, const float* W_ih, int64_t ldwi,
+                         const float* W_hh, int64_t ldwh, const float* b_ih, const float* b_hh, const int64_t* indptr,
+                         const int32_t* items, const int32_t* order, int64_t M, int64_t nnz, int32_t T,
+                         const int64_t* active_host, const float* h0, int64_t ldh0, const float* c0, int64_t ldc0,
+                         int32_t all_states, float* U, int64_t ldu, float* C, int64_t ldc, void* workspace,
+                         uint64_t workspace_bytes, void* stream);
+uint64_t dae_rnn_user_states_workspace(int32_t Na, int32_t D, int32_t H, int64_t M);
+int dae_rnn_user_states(const float* E, int64_t lde, int32_t Na, int32_t D, int32_t H, const float* W_ih, int64_t ldwi,
+                        const float* W_hh, int64_t ldwh, const float* b_ih, const float* b_hh, const int64_t* indptr,
+                        const int32_t* items, const int32_t* order, int64_t M, int64_t nnz, int32_t T,
+                        const int64_t* active_host, const float* h0, int64_t ldh0, int32_t all_states, float* U,
+                        int64_t ldu, void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
  * Training step of the GRU user model: the pairwise ranking loss of dae_user_pair_loss on the states of
  * dae_gru_user_states, forward and backward through time over one mini-batch of histories, with the gradients of the
  * four weight arrays (helpers.gru_pair_loss, helpers.fit_gru_user_model).  E is fixed and gets no gradient.

@@ -156,11 +156,16 @@ def build_parser():
                         "order, clicks after publication), and every user is recommended, ranked and compared with the baseline only among "
                         "the articles published by the time of the held-out click and at most HOURS before it (`inf`: any age); the files "
                         "are article_encoded_recommend{K}_window.npz / article_encoded_ranks_window.npz.  0: off")
-    p.add_argument("--user_model", default="decay", choices=["decay", "gru"],
+    p.add_argument("--user_model", default="decay", choices=["decay", "gru", "lstm", "rnn"],
                    help="the user model of --sessions S --recommend K.  decay (default): the decayed user states.  gru: ALSO the recurrent "
                         "user model -- GRU states (helpers.gru_user_states) from the weights in --gru_weights, through the same "
                         "recommend, --rank_metrics and --max_age paths; its files carry `_gru` in their names and its metrics are "
-                        "printed beside the decay model's")
+                        "printed beside the decay model's.  lstm / rnn: the same with the LSTM / plain-RNN states "
+                        "(helpers.lstm_user_states / helpers.rnn_user_states) from the weights in --user_weights; files `_lstm` / `_rnn`")
+    p.add_argument("--user_weights", default="",
+                   help="with --user_model lstm / rnn: an .npz with weight_ih, weight_hh, bias_ih, bias_hh in the layout of torch.nn.LSTM / "
+                        "torch.nn.RNN (helpers.LSTMUserModel / helpers.RNNUserModel; tools/gru_fit_torch.py --cell lstm / rnn writes one); "
+                        "input and hidden size must equal the embedding size")
     p.add_argument("--gru_weights", default="",
                    help="an .npz with weight_ih, weight_hh, bias_ih, bias_hh in the layout of torch.nn.GRU (helpers.GRUUserModel; "
                         "tools/gru_fit_torch.py writes one); the hidden size must equal the embedding size")
@@ -217,8 +222,10 @@ def validate(a):
     assert a.rec_mmr_pool == 0 or a.recommend <= a.rec_mmr_pool <= 128, "--rec_mmr_pool is a number in K..128"
     assert a.rec_max_per_label >= 0 and (a.rec_max_per_label == 0 or a.rec_mmr is not None), "--rec_max_per_label N needs --rec_mmr LAMBDA"
     assert not a.fit_user_model or (a.sessions != '' and a.recommend > 0), "--fit_user_model needs --sessions S --recommend K"
-    assert a.user_model == 'decay' or (a.sessions != '' and a.recommend > 0 and (a.gru_weights != '' or a.fit_gru)), \
+    assert a.user_model != 'gru' or (a.sessions != '' and a.recommend > 0 and (a.gru_weights != '' or a.fit_gru)), \
         "--user_model gru needs --sessions S --recommend K and --gru_weights PATH or --fit_gru"
+    assert a.user_model not in ('lstm', 'rnn') or (a.sessions != '' and a.recommend > 0 and a.user_weights != ''), \
+        "--user_model lstm / rnn needs --sessions S --recommend K and --user_weights PATH"
     assert not a.fit_gru or a.user_model == 'gru', "--fit_gru needs --user_model gru"
     assert a.gru_epochs >= 0
     assert not a.every_click or a.recommend > 0, "--every_click needs --recommend K"
@@ -428,8 +435,8 @@ def evaluate_recommend(a, trY, emb, data_dir):
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir)
     if a.fit_user_model:
         models['fitted'] = evaluate_fitted_user_model(a, emb, hist, targets, n, data_dir, timestamps=None if t is None else t[keep])
-    if a.user_model == 'gru':
-        evaluate_gru_user_model(a, emb, hist, targets, n, data_dir, models=models)
+    if a.user_model != 'decay':
+        evaluate_recurrent_user_model(a, emb, hist, targets, n, data_dir, models=models)
     if a.every_click:
         evaluate_every_click(a, emb, (indptr, items), t, None, models, data_dir)
     return idx, score, targets
@@ -592,8 +599,8 @@ def evaluate_recommend_window(a, trY, emb, data_dir):
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir, window=window, max_age=a.max_age)
     if a.fit_user_model:
         models['fitted'] = evaluate_fitted_user_model(a, emb, hist, targets, n, data_dir, timestamps=t[keep], window=window)
-    if a.user_model == 'gru':
-        evaluate_gru_user_model(a, emb, hist, targets, n, data_dir, window=window, models=models)
+    if a.user_model != 'decay':
+        evaluate_recurrent_user_model(a, emb, hist, targets, n, data_dir, window=window, models=models)
     if a.every_click:
         evaluate_every_click(a, emb, (indptr, items), t, publish, models, data_dir)
     return idx, score, targets
@@ -626,7 +633,7 @@ def evaluate_fitted_user_model(a, emb, hist, targets, n, data_dir, timestamps=No
     return model
 
 
-def evaluate_gru_user_model(a, emb, hist, targets, n, data_dir, window=None, models=None):
+def evaluate_recurrent_user_model(a, emb, hist, targets, n, data_dir, window=None, models=None):
     """--user_model gru: the recurrent user model on the histories the decayed states were built from.  The states come from
     helpers.gru_user_states with the weights of --gru_weights (helpers.GRUUserModel) -- or, with --fit_gru, with weights trained
     here by helpers.fit_gru_user_model on these histories and saved as gru_user_model.npz -- and go through the same helpers.recommend
@@ -634,11 +641,18 @@ def evaluate_gru_user_model(a, emb, hist, targets, n, data_dir, window=None, mod
     files are those of the decay model with `_gru` appended to the name: article_encoded_recommend{K}[_window]_gru.npz
     (``indices`` / ``scores`` / ``targets``) and article_encoded_ranks[_window]_gru.npz.  With --gru_validation FRACTION that share of
     the users (drawn by the fit's seed) is kept out of the fit and scored after every epoch by the every-click protocol
-    (helpers.fit_gru_user_model(validation=...)).  ``models``: a dict that receives the model under 'gru' (for --every_click)."""
+    (helpers.fit_gru_user_model(validation=...)).  ``models``: a dict that receives the model under 'gru' (for --every_click).
+    --user_model lstm / rnn: the same path with helpers.lstm_user_states / helpers.rnn_user_states on the weights of --user_weights
+    (helpers.LSTMUserModel / helpers.RNNUserModel; there is no device fit for them), `_lstm` / `_rnn` in the file names, the model
+    under 'lstm' / 'rnn' in ``models``."""
     from dae_rnn_news_recommendation_amd import helpers
     K = a.recommend
-    print('gru user model')
-    model = helpers.GRUUserModel.load(a.gru_weights) if a.gru_weights else None
+    cell = a.user_model
+    print('%s user model' % cell)
+    if cell == 'gru':
+        model = helpers.GRUUserModel.load(a.gru_weights) if a.gru_weights else None
+    else:
+        model = {'lstm': helpers.LSTMUserModel, 'rnn': helpers.RNNUserModel}[cell].load(a.user_weights)
     if a.fit_gru:
         seed = a.seed if a.seed >= 0 else 1234
         if a.gru_validation > 0:
@@ -656,23 +670,24 @@ def evaluate_gru_user_model(a, emb, hist, targets, n, data_dir, window=None, mod
         model.save(data_dir + 'gru_user_model.npz')
         print('  -> gru_user_model.npz')
     if models is not None:
-        models['gru'] = model
+        models[cell] = model
     assert model.input_size == emb.shape[1] and model.hidden_size == emb.shape[1], \
-        "--gru_weights: input and hidden size (%d, %d) must equal the embedding size %d" % (model.input_size, model.hidden_size, emb.shape[1])
+        "--%s_weights: input and hidden size (%d, %d) must equal the embedding size %d" \
+        % ('gru' if cell == 'gru' else 'user', model.input_size, model.hidden_size, emb.shape[1])
     w = '' if window is None else '_window'
-    states = helpers.gru_user_states(hist, emb, model, return_tensor=True)
+    states = model.states(hist, emb, return_tensor=True)
     idx, score = helpers.recommend(states, emb, k=K, seen=hist, window=window)
-    np.savez(data_dir + 'article_encoded_recommend%d%s_gru.npz' % (K, w), indices=idx, scores=score, targets=targets)
+    np.savez(data_dir + 'article_encoded_recommend%d%s_%s.npz' % (K, w, cell), indices=idx, scores=score, targets=targets)
     m = helpers.next_click_metrics(idx, targets)
-    print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f  -> article_encoded_recommend%d%s_gru.npz'
-          % (K, 'gru user state', m['hit'], m['mrr'], m['ndcg'], K, w))
+    print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f  -> article_encoded_recommend%d%s_%s.npz'
+          % (K, cell + ' user state', m['hit'], m['mrr'], m['ndcg'], K, w, cell))
     if a.rank_metrics:
         rank, rscore, n_cand = helpers.recommend_ranks(states, emb, targets, seen=hist, window=window)
-        np.savez(data_dir + 'article_encoded_ranks%s_gru.npz' % w, rank=rank, score=rscore, n_candidates=n_cand, targets=targets)
+        np.savez(data_dir + 'article_encoded_ranks%s_%s.npz' % (w, cell), rank=rank, score=rscore, n_candidates=n_cand, targets=targets)
         m = helpers.rank_metrics(rank, n_cand, targets, ks=(1, 10, 100))
         print('  ranks %-20s AUC %.4f  MRR %.4f  mean rank %.1f  median rank %.1f  hit@1 %.4f  hit@10 %.4f  hit@100 %.4f'
-              % ('gru user state', m['auc'], m['mrr'], m['mean_rank'], m['median_rank'], m['hit@1'], m['hit@10'], m['hit@100']))
-    print('gru user model done')
+              % (cell + ' user state', m['auc'], m['mrr'], m['mean_rank'], m['median_rank'], m['hit@1'], m['hit@10'], m['hit@100']))
+    print('%s user model done' % cell)
     return idx, score
 
 
@@ -682,7 +697,7 @@ def evaluate_every_click(a, emb, sessions, t, publish, models, data_dir):
     clicked by then -- for the decay model (--session_decay), for the fitted and the GRU model when they were selected (``models``:
     fitted here on the sessions without their last click), and for the most-clicked-unseen baseline
     (helpers.popularity_ranks_every_click).  One line of rank metrics per model, then the MRR by clicks seen
-    (helpers.rank_metrics_by_position).  Files: article_encoded_every_click[_fitted|_gru][_window].npz with ``rank`` / ``score`` /
+    (helpers.rank_metrics_by_position).  Files: article_encoded_every_click[_fitted|_gru|_lstm|_rnn][_window].npz with ``rank`` / ``score`` /
     ``n_candidates`` / ``targets`` / ``positions``.  With ``publish`` (--max_age) every click competes only with the articles
     published by the time of the next click and at most --max_age hours before it."""
     from dae_rnn_news_recommendation_amd import helpers
@@ -695,8 +710,9 @@ def evaluate_every_click(a, emb, sessions, t, publish, models, data_dir):
     runs = [('decayed user state', '', a.session_decay)]
     if 'fitted' in models:
         runs.append(('fitted user model', '_fitted', models['fitted']))
-    if 'gru' in models:
-        runs.append(('gru user state', '_gru', models['gru']))
+    for cell in ('gru', 'lstm', 'rnn'):
+        if cell in models:
+            runs.append((cell + ' user state', '_' + cell, models[cell]))
     rows = []
     for name, tag, model in runs:
         r = helpers.evaluate_every_click(sessions, emb, model, timestamps=t, window=window, ks=(1, 10, 100))

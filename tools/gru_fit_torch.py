@@ -15,6 +15,11 @@ with the negatives of helpers.sample_negatives (fresh per epoch, seeded).  Padde
 
     python tools/gru_fit_torch.py --embeddings emb.npy --sessions sessions.npz --out gru.npz [--epochs 5] [--device cpu]
     python tools/gru_fit_torch.py --synthetic 2000x64 --users 1000 --out gru.npz      # seeded embeddings and sessions
+    python tools/gru_fit_torch.py --cell lstm --embeddings emb.npy --sessions sessions.npz --out lstm.npz
+
+--cell lstm / --cell rnn train a torch.nn.LSTM / torch.nn.RNN (tanh) the same way and write helpers.LSTMUserModel's /
+helpers.RNNUserModel's .npz: the trainer of those two cells, whose states the device computes (helpers.lstm_user_states,
+helpers.rnn_user_states) but which it does not train.  The default, --cell gru, is unchanged.
 """
 import argparse
 import os
@@ -25,8 +30,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def fit(E, indptr, items, *, epochs=5, batch_users=256, n_neg=4, lr=1e-2, seed=0, max_events=50, device="cpu", log=print):
-    """Returns (torch.nn.GRU, loss per pair of every epoch)."""
+def fit(E, indptr, items, *, epochs=5, batch_users=256, n_neg=4, lr=1e-2, seed=0, max_events=50, device="cpu", log=print, cell="gru"):
+    """Returns (torch.nn.GRU -- or, by ``cell``, torch.nn.LSTM / torch.nn.RNN --, loss per pair of every epoch)."""
     import torch
     from dae_rnn_news_recommendation_amd import helpers
     torch.manual_seed(seed)
@@ -36,7 +41,7 @@ def fit(E, indptr, items, *, epochs=5, batch_users=256, n_neg=4, lr=1e-2, seed=0
     indptr, items = helpers.trim_histories((np.asarray(indptr, np.int64), np.asarray(items, np.int64)), max_events)
     lens = np.diff(indptr)
     users = np.flatnonzero(lens >= 2)
-    gru = torch.nn.GRU(D, D, batch_first=True).to(dev)
+    gru = {"gru": torch.nn.GRU, "lstm": torch.nn.LSTM, "rnn": torch.nn.RNN}[cell](D, D, batch_first=True).to(dev)
     opt = torch.optim.Adam(gru.parameters(), lr=lr)
     rng = np.random.default_rng(seed)
     history = []
@@ -86,6 +91,7 @@ def main(argv=None):
     p.add_argument("--max_events", type=int, default=50)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", default="cpu")
+    p.add_argument("--cell", default="gru", choices=["gru", "lstm", "rnn"], help="the recurrent cell: torch.nn.GRU (default), LSTM or RNN (tanh)")
     a = p.parse_args(argv)
     from dae_rnn_news_recommendation_amd import helpers
     if a.synthetic:
@@ -102,8 +108,8 @@ def main(argv=None):
         with np.load(a.sessions) as f:
             indptr, items = np.asarray(f["indptr"], np.int64), np.asarray(f["items"], np.int64)
     gru, history = fit(E, indptr, items, epochs=a.epochs, batch_users=a.batch_users, n_neg=a.n_neg, lr=a.lr, seed=a.seed,
-                       max_events=a.max_events, device=a.device)
-    helpers.GRUUserModel.from_torch(gru).save(a.out)
+                       max_events=a.max_events, device=a.device, cell=a.cell)
+    {"gru": helpers.GRUUserModel, "lstm": helpers.LSTMUserModel, "rnn": helpers.RNNUserModel}[a.cell].from_torch(gru).save(a.out)
     print("wrote %s (H = %d, %d epochs, loss per pair %.4f -> %.4f)" % (a.out, E.shape[1], history.size, history[0], history[-1]))
     return 0
 
