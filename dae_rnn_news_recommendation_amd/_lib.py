@@ -146,6 +146,12 @@ SIGNATURES = {
     "dae_gru_pair_loss_workspace": (u64, [i32, i32, i64, i64, i32, i32]),
     "dae_gru_pair_loss": (i32, [vp, i64, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, i32, vp, vp, vp, i64, vp, i64,
                                 vp, vp, vp, vp, u64, vp]),
+    "dae_lstm_pair_loss_workspace": (u64, [i32, i32, i64, i64, i32, i32]),
+    "dae_lstm_pair_loss": (i32, [vp, i64, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, i32, vp, vp, vp, i64, vp, i64,
+                                 vp, vp, vp, vp, u64, vp]),
+    "dae_rnn_pair_loss_workspace": (u64, [i32, i32, i64, i64, i32, i32]),
+    "dae_rnn_pair_loss": (i32, [vp, i64, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, i32, vp, vp, vp, i64, vp, i64,
+                                vp, vp, vp, vp, u64, vp]),
     "dae_threshold_pairs_workspace": (u64, [i32, i32, i32, u64]),
     "dae_threshold_pairs": (i32, [vp, i64, i32, vp, i64, i32, i32, i32, i32, f32, vp, vp, vp, u64, vp, vp, u64, vp]),
     "dae_dedup_lists_workspace": (u64, [i32, i32, i32, i32]),

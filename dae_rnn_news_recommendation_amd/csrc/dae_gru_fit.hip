@@ -21,8 +21,8 @@
 // Forward: gru_step_kernel<SKIP_K, GruTrainParams> (dae_gru_step.h) -- the inference kernel's three K loops and gate arithmetic;
 // the epilogues store r, then q and n, then z and h' as each is first complete.
 //
-// Loss: gru_loss_kernel, one wave per stash row.  Lane l owns the columns l, l + 64, ...; a margin is the lanes' fmaf chains in
-// column order added by the DPP tree of dae_common.h.  The row's partial loss (fp64) and pair count go to per-row slots that
+// Loss: gru_loss_kernel (in dae_fit_kernels.h, which dae_rnn_fit.hip shares, as are the fold and the transpose), one wave per
+// stash row.  Lane l owns the columns l, l + 64, ...; a margin is the lanes' fmaf chains in column order added by the DPP tree of dae_common.h.  The row's partial loss (fp64) and pair count go to per-row slots that
 // gru_loss_fold_kernel adds in a fixed order; no atomics.
 //
 // Backward: gru_back_kernel, one launch per step from S - 1 down to 0, grid pad128(n_s) / 128 x Hp / 128.  One K loop of length 3 Hp
@@ -39,14 +39,11 @@
 // Everything is a fixed-order sum: bit-identical run to run.  The margins and the pair count are per-row quantities of states that
 // do not depend on the other users (dae_gru.hip), so they do not depend on the order of the users; the gradients sum over rows in
 // stash order and agree under a permutation to rounding only.
-#include "dae_gru_step.h"
+#include "dae_fit_kernels.h"    // gru_loss_kernel, gru_loss_fold_kernel, gru_transpose_kernel; dae_gru_step.h
 
 #include <vector>
 
 namespace dae {
-
-constexpr int GF_MAX_NEG = 16;
-constexpr int GF_MAX_SPLITS = 16;
 
 // WhT[j][g Hp + k] = W_hh[g H + k][j]: the Bt operand of the backward step, zero outside H x H of every gate block
 __global__ __launch_bounds__(256) void gru_wht_kernel(const float* __restrict__ W_hh, int64_t ldwh, int H, int Hp, float* __restrict__ WhT) {
@@ -55,82 +52,6 @@ __global__ __launch_bounds__(256) void gru_wht_kernel(const float* __restrict__ 
         const int g = q / Hp, k = q - g * Hp;
         WhT[(int64_t)j * 3 * Hp + q] = (j < H && k < H) ? W_hh[((int64_t)g * H + k) * ldwh + j] : 0.f;
     }
-}
-
-struct GruLossParams {
-    const float* E; int64_t lde; int Na, H, Hp;
-    const int32_t* items; const int32_t* negatives; int n_neg; int64_t nnz;
-    float* hg;                    // [R x Hp] in: the state after the row's event; out: G
-    const int64_t* row_event;     // [R]
-    int64_t R;
-    double* rowloss; int32_t* rowpairs; float* margin;
-};
-
-__global__ __launch_bounds__(256) void gru_loss_kernel(GruLossParams p) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (row >= p.R) return;
-    const int64_t ev = p.row_event[row];
-    if (ev < 0) {                                               // padding: its row of HG is zero already
-        if (lane == 0) { p.rowloss[row] = 0.0; p.rowpairs[row] = 0; }
-        return;
-    }
-    const int64_t e = min(ev + 1, p.nnz - 1);                    // the event this state predicts (ev + 1 by the schedule's contract)
-    const int raw = p.items[e];
-    const float* pos = p.E + (int64_t)min(max(raw, 0), p.Na - 1) * p.lde;
-    float* h = p.hg + row * p.Hp;
-    float cj[GF_MAX_NEG];
-    int nj[GF_MAX_NEG];
-    double loss = 0.0;
-    int pairs = 0;
-#pragma unroll
-    for (int j = 0; j < GF_MAX_NEG; ++j) {
-        cj[j] = 0.f; nj[j] = -1;
-        if (j < p.n_neg) {
-            const int v = p.negatives[e * p.n_neg + j];
-            if (v >= 0 && v != raw) {                           // the same in every lane
-                nj[j] = min(v, p.Na - 1);
-                const float* ng = p.E + (int64_t)nj[j] * p.lde;
-                float s = 0.f;
-                for (int col = lane; col < p.H; col += 64) s = fmaf(h[col], pos[col] - ng[col], s);
-                const float x = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wave64_sum_hi(s)), 63));
-                const float ee = expf(-fabsf(x));
-                const float rr = 1.0f / (1.0f + ee);
-                cj[j] = -(x >= 0.f ? ee * rr : rr);             // -sigmoid(-x)
-                loss += (double)(fmaxf(-x, 0.f) + log1pf(ee));  // softplus(-x)
-                ++pairs;
-                if (p.margin && lane == 0) p.margin[e * p.n_neg + j] = x;
-            }
-        }
-    }
-    for (int col = lane; col < p.Hp; col += 64) {
-        float gsum = 0.f;
-        if (col < p.H) {
-            const float pv = pos[col];
-#pragma unroll
-            for (int j = 0; j < GF_MAX_NEG; ++j)
-                if (nj[j] >= 0) gsum = fmaf(cj[j], pv - p.E[(int64_t)nj[j] * p.lde + col], gsum);
-        }
-        h[col] = gsum;
-    }
-    if (lane == 0) { p.rowloss[row] = loss; p.rowpairs[row] = pairs; }
-}
-
-// one workgroup: thread t adds the rows t, t + 256, ... in ascending order, then the 256 sums are added pairwise in LDS
-__global__ __launch_bounds__(256) void gru_loss_fold_kernel(const double* __restrict__ rowloss, const int32_t* __restrict__ rowpairs, int64_t R,
-                                                            double* __restrict__ loss, int64_t* __restrict__ n_pairs) {
-    __shared__ double sl[256];
-    __shared__ long long sp[256];
-    double l = 0.0;
-    long long n = 0;
-    for (int64_t r = threadIdx.x; r < R; r += 256) { l += rowloss[r]; n += rowpairs[r]; }
-    sl[threadIdx.x] = l; sp[threadIdx.x] = n;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { sl[threadIdx.x] += sl[threadIdx.x + o]; sp[threadIdx.x] += sp[threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { *loss = sl[0]; *n_pairs = sp[0]; }
 }
 
 struct GruBackParams {
@@ -180,36 +101,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gru_back_kernel(GruBackParams
         }
 }
 
-// dst[c][r] = src[r][c] on 64 x 64 tiles through LDS; grid (rows / 64, cols / 64).  GATHER: src row r is E[items[row_event[r]]]
-// (columns >= H and the padding rows read as zero) instead of a row of a stash image.
-template <bool GATHER>
-__global__ __launch_bounds__(256) void gru_transpose_kernel(const float* __restrict__ src, int64_t ld_src, const int64_t* __restrict__ row_event,
-                                                            const int32_t* __restrict__ items, int Na, int H, float* __restrict__ dst,
-                                                            int64_t ld_dst) {
-    __shared__ float t[64][65];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int64_t r0 = (int64_t)blockIdx.x * 64;
-    const int c0 = (int)blockIdx.y * 64;
-#pragma unroll 4
-    for (int k = 0; k < 16; ++k) {
-        const int rr = ty + 4 * k;
-        float v = 0.f;
-        if constexpr (GATHER) {
-            const int64_t e = row_event[r0 + rr];
-            if (e >= 0 && c0 + tx < H) v = src[(int64_t)min(max(items[e], 0), Na - 1) * ld_src + c0 + tx];
-        } else {
-            v = src[(r0 + rr) * ld_src + c0 + tx];
-        }
-        t[rr][tx] = v;
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int k = 0; k < 16; ++k) {
-        const int cc = ty + 4 * k;
-        dst[(int64_t)(c0 + cc) * ld_dst + r0 + tx] = t[tx][cc];
-    }
-}
-
 // dW[(g H + k) ld + j] = the sum over the slabs, in slab order, of S[(m_g Hp + k) Hp + j]; block = one row g H + k
 __global__ __launch_bounds__(256) void gru_dw_fold_kernel(const float* __restrict__ slabs, int splits, int64_t slab_stride, int H, int Hp, int m0, int m1,
                                                           int m2, float* __restrict__ dW, int64_t ld) {
@@ -244,9 +135,6 @@ __global__ __launch_bounds__(256) void gru_db_kernel(const float* __restrict__ D
         else db_hh[2 * H + j] = v;
     }
 }
-
-// rows of the stash a call can need at most: every step's slab is padded to 128 rows
-static int64_t gf_rows_bound(int64_t nnz, int64_t T) { return pad128(nnz + 128 * T); }
 
 static uint64_t gf_workspace(int64_t Nap, int64_t Hp, int64_t Mp, int64_t Rb) {
     // E, W_ih, W_hh, W_hh^T images, P, b_hn image; 12 stash images; carry; row_event, rowloss, rowpairs; split-K slabs

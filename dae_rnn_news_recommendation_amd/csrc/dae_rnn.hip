@@ -1,5 +1,5 @@
 // dae_rnn.hip -- user states from browsing histories by an LSTM (dae_lstm_user_states) and by a plain tanh RNN (dae_rnn_user_states):
-// the other two recurrent user models of "Embedding-based News Recommendation for Millions of Users" (KDD'17), inference only, weights
+// the other two recurrent user models of "Embedding-based News Recommendation for Millions of Users" (KDD'17), inference (their training: dae_rnn_fit.hip), weights
 // in the layout of torch.nn.LSTM and torch.nn.RNN(nonlinearity='tanh').  The GRU is dae_gru.hip; this file follows its form.
 //
 // Per user, events oldest first, x = E[items[e]] (D floats), h and c (H floats, zero or the caller's rows at the start):
@@ -15,7 +15,7 @@
 // by the exact-fp32 NT GEMM of dae_gemm.hip on zero-padded images of E and W_ih (every gate block padded to Hp rows), then
 // rnn_bias_kernel.  No bias is multiplied by a gate here, so there is no separate image of a recurrent bias.
 //
-// lstm_step_kernel runs the K loop of gemm_mainloop<float, 2> four times, A = the previous state buffer, Bt = the i, g, f, o row
+// lstm_step_kernel (dae_rnn_step.h, shared with the trainer) runs the K loop of gemm_mainloop<float, 2> four times, A = the previous state buffer, Bt = the i, g, f, o row
 // blocks of the W_hh image [4 Hp x Hp], in that order, with one f32x16[2][2] carry (64 registers per lane) beside the accumulators:
 // the i pass leaves sigmoid(.) in the carry, the g pass multiplies tanh(.) into it, the f pass reads the row's c, forms
 // c' = f * c + carry, writes c' back and keeps it in the carry, the o pass writes h' = o * tanh(c') to the next state buffer and to U
@@ -34,22 +34,9 @@
 // depends on its own A row and Bt row alone; expf (gru_sigmoid) / tanhf and IEEE division in the gates; no atomics.  So a user's
 // states are bit-identical run to run and do not depend on the other users of the call, their order, the tile or the launch a row
 // falls into, on all_states or on the caller's chunking; continuing from stored (h, c) runs the instructions the unsplit history runs.
-#include "dae_gru_step.h"       // gru_sigmoid and, through dae_score_sweep.h, gemm_mainloop, sweep_launch, al256
+#include "dae_rnn_step.h"       // RnnStepParams, lstm_step_kernel, rnn_step_kernel; gru_sigmoid, gemm_mainloop, sweep_launch, al256
 
 namespace dae {
-
-constexpr int RNN_LDS = GRU_RING + 128 * 4 + 128 * 8;                // ring, items, U rows
-constexpr int LSTM_LDS = RNN_LDS + 128 * 8;                         // and C rows
-
-// P += b_ih + b_hh (rows < Na, columns < H of each of the G gate blocks)
-__global__ __launch_bounds__(256) void rnn_bias_kernel(float* __restrict__ P, int H, int Hp, int G, const float* __restrict__ b_ih,
-                                                       const float* __restrict__ b_hh) {
-    float* p = P + (int64_t)blockIdx.x * G * Hp;
-    for (int q = threadIdx.x; q < G * Hp; q += 256) {
-        const int g = q / Hp, j = q - g * Hp;
-        if (j < H) p[q] += b_ih[g * H + j] + b_hh[g * H + j];
-    }
-}
 
 // S0[i] = h0[order[i]] or zero and (LSTM) C0[i] = c0[order[i]] or zero, zero in the columns >= H; a user without events gets its
 // row of U (last-state mode) and of C
@@ -70,175 +57,6 @@ __global__ __launch_bounds__(256) void rnn_init_kernel(float* __restrict__ S0, f
             if (empty && C && j < H) C[u * ldc + j] = w;
         }
     }
-}
-
-struct RnnStepParams {
-    GemmParams g;                 // one K segment: A = previous state buffer, Bt = W_hh image (gate q = tile rows q * Hp / 128 ...)
-    const float* hprev;           // = g.seg[0].A
-    float* hnext;                 // [pad128(M) x Hp]
-    float* cell;                  // LSTM: [pad128(M) x Hp], updated in place
-    const float* P;               // [pad128(Na) x G Hp]
-    const int64_t* indptr; const int32_t* items; const int32_t* order;
-    float* U; int64_t ldu;
-    float* C; int64_t ldc;        // LSTM: [M x ldc] or NULL
-    int64_t nnz;
-    int Na, H, Hp, t, active, all_states;
-};
-
-// the tile's users: the item of this step, the row of U to write and (CELL: the LSTM) the row of C to write (-1: none)
-template <bool CELL>
-__device__ __forceinline__ void rnn_tile_rows(const RnnStepParams& p, int tm, int tid, int* s_item, long long* s_urow, long long* s_crow) {
-    if (tid < 128) {
-        const int i = tm * BM + tid;
-        int it = 0;
-        long long urow = -1;
-        [[maybe_unused]] long long crow = -1;
-        if (i < p.active) {
-            const int64_t u = p.order[i];
-            const int64_t e0 = p.indptr[u], e1 = p.indptr[u + 1];
-            // e0 + t by the schedule's contract; a caller error (see dae_hip.h) must not become a stray read
-            const int64_t e = max(min(min(e0 + p.t, e1 - 1), p.nnz - 1), (int64_t)0);
-            it = min(max(p.items[e], 0), p.Na - 1);
-            urow = p.all_states ? e : (e == e1 - 1 ? u : -1);
-            if constexpr (CELL) crow = (p.C && e == e1 - 1) ? u : -1;
-        }
-        s_item[tid] = it;
-        s_urow[tid] = urow;
-        if constexpr (CELL) s_crow[tid] = crow;
-    }
-    __syncthreads();
-}
-
-template <bool SKIP_K>
-__global__ __launch_bounds__(GEMM_THREADS, 1) void lstm_step_kernel(RnnStepParams p) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    int* s_item = reinterpret_cast<int*>(lds + GRU_RING);
-    long long* s_urow = reinterpret_cast<long long*>(lds + GRU_RING + 128 * 4);
-    long long* s_crow = reinterpret_cast<long long*>(lds + GRU_RING + 128 * 4 + 128 * 8);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, g = lane >> 5, c = lane & 31;
-    const int tiles_n = p.Hp / BN;
-    const int tm = blockIdx.x / tiles_n, tn = blockIdx.x % tiles_n;
-    rnn_tile_rows<true>(p, tm, tid, s_item, s_urow, s_crow);
-    const int Hp = p.Hp;
-    const int col0 = tn * BN + wn * 64 + c;                     // this lane's columns: col0, col0 + 32
-    const int rbase = wm * 64 + 4 * g;                          // its rows: rbase + acc_row(mt, r, 0)
-    f32x16 acc[2][2], keep[2][2];                               // keep: i, then i * g, then c'
-    // ---- i = sigmoid(P_i + acc) ----
-    if constexpr (SKIP_K) zero_acc(acc);
-    else gemm_mainloop<float, 2>(p.g, tm, tn, 0, p.g.ktiles_total, lds, acc);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float* pr = p.P + (int64_t)s_item[rbase + acc_row(mt, r, 0)] * (4 * Hp) + col0;
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) keep[mt][nt][r] = gru_sigmoid(pr[nt * 32] + acc[mt][nt][r]);
-            if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);     // four rows' P values in flight, not all 32 (VGPRs)
-        }
-    __syncthreads();                                            // every wave is done with the staging ring
-    // ---- g = tanh(P_g + acc), carry = i * g ----
-    if constexpr (SKIP_K) zero_acc(acc);
-    else gemm_mainloop<float, 2>(p.g, tm, 2 * tiles_n + tn, 0, p.g.ktiles_total, lds, acc);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float* pr = p.P + (int64_t)s_item[rbase + acc_row(mt, r, 0)] * (4 * Hp) + 2 * Hp + col0;
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) keep[mt][nt][r] = keep[mt][nt][r] * tanhf(pr[nt * 32] + acc[mt][nt][r]);
-            if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-        }
-    __syncthreads();
-    // ---- f = sigmoid(P_f + acc), c' = f * c + carry ----
-    if constexpr (SKIP_K) zero_acc(acc);
-    else gemm_mainloop<float, 2>(p.g, tm, tiles_n + tn, 0, p.g.ktiles_total, lds, acc);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int lrow = rbase + acc_row(mt, r, 0);
-            const int i = tm * BM + lrow;
-            if (i < p.active) {
-                const float* pr = p.P + (int64_t)s_item[lrow] * (4 * Hp) + Hp + col0;
-                float* cp = p.cell + (int64_t)i * Hp + col0;
-                const long long crow = s_crow[lrow];
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    const float f = gru_sigmoid(pr[nt * 32] + acc[mt][nt][r]);
-                    const bool in = col0 + nt * 32 < p.H;
-                    const float v = in ? f * cp[nt * 32] + keep[mt][nt][r] : 0.f;
-                    cp[nt * 32] = v;
-                    keep[mt][nt][r] = v;
-                    if (crow >= 0 && in) p.C[crow * p.ldc + col0 + nt * 32] = v;
-                }
-            }
-            if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-        }
-    __syncthreads();
-    // ---- o = sigmoid(P_o + acc), h' = o * tanh(c') ----
-    if constexpr (SKIP_K) zero_acc(acc);
-    else gemm_mainloop<float, 2>(p.g, tm, 3 * tiles_n + tn, 0, p.g.ktiles_total, lds, acc);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int lrow = rbase + acc_row(mt, r, 0);
-            const int i = tm * BM + lrow;
-            if (i < p.active) {
-                const float* pr = p.P + (int64_t)s_item[lrow] * (4 * Hp) + 3 * Hp + col0;
-                float* hn = p.hnext + (int64_t)i * Hp + col0;
-                const long long urow = s_urow[lrow];
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    const float o = gru_sigmoid(pr[nt * 32] + acc[mt][nt][r]);
-                    const bool in = col0 + nt * 32 < p.H;
-                    const float v = in ? o * tanhf(keep[mt][nt][r]) : 0.f;
-                    hn[nt * 32] = v;
-                    if (urow >= 0 && in) p.U[urow * p.ldu + col0 + nt * 32] = v;
-                }
-            }
-            if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-        }
-}
-
-template <bool SKIP_K>
-__global__ __launch_bounds__(GEMM_THREADS, 2) void rnn_step_kernel(RnnStepParams p) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    int* s_item = reinterpret_cast<int*>(lds + GRU_RING);
-    long long* s_urow = reinterpret_cast<long long*>(lds + GRU_RING + 128 * 4);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, g = lane >> 5, c = lane & 31;
-    const int tiles_n = p.Hp / BN;
-    const int tm = blockIdx.x / tiles_n, tn = blockIdx.x % tiles_n;
-    rnn_tile_rows<false>(p, tm, tid, s_item, s_urow, nullptr);
-    const int Hp = p.Hp;
-    const int col0 = tn * BN + wn * 64 + c;
-    const int rbase = wm * 64 + 4 * g;
-    f32x16 acc[2][2];
-    // ---- h' = tanh(P + acc) ----
-    if constexpr (SKIP_K) zero_acc(acc);
-    else gemm_mainloop<float, 2>(p.g, tm, tn, 0, p.g.ktiles_total, lds, acc);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int lrow = rbase + acc_row(mt, r, 0);
-            const int i = tm * BM + lrow;
-            if (i < p.active) {
-                const float* pr = p.P + (int64_t)s_item[lrow] * Hp + col0;
-                float* hn = p.hnext + (int64_t)i * Hp + col0;
-                const long long urow = s_urow[lrow];
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    const bool in = col0 + nt * 32 < p.H;
-                    const float v = in ? tanhf(pr[nt * 32] + acc[mt][nt][r]) : 0.f;
-                    hn[nt * 32] = v;
-                    if (urow >= 0 && in) p.U[urow * p.ldu + col0 + nt * 32] = v;
-                }
-            }
-            if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-        }
 }
 
 }  // namespace dae

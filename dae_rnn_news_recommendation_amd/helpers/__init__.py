@@ -14,7 +14,8 @@ is importable from here; the code lives by subject:
 * ``user_models`` -- the user models of "Embedding-based News Recommendation for Millions of Users": ``user_states`` (decaying;
   ``decay_factors``), ``fit_user_model`` / ``UserModel`` on ``user_pair_loss`` (``sample_negatives``,
   ``decay_factor_derivatives``); ``GRUUserModel``, ``gru_user_states`` (``gru_schedule``, ``trim_histories``),
-  ``fit_gru_user_model`` on ``gru_pair_loss``; ``LSTMUserModel`` / ``lstm_user_states`` and ``RNNUserModel`` / ``rnn_user_states``.
+  ``fit_gru_user_model`` on ``gru_pair_loss``; ``LSTMUserModel`` / ``lstm_user_states`` / ``fit_lstm_user_model`` on ``lstm_pair_loss``
+  and ``RNNUserModel`` / ``rnn_user_states`` / ``fit_rnn_user_model`` on ``rnn_pair_loss``.
 * ``evaluation`` -- ``recommend`` / ``recommend_ranks`` with ``next_click_metrics`` / ``rank_metrics``, ``recommend_diverse``
   (``recommend`` + ``diversify_lists``) with ``list_diversity`` (nearest similarity, labels per list), the popularity baseline
   (``popularity_recommend``, ``popularity_ranks``), and the every-click protocol (``click_prefix_lists``, ``every_click_rows``,
@@ -45,7 +46,8 @@ from .sweeps import (SWEEP_AUTO_IMAGE_BYTES, SweepOperand, candidate_windows, de
                      normalize_exclusions, normalize_shared_exclusions, normalize_window, pairwise_similarity, permute_histories,
                      shared_pairs, shared_row_chunks, similar_pairs, sweep_chunk_plan, sweep_chunk_rows, target_ranks)
 from .user_models import (GRUUserModel, LSTMUserModel, RNNUserModel, UserModel, decay_factor_derivatives, decay_factors,
-                          fit_gru_user_model, fit_user_model, gru_pair_loss, gru_schedule, gru_user_states, lstm_user_states,
-                          rnn_user_states, sample_negatives, trim_histories, user_pair_loss, user_states)
+                          fit_gru_user_model, fit_lstm_user_model, fit_rnn_user_model, fit_user_model, gru_pair_loss, gru_schedule,
+                          gru_user_states, lstm_pair_loss, lstm_user_states, rnn_pair_loss, rnn_user_states, sample_negatives,
+                          trim_histories, user_pair_loss, user_states)
 from .vectorize import (TfidfTransformer, binarize, column_stats, device_csr_to_scipy, limit_features, limit_features_columns,
                         select_columns)

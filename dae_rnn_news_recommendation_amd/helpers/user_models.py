@@ -2,8 +2,9 @@
 model: ``user_states`` (``decay_factors``), and its trained form ``fit_user_model`` -> ``UserModel`` on the loss and gradients of
 ``user_pair_loss`` (``sample_negatives``, ``decay_factor_derivatives``).  The recurrent model: ``GRUUserModel`` (weights in the
 layout of ``torch.nn.GRU``), ``gru_user_states`` (``gru_schedule``, ``trim_histories``), and its training ``fit_gru_user_model`` on
-``gru_pair_loss`` (back-propagation through time on the device).  The paper's other two recurrent cells, states from given
-weights: ``LSTMUserModel`` / ``lstm_user_states`` and ``RNNUserModel`` / ``rnn_user_states``."""
+``gru_pair_loss`` (back-propagation through time on the device).  The paper's other two recurrent cells, in the same
+three parts: ``LSTMUserModel`` / ``lstm_user_states`` / ``fit_lstm_user_model`` on ``lstm_pair_loss`` and ``RNNUserModel`` /
+``rnn_user_states`` / ``fit_rnn_user_model`` on ``rnn_pair_loss``."""
 from __future__ import annotations
 
 import numpy as np
@@ -278,7 +279,9 @@ class _TorchCellUserModel:
     NAMES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
     GATES, MODULE = 0, ""
 
-    def __init__(self, weight_ih, weight_hh, bias_ih, bias_hh):
+    def __init__(self, weight_ih, weight_hh, bias_ih, bias_hh, history=None, validation=None):
+        self.history = history                                              # a trainer's loss per pair of every epoch; not saved
+        self.validation = validation                                        # and its validation metrics; not saved
         G, rows = self.GATES, ("%dH" % self.GATES if self.GATES > 1 else "H")
         w = [np.ascontiguousarray(np.asarray(a, dtype=np.float32)) for a in (weight_ih, weight_hh, bias_ih, bias_hh)]
         self.weight_ih, self.weight_hh, self.bias_ih, self.bias_hh = w
@@ -337,8 +340,8 @@ class _TorchCellUserModel:
 class LSTMUserModel(_TorchCellUserModel):
     """The weights of the LSTM user model, float32 in the layout of ``torch.nn.LSTM`` (one layer, gate row blocks i, f, g, o):
     ``weight_ih`` [4H x D], ``weight_hh`` [4H x H], ``bias_ih`` and ``bias_hh`` [4H].  ``save`` / ``load`` keep them in an ``.npz`` under
-    those four names (``tools/gru_fit_torch.py --cell lstm`` writes the file).  Host code; the states come from
-    ``lstm_user_states`` (or ``.states``)."""
+    those four names (``fit_lstm_user_model`` returns one, with ``.history`` and ``.validation``, which are not saved;
+    ``tools/gru_fit_torch.py --cell lstm`` writes the file too).  Host code; the states come from ``lstm_user_states`` (or ``.states``)."""
     GATES, MODULE = 4, "LSTM"
 
     def states(self, histories, embeddings, **kw):
@@ -348,8 +351,8 @@ class LSTMUserModel(_TorchCellUserModel):
 class RNNUserModel(_TorchCellUserModel):
     """The weights of the plain-RNN user model, float32 in the layout of ``torch.nn.RNN(nonlinearity='tanh')`` (one layer):
     ``weight_ih`` [H x D], ``weight_hh`` [H x H], ``bias_ih`` and ``bias_hh`` [H].  ``save`` / ``load`` keep them in an ``.npz`` under
-    those four names (``tools/gru_fit_torch.py --cell rnn`` writes the file).  Host code; the states come from
-    ``rnn_user_states`` (or ``.states``)."""
+    those four names (``fit_rnn_user_model`` returns one, with ``.history`` and ``.validation``, which are not saved;
+    ``tools/gru_fit_torch.py --cell rnn`` writes the file too).  Host code; the states come from ``rnn_user_states`` (or ``.states``)."""
     GATES, MODULE = 1, "RNN"
 
     def states(self, histories, embeddings, **kw):
@@ -630,10 +633,11 @@ def _gru_fit_checks(embeddings, H, D, items):
     return Na, H
 
 
-def _gru_pair_loss_call(torch, E, w, indptr, it_d, ng_d, n_neg, grads, scal, margins=None):
-    """One ``dae_gru_pair_loss`` on device operands, nothing read back.  ``indptr``: host int64 [M + 1] starting at 0; ``it_d``
-    int32 [nnz], ``ng_d`` int32 [nnz x n_neg]; ``w`` / ``grads``: the four float32 weight tensors and their gradients (contiguous);
-    ``scal``: float64 [2] that receives the loss and the bits of the int64 pair count; ``margins``: float32 [nnz x n_neg] or None."""
+def _gru_pair_loss_call(torch, E, w, indptr, it_d, ng_d, n_neg, grads, scal, margins=None, cell="gru"):
+    """One ``dae_gru_pair_loss`` (``cell``: ``dae_lstm_pair_loss`` / ``dae_rnn_pair_loss``) on device operands, nothing read back.
+    ``indptr``: host int64 [M + 1] starting at 0; ``it_d`` int32 [nnz], ``ng_d`` int32 [nnz x n_neg]; ``w`` / ``grads``: the four
+    float32 weight tensors and their gradients (contiguous); ``scal``: float64 [2] that receives the loss and the bits of the int64
+    pair count; ``margins``: float32 [nnz x n_neg] or None."""
     import ctypes
     dev = E.device
     lib = L.load()
@@ -644,9 +648,9 @@ def _gru_pair_loss_call(torch, E, w, indptr, it_d, ng_d, n_neg, grads, scal, mar
     ip_d = torch.from_numpy(np.array(indptr, dtype=np.int64)).to(dev)
     or_d = upload(order, dev)
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.dae_gru_pair_loss_workspace(Na, H, M, nnz, T, n_neg))
+        ws_bytes = int(getattr(lib, f"dae_{cell}_pair_loss_workspace")(Na, H, M, nnz, T, n_neg))
         ws_ptr, ws = workspace(dev, ws_bytes)
-        L.call("dae_gru_pair_loss", L.ptr(E), E.stride(0), Na, H, L.ptr(w[0]), H, L.ptr(w[1]), H, L.ptr(w[2]), L.ptr(w[3]), L.ptr(ip_d),
+        L.call(f"dae_{cell}_pair_loss", L.ptr(E), E.stride(0), Na, H, L.ptr(w[0]), H, L.ptr(w[1]), H, L.ptr(w[2]), L.ptr(w[3]), L.ptr(ip_d),
                L.ptr(it_d), L.ptr(or_d), M, nnz, T, active.ctypes.data_as(ctypes.c_void_p), L.ptr(ng_d), n_neg,
                ctypes.c_void_p(scal.data_ptr()), ctypes.c_void_p(scal.data_ptr() + 8), L.ptr(grads[0]), H, L.ptr(grads[1]), H,
                L.ptr(grads[2]), L.ptr(grads[3]), L.ptr(margins), ws_ptr, ws_bytes, L.current_stream())
@@ -668,8 +672,14 @@ def gru_pair_loss(histories, embeddings, model, negatives, *, return_margins=Fal
     shapes}`` -- sums over the valid pairs, NOT divided by ``n_pairs`` -- and with ``return_margins=True`` also ``'margins'``:
     float32 ``[events x n_neg]``, 0 where there is no pair.  Bit-identical run to run; ``n_pairs`` and the margins do not depend
     on the order of the users, the gradients agree under a permutation of the users to rounding."""
-    if not isinstance(model, GRUUserModel):
-        raise TypeError("model must be a GRUUserModel (GRUUserModel.load / from_torch)")
+    return _recurrent_pair_loss("gru", GRUUserModel, histories, embeddings, model, negatives, return_margins, device)
+
+
+def _recurrent_pair_loss(cell, cls, histories, embeddings, model, negatives, return_margins, device):
+    """The intake and read-back shared by ``gru_pair_loss``, ``lstm_pair_loss`` and ``rnn_pair_loss``: one ``dae_{cell}_pair_loss`` on
+    the weights of ``model`` (a ``cls``)."""
+    if not isinstance(model, cls):
+        raise TypeError(f"model must be a {cls.__name__} ({cls.__name__}.load / from_torch)")
     indptr, items = csr_lists(histories)
     Na, H = _gru_fit_checks(embeddings, model.hidden_size, model.input_size, items)
     nnz = int(items.size)
@@ -677,18 +687,34 @@ def gru_pair_loss(histories, embeddings, model, negatives, *, return_margins=Fal
     n_neg = int(neg.shape[1])
     torch, _, dev = device_and_library(device)
     E = device_matrix(torch, embeddings, dev, in_place=True)
-    w = [torch.from_numpy(getattr(model, n)).to(dev) for n in GRUUserModel.NAMES]
+    w = [torch.from_numpy(getattr(model, n)).to(dev) for n in cls.NAMES]
     grads = [torch.empty_like(a) for a in w]
     scal = torch.zeros(2, dtype=torch.float64, device=dev)
     mg = torch.empty((max(nnz, 1), n_neg), dtype=torch.float32, device=dev) if return_margins else None
-    _gru_pair_loss_call(torch, E, w, indptr, upload(items.astype(np.int32), dev), upload(neg, dev), n_neg, grads, scal, mg)
+    _gru_pair_loss_call(torch, E, w, indptr, upload(items.astype(np.int32), dev), upload(neg, dev), n_neg, grads, scal, mg, cell=cell)
     host = scal.cpu().numpy()
     res = {"loss": float(host[0]), "n_pairs": int(host[1:].view(np.int64)[0])}
-    for name, g in zip(GRUUserModel.NAMES, grads):
+    for name, g in zip(cls.NAMES, grads):
         res[name] = g.cpu().numpy()
     if return_margins:
         res["margins"] = mg[:nnz].cpu().numpy()
     return res
+
+
+def lstm_pair_loss(histories, embeddings, model, negatives, *, return_margins=False, device=None):
+    """The training step of the LSTM user model (``dae_lstm_pair_loss``): ``gru_pair_loss`` on the states of ``lstm_user_states`` --
+    the same margins, loss, pairs and errors -- with the gradients of the four weight arrays of ``model`` (an ``LSTMUserModel``
+    whose hidden size equals the embedding size; ``h`` and ``c`` start at zero) by back-propagation through time on the device.
+    Returns the dict of ``gru_pair_loss`` with gradients in the model's shapes ([4H x H], [4H]; gate row blocks i, f, g, o)."""
+    return _recurrent_pair_loss("lstm", LSTMUserModel, histories, embeddings, model, negatives, return_margins, device)
+
+
+def rnn_pair_loss(histories, embeddings, model, negatives, *, return_margins=False, device=None):
+    """The training step of the plain-RNN user model (``dae_rnn_pair_loss``): ``gru_pair_loss`` on the states of ``rnn_user_states``
+    -- the same margins, loss, pairs and errors -- with the gradients of the four weight arrays of ``model`` (an ``RNNUserModel``
+    whose hidden size equals the embedding size; ``h`` starts at zero) by back-propagation through time on the device.  Returns
+    the dict of ``gru_pair_loss`` with gradients in the model's shapes ([H x H], [H])."""
+    return _recurrent_pair_loss("rnn", RNNUserModel, histories, embeddings, model, negatives, return_margins, device)
 
 
 def fit_gru_user_model(histories, embeddings, *, epochs=5, batch_users=256, n_neg=4, lr=1e-2, seed=0, max_events=50, init=None,
@@ -714,6 +740,14 @@ def fit_gru_user_model(histories, embeddings, *, epochs=5, batch_users=256, n_ne
     epoch with the highest validation ``mrr`` (the first of equals) are returned instead of the last epoch's.
 
     Returns a ``GRUUserModel`` whose ``.history`` is the loss per pair of every epoch (float64 [epochs])."""
+    return _fit_recurrent_user_model("gru", GRUUserModel, 3, histories, embeddings, epochs, batch_users, n_neg, lr, seed, max_events, init,
+                                     window, validation, validation_every, keep_best, device)
+
+
+def _fit_recurrent_user_model(cell, cls, gates, histories, embeddings, epochs, batch_users, n_neg, lr, seed, max_events, init, window,
+                              validation, validation_every, keep_best, device):
+    """The loop of ``fit_gru_user_model``, ``fit_lstm_user_model`` and ``fit_rnn_user_model``: mini-batch Adam on
+    ``dae_{cell}_pair_loss`` for a model class ``cls`` with ``gates`` row blocks of H rows."""
     from .evaluation import evaluate_every_click                      # (evaluation imports this module)
     if int(epochs) < 0 or not float(lr) > 0.0:
         raise ValueError("epochs must not be negative and lr must be positive")
@@ -725,8 +759,8 @@ def fit_gru_user_model(histories, embeddings, *, epochs=5, batch_users=256, n_ne
         raise ValueError(f"batch_users must be positive (got {batch_users})")
     if not 1 <= int(n_neg) <= 16:
         raise ValueError(f"n_neg must be in 1..16 (got {n_neg})")
-    if init is not None and not isinstance(init, GRUUserModel):
-        raise TypeError("init must be a GRUUserModel")
+    if init is not None and not isinstance(init, cls):
+        raise TypeError(f"init must be a {cls.__name__}")
     indptr, items = csr_lists(histories)
     D = matrix_shape(embeddings)[1]
     H = D if init is None else init.hidden_size
@@ -736,9 +770,9 @@ def fit_gru_user_model(histories, embeddings, *, epochs=5, batch_users=256, n_ne
     rng = np.random.default_rng(seed)
     if init is None:
         k = 1.0 / np.sqrt(H)
-        start = [rng.uniform(-k, k, s).astype(np.float32) for s in ((3 * H, H), (3 * H, H), (3 * H,), (3 * H,))]
+        start = [rng.uniform(-k, k, s).astype(np.float32) for s in ((gates * H, H), (gates * H, H), (gates * H,), (gates * H,))]
     else:
-        start = [getattr(init, n) for n in GRUUserModel.NAMES]
+        start = [getattr(init, n) for n in cls.NAMES]
     torch, _, dev = device_and_library(device)
     E = device_matrix(torch, embeddings, dev, in_place=True)
     w = [torch.from_numpy(np.array(a, dtype=np.float32)).to(dev) for a in start]
@@ -760,7 +794,7 @@ def fit_gru_user_model(histories, embeddings, *, epochs=5, batch_users=256, n_ne
             take = np.repeat(indptr[:-1][ub] - ip[:-1], n) + np.arange(int(ip[-1]), dtype=np.int64)
             it_d = torch.from_numpy(items[take].astype(np.int32)).to(dev)
             ng_d = torch.from_numpy(np.ascontiguousarray(neg[take])).to(dev)
-            _gru_pair_loss_call(torch, E, w, ip, it_d, ng_d, n_neg, grads, scal)
+            _gru_pair_loss_call(torch, E, w, ip, it_d, ng_d, n_neg, grads, scal, cell=cell)
             host = scal.cpu().numpy()                                  # two scalars; the gradients stay on the device
             n_pairs = int(host[1:].view(np.int64)[0])
             if n_pairs == 0:
@@ -777,10 +811,34 @@ def fit_gru_user_model(histories, embeddings, *, epochs=5, batch_users=256, n_ne
         history.append(total / max(pairs, 1))
         if validation is not None and (epoch + 1) % int(validation_every) == 0:
             host = [a.cpu().numpy() for a in w]                       # a copy: the fit goes on with the device tensors
-            m = evaluate_every_click(validation, E, GRUUserModel(*host), device=device)["metrics"]
+            m = evaluate_every_click(validation, E, cls(*host), device=device)["metrics"]
             m["epoch"] = epoch + 1
             scored.append(m)
             if keep_best and m["mrr"] == m["mrr"] and (best is None or m["mrr"] > best):      # NaN (no click to score): never the best
                 best, best_w = m["mrr"], host
     final = best_w if keep_best and best_w is not None else [a.cpu().numpy() for a in w]
-    return GRUUserModel(*final, history=np.asarray(history, dtype=np.float64), validation=scored if validation is not None else None)
+    return cls(*final, history=np.asarray(history, dtype=np.float64), validation=scored if validation is not None else None)
+
+
+def fit_lstm_user_model(histories, embeddings, *, epochs=5, batch_users=256, n_neg=4, lr=1e-2, seed=0, max_events=50, init=None,
+                        window=None, validation=None, validation_every=1, keep_best=False, device=None):
+    """Trains the LSTM user model of the KDD'17 paper on click histories, on the device: ``fit_gru_user_model`` with the loss and
+    gradients of ``lstm_pair_loss`` (``dae_lstm_pair_loss``) -- the same arguments, negatives, permutations, Adam, ``validation`` /
+    ``keep_best`` and errors.  The weights start from ``torch.nn.LSTM``'s rule, uniform in +-1 / sqrt(H), drawn from
+    ``numpy.random.default_rng(seed)`` in the order weight_ih, weight_hh, bias_ih, bias_hh before the permutations -- or from
+    ``init``, an ``LSTMUserModel``.  Two fits with equal arguments return bit-equal weights.  Returns an ``LSTMUserModel`` with
+    ``.history`` and ``.validation``."""
+    return _fit_recurrent_user_model("lstm", LSTMUserModel, 4, histories, embeddings, epochs, batch_users, n_neg, lr, seed, max_events, init,
+                                     window, validation, validation_every, keep_best, device)
+
+
+def fit_rnn_user_model(histories, embeddings, *, epochs=5, batch_users=256, n_neg=4, lr=1e-2, seed=0, max_events=50, init=None,
+                       window=None, validation=None, validation_every=1, keep_best=False, device=None):
+    """Trains the plain-RNN user model of the KDD'17 paper on click histories, on the device: ``fit_gru_user_model`` with the loss
+    and gradients of ``rnn_pair_loss`` (``dae_rnn_pair_loss``) -- the same arguments, negatives, permutations, Adam, ``validation`` /
+    ``keep_best`` and errors.  The weights start from ``torch.nn.RNN``'s rule, uniform in +-1 / sqrt(H), drawn from
+    ``numpy.random.default_rng(seed)`` in the order weight_ih, weight_hh, bias_ih, bias_hh before the permutations -- or from
+    ``init``, an ``RNNUserModel``.  Two fits with equal arguments return bit-equal weights.  Returns an ``RNNUserModel`` with
+    ``.history`` and ``.validation``."""
+    return _fit_recurrent_user_model("rnn", RNNUserModel, 1, histories, embeddings, epochs, batch_users, n_neg, lr, seed, max_events, init,
+                                     window, validation, validation_every, keep_best, device)

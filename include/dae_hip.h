@@ -635,7 +635,7 @@ int dae_gru_user_states(const float* E, int64_t lde, int32_t Na, int32_t D, int3
                         int64_t ldu, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------------------------------------------------
- * LSTM and plain-RNN user states: the other two recurrent user models of the same paper, inference only
+ * LSTM and plain-RNN user states: the other two recurrent user models of the same paper, inference
  * (helpers.lstm_user_states, helpers.rnn_user_states), from weights in the layout of torch.nn.LSTM (gate row blocks
  * i, f, g, o: W_ih [4H x ldwi], W_hh [4H x ldwh], b_ih, b_hh float[4H]) and of torch.nn.RNN(nonlinearity='tanh') (one
  * block: W_ih [H x ldwi], W_hh [H x ldwh], b_ih, b_hh float[H]).  Per user, events oldest first, x = E[items[e]]:
@@ -711,6 +711,51 @@ int dae_rnn_user_states(const float* E, int64_t lde, int32_t Na, int32_t D, int3
  * ------------------------------------------------------------------------------------------------- */
 uint64_t dae_gru_pair_loss_workspace(int32_t Na, int32_t H, int64_t M, int64_t nnz, int32_t T, int32_t n_neg);
 int dae_gru_pair_loss(const float* E, int64_t lde, int32_t Na, int32_t H, const float* W_ih, int64_t ldwi, const float* W_hh,
+                      int64_t ldwh, const float* b_ih, const float* b_hh, const int64_t* indptr, const int32_t* items,
+                      const int32_t* order, int64_t M, int64_t nnz, int32_t T, const int64_t* active_host,
+                      const int32_t* negatives, int32_t n_neg, double* loss, int64_t* n_pairs, float* dW_ih, int64_t ld_dwi,
+                      float* dW_hh, int64_t ld_dwh, float* db_ih, float* db_hh, float* margin, void* workspace,
+                      uint64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
+ * Training steps of the LSTM and plain-RNN user models: dae_gru_pair_loss for the other two cells, on the states of
+ * dae_lstm_user_states / dae_rnn_user_states (helpers.lstm_pair_loss / fit_lstm_user_model, helpers.rnn_pair_loss /
+ * fit_rnn_user_model).  The contract is that of dae_gru_pair_loss, argument for argument: D = H, E fixed and without a
+ * gradient, h (and the LSTM's c) start at zero, the schedule, the negatives, what a valid pair is, loss / n_pairs /
+ * margin, the histories run without their last event, sums NOT divided by n_pairs, the argument checks (every one
+ * reported before any HIP call, messages prefixed "lstm_pair_loss: " / "rnn_pair_loss: ") and the call without a pair
+ * to score, which needs no workspace and writes zero loss, zero pairs and zero gradients.
+ *   Weights and gradients in the layout of torch.nn.LSTM (gate row blocks i, f, g, o: W_ih, dW_ih [4H x ld], W_hh,
+ *   dW_hh [4H x ld], b_ih, b_hh, db_ih, db_hh float[4H]) and of torch.nn.RNN(nonlinearity='tanh') ([H x ld], float[H]).
+ *   Back-propagation through time, per event with the stored gates and states (dh = the loss term plus the carry from
+ *   the next event, x = E[items[e]], h_prev and c_prev the state and cell before the event):
+ *     LSTM:  tc = tanh(c')      dc = dh o (1 - tc^2) + carry_c      da_o = dh tc o (1 - o)      da_i = dc g i (1 - i)
+ *            da_g = dc i (1 - g^2)      da_f = dc c_prev f (1 - f)      da = [da_i, da_f, da_g, da_o]
+ *            carry_c to c_prev = dc f      carry to h_prev = da . W_hh
+ *     RNN:   da = dh (1 - h'^2)      carry to h_prev = da . W_hh
+ *     both:  dW_ih += da^T x      dW_hh += da^T h_prev      db_ih += da      db_hh += da
+ *   Arithmetic and guarantees as dae_gru_pair_loss: fp32 (exact-fp32 MFMA chains in a fixed k order, expf / tanhf /
+ *   log1pf, IEEE division), pair losses widened to fp64 before any sum, no atomics of any kind, every output
+ *   bit-identical run to run; n_pairs and margin independent of the order of the users, the gradients equal under a
+ *   permutation to rounding.  The forward states are the bits of dae_lstm_user_states / dae_rnn_user_states.
+ *   workspace, 256-byte aligned, with pad = round up to 128, al = round up to 256, Hp = pad(H), Rb = pad(nnz + 128 T),
+ *   G = 4 and I = 13 (LSTM) or G = 1 and I = 6 (RNN):
+ *       al(4 pad(Na) Hp) + 3 al(4 G Hp Hp) + al(4 G pad(Na) Hp) + I al(4 Rb Hp) + [LSTM: al(4 pad(M) Hp)]
+ *       + 2 al(8 Rb) + al(4 Rb) + al(64 G Hp Hp)
+ *   bytes -- the images of E, W_ih, W_hh and W_hh^T, the input projection of every article, the time-major stash (LSTM:
+ *   h_prev, h, i, f, g, o, c', the four transposed gate gradients, h_prev^T and x^T; RNN: h_prev, h, its copy, da^T,
+ *   h_prev^T, x^T), the LSTM's cell carry, three per-row arrays and 16 split-K slabs [G Hp x Hp].  Every image must stay
+ *   below 4 GiB: 4 G Hp Rb < 2^32 (train in mini-batches of users).  lde, ldwi, ldwh, ld_dwi, ld_dwh >= H.
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_lstm_pair_loss_workspace(int32_t Na, int32_t H, int64_t M, int64_t nnz, int32_t T, int32_t n_neg);
+int dae_lstm_pair_loss(const float* E, int64_t lde, int32_t Na, int32_t H, const float* W_ih, int64_t ldwi, const float* W_hh,
+                       int64_t ldwh, const float* b_ih, const float* b_hh, const int64_t* indptr, const int32_t* items,
+                       const int32_t* order, int64_t M, int64_t nnz, int32_t T, const int64_t* active_host,
+                       const int32_t* negatives, int32_t n_neg, double* loss, int64_t* n_pairs, float* dW_ih, int64_t ld_dwi,
+                       float* dW_hh, int64_t ld_dwh, float* db_ih, float* db_hh, float* margin, void* workspace,
+                       uint64_t workspace_bytes, void* stream);
+uint64_t dae_rnn_pair_loss_workspace(int32_t Na, int32_t H, int64_t M, int64_t nnz, int32_t T, int32_t n_neg);
+int dae_rnn_pair_loss(const float* E, int64_t lde, int32_t Na, int32_t H, const float* W_ih, int64_t ldwi, const float* W_hh,
                       int64_t ldwh, const float* b_ih, const float* b_hh, const int64_t* indptr, const int32_t* items,
                       const int32_t* order, int64_t M, int64_t nnz, int32_t T, const int64_t* active_host,
                       const int32_t* negatives, int32_t n_neg, double* loss, int64_t* n_pairs, float* dW_ih, int64_t ld_dwi,

@@ -18,8 +18,9 @@ with the negatives of helpers.sample_negatives (fresh per epoch, seeded).  Padde
     python tools/gru_fit_torch.py --cell lstm --embeddings emb.npy --sessions sessions.npz --out lstm.npz
 
 --cell lstm / --cell rnn train a torch.nn.LSTM / torch.nn.RNN (tanh) the same way and write helpers.LSTMUserModel's /
-helpers.RNNUserModel's .npz: the trainer of those two cells, whose states the device computes (helpers.lstm_user_states,
-helpers.rnn_user_states) but which it does not train.  The default, --cell gru, is unchanged.
+helpers.RNNUserModel's .npz: the comparison route of helpers.fit_lstm_user_model / helpers.fit_rnn_user_model (dae_lstm_pair_loss,
+dae_rnn_pair_loss), as the default is of the GRU's -- what tests/test_hip_lstm_rnn_fit.py holds the device fits against and
+tools/rnn_fit_bench.py times them against.  The default, --cell gru, is unchanged.
 """
 import argparse
 import os
