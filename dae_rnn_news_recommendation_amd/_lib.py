@@ -176,6 +176,10 @@ SIGNATURES = {
     "dae_kmeans_assign": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, u64, vp]),
     "dae_kmeans_update_workspace": (u64, [i32, i32, i32]),
     "dae_kmeans_update": (i32, [vp, i32, i32, vp, i32, vp, i64, vp, vp, vp, vp, vp, u64, vp]),
+    "dae_covisit_record_bound": (u64, [vp, i32, i32, i32]),
+    "dae_covisit_neighbors_workspace": (u64, [u64, i32, i32]),
+    "dae_covisit_neighbors": (i32, [vp, vp, vp, i32, i64, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, u64, vp]),
+    "dae_covisit_recommend": (i32, [vp, vp, i64, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp]),
     "dae_csr_column_stats_workspace": (u64, []),
     "dae_csr_column_stats": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, u64, vp]),
     "dae_csr_select_columns_workspace": (u64, [i32]),

@@ -27,6 +27,9 @@ is importable from here; the code lives by subject:
 * ``clustering`` -- spherical k-means on the device (``kmeans`` -> ``KMeansResult``, ``kmeans_assign``, ``relocation_rows``),
   ``cluster_label_scores`` (purity / NMI / ARI against labels; host code) and ``ClusterIndex``, cluster-probed top-k on the windowed
   ``most_similar`` (``merge_probe_lists``).
+* ``covisit`` -- the co-visitation baseline, built from co-clicks alone: ``covisit_neighbors`` -> ``CovisitIndex`` (``recommend``,
+  ``similar``, ``save`` / ``load``), ``covisit_recommend``, ``fill_popular_tails`` and ``list_overlap`` (two neighbour tables
+  compared; host code).
 * ``_device`` -- what every device call starts and ends with, once: device and library, the ``norm`` / ``metric`` check, the
   matrix and history intakes, uploads, workspaces, the result tail.
 
@@ -34,6 +37,7 @@ The device functions have no CPU implementation: without the built library / a G
 imported inside the functions that need them; importing this package needs numpy alone."""
 from .clustering import (ClusterIndex, KMeansResult, cluster_label_scores, kmeans, kmeans_assign, merge_probe_lists,
                          relocation_rows)
+from .covisit import CovisitIndex, covisit_neighbors, covisit_recommend, fill_popular_tails, list_overlap
 from .evaluation import (click_prefix_lists, evaluate_every_click, every_click_rows, list_diversity, next_click_metrics,
                          popularity_ranks, popularity_ranks_every_click, popularity_recommend, rank_metrics, rank_metrics_by_position,
                          recommend, recommend_diverse, recommend_every_click, recommend_ranks, recommend_ranks_every_click)

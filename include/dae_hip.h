@@ -962,6 +962,55 @@ int dae_kmeans_update(const float* Xi, int32_t N, int32_t D, const int32_t* labe
                       uint64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------------------------------------------------
+ * Co-visitation, the item-to-item baseline (helpers.covisit_neighbors / CovisitIndex): "readers of this article also read ...",
+ * from co-clicks alone -- no embeddings, no Na x Na matrix (emit -> sort -> run-length -> select; csrc/dae_covisit.hip).
+ * The log is a history CSR: indptr int64[M + 1], items int32[nnz], oldest click first, over Na articles.
+ *   records: for every user and every pair of positions p < q <= p + window of that user's history, a = items[p], b = items[q]:
+ *   if a != b the record (a, b), and with both = 1 also (b, a).  Equal items emit nothing; a repeat of an article is an ordinary
+ *   click.  (An item outside [0, Na) is no click and pairs with nothing.)  c[a, b] = the number of records (a, b); clicks[a] = the
+ *   occurrences of a in items; degree[a] = the number of distinct b with c[a, b] > 0.
+ *   similarity, fp32 with one rounding per operation: normalize 0 (none) s = (float) c; normalize 1 (cosine)
+ *   s = (float) c / sqrtf((float) clicks[a] * (float) clicks[b]) -- a correctly rounded product, root and quotient, so the table
+ *   equals a NumPy float32 restatement bit for bit.
+ *   table: row a holds its min(K, degree[a]) best neighbours by (s descending, b ascending) as nbr int32 / sim fp32 / cnt int32
+ *   [Na x ld], ld >= K; the tail of a row is -1 / 0 / 0; columns K .. ld are not touched.  1 <= K <= 128, window >= 1.
+ *   dae_covisit_record_bound (host only, no GPU): sum over the users and p of min(window, L - 1 - p), doubled for both -- the number
+ *   of records when no pair has equal items, and an upper bound otherwise.  0 for M <= 0 or window < 1.
+ *   dae_covisit_neighbors: indptr / items on the device, indptr_host a host copy of indptr: the call takes the bound from it and
+ *   checks the workspace against it before anything is launched, and a record is stored only below the bound, so the record
+ *   buffers cannot be overrun.  degree / clicks int32[Na]; totals int64[2] (device): records emitted, distinct pairs.  All integer
+ *   counts (the click counts and the record cursor use integer atomics: exact), every float one fixed chain of roundings: the
+ *   outputs are bit-identical from run to run and do not depend on the order of the users or on the workspace size.  Rows are
+ *   skewed, so a row of up to 256 distinct neighbours is selected by one wave and a longer one by a whole workgroup in passes.
+ *   M == 0, nnz == 0 or a bound of 0 (no history of two clicks): tails and zeros, no workspace needed.  The call synchronises.
+ *   memory: dae_covisit_neighbors_workspace(record_bound, Na, K) = 20 bytes per record of the bound (two 8-byte key buffers and
+ *   the 4-byte run counts) + 8 (Na + 1) + the scratch rocprim asks for on the current device (0: bound 0, a bad argument or a
+ *   failed query); 256-byte aligned.  One call takes a bound below 2^31 records; a larger log has to be built from fewer users
+ *   (merging count tables of user batches is not provided).
+ *   dae_covisit_recommend: per user u of a query CSR (indptr int64[M + 1], items int32; need not be the log of the table) the
+ *   sources are the last min(last, L) clicks, walked oldest first; the source of age j (0: the newest click) with item x adds
+ *   __fmul_rn(age_weight[j], sim[x, t]) to the fp32 accumulator of candidate nbr[x, t] for every filled slot t, with __fadd_rn
+ *   from 0 in the order of the sources; an article clicked twice among them contributes twice.  A candidate is any article
+ *   reached, whatever its sum, that is not in the user's seen list (seen_indptr int64[M + 1], seen_items int32: every row ascending
+ *   and unique -- helpers.normalize_exclusions) and, with win_lo / win_hi int32[M] (both or neither), has win_lo[u] <= c <
+ *   win_hi[u].  idx int32 / score fp32 [M x ldo], ldo >= k: the k best by (score descending, index ascending), -0 and +0 one
+ *   score, tail -1 / -inf (the convention of dae_topk_similarity); columns k .. ldo are not touched.  1 <= last <= 32, 1 <= k <=
+ *   128, age_weight fp32[last] on the device.  One workgroup per user, at most last * K <= 4096 entries in 48 KiB of LDS; no
+ *   workspace, no synchronisation.  Bit-identical from run to run.
+ * Argument errors are reported before any HIP call, with the prefixes "covisit_neighbors: " / "covisit_recommend: ".
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_covisit_record_bound(const int64_t* indptr_host, int32_t M, int32_t window, int32_t both);
+uint64_t dae_covisit_neighbors_workspace(uint64_t record_bound, int32_t Na, int32_t K);
+int dae_covisit_neighbors(const int64_t* indptr, const int32_t* items, const int64_t* indptr_host, int32_t M, int64_t nnz,
+                          int32_t Na, int32_t window, int32_t both, int32_t normalize, int32_t K, int32_t* nbr, float* sim,
+                          int32_t* cnt, int64_t ld, int32_t* degree, int32_t* clicks, int64_t* totals, void* workspace,
+                          uint64_t workspace_bytes, void* stream);
+int dae_covisit_recommend(const int32_t* nbr, const float* sim, int64_t ld, int32_t Na, int32_t K, const int64_t* indptr,
+                          const int32_t* items, int32_t M, const int64_t* seen_indptr, const int32_t* seen_items,
+                          const int32_t* win_lo, const int32_t* win_hi, const float* age_weight, int32_t last, int32_t k,
+                          int32_t* idx, float* score, int64_t ldo, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
  * From a count matrix to the training input (helpers.column_stats / limit_features / select_columns / TfidfTransformer): what
  * sklearn's CountVectorizer._limit_features and TfidfTransformer do to a bag of words, on CSR rows that stay on the device.
  * CSR as dae_sweep_image_csr: indptr int64[rows + 1] points at the chunk's first row and holds offsets into indices int32 /

@@ -23,6 +23,7 @@ examples:
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --rec_mmr 0.7 --rec_max_per_label 3 --similarity False
   python main_autoencoder.py --model_name topics --cluster 40 --validation --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --ann_clusters 64 --ann_probe 8 --similarity False
+  python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --covisit --covisit_window 3 --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --every_click --user_model gru --fit_gru --gru_validation 0.2 --similarity False
 """
 import argparse
@@ -203,6 +204,16 @@ def build_parser():
                         "every user scored against the articles of the --ann_probe nearest clusters only): recall@K against the exact "
                         "lists, hit / MRR / nDCG and the share of the corpus scored per user; saves article_encoded_recommend{K}_ann.npz")
     p.add_argument("--ann_probe", type=int, default=8, help="clusters probed per user by --ann_clusters C, 1..128")
+    p.add_argument("--covisit", action="store_true",
+                   help="with --sessions S --recommend K: ALSO the co-visitation baseline, readers of this article also read ... -- a "
+                        "neighbour table built on the device from the co-clicks of the same histories (helpers.covisit_neighbors: no "
+                        "embeddings, no articles x articles matrix), recommended from (CovisitIndex.recommend); prints hit@K / MRR / nDCG "
+                        "as `co-visited articles` and the overlap of the co-click neighbours with the embedding neighbours "
+                        "(helpers.list_overlap against helpers.most_similar), and saves article_encoded_recommend{K}_covisit.npz; honours "
+                        "--max_age.  The other output and files stay what they are")
+    p.add_argument("--covisit_window", type=int, default=3, help="W >= 1: two clicks of a user at most W positions apart co-occur (--covisit)")
+    p.add_argument("--covisit_neighbors", type=int, default=50, help="N in 1..128: neighbours kept per article by --covisit")
+    p.add_argument("--covisit_last", type=int, default=10, help="M in 1..32: the most recent clicks --covisit recommends from")
     return p
 
 
@@ -247,6 +258,9 @@ def validate(a):
     assert a.ann_clusters == 0 or (a.ann_clusters > 0 and a.recommend > 0 and a.max_age == 0.), \
         "--ann_clusters C needs --recommend K (and does not go with --max_age: an index takes no windows)"
     assert 1 <= a.ann_probe <= 128, "--ann_probe is a number in 1..128"
+    assert not a.covisit or (a.sessions != '' and a.recommend > 0), "--covisit needs --sessions S --recommend K"
+    assert a.covisit_window >= 1 and 1 <= a.covisit_neighbors <= 128 and 1 <= a.covisit_last <= 32, \
+        "--covisit_window W >= 1, --covisit_neighbors N in 1..128, --covisit_last M in 1..32"
     assert a.max_age == 0. or (a.sessions == 'synthetic' and a.recommend > 0), "--max_age needs --sessions synthetic --recommend K"
     return a
 
@@ -441,6 +455,8 @@ def evaluate_recommend(a, trY, emb, data_dir):
         evaluate_recommend_mmr(a, trY, states, emb, hist, targets, data_dir)
     if a.ann_clusters > 0:
         evaluate_recommend_ann(a, states, emb, hist, idx, targets, data_dir)
+    if a.covisit:
+        evaluate_recommend_covisit(a, emb, hist, targets, data_dir)
     models = {}
     if a.rank_metrics:
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir)
@@ -474,6 +490,33 @@ def evaluate_recommend_ann(a, states, emb, hist, exact, targets, data_dir):
     print('  recall@%d against the exact lists %.4f, %.4f of the corpus scored per user -> %s' % (K, recall, index.probed_fraction(states, P), name))
     print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'cluster index', m['hit'], m['mrr'], m['ndcg']))
     print('calculate recommend through clusters done')
+    return idx, score
+
+
+def evaluate_recommend_covisit(a, emb, hist, targets, data_dir, window=None):
+    """--covisit: the co-visitation baseline beside the embedding models.  The neighbour table is built on the device from the
+    co-clicks of the histories the other models see -- the held-out click is not among them -- (helpers.covisit_neighbors:
+    --covisit_window, both directions, cosine, --covisit_neighbors per article) and every user is recommended the K unseen articles
+    the neighbours of the last --covisit_last clicks point at (CovisitIndex.recommend; with ``window`` inside the candidate windows
+    of --max_age).  Prints hit@K / MRR@K / nDCG@K as `co-visited articles` and the share of an article's co-click neighbours that
+    are also among its nearest embedding neighbours (helpers.list_overlap against helpers.most_similar).  Saves ``indices`` /
+    ``scores`` / ``targets`` / ``hist_indptr`` / ``hist_items`` / ``neighbors`` / ``sims`` / ``counts`` to
+    article_encoded_recommend{K}[_window]_covisit.npz."""
+    from dae_rnn_news_recommendation_amd import helpers
+    K, n, N = a.recommend, emb.shape[0], a.covisit_neighbors
+    name = 'article_encoded_recommend%d%s_covisit.npz' % (K, '' if window is None else '_window')
+    print('calculate recommend %d covisit' % K)
+    index = helpers.covisit_neighbors(hist, n, window=a.covisit_window, n_neighbors=N)
+    idx, score = index.recommend(hist, K, last=a.covisit_last, window=window)
+    np.savez(data_dir + name, indices=idx, scores=score, targets=targets, hist_indptr=hist[0], hist_items=hist[1],
+             neighbors=index.neighbors, sims=index.sims, counts=index.counts)
+    m = helpers.next_click_metrics(idx, targets)
+    print('  window %d, %d neighbours, last %d clicks: %d records, %d distinct pairs, %.1f neighbours per article -> %s' % (
+        a.covisit_window, N, a.covisit_last, index.n_records, index.n_pairs, float(index.degree.mean()), name))
+    print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'co-visited articles', m['hit'], m['mrr'], m['ndcg']))
+    near = helpers.most_similar(emb, k=min(N, max(n - 1, 1)))[0]
+    print('  co-click neighbours among the %d nearest embedding neighbours: %.4f' % (near.shape[1], helpers.list_overlap(index.neighbors, near)[1]))
+    print('calculate recommend %d covisit done' % K)
     return idx, score
 
 
@@ -605,6 +648,8 @@ def evaluate_recommend_window(a, trY, emb, data_dir):
         evaluate_recommend_dedup(a, states, emb, hist, targets, data_dir, window=window)
     if a.rec_mmr is not None:
         evaluate_recommend_mmr(a, trY, states, emb, hist, targets, data_dir, window=window)
+    if a.covisit:
+        evaluate_recommend_covisit(a, emb, hist, targets, data_dir, window=window)
     models = {}
     if a.rank_metrics:
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir, window=window, max_age=a.max_age)
