@@ -180,6 +180,14 @@ SIGNATURES = {
     "dae_covisit_neighbors_workspace": (u64, [u64, i32, i32]),
     "dae_covisit_neighbors": (i32, [vp, vp, vp, i32, i64, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, u64, vp]),
     "dae_covisit_recommend": (i32, [vp, vp, i64, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp]),
+    "dae_als_interactions_workspace": (u64, [i64, i32, i32]),
+    "dae_als_interactions": (i32, [vp, vp, i32, i64, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp, u64, vp]),
+    "dae_als_gram_workspace": (u64, [i32, i32]),
+    "dae_als_gram": (i32, [vp, i64, i32, i32, f32, vp, vp, u64, vp]),
+    "dae_als_solve_rows_workspace": (u64, [i32]),
+    "dae_als_solve_rows": (i32, [vp, vp, vp, i32, vp, i64, i32, i32, vp, f32, i32, vp, i64, vp, u64, vp]),
+    "dae_als_loss_workspace": (u64, [i32, i32, i32]),
+    "dae_als_loss": (i32, [vp, vp, vp, i32, vp, i64, vp, i64, i32, i32, f32, f32, vp, vp, u64, vp]),
     "dae_csr_column_stats_workspace": (u64, []),
     "dae_csr_column_stats": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, u64, vp]),
     "dae_csr_select_columns_workspace": (u64, [i32]),

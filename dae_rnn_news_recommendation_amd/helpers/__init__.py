@@ -30,11 +30,16 @@ is importable from here; the code lives by subject:
 * ``covisit`` -- the co-visitation baseline, built from co-clicks alone: ``covisit_neighbors`` -> ``CovisitIndex`` (``recommend``,
   ``similar``, ``save`` / ``load``), ``covisit_recommend``, ``fill_popular_tails`` and ``list_overlap`` (two neighbour tables
   compared; host code).
+* ``als`` -- implicit-feedback matrix factorisation by alternating least squares, the ID-based collaborative filter:
+  ``als_interactions`` -> ``ALSInteractions`` (both orientations of the click counts), ``als_gram``, ``als_solve_rows`` (one
+  half-sweep of conjugate gradient per row), ``als_loss``, and ``fit_als`` -> ``ALSModel`` (``user_states``, ``recommend``,
+  ``similar``, ``save`` / ``load``).
 * ``_device`` -- what every device call starts and ends with, once: device and library, the ``norm`` / ``metric`` check, the
   matrix and history intakes, uploads, workspaces, the result tail.
 
 The device functions have no CPU implementation: without the built library / a GPU they raise.  torch, scipy and pandas are
 imported inside the functions that need them; importing this package needs numpy alone."""
+from .als import ALSInteractions, ALSModel, als_gram, als_interactions, als_loss, als_solve_rows, fit_als
 from .clustering import (ClusterIndex, KMeansResult, cluster_label_scores, kmeans, kmeans_assign, merge_probe_lists,
                          relocation_rows)
 from .covisit import CovisitIndex, covisit_neighbors, covisit_recommend, fill_popular_tails, list_overlap

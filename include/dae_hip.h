@@ -1011,6 +1011,60 @@ int dae_covisit_recommend(const int32_t* nbr, const float* sim, int64_t ld, int3
                           int32_t* idx, float* score, int64_t ldo, void* stream);
 
 /* -------------------------------------------------------------------------------------------------
+ * Implicit-feedback matrix factorisation by alternating least squares (helpers.fit_als / ALSModel; Hu, Koren, Volinsky 2008;
+ * csrc/dae_als.hip).  r_ui = the number of times user u clicked article i, c_ui = 1 + alpha r_ui, p_ui = [r_ui > 0];
+ *   L = sum over ALL u, i of c_ui (p_ui - x_u . y_i)^2 + lambda (|X|^2 + |Y|^2), X fp32 [M x F], Y fp32 [Na x F], 1 <= F <= 128.
+ * One half-sweep holds Y and solves A_u x_u = b_u for every row u of a CSR (ptr int64[R + 1], idx int32, cnt int32):
+ *   A_u = G + sum_j alpha cnt_j y_j y_j^T,  G = Y^T Y + lambda I,  b_u = sum_j (1 + alpha cnt_j) y_j,  j over the row's entries,
+ * by cg_steps steps of conjugate gradient from the row's current factor; A_u is never formed.  The other half-sweep is the same
+ * call on the other orientation with X and Y swapped.
+ *   dae_als_interactions: the history CSR (indptr int64[M + 1], items int32[nnz], on the device) as both orientations of the
+ *   de-duplicated interaction matrix: user_ptr int64[M + 1], user_idx / user_cnt int32 (per user the distinct articles ascending
+ *   and how often each was clicked), item_ptr int64[Na + 1], item_idx / item_cnt (per article its distinct users ascending).
+ *   The idx / cnt buffers hold cap >= nnz cells; only the first `distinct pairs` cells are written.  totals int64[2] (device):
+ *   events, distinct pairs.  An item outside [0, Na) is no event.  Integer arithmetic only: 64-bit keys, rocprim radix sort over
+ *   the bits in use, run-length encode, row offsets by binary search.  nnz < 2^31 per call.  workspace:
+ *   dae_als_interactions_workspace(nnz, M, Na) = 24 bytes per event + the scratch rocprim asks for on the current device (0:
+ *   nnz 0, a bad argument or a failed query); 256-byte aligned; nnz == 0 needs none.  The call synchronises.
+ *   dae_als_gram: G fp32 [F x F] (contiguous) = fl32(Y^T Y + lambda I) of Y fp32 [N x ldy]: fp64 sums over
+ *   nb = min(256, ceil(N / 64)) blocks of ceil(N / nb) consecutive rows, each block ascending, the blocks added ascending, lambda
+ *   added in fp64, one rounding to fp32.  workspace: dae_als_gram_workspace(N, F) = 8 nb F^2 bytes.
+ *   dae_als_solve_rows: X fp32 [R x ldx] updated in place from Y fp32 [N x ldy] (X and Y must differ), ldx, ldy >= F; columns
+ *   F .. ld are not touched.  1 <= cg_steps <= 32.  Per row, in fp32 with one rounding per operation (no contraction):
+ *     no entries: x = 0 exactly.  Otherwise r = b - A x, p = r, rs = r . r; per step: stop if rs <= 1e-20; Ap = A p; stop unless
+ *     p . Ap > 0; a = rs / (p . Ap); x += a p; r -= a Ap; rs' = r . r; p = r + (rs' / rs) p; rs = rs'.
+ *   A v = G v + sum_j (alpha cnt_j) (y_j . v) y_j is one sum of scaled rows -- the rows of G ascending, then the entries in stored
+ *   order; an entry whose index lies outside [0, N) adds nothing.  The terms are dealt round-robin to Gt groups of lanes, each
+ *   group adds its terms in that order, and the group sums are added in a fixed tree.  Gt depends on F and on whether the row has
+ *   at most 256 entries (one wave per row) or more (one workgroup of 16 waves per row) -- on the row's length and on nothing else:
+ *   not on the row's position, its neighbours in the launch or the workspace.  No floating-point atomics: bit-identical from run
+ *   to run and under any permutation of the rows.  workspace: dae_als_solve_rows_workspace(R) = 256 + 4 R bytes (the list of
+ *   the long rows).  No synchronisation.
+ *   dae_als_loss: *loss (device, double) = L above without the M x Na matrix,
+ *     L = <X^T X, Y^T Y> + sum over the stored entries of [c (1 - s)^2 - s^2] + lambda (|X|^2 + |Y|^2),  s = x_u . y_i,
+ *   all in fp64: both Grams by the kernels of dae_als_gram, one partial per row of X (its entries and lambda |x_u|^2), one per row
+ *   of Y, one per Gram cell, summed in a fixed order (256 chunks, then one).  alpha and lambda are the fp32 numbers the solve and
+ *   the Gram were given.  workspace: dae_als_loss_workspace(R, N, F).  No synchronisation.
+ * Argument errors are reported before any HIP call, with the prefixes "als_interactions: " / "als_gram: " / "als_solve_rows: " /
+ * "als_loss: ".
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_als_interactions_workspace(int64_t nnz, int32_t M, int32_t Na);
+int dae_als_interactions(const int64_t* indptr, const int32_t* items, int32_t M, int64_t nnz, int32_t Na, int64_t* user_ptr,
+                         int32_t* user_idx, int32_t* user_cnt, int64_t* item_ptr, int32_t* item_idx, int32_t* item_cnt, int64_t cap,
+                         int64_t* totals, void* workspace, uint64_t workspace_bytes, void* stream);
+uint64_t dae_als_gram_workspace(int32_t N, int32_t F);
+int dae_als_gram(const float* Y, int64_t ldy, int32_t N, int32_t F, float lambda, float* G, void* workspace, uint64_t workspace_bytes,
+                 void* stream);
+uint64_t dae_als_solve_rows_workspace(int32_t R);
+int dae_als_solve_rows(const int64_t* ptr, const int32_t* idx, const int32_t* cnt, int32_t R, const float* Y, int64_t ldy, int32_t N,
+                       int32_t F, const float* G, float alpha, int32_t cg_steps, float* X, int64_t ldx, void* workspace,
+                       uint64_t workspace_bytes, void* stream);
+uint64_t dae_als_loss_workspace(int32_t R, int32_t N, int32_t F);
+int dae_als_loss(const int64_t* ptr, const int32_t* idx, const int32_t* cnt, int32_t R, const float* X, int64_t ldx, const float* Y,
+                 int64_t ldy, int32_t N, int32_t F, float alpha, float lambda, double* loss, void* workspace, uint64_t workspace_bytes,
+                 void* stream);
+
+/* -------------------------------------------------------------------------------------------------
  * From a count matrix to the training input (helpers.column_stats / limit_features / select_columns / TfidfTransformer): what
  * sklearn's CountVectorizer._limit_features and TfidfTransformer do to a bag of words, on CSR rows that stay on the device.
  * CSR as dae_sweep_image_csr: indptr int64[rows + 1] points at the chunk's first row and holds offsets into indices int32 /

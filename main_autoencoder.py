@@ -24,6 +24,7 @@ examples:
   python main_autoencoder.py --model_name topics --cluster 40 --validation --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --ann_clusters 64 --ann_probe 8 --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --covisit --covisit_window 3 --similarity False
+  python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --als --als_factors 64 --als_iterations 15 --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --every_click --user_model gru --fit_gru --gru_validation 0.2 --similarity False
 """
 import argparse
@@ -214,6 +215,15 @@ def build_parser():
     p.add_argument("--covisit_window", type=int, default=3, help="W >= 1: two clicks of a user at most W positions apart co-occur (--covisit)")
     p.add_argument("--covisit_neighbors", type=int, default=50, help="N in 1..128: neighbours kept per article by --covisit")
     p.add_argument("--covisit_last", type=int, default=10, help="M in 1..32: the most recent clicks --covisit recommends from")
+    p.add_argument("--als", action="store_true",
+                   help="with --sessions S --recommend K: ALSO implicit-feedback matrix factorisation by alternating least squares, the "
+                        "ID-based collaborative filter, trained on the device on the same histories (helpers.fit_als); prints hit@K / MRR / "
+                        "nDCG as `ALS factors` (and its line of --rank_metrics), saves article_encoded_recommend{K}_als.npz and "
+                        "als_model.npz; honours --max_age.  The other output and files stay what they are")
+    p.add_argument("--als_factors", type=int, default=64, help="F in 1..128: the number of factors of --als")
+    p.add_argument("--als_iterations", type=int, default=15, help="iterations of --als (a user and an article half-sweep each)")
+    p.add_argument("--als_alpha", type=float, default=40.0, help="the confidence of a click of --als: c = 1 + alpha * clicks")
+    p.add_argument("--als_reg", type=float, default=0.01, help="the regularisation lambda of --als")
     return p
 
 
@@ -262,6 +272,9 @@ def validate(a):
     assert a.covisit_window >= 1 and 1 <= a.covisit_neighbors <= 128 and 1 <= a.covisit_last <= 32, \
         "--covisit_window W >= 1, --covisit_neighbors N in 1..128, --covisit_last M in 1..32"
     assert a.max_age == 0. or (a.sessions == 'synthetic' and a.recommend > 0), "--max_age needs --sessions synthetic --recommend K"
+    assert not a.als or (a.sessions != '' and a.recommend > 0), "--als needs --sessions S --recommend K"
+    assert 1 <= a.als_factors <= 128 and a.als_iterations >= 0 and a.als_alpha >= 0. and a.als_reg >= 0., \
+        "--als_factors F in 1..128, --als_iterations N >= 0, --als_alpha A >= 0, --als_reg L >= 0"
     return a
 
 
@@ -457,6 +470,8 @@ def evaluate_recommend(a, trY, emb, data_dir):
         evaluate_recommend_ann(a, states, emb, hist, idx, targets, data_dir)
     if a.covisit:
         evaluate_recommend_covisit(a, emb, hist, targets, data_dir)
+    if a.als:
+        evaluate_recommend_als(a, hist, targets, n, data_dir)
     models = {}
     if a.rank_metrics:
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir)
@@ -517,6 +532,40 @@ def evaluate_recommend_covisit(a, emb, hist, targets, data_dir, window=None):
     near = helpers.most_similar(emb, k=min(N, max(n - 1, 1)))[0]
     print('  co-click neighbours among the %d nearest embedding neighbours: %.4f' % (near.shape[1], helpers.list_overlap(index.neighbors, near)[1]))
     print('calculate recommend %d covisit done' % K)
+    return idx, score
+
+
+def evaluate_recommend_als(a, hist, targets, n, data_dir, window=None):
+    """--als: implicit-feedback matrix factorisation beside the embedding models.  The factors are fitted on the device to the
+    histories the other models see -- the held-out click is not among them -- (helpers.fit_als: --als_factors, --als_iterations,
+    --als_alpha, --als_reg) and every user is recommended the K unseen articles with the largest inner product of the user's and
+    the article's factors (ALSModel.recommend; with ``window`` inside the candidate windows of --max_age).  Prints hit@K / MRR@K /
+    nDCG@K as `ALS factors`, and with --rank_metrics the line of evaluate_rank_metrics for the same model.  Saves ``indices`` /
+    ``scores`` / ``targets`` / ``hist_indptr`` / ``hist_items`` (and ``rank`` / ``n_candidates`` with --rank_metrics) to
+    article_encoded_recommend{K}[_window]_als.npz and the model to als_model.npz."""
+    from dae_rnn_news_recommendation_amd import helpers
+    K = a.recommend
+    name = 'article_encoded_recommend%d%s_als.npz' % (K, '' if window is None else '_window')
+    print('calculate recommend %d als' % K)
+    model = helpers.fit_als(hist, n, factors=a.als_factors, regularization=a.als_reg, alpha=a.als_alpha, iterations=a.als_iterations,
+                            compute_loss=True)
+    idx, score = model.recommend(hist, K, window=window)
+    extra = {}
+    m = helpers.next_click_metrics(idx, targets)
+    curve = model.loss_curve
+    print('  %d factors, %d iterations, alpha %g, lambda %g: loss %s -> %s' % (
+        model.factors, model.iterations, model.alpha, model.regularization,
+        '%.6g to %.6g' % (curve[0], curve[-1]) if curve else 'not computed', name))
+    print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'ALS factors', m['hit'], m['mrr'], m['ndcg']))
+    if a.rank_metrics:
+        rank, _, n_cand = helpers.recommend_ranks(model.user_states(hist), model.item_factors, targets, seen=hist, window=window)
+        r = helpers.rank_metrics(rank, n_cand, targets, ks=(1, 10, 100))
+        print('  ranks %-20s AUC %.4f  MRR %.4f  mean rank %.1f  median rank %.1f  hit@1 %.4f  hit@10 %.4f  hit@100 %.4f'
+              % ('ALS factors', r['auc'], r['mrr'], r['mean_rank'], r['median_rank'], r['hit@1'], r['hit@10'], r['hit@100']))
+        extra = dict(rank=rank, n_candidates=n_cand)
+    np.savez(data_dir + name, indices=idx, scores=score, targets=targets, hist_indptr=hist[0], hist_items=hist[1], **extra)
+    model.save(data_dir + 'als_model.npz')
+    print('calculate recommend %d als done' % K)
     return idx, score
 
 
@@ -650,6 +699,8 @@ def evaluate_recommend_window(a, trY, emb, data_dir):
         evaluate_recommend_mmr(a, trY, states, emb, hist, targets, data_dir, window=window)
     if a.covisit:
         evaluate_recommend_covisit(a, emb, hist, targets, data_dir, window=window)
+    if a.als:
+        evaluate_recommend_als(a, hist, targets, n, data_dir, window=window)
     models = {}
     if a.rank_metrics:
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir, window=window, max_age=a.max_age)
