@@ -124,6 +124,7 @@ __global__ __launch_bounds__(256) void split_pairs_kernel(const float* __restric
         int32_t lj = -1;
         float s = 0.f;
         if (j < i) { lj = labels[j]; s = S[(int64_t)i * lds + j]; }
+        if (s == 0.f) s = 0.f;                                  // -0 and +0 are one score (a tie), as in pair_key: score_key tells them apart
         const bool valid = lj >= 0;
         const bool is_rel = valid && lj == li, is_un = valid && lj != li;
         const unsigned long long br = __ballot(is_rel), bu = __ballot(is_un);

@@ -111,10 +111,7 @@ def visualize_pairwise_similarity(labels, pairwise_similarity_metrics, plot='box
     if S.stride(1) != 1:
         S = S.contiguous()
     N = int(S.shape[0])
-    lab = np.asarray(labels).reshape(N, -1)[:, 0]
-    if lab.dtype.kind == 'f':                      # NaN / inf 'missing' labels: the reference filters them with labels >= 0
-        lab = np.where(np.isfinite(lab), lab, -1.0)
-    lab = np.ascontiguousarray(lab.astype(np.int32))
+    lab = _label_ids(labels, N)                    # NaN / inf / negative labels are missing: the reference filters with labels >= 0
     ws_bytes = int(lib.dae_pair_stats_workspace(N))
     ws_p, ws = workspace(S.device, ws_bytes)
     out = (ctypes.c_double * 16)()

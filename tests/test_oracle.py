@@ -350,3 +350,28 @@ def test_pair_stats_auroc_vs_sklearn():
     assert got["n_related"] == len(rel) and got["n_unrelated"] == len(un)
     assert abs(got["auroc"] - auc(fpr, tpr)) < 1e-12
     assert abs(got["related"]["median"] - np.median(rel)) < 1e-12
+
+
+def test_pair_stats_signed_zeros_tie_like_sklearn():
+    """-0.0 and +0.0 are one score, a tie, for oracle.pair_stats as for scikit-learn's roc_auc_score: the rule the signed-zero tests
+    of tests/test_hip_similarity.py hold dae_pair_stats to.  First the case where an order with -0.0 below +0.0 gives 0 instead of
+    0.5, then both zeros in both classes among other values."""
+    from sklearn.metrics import roc_auc_score
+    S = np.zeros((4, 4))
+    S[1, 0] = S[3, 2] = -0.0
+    got = O.pair_stats(np.array([0, 0, 1, 1]), S)
+    assert (got["n_related"], got["n_unrelated"], got["auroc"]) == (2, 4, 0.5)
+    assert roc_auc_score([1, 1, 0, 0, 0, 0], [-0.0, -0.0, 0.0, 0.0, 0.0, 0.0]) == 0.5
+    rng = np.random.default_rng(13)
+    n = 50
+    lab = rng.integers(-1, 3, n)
+    S = rng.choice(np.array([-1.0, -0.0, 0.0, 0.5, 1.0]), (n, n))
+    got = O.pair_stats(lab, S)
+    ok = (lab[None, :] >= 0) & (lab[:, None] >= 0)
+    same = (lab[None, :] == lab[:, None]) & ok
+    low = np.tril(np.ones((n, n), bool), -1)
+    rel, un = S[same & low], S[(~same) & ok & low]
+    for v in (rel, un):
+        assert np.signbit(v[v == 0]).any() and not np.signbit(v[v == 0]).all()
+    assert got["n_related"] == len(rel) and got["n_unrelated"] == len(un)
+    assert abs(got["auroc"] - roc_auc_score([1] * len(rel) + [0] * len(un), np.concatenate([rel, un]))) < 1e-12
