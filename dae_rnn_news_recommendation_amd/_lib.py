@@ -180,6 +180,14 @@ SIGNATURES = {
     "dae_covisit_neighbors_workspace": (u64, [u64, i32, i32]),
     "dae_covisit_neighbors": (i32, [vp, vp, vp, i32, i64, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, u64, vp]),
     "dae_covisit_recommend": (i32, [vp, vp, i64, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp]),
+    "dae_word_profiles_bytes": (u64, [i32, i32]),
+    "dae_word_profiles": (i32, [vp, vp, i64, i32, i32, vp, vp, i64, i32, i32, vp, u64, vp, vp]),
+    "dae_word_entry_weights_bytes": (u64, [i64]),
+    "dae_word_entry_weights": (i32, [vp, vp, i64, i32, vp, vp, vp]),
+    "dae_word_topk_workspace": (u64, [i32, i32, i32]),
+    "dae_word_topk": (i32, [vp, i32, i32, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, u64, vp]),
+    "dae_word_rank_workspace": (u64, [i32]),
+    "dae_word_rank": (i32, [vp, i32, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]),
     "dae_als_interactions_workspace": (u64, [i64, i32, i32]),
     "dae_als_interactions": (i32, [vp, vp, i32, i64, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp, u64, vp]),
     "dae_als_gram_workspace": (u64, [i32, i32]),

@@ -127,8 +127,104 @@ __device__ __forceinline__ void window_prologue(const int32_t* win_lo, const int
     ct0 = t0 + (int)((int64_t)nt * split / splits); ct1 = t0 + (int)((int64_t)nt * (split + 1) / splits);
 }
 
+// ---- the running top-k of a score tile ----
+// What dae_topk.hip (scores from the MFMA) and dae_words.hip (scores from bitmap profiles) do with a [128][128] fp32 score tile in
+// LDS; the description stands at the top of dae_topk.hip.
+constexpr int TOPK_MAX = 128;
+constexpr int TOPK_SLOTS = 512;            // workgroups in flight on the MI355X: 256 CUs x 2 (the slice count is sized for it)
+constexpr int TOPK_MAX_SPLITS = 32;        // bounds phase B's LDS (32 lists x 128 keys x 8 B)
+constexpr int TOPK_TILE_BYTES = BM * BN * 4;
+constexpr int TOPK_LDS = TOPK_TILE_BYTES + 128 * 8 + 128 * 4 + 4 * 2 * TOPK_MAX * 8;
+constexpr int TOPK_WIN_LDS = TOPK_LDS + 2 * 128 * 4 + 16;   // + the query tile's windows and their union
+
+// number of keys of the descending list L[0, n) above x
+__device__ __forceinline__ int keys_above(const uint64_t* L, int n, uint64_t x) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int m = (lo + hi) >> 1;
+        if (L[m] > x) lo = m + 1; else hi = m;
+    }
+    return lo;
+}
+
+// The epilogue of one score tile: `tile` holds the scores of query tile qt (rows) against corpus tile ct (columns); wave w merges the
+// candidates of its rows 32w .. 32w+31 into the rows' sorted lists of slice `split`.  th / len: the rows' thresholds and list lengths,
+// Ls / Cs: this wave's merge scratch, wlo / whi: the rows' windows (WIN only), row0 / col0: the global ids of image row / column 0
+// (CHUNK only, else 0), k = p.k, lane / wave of the thread and below = the mask of the lanes under it: values the kernel keeps across its
+// tile loop.  P: the kernel's parameter block -- Nq, Nc, Nqp, k, part ([splits][Nqp][k] sorted keys) and the RowFilter f.
+// The caller's barriers frame it.
+template <bool EXCL, bool WIN, bool SEQ, bool CHUNK, typename P>
+__device__ __forceinline__ void topk_tile_epilogue(const P& p, const float* tile, uint64_t* th, int* len, uint64_t* Ls, uint64_t* Cs,
+                                                   const int* wlo, const int* whi, int qt, int ct, int split, int row0, int col0, int k,
+                                                   int lane, int wave, uint64_t below) {
+    const int j0 = ct * BN + lane, j1 = j0 + 64;
+    const int gj0 = col0 + j0, gj1 = col0 + j1;          // the candidates' ids
+    for (int rr = 0; rr < 32; ++rr) {
+        const int row = wave * 32 + rr, gi = qt * BM + row;
+        if (gi >= p.Nq) break;
+        int wl = 0, wh = INT32_MAX;
+        if constexpr (WIN) {
+            wl = wlo[row]; wh = whi[row];
+            if (wh <= ct * BN || wl >= (ct + 1) * BN) continue;      // the row's window misses this tile (wave-uniform)
+        }
+        const uint64_t t = th[row];
+        const bool ok0 = j0 < p.Nc && !(p.f.exclude_self && gj0 == row0 + gi) && (!WIN || (j0 >= wl && j0 < wh)),
+                   ok1 = j1 < p.Nc && !(p.f.exclude_self && gj1 == row0 + gi) && (!WIN || (j1 >= wl && j1 < wh));
+        const uint64_t c0 = ok0 ? pair_key(tile[row * BN + lane], gj0) : 0, c1 = ok1 ? pair_key(tile[row * BN + 64 + lane], gj1) : 0;
+        bool in0 = c0 > t, in1 = c1 > t;
+        uint64_t b0 = __ballot(in0), b1 = __ballot(in1);
+        if ((b0 | b1) == 0) continue;
+        if constexpr (EXCL) {                               // drop the candidates the row's list bars, then ballot again
+            const RowList l = row_list_of<SEQ>(p.f, gi);
+            if (l.n > 0) {
+                if (in0 && list_has<SEQ>(l, gj0)) in0 = false;
+                if (in1 && list_has<SEQ>(l, gj1)) in1 = false;
+                b0 = __ballot(in0); b1 = __ballot(in1);
+                if ((b0 | b1) == 0) continue;
+            }
+        }
+        // ---- merge the candidates into the row's list ----
+        const int n0 = __popcll(b0), n = n0 + __popcll(b1);
+        const int m = len[row];
+        uint64_t* L = p.part + ((int64_t)split * p.Nqp + gi) * k;
+        const uint64_t e0 = lane < m ? L[lane] : 0, e1 = lane + 64 < m ? L[lane + 64] : 0;
+        if (in0) Cs[__popcll(b0 & below)] = c0;
+        if (in1) Cs[n0 + __popcll(b1 & below)] = c1;
+        if (lane < m) Ls[lane] = e0;
+        if (lane + 64 < m) Ls[lane + 64] = e1;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        int r0 = lane, r1 = lane + 64, q0 = 0, q1 = 0;      // new positions: old entries / candidates
+        for (int q = 0; q < n; ++q) {
+            const uint64_t x = Cs[q];
+            r0 += x > e0; r1 += x > e1; q0 += x > c0; q1 += x > c1;
+        }
+        if (in0) q0 += keys_above(Ls, m, c0);
+        if (in1) q1 += keys_above(Ls, m, c1);
+        if (lane < m && r0 < k) L[r0] = e0;
+        if (lane + 64 < m && r1 < k) L[r1] = e1;
+        if (in0 && q0 < k) L[q0] = c0;
+        if (in1 && q1 < k) L[q1] = c1;
+        const int m2 = min(k, m + n);
+        if (m2 == k) {                                      // the k-th entry is the new threshold
+            if (lane < m && r0 == k - 1) th[row] = e0;
+            if (lane + 64 < m && r1 == k - 1) th[row] = e1;
+            if (in0 && q0 == k - 1) th[row] = c0;
+            if (in1 && q1 == k - 1) th[row] = c1;
+        }
+        if (lane == 0) len[row] = m2;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // Ls / Cs are rewritten by the next row's merge
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // ---- host ----
 static inline uint64_t al256(uint64_t b) { return (b + 255) / 256 * 256; }
+
+// Phase B of a top-k sweep (dae_topk.hip: topk_merge_kernel<false>): one workgroup per query row merges the row's `splits` sorted
+// lists part [splits][Nqp][k] / part_n [splits][Nqp] and writes idx / score [Nq x ldk], tails -1 / -inf.
+int topk_merge_launch(const uint64_t* part, const int* part_n, int Nq, int Nqp, int splits, int k, int32_t* idx, float* score, int64_t ldk,
+                      hipStream_t st);
 
 // the two operand images every *_workspace starts with
 static inline uint64_t sweep_images_bytes(int Nq, int Nc, int D) {

@@ -21,6 +21,7 @@
 //      look their column up in the list their row reads (row_list_of, list_has: a binary search) and the ballot is taken again:
 //      the test runs only on the few candidates that would enter a merge, and an excluded candidate never takes one of the k
 //      slots.  topk_tiles_kernel<false> is the kernel without lists, unchanged.
+//      Step 3's code is topk_tile_epilogue in dae_score_sweep.h: dae_words.hip runs it on score tiles of its own.
 // LDS: 64 KiB tile / staging + 1 KiB thresholds + 0.5 KiB list lengths + 4 x 2 KiB merge scratch = 73.5 KiB, two
 // workgroups per CU.  Phase B, topk_merge_kernel: one workgroup per query row merges the `splits` sorted lists the same
 // way (each entry's rank = its position + the entries above it in the other lists) and writes idx / score.
@@ -47,23 +48,6 @@
 #include "dae_score_sweep.h"
 
 namespace dae {
-
-constexpr int TOPK_MAX = 128;
-constexpr int TOPK_SLOTS = 512;            // workgroups in flight on the MI355X: 256 CUs x 2 (the slice count is sized for it)
-constexpr int TOPK_MAX_SPLITS = 32;        // bounds phase B's LDS (32 lists x 128 keys x 8 B)
-constexpr int TOPK_TILE_BYTES = BM * BN * 4;
-constexpr int TOPK_LDS = TOPK_TILE_BYTES + 128 * 8 + 128 * 4 + 4 * 2 * TOPK_MAX * 8;
-constexpr int TOPK_WIN_LDS = TOPK_LDS + 2 * 128 * 4 + 16;   // + the query tile's windows and their union
-
-// number of keys of the descending list L[0, n) above x
-__device__ __forceinline__ int keys_above(const uint64_t* L, int n, uint64_t x) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int m = (lo + hi) >> 1;
-        if (L[m] > x) lo = m + 1; else hi = m;
-    }
-    return lo;
-}
 
 struct TopkParams {
     GemmParams g;                 // one K segment: A = query image, Bt = corpus image
@@ -110,65 +94,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void topk_tiles_kernel(TopkParams 
         __syncthreads();                                        // every wave is done with the staging ring
         acc_to_tile(acc, tile, wm, wn, g, c);
         __syncthreads();
-        const int j0 = ct * BN + lane, j1 = j0 + 64;
-        const int gj0 = col0 + j0, gj1 = col0 + j1;          // the candidates' ids
-        for (int rr = 0; rr < 32; ++rr) {
-            const int row = wave * 32 + rr, gi = qt * BM + row;
-            if (gi >= p.Nq) break;
-            int wl = 0, wh = INT32_MAX;
-            if constexpr (WIN) {
-                wl = wlo[row]; wh = whi[row];
-                if (wh <= ct * BN || wl >= (ct + 1) * BN) continue;      // the row's window misses this tile (wave-uniform)
-            }
-            const uint64_t t = th[row];
-            const bool ok0 = j0 < p.Nc && !(p.f.exclude_self && gj0 == row0 + gi) && (!WIN || (j0 >= wl && j0 < wh)),
-                       ok1 = j1 < p.Nc && !(p.f.exclude_self && gj1 == row0 + gi) && (!WIN || (j1 >= wl && j1 < wh));
-            const uint64_t c0 = ok0 ? pair_key(tile[row * BN + lane], gj0) : 0, c1 = ok1 ? pair_key(tile[row * BN + 64 + lane], gj1) : 0;
-            bool in0 = c0 > t, in1 = c1 > t;
-            uint64_t b0 = __ballot(in0), b1 = __ballot(in1);
-            if ((b0 | b1) == 0) continue;
-            if constexpr (EXCL) {                               // drop the candidates the row's list bars, then ballot again
-                const RowList l = row_list_of<SEQ>(p.f, gi);
-                if (l.n > 0) {
-                    if (in0 && list_has<SEQ>(l, gj0)) in0 = false;
-                    if (in1 && list_has<SEQ>(l, gj1)) in1 = false;
-                    b0 = __ballot(in0); b1 = __ballot(in1);
-                    if ((b0 | b1) == 0) continue;
-                }
-            }
-            // ---- merge the candidates into the row's list ----
-            const int n0 = __popcll(b0), n = n0 + __popcll(b1);
-            const int m = len[row];
-            uint64_t* L = p.part + ((int64_t)split * p.Nqp + gi) * k;
-            const uint64_t e0 = lane < m ? L[lane] : 0, e1 = lane + 64 < m ? L[lane + 64] : 0;
-            if (in0) Cs[__popcll(b0 & below)] = c0;
-            if (in1) Cs[n0 + __popcll(b1 & below)] = c1;
-            if (lane < m) Ls[lane] = e0;
-            if (lane + 64 < m) Ls[lane + 64] = e1;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            int r0 = lane, r1 = lane + 64, q0 = 0, q1 = 0;      // new positions: old entries / candidates
-            for (int q = 0; q < n; ++q) {
-                const uint64_t x = Cs[q];
-                r0 += x > e0; r1 += x > e1; q0 += x > c0; q1 += x > c1;
-            }
-            if (in0) q0 += keys_above(Ls, m, c0);
-            if (in1) q1 += keys_above(Ls, m, c1);
-            if (lane < m && r0 < k) L[r0] = e0;
-            if (lane + 64 < m && r1 < k) L[r1] = e1;
-            if (in0 && q0 < k) L[q0] = c0;
-            if (in1 && q1 < k) L[q1] = c1;
-            const int m2 = min(k, m + n);
-            if (m2 == k) {                                      // the k-th entry is the new threshold
-                if (lane < m && r0 == k - 1) th[row] = e0;
-                if (lane + 64 < m && r1 == k - 1) th[row] = e1;
-                if (in0 && q0 == k - 1) th[row] = c0;
-                if (in1 && q1 == k - 1) th[row] = c1;
-            }
-            if (lane == 0) len[row] = m2;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // Ls / Cs are rewritten by the next row's merge
-            __builtin_amdgcn_wave_barrier();
-        }
+        topk_tile_epilogue<EXCL, WIN, SEQ, CHUNK>(p, tile, th, len, Ls, Cs, wlo, whi, qt, ct, split, row0, col0, k, lane, wave, below);
         __syncthreads();                                        // the tile is the next K loop's staging ring
     }
     if (tid < 128 && qt * BM + tid < p.Nq) p.part_n[(int64_t)split * p.Nqp + qt * BM + tid] = len[tid];
@@ -212,6 +138,14 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* __restr
     }
     for (int r = total + tid; r < k; r += 256) { oi[r] = -1; os[r] = -__builtin_inff(); }
     if (CARRY && tid == 0) carry_n[row] = min(total, k);
+}
+
+int topk_merge_launch(const uint64_t* part, const int* part_n, int Nq, int Nqp, int splits, int k, int32_t* idx, float* score, int64_t ldk,
+                      hipStream_t st) {
+    DAE_LAUNCH(topk_merge_kernel<false>, dim3(Nq), dim3(256), 0, st, part, part_n, Nqp, splits, k, idx, score, ldk, (uint64_t*)nullptr,
+               (int*)nullptr);
+    DAE_CHECK_LAUNCH();
+    return 0;
 }
 
 static int topk_splits(int Nq, int Nc) { return sweep_splits(Nq, Nc, TOPK_SLOTS, TOPK_MAX_SPLITS); }
@@ -261,10 +195,7 @@ static int topk_run(const float* Q, int64_t ldq, int32_t Nq, const float* C, int
     p.part = (uint64_t*)o.rest; p.part_n = (int*)(o.rest + al256((uint64_t)splits * o.Nqp * k * 8));
     p.f = f;
     if (int rc = DAE_SWEEP_LAUNCH_FILTERED(topk_tiles_kernel, f, TOPK_LDS, TOPK_WIN_LDS, o.Nqp / BM * splits, st, p)) return rc;
-    DAE_LAUNCH(topk_merge_kernel<false>, dim3(Nq), dim3(256), 0, st, p.part, p.part_n, p.Nqp, splits, k, idx, score, ldk, (uint64_t*)nullptr,
-               (int*)nullptr);
-    DAE_CHECK_LAUNCH();
-    return 0;
+    return topk_merge_launch(p.part, p.part_n, Nq, p.Nqp, splits, k, idx, score, ldk, st);
 }
 
 extern "C" uint64_t dae_topk_carry_bytes(int32_t Nq, int32_t k) {

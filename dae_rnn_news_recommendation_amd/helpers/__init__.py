@@ -34,6 +34,9 @@ is importable from here; the code lives by subject:
   ``als_interactions`` -> ``ALSInteractions`` (both orientations of the click counts), ``als_gram``, ``als_solve_rows`` (one
   half-sweep of conjugate gradient per row), ``als_loss``, and ``fit_als`` -> ``ALSModel`` (``user_states``, ``recommend``,
   ``similar``, ``save`` / ``load``).
+* ``words`` -- the paper's word-based baseline: ``word_profiles`` -> ``WordProfiles`` (the users' word sets as device bitmaps;
+  ``to_scipy``), ``word_recommend`` (top-k of the weighted count of shared words, sparse on both sides), ``word_ranks`` (its
+  full-rank twin, in the form ``rank_metrics`` takes) and ``idf_weights`` (sklearn's smooth idf as term weights).
 * ``_device`` -- what every device call starts and ends with, once: device and library, the ``norm`` / ``metric`` check, the
   matrix and history intakes, uploads, workspaces, the result tail.
 
@@ -60,3 +63,4 @@ from .user_models import (GRUUserModel, LSTMUserModel, RNNUserModel, UserModel, 
                           trim_histories, user_pair_loss, user_states)
 from .vectorize import (TfidfTransformer, binarize, column_stats, device_csr_to_scipy, limit_features, limit_features_columns,
                         select_columns)
+from .words import WordProfiles, idf_weights, word_profiles, word_ranks, word_recommend

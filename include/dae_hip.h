@@ -1011,6 +1011,59 @@ int dae_covisit_recommend(const int32_t* nbr, const float* sim, int64_t ld, int3
                           int32_t* idx, float* score, int64_t ldo, void* stream);
 
 /* -------------------------------------------------------------------------------------------------
+ * The word-based user model, the baseline of "Embedding-based News Recommendation for Millions of Users" (section 5.1;
+ * helpers.word_profiles / word_recommend / word_ranks; csrc/dae_words.hip).  An article is the set of its words: row a of a CSR
+ * matrix [Na x V] (art_indptr int64[Na + 1], art_indices int32[nnz] ascending and unique per row, values fp32[nnz] or NULL: all
+ * ones).  A user is the set of the words of the articles clicked; the relevance is a weighted count of the words the two share.
+ *   profile: word w is in profile(u) when some article among the last max_events clicks of user u (history CSR hist_indptr
+ *   int64[M + 1], hist_items int32[hist_nnz], oldest first; max_events 0: every click) stores column w -- explicit zeros count,
+ *   repeated clicks change nothing.  An item outside [0, Na) and a column outside [0, V) are dropped, never written.
+ *   bitmaps: word-major per tile of 128 users, uint32 [ceil(M / 128)][V][4]; bit (u & 31) of word (u & 127) >> 5 of cell
+ *   (u >> 7, w) says "user u has word w".  dae_word_profiles_bytes(M, V) = ceil(M / 128) * V * 16 bytes; 16-byte aligned.
+ *   dae_word_profiles zeroes the bitmaps, sets the bits with integer atomicOr (exact, whatever the schedule) and writes
+ *   sizes int32[M], the number of distinct words of every profile, from a bit-counting pass over the bitmaps (no atomics).
+ *   entry weights: dae_word_entry_weights writes weights fp32[nnz] once per stored entry p with column c_p and value x_p (1 without
+ *   values): e_p = x_p when term_weights is NULL, else __fmul_rn(term_weights[c_p], x_p) (term_weights fp32[V]); +0 for a column
+ *   outside [0, V).  dae_word_entry_weights_bytes(nnz) = the size of that array.
+ *   score: R(u, a) = s_n with s_0 = +0 and s_i = __fadd_rn(s_{i-1}, c_i in profile(u) ? e_i : +0) over a's entries in storage
+ *   order -- the sequential fp32 sum of the co-occurring entry weights, nothing contracted.  With values = term_weights = NULL it
+ *   is the co-occurrence count, an exact integer.
+ *   dae_word_topk: per user the k best articles by (score descending, index ascending), -0 and +0 one score (the order and the
+ *   outputs of dae_topk_similarity: idx int32 / score fp32 [M x ldk], tail -1 / -inf, 1 <= k <= 128).  excl_indptr int64[M + 1] /
+ *   excl_items int32 (both or neither; every row ascending and unique): an excluded article never takes one of the k slots.
+ *   win_lo / win_hi int32[M] (both or neither): user u admits the articles win_lo[u] <= a < win_hi[u], clamped to [0, Na].
+ *   grid = (user tiles) x (corpus slices); per 128-article tile a thread keeps 64 users' partial scores of one article in
+ *   registers, the tile's CSR rows are staged through LDS, and every entry costs one 8-byte mask load and 64 select-adds; the
+ *   epilogue and the merge are those of dae_topk_similarity.  dae_word_topk_workspace(M, Na, k) = the slices' partial lists.
+ *   dae_word_rank: rank[u] = 1 + #{ a < Na, a != t, a not in u's list, a in u's window : key(R(u, a), a) > key(R(u, t), t) } for
+ *   t = targets[u] (the definition at the top of csrc/dae_rank.hip on these scores); target_score[u] = R(u, t), bit-equal to the
+ *   score dae_word_topk writes for that pair.  t < 0 (or >= Na): rank 0, target_score -inf.  The target is ranked whether or not
+ *   the list or the window holds it (the caller decides what such a rank means).  Integer atomics only.
+ *   dae_word_rank_workspace(M) = one key per user.
+ *   Every row range read from art_indptr / hist_indptr is clamped to [0, nnz] / [0, hist_nnz].  The results are bit-identical
+ *   from run to run and independent of the workspace size and of the order of the users.  No call synchronises.
+ * Argument errors are reported before any HIP call, with the prefixes "word_profiles: " / "word_entry_weights: " / "word_topk: " /
+ * "word_rank: ".
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dae_word_profiles_bytes(int32_t M, int32_t V);
+int dae_word_profiles(const int64_t* hist_indptr, const int32_t* hist_items, int64_t hist_nnz, int32_t M, int32_t max_events,
+                      const int64_t* art_indptr, const int32_t* art_indices, int64_t nnz, int32_t Na, int32_t V, void* bitmaps,
+                      uint64_t bitmap_bytes, int32_t* sizes, void* stream);
+uint64_t dae_word_entry_weights_bytes(int64_t nnz);
+int dae_word_entry_weights(const int32_t* art_indices, const float* art_values, int64_t nnz, int32_t V, const float* term_weights,
+                           float* weights, void* stream);
+uint64_t dae_word_topk_workspace(int32_t M, int32_t Na, int32_t k);
+int dae_word_topk(const void* bitmaps, int32_t M, int32_t V, const int64_t* art_indptr, const int32_t* art_indices,
+                  const float* weights, int64_t nnz, int32_t Na, int32_t k, const int64_t* excl_indptr, const int32_t* excl_items,
+                  const int32_t* win_lo, const int32_t* win_hi, int32_t* idx, float* score, int64_t ldk, void* workspace,
+                  uint64_t workspace_bytes, void* stream);
+uint64_t dae_word_rank_workspace(int32_t M);
+int dae_word_rank(const void* bitmaps, int32_t M, int32_t V, const int64_t* art_indptr, const int32_t* art_indices,
+                  const float* weights, int64_t nnz, int32_t Na, const int64_t* excl_indptr, const int32_t* excl_items,
+                  const int32_t* win_lo, const int32_t* win_hi, const int32_t* targets, int32_t* rank, float* target_score,
+                  void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------------
  * Implicit-feedback matrix factorisation by alternating least squares (helpers.fit_als / ALSModel; Hu, Koren, Volinsky 2008;
  * csrc/dae_als.hip).  r_ui = the number of times user u clicked article i, c_ui = 1 + alpha r_ui, p_ui = [r_ui > 0];
  *   L = sum over ALL u, i of c_ui (p_ui - x_u . y_i)^2 + lambda (|X|^2 + |Y|^2), X fp32 [M x F], Y fp32 [Na x F], 1 <= F <= 128.

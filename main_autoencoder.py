@@ -25,6 +25,7 @@ examples:
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --ann_clusters 64 --ann_probe 8 --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --covisit --covisit_window 3 --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --als --als_factors 64 --als_iterations 15 --similarity False
+  python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --words --words_idf --rank_metrics --similarity False
   python main_autoencoder.py --model_name rec --sessions synthetic --recommend 10 --every_click --user_model gru --fit_gru --gru_validation 0.2 --similarity False
 """
 import argparse
@@ -220,6 +221,15 @@ def build_parser():
                         "ID-based collaborative filter, trained on the device on the same histories (helpers.fit_als); prints hit@K / MRR / "
                         "nDCG as `ALS factors` (and its line of --rank_metrics), saves article_encoded_recommend{K}_als.npz and "
                         "als_model.npz; honours --max_age.  The other output and files stay what they are")
+    p.add_argument("--words", action="store_true",
+                   help="with --sessions S --recommend K: ALSO the paper's word-based model -- an article is the set of its words (the "
+                        "train matrix the autoencoder was fed, binary or tf-idf per --input_format), a user the set of the words of the "
+                        "articles clicked, the relevance the weighted count of shared words (helpers.word_recommend: bitmap profiles, "
+                        "sparse on both sides); prints hit@K / MRR / nDCG as `word-based model` (and its line of --rank_metrics), saves "
+                        "article_encoded_recommend{K}_words.npz (and article_encoded_ranks_words.npz); honours --max_age.  The other "
+                        "output and files stay what they are")
+    p.add_argument("--words_idf", action="store_true", help="--words: weight every word by its smooth idf (helpers.idf_weights)")
+    p.add_argument("--words_last", type=int, default=0, help="M > 0: --words builds a profile from the user's last M clicks only (0: all)")
     p.add_argument("--als_factors", type=int, default=64, help="F in 1..128: the number of factors of --als")
     p.add_argument("--als_iterations", type=int, default=15, help="iterations of --als (a user and an article half-sweep each)")
     p.add_argument("--als_alpha", type=float, default=40.0, help="the confidence of a click of --als: c = 1 + alpha * clicks")
@@ -269,6 +279,9 @@ def validate(a):
         "--ann_clusters C needs --recommend K (and does not go with --max_age: an index takes no windows)"
     assert 1 <= a.ann_probe <= 128, "--ann_probe is a number in 1..128"
     assert not a.covisit or (a.sessions != '' and a.recommend > 0), "--covisit needs --sessions S --recommend K"
+    assert not a.words or (a.sessions != '' and a.recommend > 0), "--words needs --sessions S --recommend K"
+    assert a.words or not (a.words_idf or a.words_last), "--words_idf and --words_last M belong to --words"
+    assert a.words_last >= 0, "--words_last M >= 0"
     assert a.covisit_window >= 1 and 1 <= a.covisit_neighbors <= 128 and 1 <= a.covisit_last <= 32, \
         "--covisit_window W >= 1, --covisit_neighbors N in 1..128, --covisit_last M in 1..32"
     assert a.max_age == 0. or (a.sessions == 'synthetic' and a.recommend > 0), "--max_age needs --sessions synthetic --recommend K"
@@ -417,7 +430,7 @@ def evaluate_duplicates(a, trY, vlY, emb, emb_v, data_dir):
     return out
 
 
-def evaluate_recommend(a, trY, emb, data_dir):
+def evaluate_recommend(a, trY, emb, data_dir, trX=None):
     """--sessions S --recommend K: next-click evaluation of the decaying user model.  Every user's last click is held out; the
     user state is the decay-weighted mean of the train embeddings of the clicks before it (helpers.user_states); the K unseen
     articles with the largest inner product are recommended (helpers.recommend: no users x articles matrix) and saved as
@@ -435,7 +448,7 @@ def evaluate_recommend(a, trY, emb, data_dir):
     print('calculate recommend %d' % K)
     t = None
     if a.max_age > 0:
-        return evaluate_recommend_window(a, trY, emb, data_dir)
+        return evaluate_recommend_window(a, trY, emb, data_dir, trX)
     if a.sessions == 'synthetic':
         assert trY is not None, "--sessions synthetic needs labels"
         seed = a.seed if a.seed >= 0 else 1234
@@ -472,6 +485,8 @@ def evaluate_recommend(a, trY, emb, data_dir):
         evaluate_recommend_covisit(a, emb, hist, targets, data_dir)
     if a.als:
         evaluate_recommend_als(a, hist, targets, n, data_dir)
+    if a.words:
+        evaluate_recommend_words(a, trX, hist, targets, data_dir)
     models = {}
     if a.rank_metrics:
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir)
@@ -569,6 +584,50 @@ def evaluate_recommend_als(a, hist, targets, n, data_dir, window=None):
     return idx, score
 
 
+def evaluate_recommend_words(a, trX, hist, targets, data_dir, window=None):
+    """--words: the paper's word-based model beside the embedding models.  An article is the set of the words of its row of the
+    train matrix ``trX`` (what the autoencoder was fed: binary or tf-idf per --input_format), a user the set of the words of the
+    articles of the history the other models see -- the held-out click is not among them; --words_last M: of its last M clicks --
+    and every user is recommended the K unseen articles with the largest sum of the article's entries over the shared words
+    (helpers.word_recommend; --words_idf: every entry times the word's smooth idf, helpers.idf_weights; with ``window`` inside the
+    candidate windows of --max_age).  Prints hit@K / MRR@K / nDCG@K as `word-based model`, and with --rank_metrics the line of
+    evaluate_rank_metrics for the same model (helpers.word_ranks; a re-click of an article of the history counts as a miss, as it
+    does for the other models).  Saves ``indices`` / ``scores`` / ``targets`` / ``hist_indptr`` / ``hist_items`` /
+    ``profile_sizes`` to article_encoded_recommend{K}[_window]_words.npz and, with --rank_metrics, ``rank`` / ``score`` /
+    ``n_candidates`` / ``targets`` to article_encoded_ranks[_window]_words.npz."""
+    import scipy.sparse as sp
+    from dae_rnn_news_recommendation_amd import helpers
+    from dae_rnn_news_recommendation_amd.helpers.sweeps import competitors
+    K = a.recommend
+    tag = '' if window is None else '_window'
+    name = 'article_encoded_recommend%d%s_words.npz' % (K, tag)
+    print('calculate recommend %d words' % K)
+    articles = sp.csr_matrix(trX, dtype=np.float32)
+    articles.sum_duplicates()
+    articles.sort_indices()
+    n, V = articles.shape
+    weights = helpers.idf_weights(articles) if a.words_idf else None
+    last = a.words_last if a.words_last > 0 else None
+    profiles = helpers.word_profiles(hist, articles, max_events=last)
+    idx, score = helpers.word_recommend(profiles, articles, K, seen=hist, term_weights=weights, window=window)
+    np.savez(data_dir + name, indices=idx, scores=score, targets=targets, hist_indptr=hist[0], hist_items=hist[1], profile_sizes=profiles.sizes)
+    m = helpers.next_click_metrics(idx, targets)
+    print('  %d words, %.1f per article, %.1f per profile%s%s -> %s' % (
+        V, articles.nnz / max(n, 1), float(profiles.sizes.mean()) if profiles.sizes.size else 0.0, ', idf weights' if a.words_idf else '',
+        ', last %d clicks' % last if last else '', name))
+    print('  hit@%d %-20s %.4f  MRR %.4f  nDCG %.4f' % (K, 'word-based model', m['hit'], m['mrr'], m['ndcg']))
+    if a.rank_metrics:
+        rank, t_score, n_cand = helpers.word_ranks(profiles, articles, targets, seen=hist, term_weights=weights, window=window)
+        rank = np.where(competitors(targets, len(targets), n, False, *helpers.normalize_exclusions(hist, len(targets), n), window)[1],
+                        0, rank)                                       # a target the user can never be shown: a miss
+        r = helpers.rank_metrics(rank, n_cand, targets, ks=(1, 10, 100))
+        print('  ranks %-20s AUC %.4f  MRR %.4f  mean rank %.1f  median rank %.1f  hit@1 %.4f  hit@10 %.4f  hit@100 %.4f'
+              % ('word-based model', r['auc'], r['mrr'], r['mean_rank'], r['median_rank'], r['hit@1'], r['hit@10'], r['hit@100']))
+        np.savez(data_dir + 'article_encoded_ranks%s_words.npz' % tag, rank=rank, score=t_score, n_candidates=n_cand, targets=targets)
+    print('calculate recommend %d words done' % K)
+    return idx, score
+
+
 def evaluate_clusters(a, trY, vlY, emb, emb_v, data_dir):
     """--cluster K: spherical k-means of the train embeddings (helpers.kmeans, on the device): iterations, mean score, the largest
     and the smallest cluster and the empty clusters relocated; with labels purity / NMI / ARI against them
@@ -661,7 +720,7 @@ def evaluate_recommend_mmr(a, trY, states, emb, hist, targets, data_dir, window=
     return idx, score
 
 
-def evaluate_recommend_window(a, trY, emb, data_dir):
+def evaluate_recommend_window(a, trY, emb, data_dir, trX=None):
     """--max_age HOURS: evaluate_recommend inside per-user candidate windows (see there)."""
     from dae_rnn_news_recommendation_amd import helpers
     from dae_rnn_news_recommendation_amd.synthetic import synthetic_timed_sessions
@@ -701,6 +760,8 @@ def evaluate_recommend_window(a, trY, emb, data_dir):
         evaluate_recommend_covisit(a, emb, hist, targets, data_dir, window=window)
     if a.als:
         evaluate_recommend_als(a, hist, targets, n, data_dir, window=window)
+    if a.words:
+        evaluate_recommend_words(a, trX, hist, targets, data_dir, window=window)
     models = {}
     if a.rank_metrics:
         evaluate_rank_metrics(states, emb, hist, targets, n, data_dir, window=window, max_age=a.max_age)
@@ -1005,7 +1066,7 @@ def main(argv=None):
     if a.cluster > 0 and dp.rank() == 0:
         evaluate_clusters(a, trY, vlY, emb, emb_v, model.data_dir)
     if a.recommend > 0 and dp.rank() == 0:
-        evaluate_recommend(a, trY, emb, model.data_dir)
+        evaluate_recommend(a, trY, emb, model.data_dir, trX)
     if model.samples_per_sec:
         print('training throughput: %.0f samples/s over %d epochs; embeddings %s -> %s' %
               (model.samples_per_sec, a.num_epochs, emb.shape, model.data_dir))
